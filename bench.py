@@ -4,9 +4,12 @@ step, three Adams; celebA/EAD-GAN_celebA.py:299-401) at 64x64, batch 128 per GPU
 weights, synthetic data, on N MI355X of one node (weak scaling, RCCL all-reduce of the gradient arenas).
 
     python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --full                               # the same line with the roofline and cpu_baseline objects filled in
+    python bench.py --dump-outputs DIR                   # also writes the last timed step's results as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  A plain run only sets up, warms up,
+times the --steps steps (and writes --dump-outputs); the two extra objects are measured with --full only (null otherwise):
   roofline     : dominant kernel (by time) of the step, algorithmic FLOPs per launch / measured launch duration
                  (HIP events on the launch stream, in this process) against the dense bf16 MFMA peak; `algorithmic_bytes` per
                  launch (inputs + weights + outputs once); `traffic` = HBM bytes per launch from the committed PMC passes
@@ -48,8 +51,12 @@ def parse():
     ap.add_argument("--no-probe", action="store_true", help="skip the child-process capture probe (see decide_graph) and capture directly; a capture "
                     "failure then ends this process with a non-zero exit code")
     ap.add_argument("--probe-capture", action="store_true", help=argparse.SUPPRESS)     # internal: this process IS the probe child
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the roofline pass (dominant "
+                    "kernel, per-kernel table) and the CPU-oracle baseline.  A plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed (losses, "
+                    "module state; large tensors as a fixed seeded sample) as DIR/<name>.npy, to compare two builds output for output")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline pass")
     ap.add_argument("--cpu-steps", type=int, default=5)
     ap.add_argument("--force-dist", action="store_true", help="initialise a process group and run the all-reduce hooks even with one rank "
                                                               "(rehearses the N>1 code path, incl. RCCL capture into the hipGraph, on one GPU)")
@@ -141,6 +148,27 @@ def roofline_pass(eg, trainer, dtype, workload="celeba", iters=3):
                     note=f"{intensity:.0f} FLOP per algorithmic byte (machine balance {peak * 1e12 / (PEAK_HBM_GBS * 1e9):.0f}); {achieved:.1f} TFLOP/s; "
                          f"launches of {avg_us:.1f} us are launch-latency bound rather than bandwidth bound")
     return roof, table
+
+
+DUMP_SAMPLE = 1 << 18          # --dump-outputs: tensors above this many elements are written as a sample of this size
+
+
+def dump_outputs(path, losses, modules):
+    """--dump-outputs: what the timed path computed in its last step -- the step's losses and the state it leaves in the modules (fp32
+    masters, BatchNorm running statistics, spectral-norm vectors) -- one DIR/<name>.npy each, float32 (integer buffers as float64).  A
+    tensor above DUMP_SAMPLE elements is written at DUMP_SAMPLE indices drawn by a generator seeded with 0 (the same indices in every run
+    for the same size), which keeps a CelebA dump near 10 MB.  Runs right after the timed loop: nothing else has touched the state yet."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"losses": losses}
+    for prefix, m in modules.items():
+        for k, v in m.state_dict().items():
+            arrays[f"{prefix}.{k}"] = v
+    for name, t in arrays.items():
+        x = t.detach().reshape(-1).cpu()
+        x = x.float().numpy() if x.is_floating_point() else x.double().numpy()
+        if x.size > DUMP_SAMPLE:
+            x = x[np.sort(np.random.default_rng(0).choice(x.size, DUMP_SAMPLE, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), x)
 
 
 def kernel_table(table):
@@ -267,8 +295,10 @@ def main_mnist(a, eg, rank, world, local, dev):
     torch.cuda.synchronize()
     eg.dp.barrier()
     dt = eg.dp.max_over_ranks(time.perf_counter() - t0, dev)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, tr.losses[:3], {"G": G, "D": D, "E": E})
     roof = table = None
-    if not a.no_roofline and rank == 0:
+    if a.full and not a.no_roofline and rank == 0:
         roof, table = roofline_pass(eg, tr, a.dtype, "mnist")
     if rank == 0:
         ips = B * world * a.steps / dt
@@ -321,8 +351,10 @@ def main_sprites(a, eg, rank, world, local, dev):
     torch.cuda.synchronize()
     eg.dp.barrier()
     dt = eg.dp.max_over_ranks(time.perf_counter() - t0, dev)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, tr.losses[:5], {"P": P, "G": G, "D": D, "E": E})
     roof = table = None
-    if not a.no_roofline and rank == 0:
+    if a.full and not a.no_roofline and rank == 0:
         roof, table = roofline_pass(eg, tr, a.dtype, a.workload)
     if rank == 0:
         ips = B * world * a.steps / dt
@@ -360,6 +392,8 @@ def main_pxy(a, eg, rank, world, local, dev):
     torch.cuda.synchronize()
     eg.dp.barrier()
     dt = eg.dp.max_over_ranks(time.perf_counter() - t0, dev)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, tr.losses[:1], {"P": P})
     if rank == 0:
         print(json.dumps({"metric": "imgs/sec per train step, dSprites stage-1 (Encoder_pxy)", "value": round(B * world * a.steps / dt, 1), "unit": "imgs/s",
                           "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True,
@@ -429,12 +463,14 @@ def main():
     dt = time.perf_counter() - t0
     dt = eg.dp.max_over_ranks(dt, dev)
     losses = tr.losses.tolist()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, tr.losses[:3], {"G": G, "D": D})
 
     roof = table = None
-    if not a.no_roofline and rank == 0:
+    if a.full and not a.no_roofline and rank == 0:
         roof, table = roofline_pass(eg, tr, a.dtype)
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(B, a.cpu_steps)
 
     if rank == 0:

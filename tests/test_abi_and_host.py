@@ -144,3 +144,38 @@ def test_bench_decides_graph_or_eager_from_the_probe_child(monkeypatch):
     assert bench.decide_graph(argparse.Namespace(no_graph=False, graph_dist=False, no_probe=True, probe_capture=False), 1) == (True, "")
     assert bench.decide_graph(argparse.Namespace(no_graph=False, graph_dist=False, no_probe=False, probe_capture=True), 1) == (True, "")   # the child itself
     assert len(calls) == n
+
+
+def test_bench_options_and_dump_outputs(tmp_path):
+    """bench.py: the roofline pass and the CPU baseline run behind --full only; --dump-outputs writes float .npy files, large tensors as
+    a sample whose indices are the same in every run, the whole CelebA dump far below 64 MB."""
+    import numpy as np
+    import bench
+    eg = _pkg()
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--steps", "7", "--warmup", "2"]
+        a = bench.parse()
+        assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+        sys.argv = ["bench.py", "--full", "--dump-outputs", str(tmp_path)]
+        a = bench.parse()
+        assert a.full and a.dump_outputs == str(tmp_path)
+    finally:
+        sys.argv = argv
+    torch.manual_seed(0)
+    mods = {"G": eg.celeba.Generator(dtype="bf16"), "D": eg.celeba.Discriminator(dtype="bf16")}
+    bench.dump_outputs(str(tmp_path / "a"), torch.tensor([0.5, 1.5, 2.5]), mods)
+    bench.dump_outputs(str(tmp_path / "b"), torch.tensor([0.5, 1.5, 2.5]), mods)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert "losses.npy" in names and "G.conv_blocks.0.weight.npy" in names and "D.main.6.weight_orig.npy" in names
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and x.ndim == 1 and x.size <= bench.DUMP_SAMPLE, n
+        np.testing.assert_array_equal(x, y)
+        total += x.nbytes
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "losses.npy"), np.float32([0.5, 1.5, 2.5]))
+    w = mods["G"].state_dict()["conv_blocks.0.bias"].numpy()
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "G.conv_blocks.0.bias.npy"), w)      # small tensors in full
+    assert np.load(tmp_path / "a" / "G.conv_blocks.1.weight.npy").size == bench.DUMP_SAMPLE   # 8.4M elements: sampled
+    assert total < 64 << 20

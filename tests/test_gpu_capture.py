@@ -25,3 +25,20 @@ def test_bench_probes_the_capture_in_a_child_process_first():
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert "hipGraph replay" in line["config"]["workload"], line["config"]
     assert "capture probe ok" in r.stderr          # the child's verdict (its stderr is inherited)
+
+
+def test_plain_bench_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run prints the contract line without the --full measurements, and --dump-outputs writes the last timed step's results."""
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "8", "--steps", "4", "--warmup", "2", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 4 and line["ms_per_step"] > 0 and line["roofline"] is None and line["cpu_baseline"] is None, line
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype"):
+        assert k in line, k
+    losses = np.load(tmp_path / "losses.npy")
+    assert losses.dtype == np.float32 and losses.shape == (3,) and np.isfinite(losses).all()
+    np.testing.assert_allclose(losses, [line["final_losses"][k] for k in ("g", "d", "info")], atol=1e-4)
+    w = np.load(tmp_path / "G.conv_blocks.0.bias.npy")
+    assert w.dtype == np.float32 and w.shape == (1024,) and np.isfinite(w).all()

@@ -4,15 +4,22 @@ import os
 import numpy as np
 import pytest
 import torch
+import torch.nn.functional as F
 
 from conftest import GOLDEN
 from oracle import celeba_oracle as co
 from oracle import mnist_oracle as mo
 
 
-def check_probes(prefix, tensors, gold, rtol, atol, noise_floor=0.0):
+def check_probes(prefix, tensors, gold, rtol, atol, noise_floor=0.0, noise_grads=None, init=None, max_step=0.0):
     """tensors: name -> tensor; compares head/sum/abs fingerprints.  Scale-aware: tolerances are relative
-    to the mean |value| of the tensor so that near-zero entries do not dominate."""
+    to the mean |value| of the tensor so that near-zero entries do not dominate.
+
+    Post-Adam state (noise_grads = prefix of the gradient probes): where the golden gradient is rounding noise (mean |g| below 1e-8,
+    the floor of the gradient check: conv biases in front of a BatchNorm), a first Adam step moves every entry by up to its learning
+    rate in a direction that rounding picks, so the sum and |sum| fingerprints depend on the host's BLAS kernels.  For those tensors
+    they are replaced by what holds on every host: each entry lies within max_step (the summed learning rates) of its seeded value in
+    init (the head check, sized for such moves, stays)."""
     for k, v in tensors.items():
         t = v.detach().double().flatten().cpu()
         ab = float(gold[f"{prefix}/{k}/abs"])
@@ -21,6 +28,11 @@ def check_probes(prefix, tensors, gold, rtol, atol, noise_floor=0.0):
             continue
         tol = rtol * scale + atol
         np.testing.assert_allclose(t[:8].numpy(), gold[f"{prefix}/{k}/head"], rtol=0, atol=8 * tol, err_msg=f"{prefix}/{k}")
+        g_abs = f"{noise_grads}/{k}/abs"
+        if noise_grads is not None and g_abs in gold and float(gold[g_abs]) / max(t.numel(), 1) < 1e-8:
+            moved = (t - init[k].detach().double().flatten()).abs().max().item()
+            assert moved <= max_step * (1 + 1e-3), f"{prefix}/{k} moved {moved} > {max_step}"
+            continue
         assert abs(t.abs().sum().item() - ab) <= rtol * ab + atol * t.numel() ** 0.5, f"{prefix}/{k} abs"
         assert abs(t.sum().item() - float(gold[f"{prefix}/{k}/sum"])) <= rtol * ab + atol * t.numel() ** 0.5, f"{prefix}/{k} sum"
 
@@ -30,14 +42,17 @@ def test_celeba_step_matches_reference():
     B, steps, seed = int(gold["B"]), int(gold["steps"]), int(gold["seed"])
     torch.set_num_threads(8)
     orc = co.CelebAOracle(seed=seed)
+    init_G, init_D = ({k: v.detach().clone() for k, v in m.items()} for m in (orc.G, orc.D))
+    lr = lambda opt: opt.param_groups[0]["lr"]
     rng = np.random.RandomState(seed)
     real = co.synthetic_real(B * steps, seed=int(gold["real_seed"])).view(steps, B, 3, 64, 64)
     for i in range(steps):
         z, code, labels = co.draw_step_inputs(rng, B)
         out = orc.train_step(real[i], z, code, labels)
         # step 0 is a pure function of the seeded init; later steps pass through Adam's first-step
-        # sign amplification of rounding noise, hence the looser bound.
-        tol = (2e-6, 3e-4, 5e-3)[i]
+        # sign amplification of rounding noise, hence the looser bound.  Its size depends on the host's BLAS kernels: step 1 moved
+        # by up to 2e-5 where the golden file was made and by 0.8e-3 - 1.2e-3 on hosts whose MKL takes other kernels (AMD, AVX2 path).
+        tol = (2e-6, 2e-3, 5e-3)[i]
         for k in ("g_loss", "d_loss", "info_loss"):
             assert abs(out[k] - gold[k][i]) < tol, (i, k, out[k], gold[k][i])
         if i == 0:
@@ -45,8 +60,28 @@ def test_celeba_step_matches_reference():
             check_probes("gG1", {k: v.grad for k, v in orc.G.items() if getattr(v, "grad", None) is not None}, gold, 1e-2, 1e-9, noise_floor=1e-8)
             check_probes("gD1", {k: v.grad for k, v in orc.D.items() if getattr(v, "grad", None) is not None}, gold, 1e-2, 1e-9, noise_floor=1e-8)
             # post-Adam state: entries with ~0 gradient move by +-lr on rounding noise -> atol 2.5e-3 on heads
-            check_probes("G1", orc.G, gold, 2e-3, 3e-4)
-            check_probes("D1", orc.D, gold, 2e-3, 3e-4)
+            check_probes("G1", orc.G, gold, 2e-3, 3e-4, noise_grads="gG1", init=init_G, max_step=lr(orc.opt_G) + lr(orc.opt_info))
+            check_probes("D1", orc.D, gold, 2e-3, 3e-4, noise_grads="gD1", init=init_D, max_step=lr(orc.opt_D) + lr(orc.opt_info))
+
+
+def grid_rounding_slack(img, theta):
+    """How far a bilinear warp may move when only the float32 rounding of its sampling grid differs.  affine_grid forms each grid
+    coordinate as a three-term dot product (base point x, y, 1 against a row of theta) in a BLAS batched matmul whose kernel, and so
+    whose rounding, depends on the host CPU: two hosts may differ by 2 * gamma_3 ~ 6 units of rounding (2**-24) of the sum of |terms|,
+    and grid_sample rounds g + 1 on its way to pixels: 8 units of |terms| + 1 in all.  An output element moves by its slope along its
+    own grid point times that: per channel, d out / d grid by autograd."""
+    N, C, H, W = img.shape
+    grid = F.affine_grid(theta, [N, C, H, W], align_corners=False).detach()
+    xs, ys = (torch.arange(W) * 2 + 1) / W - 1, (torch.arange(H) * 2 + 1) / H - 1
+    base = torch.stack((xs.view(1, W).expand(H, W), ys.view(H, 1).expand(H, W), torch.ones(H, W)), -1).abs()    # |x|, |y|, 1
+    terms = torch.einsum("hwi,ndi->nhwd", base.double(), theta.abs().double())
+    dgrid = 8 * 2.0 ** -24 * (terms + 1)
+    slack = torch.empty(N, C, H, W, dtype=torch.float64)
+    for c in range(C):
+        g = grid.clone().requires_grad_()
+        F.grid_sample(img[:, c:c + 1], g, mode="bilinear", padding_mode="border", align_corners=False).sum().backward()
+        slack[:, c] = (g.grad.abs().double() * dgrid).sum(-1)
+    return slack.numpy()
 
 
 def test_celeba_affine_functions_match_reference():
@@ -56,7 +91,9 @@ def test_celeba_affine_functions_match_reference():
     np.testing.assert_allclose(A.numpy(), gold["A"], rtol=1e-6, atol=1e-7)
     img = co.synthetic_real(4, seed=int(gold["img_seed"]))
     warped = co.warp(img, A[:4, 0:2])
-    np.testing.assert_allclose(warped.numpy(), gold["warped"], rtol=1e-5, atol=1e-6)
+    err = np.abs(warped.numpy() - gold["warped"])
+    tol = 1e-6 + 1e-5 * np.abs(gold["warped"]) + grid_rounding_slack(img, A[:4, 0:2])
+    assert (err <= tol).all(), f"{(err > tol).sum()} of {err.size} elements off, worst {err.max():.3g}"
     rc = torch.tensor(gold["real_code"], requires_grad=True)
     tc = torch.tensor(gold["trans_code"], requires_grad=True)
     pred = co.affine_regularzier(rc, tc)
