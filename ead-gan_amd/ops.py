@@ -790,3 +790,32 @@ def quantize_u8(x, C, H, W, rng2, out):
 
 def col2im_img(dtype, cols, B, C, Hin, Win, k, stride, pad, bias, act, slope, out):
     lib().call("eg_col2im_img", dtype, _p(cols), B, C, Hin, Win, k, stride, pad, _p(bias), act, slope, _p(out), _stream())
+
+
+# ---- disentanglement scores (score.hip) ------------------------------------------------------------------------------------------
+def score_stage_u8(data, idx, gain, out, B, C, HW):
+    lib().call("eg_score_stage_u8", _p(data), _p(idx), _p(gain), _p(out), B, C, HW, _stream())
+
+
+def score_rows(cat, ldcat, ncat, cont, ldcont, pxy, ldpxy, B, out):
+    lib().call("eg_score_rows", _p(cat), ldcat, ncat, _p(cont), ldcont, _p(pxy), ldpxy, B, _p(out), _stream())
+
+
+def score_digitize(codes, n, ncode, nbins, bins, lohi=None):
+    lib().call("eg_score_digitize", _p(codes), n, ncode, nbins, _p(bins), _p(lohi), _stream())
+
+
+def score_mig_ws_ints(ncode, nf, kmax, nbins):
+    return lib().query("eg_score_mig_ws_ints", ncode, nf, kmax, nbins)
+
+
+def score_mig(bins, ncode, ys, nf, n, kmax, nbins, ws, mi):
+    lib().call("eg_score_mig", _p(bins), ncode, _p(ys), nf, n, kmax, nbins, _p(ws), _p(mi), _stream())
+
+
+def score_col_std(x, n, ncol, out):
+    lib().call("eg_score_col_std", _p(x), n, ncol, _p(out), _stream())
+
+
+def score_fvae_votes(x, L, M, ncol, eval_std, labels, nlab, predict, votes):
+    lib().call("eg_score_fvae_votes", _p(x), L, M, ncol, _p(eval_std), _p(labels), nlab, _p(predict), _p(votes), _stream())

@@ -1,0 +1,279 @@
+"""Disentanglement scores of a trained dSprites / colored-dSprites encoder pair on the MI355X: MIG and FactorVAE
+(dSprites/score/MIG.py, FactorVAE.py; colored_dSprites/score/MIG.py, FactorVAE.py).
+
+The reference pushes every sampled image through Encoder_pxy -> inverse translation -> grid_sample(padding_mode='zeros') [-> divide by
+the colour gains] -> Encoder (eval) on the CPU and scores the rows [argmax(cat), cont0, cont1, pxy1, pxy2] with numpy / sklearn.  Here the
+sampling plan is host numpy (the reference's draws, in its order), the dataset sits in HBM as uint8, the encoder passes run in fixed-size
+chunks on the existing engines, and the metric arithmetic runs in float64 kernels (csrc/score.hip).  Only the plan goes up and only the
+metric's scalars / small matrices come down.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import contextlib
+
+import numpy as np
+import torch
+
+from . import colored as cd
+from . import dsprites as ds
+from . import ops
+from .celeba import _require_cuda
+
+NUM_CODES = 5           # [argmax(cat), cont0, cont1, pxy1, pxy2] for both workloads
+KINDS = ("dsprites", "colored")
+
+
+# ================================================================================================
+# sampling plans (host numpy, bit for bit the reference's draws)
+# ================================================================================================
+def _rs(rng):
+    return np.random if rng is None else rng
+
+
+def mig_plan(N, colored=False, rng=None, num_points=1000, batch_size=16):
+    """generate_batch_factor_code's draws (MIG.py:206-212): per batch of 16 ``randint(N, size=16)`` then, colored, the batch's RGB gains
+    ``uniform(0.5, 1, [16,3,1,1])`` (add_color_2_img).  -> {"idx": int64 [num_points], "gains": float64 [num_points,3] or None}"""
+    r = _rs(rng)
+    idx, gains = [], []
+    i = 0
+    while i < num_points:
+        k = min(num_points - i, batch_size)
+        idx.append(r.randint(N, size=k))
+        if colored:
+            gains.append(r.uniform(0.5, 1, [k, 3, 1, 1]).reshape(k, 3))
+        i += k
+    return {"idx": np.concatenate(idx), "gains": np.concatenate(gains) if colored else None}
+
+
+def latents_bases(latents_sizes):
+    s = np.asarray(latents_sizes)
+    return np.concatenate((s[::-1].cumprod()[::-1][1:], np.array([1, ])))
+
+
+def factor_vae_plan(latents_sizes, N, colored=False, rng=None, L=100, M=500):
+    """load_data's plan (FactorVAE.py:36-97): group i fixes latent i % 5 + 1 (one randint per latent for L samples, then the fixed latent
+    redrawn once), then the eval set ``permutation(N)[:N/10]``; colored, evaluate() then draws the eval set's gains and each group's, in
+    group order.  -> {"group_idx" int64 [M,L], "labels" int64 [M], "eval_idx" int64 [N/10] (+ "eval_gains", "group_gains" float64)}"""
+    r = _rs(rng)
+    sizes = np.asarray(latents_sizes)
+    bases = latents_bases(sizes)
+    group_idx = np.empty((M, L), dtype=np.int64)
+    labels = np.empty(M, dtype=np.int64)
+    for i in range(M):
+        fixed = i % 5 + 1
+        samples = np.zeros((L, sizes.size))
+        for lat_i, lat_size in enumerate(sizes):
+            samples[:, lat_i] = r.randint(lat_size, size=L)
+        samples[:, fixed] = r.randint(sizes[fixed], size=1)
+        group_idx[i] = np.dot(samples, bases).astype(int)
+        labels[i] = fixed - 1
+    eval_idx = r.permutation(range(N))[0:int(N / 10)]
+    plan = {"group_idx": group_idx, "labels": labels, "eval_idx": eval_idx}
+    if colored:
+        plan["eval_gains"] = r.uniform(0.5, 1, [eval_idx.size, 3, 1, 1]).reshape(-1, 3)
+        plan["group_gains"] = np.stack([r.uniform(0.5, 1, [L, 3, 1, 1]).reshape(L, 3) for _ in range(M)])
+    return plan
+
+
+# ================================================================================================
+# representation: chunked encoder passes -> float64 rows
+# ================================================================================================
+@contextlib.contextmanager
+def _eval_mode(*mods):
+    modes = [m.training for m in mods]
+    try:
+        for m in mods:
+            m.eval()
+        yield
+    finally:
+        for m, t in zip(mods, modes):
+            m.train(t)
+
+
+class Representation:
+    """The reference's representation function (MIG.py:214-243, FactorVAE.py:246-266 / 283-303; colored variants with the gain division)
+    over a uint8 sprite table in HBM, ``batch`` images per chunk on engines built once for that batch."""
+
+    def __init__(self, encoder_pxy, encoder, kind, batch=4096):
+        if kind not in KINDS:
+            raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
+        self.P, self.E, self.kind, self.B = encoder_pxy, encoder, kind, int(batch)
+        self.C = 3 if kind == "colored" else 1
+        if encoder.channels != self.C or encoder_pxy.channels != self.C:
+            raise ValueError(f"{kind} scores need {self.C}-channel encoders")
+        p = next(encoder.parameters())
+        _require_cuda(p)
+        dev = p.device
+        self.nout = encoder_pxy.fc1.weight.shape[0]
+        self.ncat, self.cdim = encoder.n_classes, encoder.code_dim
+        B, C = self.B, self.C
+        self.img = torch.zeros(B, C, 64, 64, device=dev)
+        self.warped = torch.zeros(B, C, 64, 64, device=dev)
+        self.align = torch.zeros(B, C, 64, 64, device=dev) if self.C == 3 else self.warped
+        self.theta = torch.zeros(B, 2, 3, device=dev)
+        self.device = dev
+
+    def _chunk(self, data, idx, gains, nb, out):
+        B, C = self.B, self.C
+        ops.score_stage_u8(data, idx, gains, self.img, nb, C, 64 * 64)
+        pcode = self.pe.forward(self.img)                                           # [B, 3|6] = p,x,y(,r,g,b)
+        ops.theta_pxy_align_inv(pcode, self.nout, B, self.theta)                    # inverse(get_matrix_pxy_align(code))[:, 0:2]
+        ops.warp_affine_zeros(self.img, self.theta, self.warped, B, C, 64, 64)      # trans_2D, padding_mode='zeros' (score/MIG.py:136)
+        if C == 3:
+            ops.color_scale(self.warped, pcode, self.nout, 3, 0.1, True, self.align, B, 3, 64 * 64)    # / (align_code[:,3:] * .1 + 1)
+        outs = self.ee.forward([self.align], 0, training=False, patches=False)
+        ops.score_rows(outs["cat_layer.0"], self.ncat, self.ncat, outs["cont_layer.0"], self.cdim, pcode, self.nout, nb, out)
+
+    def codes(self, dataset_u8, idx, gains=None, out=None):
+        """dataset_u8: device uint8 [N,64,64] (or [N,1,64,64]) {0,1} sprites; idx: [n] indices; gains: [n,3] RGB gains (colored).
+        -> device float64 [n,5] rows (``out`` when given)."""
+        _require_cuda(dataset_u8)
+        if dataset_u8.dtype != torch.uint8 or dataset_u8[0].numel() != 64 * 64:
+            raise ValueError("dataset_u8 must be uint8 [N,64,64]")
+        data = dataset_u8.contiguous()
+        N = data.shape[0]
+        idx_h = np.asarray(idx.cpu() if torch.is_tensor(idx) else idx).reshape(-1)
+        n = idx_h.size
+        if n and (idx_h.min() < 0 or idx_h.max() >= N):
+            raise IndexError(f"sample index out of range [0, {N})")
+        if (gains is None) != (self.C == 1):
+            raise ValueError("colored scores need per-sample gains; dSprites scores take none")
+        dev = self.device
+        idx_d = torch.from_numpy(idx_h.astype(np.int32)).to(dev)
+        g_d = None
+        if gains is not None:
+            g_h = np.asarray(gains.cpu() if torch.is_tensor(gains) else gains).reshape(n, 3)
+            g_d = torch.from_numpy(g_h.astype(np.float32)).to(dev)               # float32(gain): the reference's img.float()
+        if out is None:
+            out = torch.empty(n, NUM_CODES, device=dev, dtype=torch.float64)
+        with _eval_mode(self.P, self.E):
+            self.pe = self.P.fresh_engine(self.B)
+            self.ee = self.E.fresh_engine(self.B)
+            for off in range(0, n, self.B):
+                nb = min(self.B, n - off)
+                self._chunk(data, idx_d[off:], None if g_d is None else g_d[off:], nb, out[off:])
+        return out
+
+
+# ================================================================================================
+# metrics
+# ================================================================================================
+def discretize(codes, num_bins=20):
+    """make_discretizer(codes.T, num_bins) (MIG.py:270-275) -> device int32 [5, n] bins in 1..num_bins."""
+    _require_cuda(codes)
+    codes = codes.to(torch.float64).contiguous()
+    n, k = codes.shape
+    bins = torch.empty(k, n, device=codes.device, dtype=torch.int32)
+    ops.score_digitize(codes, n, k, num_bins, bins)
+    return bins
+
+
+def mig(codes, factor_values, num_bins=20):
+    """MIG of device codes [n,5] against host factor values [n,nf] (MIG.py:304-311).  Factor values become class ids with
+    ``np.unique(return_inverse=True)``, the partition mutual_info_score builds.  -> (score, m [5,nf], H [nf])"""
+    bins = discretize(codes, num_bins)
+    k, n = bins.shape
+    fv = np.asarray(factor_values)
+    if fv.shape[0] != n:
+        raise ValueError(f"{fv.shape[0]} factor rows for {n} codes")
+    ys, kmax = [], 1
+    for j in range(fv.shape[1]):
+        u, inv = np.unique(fv[:, j], return_inverse=True)
+        ys.append(inv.reshape(-1).astype(np.int32))
+        kmax = max(kmax, u.size)
+    nf = len(ys)
+    dev = codes.device
+    ys_d = torch.from_numpy(np.stack(ys)).to(dev)
+    ws = torch.empty(ops.score_mig_ws_ints(k, nf, kmax, num_bins), device=dev, dtype=torch.int32)
+    mi = torch.empty(k * nf + nf, device=dev, dtype=torch.float64)
+    ops.score_mig(bins, k, ys_d, nf, n, kmax, num_bins, ws, mi)
+    mi = mi.cpu().numpy()
+    m, H = mi[:k * nf].reshape(k, nf), mi[k * nf:]
+    sorted_m = np.sort(m, axis=0)[::-1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        score = np.mean(np.divide(sorted_m[0, :] - sorted_m[1, :], H[:]))
+    return float(score), m, H
+
+
+def factor_vae_votes(eval_codes, group_codes, labels, num_labels):
+    """Device part of FactorVAEMetric.evaluate (FactorVAE.py:269-312): eval_std = np.std(eval rows, axis=0), per group the argmin of
+    np.std(group rows / eval_std, axis=0), votes[argmin, label] += 1.  group_codes [M*L,5] or [M,L,5].
+    -> (eval_std float64 [5], predict int32 [M], votes int64 [5, num_labels]) on the device"""
+    _require_cuda(eval_codes)
+    ev = eval_codes.to(torch.float64).contiguous()
+    labels = np.asarray(labels).reshape(-1)
+    M = labels.size
+    gc = group_codes.to(torch.float64).contiguous().reshape(M, -1, NUM_CODES)
+    L = gc.shape[1]
+    if labels.min() < 0 or labels.max() >= num_labels:
+        raise ValueError("group labels must lie in [0, num_labels)")
+    dev = ev.device
+    eval_std = torch.empty(NUM_CODES, device=dev, dtype=torch.float64)
+    ops.score_col_std(ev, ev.shape[0], NUM_CODES, eval_std)
+    predict = torch.empty(M, device=dev, dtype=torch.int32)
+    votes = torch.empty(NUM_CODES, num_labels, device=dev, dtype=torch.int64)
+    ops.score_fvae_votes(gc, L, M, NUM_CODES, eval_std, torch.from_numpy(labels.astype(np.int32)).to(dev), num_labels, predict, votes)
+    return eval_std, predict, votes
+
+
+def factor_vae(eval_codes, group_codes, labels, num_labels):
+    """-> the reference's dict: factorVAE_metric, factorVAE_metric_revised, factorVAE_metric_detail (FactorVAE.py:314-330)."""
+    _, _, votes = factor_vae_votes(eval_codes, group_codes, labels, num_labels)
+    train_data = votes.cpu().numpy().astype(np.float64)
+    total_sample = np.sum(train_data)
+    maxs = np.amax(train_data, axis=1)
+    correct_sample = np.sum(maxs)
+    correct_sample_revised = np.sum(np.flip(np.sort(maxs), axis=0)[0:train_data.shape[1]])
+    return {"factorVAE_metric": float(correct_sample) / total_sample,
+            "factorVAE_metric_revised": float(correct_sample_revised) / total_sample,
+            "factorVAE_metric_detail": train_data}
+
+
+# ================================================================================================
+# drop-in for the scripts' module-level code
+# ================================================================================================
+def load_encoders(kind, encoder_pxy_path, encoder_path, device="cuda", dtype="f32"):
+    """load_encoder() (MIG.py:146-158): the reference's checkpoints (its key layout) into this package's modules."""
+    mod = cd if kind == "colored" else ds
+    P, E = mod.Encoder_pxy(dtype=dtype), mod.Encoder(dtype=dtype)
+    P.load_state_dict(torch.load(encoder_pxy_path, map_location="cpu", weights_only=True))
+    E.load_state_dict(torch.load(encoder_path, map_location="cpu", weights_only=True))
+    return P.to(device).eval(), E.to(device).eval()
+
+
+def run_score(kind, metric, npz_path, encoder_pxy_path, encoder_path, seed=None, batch=4096, groups=None, device="cuda"):
+    """What dSprites|colored_dSprites/score/{MIG,FactorVAE}.py do at module level, on the MI355X.  ``seed``: np.random.seed first (else the
+    global numpy stream as it stands).  ``groups``: score only the first groups of the 500-group FactorVAE plan (the plan is drawn in full).
+    Prints the score; returns it (MIG) or the reference's three-key dict (FactorVAE)."""
+    if kind not in KINDS:
+        raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
+    if metric not in ("mig", "factor_vae"):
+        raise ValueError(f"metric must be 'mig' or 'factor_vae', got {metric!r}")
+    colored = kind == "colored"
+    dataset_zip = np.load(npz_path, encoding="latin1", allow_pickle=True)
+    imgs = dataset_zip["imgs"]
+    latents_values = dataset_zip["latents_values"]
+    P, E = load_encoders(kind, encoder_pxy_path, encoder_path, device)
+    if seed is not None:
+        np.random.seed(seed)
+    rep = Representation(P, E, kind, batch)
+    N = imgs.shape[0]
+    if metric == "mig":
+        plan = mig_plan(N, colored)
+        data = torch.from_numpy(np.ascontiguousarray(imgs)).to(device)
+        codes = rep.codes(data, plan["idx"], plan["gains"])
+        score, _, _ = mig(codes, latents_values[:, 1:6][plan["idx"]])
+        print("MIG score", score)
+        return score
+    metadata = dataset_zip["metadata"][()]
+    plan = factor_vae_plan(metadata["latents_sizes"], N, colored)
+    M = plan["labels"].size if groups is None else int(groups)
+    data = torch.from_numpy(np.ascontiguousarray(imgs)).to(device)
+    ev = rep.codes(data, plan["eval_idx"], plan.get("eval_gains"))
+    gi = plan["group_idx"][:M].reshape(-1)
+    gg = plan["group_gains"][:M].reshape(-1, 3) if colored else None
+    gc = rep.codes(data, gi, gg)
+    labels = plan["labels"][:M]
+    res = factor_vae(ev, gc, labels, len(set(labels.tolist())))
+    print("score", res["factorVAE_metric"])
+    return res

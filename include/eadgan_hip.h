@@ -562,6 +562,28 @@ int eg_onehot(const long long* labels, float* out, int B, int n, eg_stream_t s);
 int eg_resample_u8(const unsigned char* src, unsigned char* dst, int planes, int in_h, int in_w, int axis, const int* bounds,
                    const int* kk, int ksize, int o0, int on, int c0, int cn, eg_stream_t s);
 
+/* Disentanglement scores of a trained encoder pair (dSprites/score/MIG.py, FactorVAE.py; colored_dSprites/score/MIG.py, FactorVAE.py).
+ * Staging: out[b][c] = data[idx[b]] * gain[b][c] (uint8 [N][HW] sprites, gain [B][C] fp32 or NULL = 1) -> fp32 NCHW; the reference's
+ * imgs[select_index] + add_color_2_img (colored MIG.py:169-184,204; FactorVAE.py:236-254,270,315). */
+int eg_score_stage_u8(const unsigned char* data, const int* idx, const float* gain, float* out, int B, int C, int HW, eg_stream_t s);
+/* out[b] = [argmax softmax(cat[b]) (first index on ties), cont[b][0], cont[b][1], pxy[b][1], pxy[b][2]] as float64 [B][5]: the
+ * np.concatenate((cat, cont[:,0:2], align_code[:,1:3]), axis=1) row of MIG.py:233-243 / FactorVAE.py:263-266,300-303 */
+int eg_score_rows(const float* cat, int ldcat, int ncat, const float* cont, int ldcont, const float* pxy, int ldpxy, int B, double* out,
+                  eg_stream_t s);
+/* make_discretizer(codes.T, nbins) (MIG.py:270-275): per column of codes [n][ncode] float64 np.digitize(x, np.histogram(x, nbins)[1][:-1])
+ * with numpy's edge arithmetic -> bins [ncode][n] int32 in 1..nbins; lohi [ncode][2] (optional) receives the (widened) range */
+int eg_score_digitize(const double* codes, int n, int ncode, int nbins, int* bins, double* lohi, eg_stream_t s);
+/* discrete_mutual_info + discrete_entropy (MIG.py:278-294) with sklearn.metrics.mutual_info_score: mi[i*nf + j] = MI(ys[j], bins[i]),
+ * mi[ncode*nf + j] = MI(ys[j], ys[j]).  ys [nf][n] int32 class ids in 0..kmax-1; bins [ncode][n] in 1..nbins.  ws: eg_score_mig_ws_ints ints */
+size_t eg_score_mig_ws_ints(int ncode, int nf, int kmax, int nbins);
+int eg_score_mig(const int* bins, int ncode, const int* ys, int nf, int n, int kmax, int nbins, int* ws, double* mi, eg_stream_t s);
+/* np.std(x, axis=0) of x [n][ncol] float64, bit for bit (numpy's row-sequential axis-0 reduction) (FactorVAE.py:269) */
+int eg_score_col_std(const double* x, int n, int ncol, double* out, eg_stream_t s);
+/* FactorVAEMetric.evaluate's vote loop (FactorVAE.py:273-312): for group g (rows g*L.. of x [M*L][ncol]) predict[g] = argmin of
+ * np.std(x_g / eval_std, axis=0) (numpy's rule: first NaN, else first minimum); votes [ncol][nlab] int64 (zeroed here) [predict][labels[g]] += 1 */
+int eg_score_fvae_votes(const double* x, int L, int M, int ncol, const double* eval_std, const int* labels, int nlab, int* predict,
+                        long long* votes, eg_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
