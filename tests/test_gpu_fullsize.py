@@ -25,6 +25,7 @@ import test_gpu_celeba as tce
 import test_gpu_colored as tco
 import test_gpu_dsprites as tds
 import test_gpu_mnist as tmn
+from layer_refs import _conv_ref, _convT_ref, _rel
 
 pytestmark = pytest.mark.gpu
 eg = None
@@ -149,29 +150,6 @@ def test_colored_b512_fp16():
     assert eg_ < 0.25 and ee < 0.1, (eg_, ee)
     _small_net_dispatch(eg.ops.EG_F16, B, 3)
     _small_net_engines_direct(tr)
-
-
-def _rel(a, b):
-    return float((a.float() - b.float()).norm() / (b.float().norm() + 1e-30))
-
-
-def _conv_ref(x, w, stride=2, pad=1):
-    """Conv2d(x, w) in fp32 as unfold + matmul (no MIOpen: nothing to tune or look up); x [B,Ci,H,W], w [Co,Ci,k,k]"""
-    import torch.nn.functional as F
-    B, Ci, H, W = x.shape
-    Co, _, k, _ = w.shape
-    cols = F.unfold(x, k, padding=pad, stride=stride)                       # [B, Ci*k*k, L]
-    OH = (H + 2 * pad - k) // stride + 1
-    return (w.reshape(Co, -1) @ cols).reshape(B, Co, OH, OH), cols
-
-
-def _convT_ref(g, w, out_hw, stride=2, pad=1):
-    """ConvTranspose2d(g, w) = fold(w^T g); g [B,Co,OH,OW], w [Co,Ci,k,k] (conv view) -> [B,Ci,H,W]"""
-    import torch.nn.functional as F
-    B, Co, OH, OW = g.shape
-    k = w.shape[-1]
-    cols = w.reshape(Co, -1).t() @ g.reshape(B, Co, OH * OW)                # [B, Ci*k*k, L]
-    return F.fold(cols, out_hw, k, padding=pad, stride=stride)
 
 
 def test_celeba_b128_bf16_layerwise_kernels():

@@ -8,6 +8,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from layer_refs import _conv_ref, _convT_ref
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 eg = None
@@ -55,7 +57,7 @@ def test_first_discriminator_layer_without_patch_rows(T, B, C, dtype):
     # and against torch on the rounded operands
     rq = lambda x: x.to(tdt).float()
     for t in range(T):
-        ref = F.leaky_relu(F.conv2d(rq(imgs[t]), rq(w), None, 2, 1) / sigma[t] + bias[None, :, None, None], 0.1).permute(0, 2, 3, 1)
+        ref = F.leaky_relu(_conv_ref(rq(imgs[t]), rq(w))[0] / sigma[t] + bias[None, :, None, None], 0.1).permute(0, 2, 3, 1)
         torch.testing.assert_close(got[t * B:(t + 1) * B].float(), ref, rtol=2e-2, atol=2e-2)
 
 
@@ -87,7 +89,7 @@ def test_first_trunk_layer_of_the_dsprites_networks_without_patch_rows(T, B, C, 
     assert torch.equal(got, want)
     rq = lambda x: x.to(tdt).float()
     for t in range(T):
-        ref = F.leaky_relu(F.conv2d(rq(imgs[t]), rq(w), None, 2, 1) / sigma[t] + bias[None, :, None, None], 0.2).permute(0, 2, 3, 1)
+        ref = F.leaky_relu(_conv_ref(rq(imgs[t]), rq(w))[0] / sigma[t] + bias[None, :, None, None], 0.2).permute(0, 2, 3, 1)
         torch.testing.assert_close(got[t * B:(t + 1) * B].float(), ref, rtol=2e-2, atol=2e-2)
 
 
@@ -191,7 +193,8 @@ def test_transposed_image_convolution_in_one_launch(B, C, act, dtype, K):
     ops.convt_img_mfma(dtype, a, wp, bias, got, B, C, Hin, Hin, act, 0.0, K=K)
     torch.cuda.synchronize()
     assert torch.equal(got, want)
-    ref = F.conv_transpose2d(a.float().permute(0, 3, 1, 2), w.to(tdt).float(), bias, 2, 1)
+    ref = _convT_ref(a.float().permute(0, 3, 1, 2), w.to(tdt).float(), (2 * Hin, 2 * Hin))
+    ref = ref if bias is None else ref + bias[None, :, None, None]
     ref = torch.tanh(ref) if act == 3 else (torch.sigmoid(ref) if act == 4 else ref)
     torch.testing.assert_close(got, ref, rtol=2e-2, atol=2e-2)
 

@@ -1057,3 +1057,87 @@ def test_few_row_deep_k_launch_splits_k_inside_the_register_staged_kernel(case, 
     rt, at = tol(dtype, Cin * 4)
     torch.testing.assert_close(nchw(zs["split"]), want_b, rtol=rt, atol=at)
     torch.testing.assert_close(zs["split"].float(), zs["plain"].float(), rtol=rt, atol=at)
+
+
+# (nsplit, n_rows, C, T): every summation path of wgrad_reduce_kernel (csrc/igemm.hip).  nsplit < 16 runs the LEAN instantiation (256 threads),
+# nsplit >= 16 the full one, with 1024 threads where T * 16 float4 > 128 and at most 2048 blocks.  Paths: float4 blocks (C % 64 == 0 chunks),
+# float4 split groups (nsplit >= 16 and 2 T * 16 <= threads), ragged split groups (a chunk narrower than 64, nsplit >= 16, T <= 2), the one-chain
+# scalar loop (ragged chunks otherwise: C = 32 / T = 16 is the small networks' 32-channel layers); C = 100 has a float4 chunk and a ragged one
+REDUCE_CASES = [
+    (1, 5, 64, 16), (3, 7, 128, 9), (7, 3, 48, 16), (8, 6, 100, 1), (9, 4, 32, 16), (15, 9, 16, 1), (15, 3, 64, 1),     # lean
+    (16, 32, 32, 16), (17, 12, 64, 16), (128, 32, 48, 1), (128, 64, 16, 1), (17, 5, 128, 9), (16, 3, 100, 9), (128, 6, 100, 1),
+    (128, 4, 64, 1), (17, 6, 48, 9), (128, 64, 32, 16), (16, 2049, 64, 16),  # 2049 blocks: the 256-thread float4 loop of the full instantiation
+]
+
+
+@pytest.mark.parametrize("case", REDUCE_CASES)
+def test_wgrad_reduce_paths_against_fp64(case):
+    """eg_wgrad_reduce / _rank1 / _perm: grad[n][c][t] (+)= sum_split slab[split][n][t][c] (- sum_tape coef u v^T; rows permuted; destination rows
+    c_row < C channels wide) against the same sums in fp64.  Bound: fp32 summation of nsplit + ntapes + 1 terms, |err| <= (n u) sum |terms| with
+    u = 2^-24, i.e. 1e-5 of the absolute sum at nsplit = 128.  Deterministic (a second call gives the same bits), and the three entry points agree bit
+    for bit where they describe the same reduction (the lean and the full instantiation, the rank-1 subtraction in the load or the store phase)."""
+    nsplit, n_rows, C, T = case
+    g = torch.Generator().manual_seed(nsplit * 1000 + C * 10 + T)
+    n_slab = n_rows + 3                                                     # slab rows past n_rows are never read
+    slab = torch.randn(nsplit, n_slab, T, C, generator=g)
+    slab[:, n_rows:] = float("nan")
+    slab_d = slab.to(DEV).contiguous()
+    S = slab[:, :n_rows].double().sum(0).permute(0, 2, 1)                  # [n][c][t]
+    A = slab[:, :n_rows].double().abs().sum(0).permute(0, 2, 1)
+    out0 = torch.randn(n_rows, C, T, generator=g)
+
+    def run(fn, init):
+        outs = []
+        for _ in range(2):
+            o = init.to(DEV).contiguous()
+            fn(o)
+            outs.append(o)
+        torch.cuda.synchronize()
+        assert torch.equal(outs[0], outs[1]), "not deterministic"
+        return outs[0].cpu()
+
+    def check(got, ref, absum):
+        err = (got.double() - ref).abs()
+        assert float((err - 1e-5 * absum).max()) <= 0, float((err / (absum + 1e-30)).max())
+
+    # plain: accumulate and overwrite
+    acc = run(lambda o: ops.wgrad_reduce(slab_d, nsplit, n_slab, n_rows, C, T, o, accumulate=True), out0)
+    check(acc, out0.double() + S, A + out0.double().abs())
+    ovw = run(lambda o: ops.wgrad_reduce(slab_d, nsplit, n_slab, n_rows, C, T, o, accumulate=False), torch.full_like(out0, float("nan")))
+    check(ovw, S, A)
+    # the other entry points without their extras: the same bits
+    assert torch.equal(run(lambda o: ops.wgrad_reduce_rank1(slab_d, nsplit, n_slab, n_rows, C, T, o, 0, None, None, None), out0), acc)
+    assert torch.equal(run(lambda o: ops.wgrad_reduce_perm(slab_d, nsplit, n_slab, n_rows, C, T, o), out0), acc)
+    # rank-1 spectral-norm terms, 1..4 tapes, full rows and rows narrower than the slab (c_row < C: zero-padded gathered columns)
+    for c_row in sorted({C, max(C - 5, 1)}, reverse=True):
+        base = out0[:, :c_row].contiguous()
+        Sc, Ac = S[:, :c_row], A[:, :c_row] + base.double().abs()
+        prev = None
+        for nt in range(5):
+            coef, u, v = torch.randn(4, generator=g), torch.randn(4, n_rows, generator=g), torch.randn(4, c_row * T, generator=g)
+            r1 = (coef[:nt, None, None].double() * u[:nt, :, None].double() * v[:nt, None, :].double()).sum(0).reshape(n_rows, c_row, T)
+            a1 = (coef[:nt, None, None].double() * u[:nt, :, None].double() * v[:nt, None, :].double()).abs().sum(0).reshape(n_rows, c_row, T)
+            got = run(lambda o: ops.wgrad_reduce_rank1(slab_d, nsplit, n_slab, n_rows, C, T, o, nt, coef.to(DEV), u.to(DEV).contiguous(),
+                                                       v.to(DEV).contiguous(), c_row if c_row < C else 0), base)
+            check(got, base.double() + Sc - r1, Ac + a1)
+            if nt == 0:
+                prev = got
+        perm0 = run(lambda o: ops.wgrad_reduce_perm(slab_d, nsplit, n_slab, n_rows, C, T, o, 0, 0, c_row if c_row < C else 0), base)
+        assert torch.equal(perm0, prev)
+    # row permutation n -> (n % row_div) * row_mul + n / row_div (n_rows = row_div * row_mul: a bijection), with and without narrow rows
+    for row_div in [d for d in (2, 3, 4, 16, 64) if n_rows % d == 0 and d < n_rows][:2]:
+        row_mul = n_rows // row_div
+        n = torch.arange(n_rows)
+        dst = (n % row_div) * row_mul + n // row_div
+        for c_row in sorted({C, max(C - 5, 1)}):
+            base = out0[:, :c_row].contiguous()
+            got = run(lambda o: ops.wgrad_reduce_perm(slab_d, nsplit, n_slab, n_rows, C, T, o, row_div, row_mul, c_row if c_row < C else 0), base)
+            ref, absum = base.double().clone(), base.double().abs()
+            ref[dst] += S[:, :c_row]
+            absum[dst] += A[:, :c_row]
+            check(got, ref, absum)
+            plain = run(lambda o: ops.wgrad_reduce_perm(slab_d, nsplit, n_slab, n_rows, C, T, o, 0, 0, c_row if c_row < C else 0),
+                        torch.zeros_like(base))
+            want = base.clone()
+            want[dst] = base[dst] + plain
+            assert torch.equal(got, want), "the row permutation changed the sums"
