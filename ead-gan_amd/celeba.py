@@ -19,7 +19,7 @@ import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
 from . import ops
-from .engine import Arena, ConvRec, SideStream, Workspace, capture_segments, capture_step, check_usable, parse_dtype
+from .engine import Arena, ConvRec, SideStream, Workspace, capture_step, check_usable, parse_dtype
 from .ops import (ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH, EG_BF16, EG_F32, OUT_NCHW_F32)
 
 # module-level hyper-parameters, mirroring the reference's global ``opt`` (argparse defaults, :39-51)
@@ -40,23 +40,21 @@ IMG_DIRECT = os.environ.get("EG_IMG_DIRECT", "1") != "0"
 # convolution that produces the tensor (eg_epilogue.stat_mode) instead of by kernels that re-read it; 0: the stand-alone kernels (A/B runs)
 FUSE_STATS = os.environ.get("EG_FUSE_STATS", "1") != "0"
 
-# optimizer.step() of a convolution weight and the refresh of its packed panels as ONE launch per layer (ops.adam_pack_conv / adam_pack_rows);
-# 0: one Adam launch over the arena (or bucket) followed by the re-packing launches (A/B runs; same bits either way)
 # the discriminator's head with the sub-step's losses and the head's input gradient in two launches (K-sliced dense head; eg_head_fused: slice
 # combine + losses + dense backward, the affine term's Jacobian spread over lanes) instead of four or five on the main chain; same bits;
 # EG_FUSE_HEAD=0: the separate launches
 FUSE_HEAD = os.environ.get("EG_FUSE_HEAD", "1") != "0"
+# optimizer.step() of a convolution weight and the refresh of its packed panels as ONE launch per layer (ops.adam_pack_conv / adam_pack_rows);
+# 0: one Adam launch over the arena (or bucket) followed by the re-packing launches (A/B runs; same bits either way)
 FUSE_ADAM = os.environ.get("EG_FUSE_ADAM", "1") != "0"
-# ... per optimizer update of the pipelined step (g1, d2, d3, g3 as in EG_BUCKET_OPT; "all")
-FUSE_ADAM_AT = os.environ.get("EG_FUSE_ADAM_AT", "g3")
 
 
-def adam_bucket(eng, arena, tag, lo, hi, m, v, lr, betas, step, zero, fuse=True):
+def adam_bucket(eng, arena, tag, lo, hi, m, v, lr, betas, step, zero):
     """optimizer.step() (+ zero_grad) on one gradient bucket [lo, hi) of ``arena`` and the refresh of the packed panels of its layers.  The
     bucket's big convolution weight (``eng.fused_weight(tag)``) is updated AND re-packed by one launch; the remaining parameters of the
     bucket (biases, BatchNorm affine) by plain Adam launches on their slices.  The step counter has been ticked by the caller."""
     b1, b2 = betas
-    fw = eng.fused_weight(tag) if (FUSE_ADAM and fuse) else None
+    fw = eng.fused_weight(tag) if FUSE_ADAM else None
     if fw is None:
         ops.adam_step_zero(arena.flat[lo:hi], arena.grad[lo:hi], m[lo:hi], v[lo:hi], hi - lo, lr, b1, b2, 1e-8, step, False, zero)
         eng.repack_bucket(tag)
@@ -191,14 +189,15 @@ class _GenEngine:
             # wp[t*C + c][ci] = W[ci][c][t]   (master [128][C][4][4])
             ops.pack_strided(dt, self._p(10, "weight"), self.l4g.wp_fwd, self.kp, G_WIDTHS[3], self.l4g.Kpad_fwd, g.channels, 1, 16, self.kp)
 
-    def forward(self, noise, labels, code, training=True, sync=None, ws=None):
+    def forward(self, noise, labels, code, training=True, sync=None):
         """``training=False``: BatchNorm with the running statistics, nothing updated (module.eval()).  ``sync`` (a dp.SyncBN):
-        batch statistics over all ranks (synchronised BatchNorm).  ``ws``: scratch to use instead of the engine's (a forward that runs
-        on its own stream beside other main-stream work; the caller also activates that workspace's split-K scratch)."""
+        batch statistics over all ranks (synchronised BatchNorm)."""
         dt, B, W = self.dtype, self.B, G_WIDTHS
-        small = (ws or self.ws).small
+        small = self.ws.small
         ops.concat_cast(dt, noise, labels, code, self.inp, B, self.cpad)
-        ops.conv_fwd(self.l0.c, dt, self.inp, self.l0.wp_fwd, self.h0, ops.epilogue(bias=self._p(0, "bias"), bias_mod=W[0], nt_variant=G0_VARIANT))
+        # ONE 128-row tile x 128 column tiles, 4 K steps (1 GFLOP): the register-staged kernel (NT_REG) runs it in ~10 us where the planner's
+        # persistent pipeline takes 22-24; same bits; step -0.6 % (profiles/r03_zh_ab_g0_variant.txt)
+        ops.conv_fwd(self.l0.c, dt, self.inp, self.l0.wp_fwd, self.h0, ops.epilogue(bias=self._p(0, "bias"), bias_mod=W[0], nt_variant=ops.NT_REG))
         x = self.h0
         for i, idx in enumerate((1, 4, 7)):
             r = self.mid[i]
@@ -242,12 +241,11 @@ class _GenEngine:
         dt, B, W, ws, gen = self.dtype, self.B, G_WIDTHS, self.ws, self.gen
         gof = lambda name: gen.arena.grad_of(name, grad)
         C, S = gen.channels, self.img.shape[-1]
-        def wgrad_side(fn, lane, tag=None):             # issued by the flush() that follows the next main-stream kernel (engine.SideStream)
+        def wgrad_side(fn, lane, tag=None):
             if side is None:
                 fn(ws)
             else:
                 side.defer(lane, fn, tag)
-        flush = side.flush if side is not None else (lambda: None)
 
         direct = IMG_DIRECT and ops.conv_img_mfma_ok(dt, C, S, S, W[3], 4, 2, 1)
         if not direct:
@@ -279,7 +277,6 @@ class _GenEngine:
             ops.conv_img_mfma(dt, [dimg], self.l4p.wp_fwd, self.da[2], B, C, S, S, ep4, gates=[self.img], gate_act=ACT_TANH)
         else:
             ops.conv_fwd(self.l4p.c, dt, self.patches, self.l4p.wp_fwd, self.da[2], None)
-        flush()
         # L3..L1
         for i, idx in ((2, 7), (1, 4), (0, 1)):
             r = self.mid[i]
@@ -315,14 +312,13 @@ class _GenEngine:
                                           stat_p=(self.mean[i - 1], self.invstd[i - 1], bnl.weight, bnl.bias), stat_act=ACT_RELU))
             else:
                 ops.conv_fwd(r.c, dt, self.dz[i], r.wp_fwd, self.da[i - 1] if i > 0 else self.dh0, None)
-            flush()
 
         # L0
         def l0_wgrad(wsw):
             ns = ops.conv_wgrad(self.l0w.c, dt, self.dh0, self.inp, wsw.slab, wsw.wgs_target)
             ops.wgrad_reduce(wsw.slab, ns, self.cpad, self.cin, W[0], 16, gof("conv_blocks.0.weight"))
             ops.bias_grad(dt, self.dh0, B * 16, W[0], wsw.small, gof("conv_blocks.0.bias"))
-        wgrad_side(l0_wgrad, 0, "G0")                   # stays pending: the caller's next main-stream kernel goes first
+        wgrad_side(l0_wgrad, 0, "G0")
 
 
 class _HipModule(nn.Module):
@@ -490,10 +486,6 @@ class _DiscEngine:
         self.imgs = [None] * NT
         self.patch_ok = [False] * NT                    # tape has its patch rows (the weight gradient of layer 0 reads them)
         self.img_direct = IMG_DIRECT and ops.conv_img_mfma_ok(dtype, C, S, S, W[0], 4, 2, 1)
-        # ... and the first layer's weight gradient from the images too (ops.wgrad_img): no patch rows in HBM at all for that layer
-        self.wgrad_direct = self.img_direct and WGRAD_IMG and self.kp == 16 * C and ops.wgrad_img_ok(dtype, C, S, S, W[0], 4, 2, 1)
-        if self.wgrad_direct:
-            self.ws.need_slab(ops.wgrad_img_splits(NT * B, W[0]) * W[0] * self.kp * 4)
         self._stat = {}                                 # (layer, T) -> (row blocks, buffer) of the fused bias-gradient / coefficient sums
         self._sn_arrays = None
         self._sn(0)
@@ -640,12 +632,11 @@ class _DiscEngine:
         g = self.geo[T]
         sl = lambda buf: buf[t0 * (buf.shape[0] // self.NT):]
         K = 16 * W[3]
-        def wgrad_side(fn, lane, tag=None):             # issued by the flush() that follows the next main-stream kernel (engine.SideStream)
+        def wgrad_side(fn, lane, tag=None):
             if side is None:
                 fn(ws)
             else:
                 side.defer(lane, fn, tag)
-        flush = side.flush if side is not None else (lambda: None)
 
         if need_wgrad:
             def head_wgrad(wsw):
@@ -658,7 +649,6 @@ class _DiscEngine:
         if not head_done:
             ops.dense_small_bwd(dt, dout, self.head.wp_fwd, sl(self.a[3]), sl(self.dz[3]), T * B, K, self.head.Kpad_fwd, self.nout, ACT_LRELU, LRELU_SLOPE,
                                 self.sigma[3][t0:], B)
-        flush()
         fused = (0, None)                               # (row blocks, sums) if dzs_i came with its column sums
         for i in (3, 2, 1, 0):
             m = self._m(i)
@@ -666,28 +656,19 @@ class _DiscEngine:
             x_in = sl(self.a[i - 1]) if i > 0 else sl(self.patches)
             if need_wgrad:
                 def layer_wgrad(wsw, i=i, m=m, geo=geo, x_in=x_in, fused=fused):
-                    direct = i == 0 and self.wgrad_direct       # straight from the tapes' images: patch rows expanded in LDS (eg_wgrad_img)
-                    if i == 0 and not direct:
+                    if i == 0:
                         for t in range(t0, t0 + T):     # patch rows of tapes whose forward ran straight from the image
                             if not self.patch_ok[t]:
                                 self._im2col_tape(t, self.imgs[t])
-
-                    def gemm():
-                        if direct:
-                            return ops.wgrad_img(dt, [self.imgs[t] for t in range(t0, t0 + T)], sl(self.dz[0]), wsw.slab, B, self.C, self.S, self.S, W[0])
-                        return ops.conv_wgrad(geo, dt, x_in, sl(self.dz[i]), wsw.slab, wsw.wgs_target)
                     # the weight-gradient GEMM first: the column sums below (only the slab reduce needs their coefficient) do not fit on a CU
                     # beside a resident GEMM workgroup and used to hold the chain's GEMM back by ~50 us
-                    if WGRAD_FIRST:
-                        ns = gemm()
+                    ns = ops.conv_wgrad(geo, dt, x_in, sl(self.dz[i]), wsw.slab, wsw.wgs_target)
                     if fused[0]:
                         tiles_m = fused[0] // 4         # row blocks (of 256 or 128 lattice rows: the kernel's tile height) per sub-pixel phase
                         ops.bias_grad_sn_fused(fused[1], fused[0], W[i], tiles_m, tiles_m // T, T, self.sigma[i][t0:], gof(f"main.{2 * i}.bias"), self.coef[i])
                     else:
                         ops.bias_grad_sn(dt, sl(self.dz[i]), sl(self.a[i]), m.bias, T * self.rows(i), W[i], self.rows(i), self.sigma[i][t0:], LRELU_SLOPE,
                                          wsw.small, gof(f"main.{2 * i}.bias"), self.coef[i])
-                    if not WGRAD_FIRST:
-                        ns = gemm()
                     taps = 16 if i > 0 else 1
                     ops.wgrad_reduce_rank1(wsw.slab, ns, W[i], W[i], self.cin[i], taps, gof(f"main.{2 * i}.weight_orig"), T, self.coef[i],
                                            self.u[i][t0:], self.v[i][t0:])
@@ -700,7 +681,6 @@ class _DiscEngine:
                 if fused[0]:
                     kw.update(stat_mode=ops.STAT_SN_BIAS, stat_out=fused[1], stat_p=(self._m(i - 1).bias,), stat_slope=LRELU_SLOPE)
                 ops.conv_bwd_data(geo, dt, sl(self.dz[i]), self.mid[i - 1].wp_bwd, sl(self.dz[i - 1]), ops.epilogue(**kw))
-                flush()
         if need_dimg:
             if IMG_GEMM and IMG_DIRECT and ops.convt_img_mfma_ok(dt, self.C, self.S // 2, self.S // 2, W[0], 4, 2, 1):
                 ops.convt_img_mfma(dt, sl(self.dz[0]), self.l1g.wp_fwd, None, self.dimg, B, self.C, self.S // 2, self.S // 2, ACT_NONE, 0.0)
@@ -709,9 +689,8 @@ class _DiscEngine:
                 ops.col2im_img(dt, self.cols1, B, self.C, self.S // 2, self.S // 2, 4, 2, 1, None, ACT_NONE, 0.0, self.dimg)
             else:
                 ops.conv_bwd_data(self.l1.c, dt, sl(self.dz[0]), self.l1.wp_bwd, self.dimg, ops.epilogue(out_mode=OUT_NCHW_F32))
-            flush()
             return self.dimg
-        return None                                     # layer 0's chain stays pending: the caller's next main-stream kernel goes first
+        return None
 
 
 class Discriminator(_HipModule):
@@ -951,7 +930,7 @@ class DeviceInputs:
                                 (ops.RNG_RANDINT, tr.labels, 0, tr.G.n_classes, 5, tr.onehot)], self.seed, self.step)
             def gather():                               # ToTensor + Normalize(.5,.5)
                 ops.gather_u8_images(self.data, self.idx, self.flips if self.flip else None, tr.real, B, C, H, W, 2.0 / 255.0, -1.0, tick=self.step)
-            if INPUTS_ON_PREP and tr.side is not None:
+            if tr.side is not None:
                 tr._inputs_tail = gather                # the pipelined body runs it on its preparation lane, in front of the warp
             else:
                 gather()
@@ -969,45 +948,8 @@ class DeviceInputs:
         ops.counter_add(self.step, 1)
 
 
-# 1: D(gen) of the generator step batched with the discriminator step's D(scaled), D(gen) as ONE three-tape forward (same weights: the
-# discriminator is not updated in between; each tape keeps its own power iteration in the reference's order).  Same results (tested with
-# the switch on), but SLOWER in the overlapped step, 4.75 -> 4.94 ms (profiles/r02_x_ab_batch_d12.txt): the discriminator step's forward
-# no longer runs beside the generator's weight-gradient lanes and update.  Default 0: two forwards (T = 1, T = 2).
-BATCH_D12 = os.environ.get("EG_BATCH_D12", "0") != "0"
-# optimizer updates bucket by bucket (each bucket behind its own weight-gradient chain) instead of one update behind all chains: "0" never,
-# "1" every update, "3" the info step's two, or a comma list of g1 (generator step), d2 (discriminator step), d3, g3 (info step: D, then G)
 # data parallel: gradient buckets that cross the links as one message, in completion order (contiguous in the arenas)
-# EXPERIMENT (default off): the captured iteration as FOUR hipGraphs on two streams (engine.MultiGraph): [inputs, steps 1 and 2] -> [D's
-# update + step 3's power iterations and patch rows, ONE chain] beside [step 3's generator forward] -> [rest of step 3].  In ONE hipGraph
-# the generator forward starts ~200 us after step 2's main chain ends, although the node graph lets it start at once.  Cut into graphs on
-# real streams the delay stays (4.35 -> 4.46 ms, profiles/r03_x_ab_multi_graph.txt; toys: profiles/scripts/graph_streams_toy.py -- a graph
-# WITH branches on a second stream holds back later launches on the first, a one-chain graph does not; more HSA queues make it far worse,
-# profiles/r03_y_ab_hwq.txt).  Same bits (tests/test_gpu_celeba.py).  Single process only.
-MULTI_GRAPH = os.environ.get("EG_MULTI_GRAPH", "0") != "0"
-# the image gather and the affine warp at the head of the iteration on the preparation lane, beside the generator forward (which needs the
-# draws only), instead of in front of it on the main chain; same bits; EG_INPUTS_ON_PREP=0: on the main chain
-INPUTS_ON_PREP = os.environ.get("EG_INPUTS_ON_PREP", "1") != "0"
-LAZY_PATCHES = os.environ.get("EG_LAZY_PATCHES", "1") != "0"
-# EXPERIMENT (default off here; on in the small networks' trunks): the first D layer's weight gradient straight from the images (ops.wgrad_img,
-# N = 128) instead of lazily built patch rows + the per-tap GEMM.  Same gradient within fp32 summation order (tests), 7 launches fewer, but
-# SLOWER in the overlapped step, 4.27 -> 4.32 ms (profiles/r03_zzf_ab_wgrad_img_celeba.txt): its 59 KiB of LDS per workgroup do not fit on a CU
-# beside a resident 8-wave GEMM workgroup, so the lane chain waits for tiles to retire where the 12-18 us patch-row launches slipped in
-WGRAD_IMG = os.environ.get("EG_WGRAD_IMG_CELEBA", "0") != "0"
-WGRAD_FIRST = os.environ.get("EG_WGRAD_FIRST", "1") != "0"     # D's lane chains: the weight-gradient GEMM before the bias-gradient sums
-# kernel hint of the generator's first layer (ONE 128-row tile x 128 column tiles, 4 K steps: 1 GFLOP): the register-staged kernel (1) runs it
-# in ~10 us where the planner's persistent pipeline (0) takes 22-24; same bits; step -0.6 % (profiles/r03_zh_ab_g0_variant.txt)
-G0_VARIANT = int(os.environ.get("EG_G0_VARIANT", "1"))
-# EXPERIMENT (default off): step 3's generator forward between the forward and the backward of step 2 (pipelined body).  Same bits, but
-# slower, 4.46 -> 4.61 ms (profiles/r03_zb_ab_g3_mid.txt): behind step 2's backward the discriminator's update and step 3's power
-# iterations then run with nothing beside them -- that chain (update -> three power iterations -> patch rows), not the generator forward,
-# is what step 3's discriminator forward waits for.
-G3_MID = os.environ.get("EG_G3_MID", "0") != "0"
-ZERO_ON_PREP = os.environ.get("EG_ZERO_ON_PREP", "1") != "0"     # gradient zeroing of steps 1 / 2 on the preparation lane (0: on the main stream)
-SPLIT2_SET = set(filter(None, os.environ.get("EG_SPLIT2", "").split(",")))      # updates done in two pieces (early layers / rest): g1, d2, d3, g3
-DP_START = os.environ.get("EG_DP_START", "lane")
 COMM_GROUPS = {"G": (("G4", "G3", "G2"), ("G1", "G0")), "D": (("D4", "D3"), ("D2", "D1", "D0"))}
-BUCKET_OPT = os.environ.get("EG_BUCKET_OPT", "g3")
-BUCKET_SET = {"0": set(), "1": {"g1", "d2", "d3", "g3"}, "3": {"d3", "g3"}}.get(BUCKET_OPT, set(BUCKET_OPT.split(",")))
 
 
 class CelebATrainer:
@@ -1058,13 +1000,6 @@ class CelebATrainer:
         # weight-gradient chains and re-packing run on a second stream beside the backward-data chain (same arithmetic, same order
         # inside every chain -> bit-identical results with and without)
         self.side = SideStream(dev, Workspace.get(dev), lanes=int(os.environ.get("EG_LANES", "4"))) if overlap else None
-        # experiment (EG_G3_EARLY=1): the info step's generator forward on a stream of its own, as soon as the generator's first update is
-        # done, beside the discriminator step -- it needs nothing the discriminator step produces
-        self.g3_early = overlap and os.environ.get("EG_G3_EARLY", "0") != "0" and sync_bn is None
-        if self.g3_early:
-            self.g3_stream = torch.cuda.Stream(dev)
-            self.g3_ws = Workspace(dev, register=False)
-            self.g3_ws._grow("small", Workspace.get(dev).small.numel())
 
     # -- the hot path ---------------------------------------------------------------------------------
     def _buckets(self, arena):
@@ -1117,36 +1052,19 @@ class CelebATrainer:
         else:
             ar(flat)
 
-    def _sn_d12(self):
-        """power iterations of the three D forwards of steps 1 and 2 in the reference's order: D(gen) of step 1 (tape 2), then D(scaled),
-        D(gen) of step 2 (tapes 0, 1); all read the same weights"""
-        for t in (2, 0, 1):
-            self.de._sn_tape(t)
-
-    def _forward_d12(self, gen, prepared=False):
-        """ONE forward over tapes 0 = D(scaled), 1 = D(gen) [step 2], 2 = D(gen) [step 1]  (celebA/EAD-GAN_celebA.py:338,357-358)"""
-        if not prepared:
-            self._sn_d12()
-            self.de._im2col_tape(0, self.scaled)
-        return self.de.forward([self.scaled, gen, gen], 0, prepared=(True, False, False))
-
     def _step_body_serial(self):
         """one stream, program order of the reference loop body (overlap=False; the pipelined body below is bit-identical)"""
         G, D, ge, de, B = self.G, self.D, self.ge, self.de, self.B
         ga, da = G.arena, D.arena
         cd, nc = G.code_dim, G.n_classes
         lcat, lcon, laff = self.lam
-        fh1 = not BATCH_D12 and de.head_fused_ok(2)      # head + losses + head backward in one launch (steps 1 and 2)
+        fh1 = de.head_fused_ok(2)                        # head + losses + head backward in one launch (steps 1 and 2)
         fh3 = de.head_fused_ok(3) and cd >= 5            # ... of the info step
         self._inputs_head()
         # ---- 1) generator adversarial step (:334-345) ----
         ops.fill_f32(ga.grad)
         gen = ge.forward(self.z, self.onehot, self.code, sync=self.sync_bn)
-        if BATCH_D12:
-            out12 = self._forward_d12(gen)
-            out = out12[2 * B:]
-        else:
-            out = de.forward([gen], 2, head=not fh1)
+        out = de.forward([gen], 2, head=not fh1)
         if fh1:
             de.head_losses(2, 1, self.dout[2 * B:], self.losses[0:1], targets=(1.0,), scales=(1.0,))
         else:
@@ -1157,7 +1075,7 @@ class CelebATrainer:
         self._adam(ga, self.mG, self.vG, self.lr[0], 0, True)
         # ---- 2) discriminator step (:353-366); gen is the (detached) output of step 1; D(scaled) then D(gen), batched ----
         ops.fill_f32(da.grad)
-        out = out12 if BATCH_D12 else de.forward([self.scaled, gen], 0, head=not fh1)
+        out = de.forward([self.scaled, gen], 0, head=not fh1)
         if fh1:
             de.head_losses(0, 2, self.dout[:2 * B], self.losses[1:2], targets=(1.0, 0.0), scales=(0.5, 0.5))
         else:
@@ -1197,27 +1115,24 @@ class CelebATrainer:
         cd, nc = G.code_dim, G.n_classes
         lcat, lcon, laff = self.lam
         side = self.side
-        side.begin_step()
         evs = {}
-        fh1 = not BATCH_D12 and de.head_fused_ok(2)      # head + losses + head backward in one launch (steps 1 and 2)
+        fh1 = de.head_fused_ok(2)                        # head + losses + head backward in one launch (steps 1 and 2)
         fh3 = de.head_fused_ok(3) and cd >= 5            # ... of the info step
 
         ar = self.allreduce
         ar_async = ar is not None and hasattr(ar, "start")
 
-        def update(arena, m, v, lr, slot, tick, zero, eng, key=None, key_w=None, where=""):
-            """Queue one network's optimizer update on the optimizer lane, bucket by bucket in the order the backward pass completes them:
-            a bucket's Adam (+ gradient zeroing in the same pass) and panel re-packing wait only for the lane chain that completes the
-            bucket's gradients and for the main-stream kernels that still read its parameters (engine.SideStream.free), so the update of
-            the upper layers runs beside the backward pass of the lower ones and only the last bucket's update is behind all of it.
-            Data parallel: each bucket's all-reduce is STARTED here, on the main stream, once its chain is done (RCCL's stream must only
-            ever wait for the capture's origin stream: a lane that RCCL waited for and that later waits for RCCL is the stream-level back
-            edge hipStreamEndCapture crashes on), and FINISHED on the optimizer lane, so the main stream waits neither for the
-            collective nor for Adam / re-packing."""
-            if side.deferred != "1":
-                side.flush()
+        def update(arena, m, v, lr, slot, tick, zero, eng, key=None, key_w=None, bucketed=False):
+            """Queue one network's optimizer update on the optimizer lane.  Default: the whole arena in one update behind ALL of its weight-
+            gradient chains (engine.SideStream.defer_opt).  ``bucketed`` (the info step's generator update, the last of the iteration,
+            profiles/r02_h_ab_bucket_opt.txt): bucket by bucket in the order the backward pass completes them -- a bucket's Adam (+ gradient
+            zeroing in the same pass) and panel re-packing wait only for the lane chain that completes the bucket's gradients and for the
+            main-stream kernels that still read its parameters (engine.SideStream.free), so the update of the upper layers runs beside the
+            backward pass of the lower ones and only the last bucket's update is behind all of it.
+            Data parallel: each bucket's all-reduce is STARTED once its chain is done (RCCL's stream must only ever wait for the capture's
+            origin stream: a lane that RCCL waited for and that later waits for RCCL is the stream-level back edge hipStreamEndCapture
+            crashes on), and FINISHED on the optimizer lane, so the main stream waits neither for the collective nor for Adam / re-packing."""
             side.close_tags()
-            fuse = FUSE_ADAM and (FUSE_ADAM_AT == "all" or where in FUSE_ADAM_AT.split(","))
             buckets = self._buckets(arena)
             hs, finished = {}, set()
 
@@ -1227,17 +1142,16 @@ class CelebATrainer:
                     finished.add(id(h))
                     ar.finish(h)
             if ar is not None:
-                capturing = torch.cuda.is_current_stream_capturing() and os.environ.get("EG_COMM_CAPTURE", "0") == "0"
-                if ar_async and not capturing:
+                if ar_async and not torch.cuda.is_current_stream_capturing():
                     # eager launches (the default at N > 1): the gradient arena crosses the links as TWO messages per update (COMM_GROUPS:
                     # the layers whose gradients are complete early / the rest -- every collective costs the host ~40 us and a ring its
-                    # latency, five per update bought nothing), each started from the communication stream behind the lane chains that
-                    # complete it and finished on the optimizer lane: the main stream waits for neither
+                    # latency, five per update bought nothing), each started behind the lane chains that complete it and finished on the
+                    # optimizer lane: the main stream waits for neither
                     span = {tag: (lo, hi) for tag, lo, hi in buckets}
                     for grp in COMM_GROUPS["G" if arena is ga else "D"]:
-                        # the stream the message is started from: DP_START = "lane": the lane that ran the group's last chain (no further
-                        # stream: eight busy streams on four hardware queues stall each other), "comm": a communication stream
-                        src = side.done_lane[grp[-1]].stream if DP_START == "lane" else side.comm
+                        # started from the lane that ran the group's last chain (no further stream: eight busy streams on four hardware
+                        # queues stall each other)
+                        src = side.done_lane[grp[-1]].stream
                         for tag in grp:
                             src.wait_event(side.done.pop(tag))              # KeyError: a bucket whose chain was never forked
                         lo, hi = min(span[t][0] for t in grp), max(span[t][1] for t in grp)
@@ -1261,62 +1175,26 @@ class CelebATrainer:
                         hs[tag] = ar.start(arena.grad[lo:hi])
                     else:
                         ar(arena.grad[lo:hi])
-            last = buckets[-1][0]
-            if where in SPLIT2_SET and ar is None:
-                # the update in TWO pieces: the layers whose gradients are complete early (COMM_GROUPS' first group: for D 77 % of the
-                # parameters) as soon as their chains are done, the rest behind all chains -- the path from the end of the backward pass
-                # to "weights are new" (the next power iteration waits for it) is an Adam over the small remainder only
-                span = {tag: (lo, hi) for tag, lo, hi in buckets}
-                early = COMM_GROUPS["G" if arena is ga else "D"][0]
-                late = tuple(t for t, _, _ in buckets if t not in early)
-
-                def piece(tags, first):
-                    lo, hi = min(span[t][0] for t in tags), max(span[t][1] for t in tags)
-                    assert sum(span[t][1] - span[t][0] for t in tags) == hi - lo
-
-                    def fn(_ws):
-                        ops.adam_step_zero(arena.flat[lo:hi], arena.grad[lo:hi], m[lo:hi], v[lo:hi], hi - lo, lr, self.betas[0], self.betas[1], 1e-8,
-                                           self.steps[slot:slot + 1], tick and first, zero)
-                        if not first and key_w:
-                            evs[key_w] = side.mark()
-                        for t in tags:
-                            eng.repack_bucket(t)
-                        if not first and key:
-                            evs[key] = side.mark()
-                    return fn
-                side.defer_opt_after(early, piece(early, True))
-                for t in late:
-                    side.done.pop(t, None)
-                    side.free.pop(t, None)
-                side.defer_opt(piece(late, False))
-                return
-            if where not in BUCKET_SET:                 # the whole arena in one update behind ALL chains
+            if not bucketed:
                 def whole(_ws):
                     for tag in hs:
                         finish(tag)
-                    if fuse:
-                        if tick:
-                            ops.adam_tick(self.steps[slot:slot + 1])
-                        for tag, lo, hi in buckets:
-                            adam_bucket(eng, arena, tag, lo, hi, m, v, lr, self.betas, self.steps[slot:slot + 1], zero)
-                        if key_w:
-                            evs[key_w] = side.mark()
-                    else:
-                        ops.adam_step_zero(arena.flat, arena.grad, m, v, arena.numel, lr, self.betas[0], self.betas[1], 1e-8, self.steps[slot:slot + 1],
-                                           tick, zero)
-                        if key_w:
-                            evs[key_w] = side.mark()
-                        eng.repack()
+                    ops.adam_step_zero(arena.flat, arena.grad, m, v, arena.numel, lr, self.betas[0], self.betas[1], 1e-8, self.steps[slot:slot + 1],
+                                       tick, zero)
+                    if key_w:
+                        evs[key_w] = side.mark()        # master weights are new
+                    eng.repack()
                     if key:
-                        evs[key] = side.mark()
+                        evs[key] = side.mark()          # panels are new, gradients zeroed
                 side.done.clear()
                 side.free.clear()
                 side.defer_opt(whole)
                 return
+            last = buckets[-1][0]
             for k, (tag, lo, hi) in enumerate(buckets):
                 def fn(_ws, tag=tag, lo=lo, hi=hi, first=(k == 0)):
                     finish(tag)
-                    if fuse:
+                    if FUSE_ADAM:
                         if tick and first:
                             ops.adam_tick(self.steps[slot:slot + 1])
                         adam_bucket(eng, arena, tag, lo, hi, m, v, lr, self.betas, self.steps[slot:slot + 1], zero)
@@ -1336,126 +1214,57 @@ class CelebATrainer:
         # step 1's power iteration -- everything that reads them (step 2, step 3, the losses the warp launch zeroes) is behind the wait
         # for that lane's event below
         tail, self._inputs_tail = getattr(self, "_inputs_tail", None), None
-        on_prep = INPUTS_ON_PREP
-        if not on_prep:
-            if tail is not None:
-                tail()
-            self._inputs_head()
         # ---- 1) generator adversarial step (:334-345); D(gen) lives in tape slot 2 so that step 2's tapes can be prepared meanwhile ----
 
         def sn1(_ws):                                   # the power iterations only need D's weights: beside the generator forward
-            if on_prep:
-                if tail is not None:
-                    tail()
-                self._inputs_head()
-            if BATCH_D12:
-                self._sn_d12()
-                de._im2col_tape(0, self.scaled)
-            else:
-                de._sn_tape(2)
+            if tail is not None:
+                tail()
+            self._inputs_head()
+            de._sn_tape(2)
             # optimizer.zero_grad() of the generator and discriminator steps (the last updates of an iteration leave their gradients in
             # place: callers and tests read them): here, beside the generator forward -- the first gradient write is a backward pass away
-            if ZERO_ON_PREP:
-                ops.fill_f32(ga.grad)
-                ops.fill_f32(da.grad)
+            ops.fill_f32(ga.grad)
+            ops.fill_f32(da.grad)
             evs["sn1"] = side.mark()
         side.defer_prep(sn1)
-        if not ZERO_ON_PREP:
-            ops.fill_f32(ga.grad)
         gen = ge.forward(self.z, self.onehot, self.code, sync=self.sync_bn)
         side.wait(evs["sn1"])
-        if BATCH_D12:
-            out12 = self._forward_d12(gen, prepared=True)
-            out = out12[2 * B:]
-        else:
-            out = de.forward([gen], 2, prepared=(False,), head=not fh1)
+        out = de.forward([gen], 2, prepared=(False,), head=not fh1)
 
-            def prep2(_ws):                             # step 2's power iterations (after step 1's in the u/v chain) and patch rows
-                de.prepare(0, [self.scaled, gen])
-                evs["prep2"] = side.mark()
-            side.defer_prep(prep2)
+        def prep2(_ws):                                 # step 2's power iterations (after step 1's in the u/v chain) and patch rows
+            de.prepare(0, [self.scaled, gen])
+            evs["prep2"] = side.mark()
+        side.defer_prep(prep2)
         if fh1:
             de.head_losses(2, 1, self.dout[2 * B:], self.losses[0:1], targets=(1.0,), scales=(1.0,))
         else:
             ops.loss_bce_sigmoid(out, 19, 0, B, 1.0, 1.0, self.losses[0:1], self.dout[2 * B:])
-        side.flush()
         dimg = de.backward(2, 1, self.dout[2 * B:], da.grad, need_wgrad=False, need_dimg=True, head_done=fh1)
         ge.backward(dimg, ga.grad, side, sync=self.sync_bn)
-        update(ga, self.mG, self.vG, self.lr[0], 0, True, True, ge, key="g", where="g1")                # beside the whole of step 2
-        if self.g3_early:
-            side.flush()
-            self.g3_stream.wait_event(evs["g"])         # new panels, gradients zeroed
-            if not BATCH_D12:
-                self.g3_stream.wait_event(evs["prep2"])     # step 2's patch rows of the step-1 image exist: the image buffer may be rewritten
-            with torch.cuda.stream(self.g3_stream), self.g3_ws.active():
-                ge.forward(self.z, self.onehot, self.code, ws=self.g3_ws)
-                evs["g3fwd"] = side.mark()
+        update(ga, self.mG, self.vG, self.lr[0], 0, True, True, ge, key="g")                # beside the whole of step 2
         # ---- 2) discriminator step (:353-366); gen is the (detached) output of step 1; D(scaled) then D(gen), batched ----
-        if not ZERO_ON_PREP:
-            ops.fill_f32(da.grad)
-        side.flush()
-        if BATCH_D12:
-            out = out12
-        else:
-            side.wait(evs["prep2"])
-            out = de.forward([self.scaled, gen], 0, prepared=(True, True), head=not fh1)
+        side.wait(evs["prep2"])
+        out = de.forward([self.scaled, gen], 0, prepared=(True, True), head=not fh1)
         if fh1:
             de.head_losses(0, 2, self.dout[:2 * B], self.losses[1:2], targets=(1.0, 0.0), scales=(0.5, 0.5))
         else:
             ops.loss_bce_sigmoid(out[:B], 19, 0, B, 1.0, 0.5, self.losses[1:2], self.dout[:B])
             ops.loss_bce_sigmoid(out[B:], 19, 0, B, 0.0, 0.5, self.losses[1:2], self.dout[B:2 * B])
-        cut = getattr(self, "_cut", None)               # capture_segments: the iteration is being captured as several hipGraphs
-        g3_mid = G3_MID and cut is None and not self.g3_early and not BATCH_D12
-        if g3_mid:
-            # Step 3's generator forward HERE, between the discriminator step's forward and backward: it reads only G (new since step
-            # 1's update, long done) and writes only G's activations and the image buffer, whose step-1 content step 2 no longer needs
-            # (the discriminator read it in its forward; the patch rows its weight gradient reads were built by prep2).  Placed where
-            # the loop has it -- behind step 2's backward -- it starts ~200 us late and runs beside the power iterations at 2/3 speed
-            # (DESIGN.md 6.0); here it is plain main-chain work between two GEMM sequences.  Same kernels, same operands: same bits.
-            side.wait(evs["g"])
-            gen3 = ge.forward(self.z, self.onehot, self.code, sync=self.sync_bn)
         de.backward(0, 2, self.dout[:2 * B], da.grad, side=side, head_done=fh1)
-        g3_first = os.environ.get("EG_G3_FIRST", "0") != "0"
-        keep = side.deferred
-        if cut is not None:
-            side.join()                                 # every chain of steps 1 and 2 (and the generator's update) ends in this segment
-            side.cut()
-            cut(1, (0,))                                # second stream, behind the first segment
-            side.inline = True                          # ... as ONE chain: update, then step 3's power iterations and patch rows
-        if g3_first:
-            side.deferred = "1"                         # layer 0's chain, D's update and step 3's preparation are CAPTURED behind the generator forward's launches
-        update(da, self.mD, self.vD, self.lr[1], 1, True, True, de, key_w="dw", where="d2")             # beside step 3's generator forward
+        update(da, self.mD, self.vD, self.lr[1], 1, True, True, de, key_w="dw")             # beside step 3's generator forward
 
         # the first layer reads the images themselves (IMG_DIRECT): the patch rows are only the weight gradient's operand and are built by
-        # its own chain in step 3's backward -- not here, on the chain step 3's discriminator forward waits for (EG_LAZY_PATCHES=0: here)
-        lazy = LAZY_PATCHES and de.img_direct
+        # its own chain in step 3's backward -- not here, on the chain step 3's discriminator forward waits for
+        lazy = de.img_direct
 
         def prep3(_ws):                                 # step 3's three power iterations (new weights) [, patch rows of scaled / real]
             side.wait(evs["dw"])
             de.prepare(0, [None, None, None] if lazy else [None, self.scaled, self.real])
         side.defer_prep(prep3)
-        if cut is not None:
-            side.flush()
-            side.inline = False
-            side.cut()
-            cut(0, ())                                  # the caller's stream again: behind the first segment by stream order
         # ---- 3) info + affine step (:375-401): D(gen), D(scaled), D(real) batched as tapes 0,1,2 ----
-        if self.g3_early:
-            side.wait(evs["g3fwd"])
-            gen = ge.img
-        elif g3_mid:
-            gen = gen3
-        else:
-            if cut is None:
-                side.wait(evs["g"])                     # G's panels and zeroed gradients (optimizer lane, step 1)
-            gen = ge.forward(self.z, self.onehot, self.code, sync=self.sync_bn)
-        side.deferred = keep
-        if cut is not None:
-            side.join()
-            side.cut()
-            cut(0, (1,))                                # behind the second stream's segment: D's panels, power iterations, patch rows
-        else:
-            side.join()                                 # D's panels, power iterations, patch rows
+        side.wait(evs["g"])                             # G's panels and zeroed gradients (optimizer lane, step 1)
+        gen = ge.forward(self.z, self.onehot, self.code, sync=self.sync_bn)
+        side.join()                                     # D's panels, power iterations, patch rows
         out = de.forward([gen, self.scaled, self.real], 0, prepared=(False, False, False) if lazy else (False, True, True), head=not fh3)
         if fh3:
             de.head_losses(0, 3, self.dout, self.losses[2:3], info=(1, cd, nc, self.code, self.labels, lcat, lcon, laff))
@@ -1465,9 +1274,9 @@ class CelebATrainer:
                                 self.dout[B:2 * B], self.dout[2 * B:])           # the three losses in one launch
         dimg = de.backward(0, 3, self.dout, da.grad, need_dimg=True, side=side, head_done=fh3)
         # D's update beside the generator backward; it ticks optimizer_info's counter (shared by both arenas), G's does not
-        update(da, self.miD, self.viD, self.lr[2], 2, True, False, de, where="d3")
+        update(da, self.miD, self.viD, self.lr[2], 2, True, False, de)
         ge.backward(dimg, ga.grad, side, sync=self.sync_bn)
-        update(ga, self.miG, self.viG, self.lr[2], 2, False, False, ge, where="g3")
+        update(ga, self.miG, self.viG, self.lr[2], 2, False, False, ge, bucketed=True)
         side.join()
 
     # -- public API -----------------------------------------------------------------------------------
@@ -1512,13 +1321,6 @@ class CelebATrainer:
             self._step_body()
         if inputs is not None:
             self.inputs = inputs
-        if MULTI_GRAPH and self.side is not None and self.allreduce is None and not self.g3_early and not BATCH_D12:
-            self.side._live = []
-            try:
-                return capture_segments(self, self._step_with_inputs)
-            finally:
-                self.side._live = None
-                self.side.inline = False
         return capture_step(self, self._step_with_inputs)
 
     def _step_with_inputs(self):

@@ -27,12 +27,6 @@ TRUNK = (32, 32, 64, 64)
 # two GEMMs over them.  Same results within fp32 summation order (tests), one launch fewer, but SLOWER in the step: dSprites 1.305 -> 1.32 ms,
 # colored 2.50 -> 2.53 (profiles/r03_zzo_ab_l4_direct.txt): the statistics instantiation of the image kernel runs two workgroups per CU
 L4_DIRECT = os.environ.get("EG_L4_DIRECT", "0") != "0"
-# EXPERIMENT (default off): two-chain step with the alignment pass behind the first generator forward (beside the second chain's generator
-# forward) instead of in front of both chains.  Same kernels on the same operands, and the node graph is shorter by ~7 launches -- but the
-# replayed step is far SLOWER, dSprites 1.31 -> 1.73 ms, colored 2.54 -> 3.05 (profiles/r03_zzh_ab_align_late.txt): the second chain then
-# forks from a point with main-chain work queued behind it, and hipGraph's stream-to-queue placement (profiles/r01_timeline_notes.md) runs
-# the two chains one after the other
-ALIGN_LATE = os.environ.get("EG_ALIGN_LATE", "0") != "0"
 
 
 def to_categorical(y, num_columns, device=None):
@@ -753,22 +747,16 @@ class DspritesTrainer(ResidentStep):
         sa_d = None if getattr(self, "tail_lanes", False) else sa          # lanes of the D step's backward
         join = lambda sd: sd.join_lanes() if sd is not None else None
         ops.fill_f32(L)
-        align_late = ALIGN_LATE
-        if not align_late:
-            self._align()                                                                    # :374-377
+        # the alignment pass in front of BOTH chains: the second chain forks from a point with no main-chain work queued behind it
+        # (behind the first generator forward the replayed step ran the two chains one after the other, profiles/r03_zzh_ab_align_late.txt)
+        self._align()                                                                        # :374-377
         gen = ge.forward(self.onehot1, self.code1)
         chain.wait_event(mark())
-        if align_late:
-            # the alignment pass (frozen Encoder_pxy forward + warp: ~7 launches) reads only the real images: behind the first generator forward
-            # on the main chain it runs beside the second chain's generator forward instead of in front of both chains
-            self._align()
-        e_align = mark()
         with torch.cuda.stream(chain), self.ws2.active():
             ops.fill_f32(ga.grad)
             ops.fill_f32(ea.grad)
             gen2 = ge2.forward(self.onehot2, self.code2)
             e_gen2 = mark()
-            chain.wait_event(e_align)
             self._transform(self.code2, self.trans2, second=True)
             eo = ee.forward([gen2, self.align, self.trans2])
             cat, cont = eo["cat_layer.0"], eo["cont_layer.0"]

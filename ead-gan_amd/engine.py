@@ -159,7 +159,7 @@ class SideStream:
     step: the weight-gradient GEMMs with their reductions and bias-gradient sums run beside the backward-data GEMMs of
     the layers below (consecutive layers on alternating lanes, so one layer's HBM-bound reductions overlap the next
     layer's GEMM), weight re-packing after an optimizer step and the spectral-norm power iterations of the next sub-step
-    run beside the current one.  ``fork(i)``: lane i waits for everything enqueued on the current stream so far;
+    run beside the current one.  ``defer(i, fn)``: lane i runs fn behind everything enqueued on the current stream so far;
     ``join()``: the current stream waits for every lane.  Both are event record/wait pairs, capturable into the step's
     hipGraph.  Lanes never launch NT convolutions (the split-K scratch belongs to the main stream)."""
 
@@ -173,10 +173,6 @@ class SideStream:
         # (X waited for Y, later Y waits for X) even though the node graph is acyclic -- profiles/scripts/capture_patterns.py.  The same
         # holds for longer cycles: the waits among the non-origin streams must form a DAG (profiles/r01_timeline_notes.md item 10).
         self.prep = _Lane(device, like)
-        # communication stream (data parallel, eager launches): a gradient bucket's all-reduce is started from here as soon as the lane
-        # chain that completes the bucket has fired its event -- the main stream never waits for a lane on the collectives' behalf
-        self.comm = torch.cuda.Stream(device)
-        self._pending = []
         self.done = {}                                 # tag -> event behind a tagged lane chain (defer(..., tag=))
         self.done_lane = {}                            # tag -> the lane that ran the chain
         # tag -> main-stream event behind the last main-stream kernel that reads the tagged bucket's parameters or panels: the event of
@@ -184,50 +180,13 @@ class SideStream:
         # the layer below), or close_tags() for the last one
         self.free = {}
         self._last_tag = None
-        self._flushing = False
-        # issue order of forked work (see defer()): "0" at once (side work captured before the main stream's next kernel), "1" always
-        # after it, "once" at once for a lane's first fork of the step and after it from then on
-        self.deferred = os.environ.get("EG_DEFER", "0")
-        self._entered = set()
-        # lanes forked since the last cut(): an iteration captured as SEVERAL hipGraphs (capture_segments) may only join -- record an
-        # event on -- the lanes that are part of the current capture; None: every lane (one capture / eager launches)
-        self._live = None
-        # True: deferred work runs on the CURRENT stream at once (no fork): a capture segment that has to stay ONE chain -- a hipGraph with
-        # branches, launched on a second stream, holds back every later graph launch on the first (profiles/scripts/graph_streams_toy.py)
-        self.inline = False
 
     def lane(self, i: int) -> _Lane:
         return self.lanes[i % len(self.lanes)]
 
-    def _touch(self, ln):
-        if self._live is not None:
-            self._live.append(ln) if ln not in self._live else None
-
-    def _joinable(self, lanes):
-        return [ln for ln in lanes if self._live is None or ln in self._live]
-
-    def cut(self):
-        """a new capture segment begins: no lane belongs to it yet (the caller has joined them all)"""
-        assert not self._pending, "cut() with deferred work pending"
-        self._live = []
-        self.done.clear()
-        self.done_lane.clear()
-        self.free.clear()
-        self._last_tag = None
-
-    def fork(self, i: int = 0) -> _Lane:
-        ln = self.lane(i)
-        ln.ensure()
-        ev = torch.cuda.Event()
-        ev.record()
-        ln.stream.wait_event(ev)
-        self._touch(ln)
-        return ln
-
-    # Deferred issue.  hipGraph's executor keeps the FIRST-created child of a node on the node's own HW queue; every other child moves to
-    # another queue behind a cross-queue wait (10-18 us on MI355X, measured: profiles/r01_timeline_notes.md).  A fork therefore records
-    # its event at once but its launches are issued by the next flush(), which the caller places right AFTER the next main-stream
-    # kernel: the critical chain stays on one queue and the hop lands on the side work.  Dependencies are unchanged (the events).
+    # Every defer* enqueues fn's launches at once: the lane waits for the events named below, then fn runs with the lane as the current
+    # stream (and its scratch as ``ws``).  The caller's stream does not wait for the lane; it joins (join / join_lanes) or waits for one
+    # event (mark / wait) where it needs the lane's results.  No lane function defers work itself.
     def defer(self, i: int, fn, tag=None):
         """lane i runs fn(lane_workspace) behind everything enqueued on the current stream so far.  ``tag``: an event is recorded on the
         lane behind fn and kept in ``self.done[tag]`` (data parallel: the gradient bucket this chain completes can be reduced as soon
@@ -237,8 +196,7 @@ class SideStream:
             if self._last_tag is not None:
                 self.free[self._last_tag] = ev
             self._last_tag = tag
-        self._pending.append(("lane", self.lane(i), ev, fn, tag))
-        self._issue(("lane", i % len(self.lanes)))
+        self._run(self.lane(i), [ev], fn, tag)
 
     def close_tags(self):
         """the current position of the current stream is behind every reader of the last tagged bucket"""
@@ -249,82 +207,35 @@ class SideStream:
     def defer_opt_after(self, tags, fn):
         """the optimizer lane runs fn(ws) behind the tagged chains ``tags`` and the main-stream readers of their buckets ONLY (not behind
         the rest of the backward pass): bucket-wise optimizer updates start while the layers below are still in their backward pass"""
-        self._pending.append(("optb", self.opt, tuple(tags), fn, None))
-        self._issue("opt")
+        evs = []
+        for t in tags:
+            d = self.done.pop(t, None)                  # None: the caller already waited for it (data parallel)
+            if d is not None:
+                evs.append(d)
+            evs.append(self.free.pop(t))
+        self._run(self.opt, evs, fn)
 
     def defer_opt(self, fn):
         """the optimizer lane runs fn(ws) behind the current stream AND every weight-gradient chain forked so far"""
-        self._pending.append(("opt", self.opt, self.mark(), fn, None))
-        self._issue("opt")
-
-    def defer_prep(self, fn):
-        self._pending.append(("prep", self.prep, self.mark(), fn, None))
-        self._issue("prep")
-
-    def _issue(self, key):
-        if self.deferred == "0" or (self.deferred == "once" and key not in self._entered):
-            self._entered.add(key)
-            self.flush()
-
-    def begin_step(self):
-        self._entered.clear()
-
-    def flush(self):
-        if self._flushing or not self._pending:
-            return
-        self._flushing = True
-        try:
-            while self._pending:
-                kind, ln, ev, fn, tag = self._pending.pop(0)
-                ln.ensure()
-                if self.inline:
-                    fn(ln.ws)                           # (the events of an "optb" entry belong to chains of this very stream)
-                    if tag is not None:
-                        self.done[tag] = self.mark()
-                        self.done_lane[tag] = ln
-                    continue
-                if kind == "optb":
-                    for t in ev:
-                        d = self.done.pop(t, None)          # None: the caller already waited for it (data parallel)
-                        if d is not None:
-                            ln.stream.wait_event(d)
-                        ln.stream.wait_event(self.free.pop(t))
-                else:
-                    ln.stream.wait_event(ev)
-                self._touch(ln)
-                if kind == "opt":
-                    for other in self._joinable(self.lanes):
-                        e2 = torch.cuda.Event()
-                        e2.record(other.stream)
-                        ln.stream.wait_event(e2)
-                with ln:
-                    fn(ln.ws)
-                    if tag is not None:
-                        self.done[tag] = self.mark()
-                        self.done_lane[tag] = ln
-        finally:
-            self._flushing = False
-
-    def fork_prep(self) -> _Lane:
-        self.prep.ensure()
-        ev = torch.cuda.Event()
-        ev.record()
-        self.prep.stream.wait_event(ev)
-        self._touch(self.prep)
-        return self.prep
-
-    def fork_opt(self) -> _Lane:
-        """the optimizer lane waits for the current stream AND for everything the weight-gradient lanes hold so far"""
-        self.opt.ensure()
-        ev = torch.cuda.Event()
-        ev.record()
-        self.opt.stream.wait_event(ev)
-        self._touch(self.opt)
-        for ln in self._joinable(self.lanes):
+        evs = [self.mark()]
+        for ln in self.lanes:
             ev = torch.cuda.Event()
             ev.record(ln.stream)
-            self.opt.stream.wait_event(ev)
-        return self.opt
+            evs.append(ev)
+        self._run(self.opt, evs, fn)
+
+    def defer_prep(self, fn):
+        self._run(self.prep, [self.mark()], fn)
+
+    def _run(self, ln, evs, fn, tag=None):
+        ln.ensure()
+        for ev in evs:
+            ln.stream.wait_event(ev)
+        with ln:
+            fn(ln.ws)
+            if tag is not None:
+                self.done[tag] = self.mark()
+                self.done_lane[tag] = ln
 
     @staticmethod
     def mark() -> "torch.cuda.Event":
@@ -340,17 +251,15 @@ class SideStream:
 
     def join_lanes(self):
         """the current stream waits for the weight-gradient lanes only (not for the optimizer / preparation lanes)"""
-        self.flush()
-        cur = torch.cuda.current_stream()
-        for ln in self._joinable(self.lanes):
-            ev = torch.cuda.Event()
-            ev.record(ln.stream)
-            cur.wait_event(ev)
+        self._join(self.lanes)
 
     def join(self):
-        self.flush()
+        self._join(self.lanes + [self.opt, self.prep])
+
+    @staticmethod
+    def _join(lanes):
         cur = torch.cuda.current_stream()
-        for ln in self._joinable(self.lanes + [self.opt, self.prep]):
+        for ln in lanes:
             ev = torch.cuda.Event()
             ev.record(ln.stream)
             cur.wait_event(ev)
@@ -518,81 +427,6 @@ def capture_step(trainer, body):
         trainer.capture_failed = f"{type(exc).__name__}: {exc}"
         raise CaptureFailed(trainer.capture_failed) from exc
     trainer.graph = graph
-    return trainer
-
-
-class MultiGraph:
-    """One training iteration as several hipGraphs replayed on TWO real streams, ordered by events (an experiment, see celeba.MULTI_GRAPH:
-    it did not remove the delay it was built against).  ``replay()`` is what ``torch.cuda.CUDAGraph.replay()`` is to a one-graph trainer."""
-
-    def __init__(self, device):
-        self.segments = []                              # (graph, stream index 0 = the caller's stream / 1 = the second stream, after)
-        self.second = torch.cuda.Stream(device)
-        self._done = []
-
-    def add(self, graph, stream, after):
-        self.segments.append((graph, int(stream), tuple(after)))
-        self._done.append(torch.cuda.Event())
-
-    def replay(self):
-        main = torch.cuda.current_stream()
-        streams = (main, self.second)
-        for i, (g, s, after) in enumerate(self.segments):
-            st = streams[s]
-            for j in after:                             # segments on the other stream this one reads from
-                st.wait_event(self._done[j])
-            if s == 0:
-                g.replay()
-            else:
-                with torch.cuda.stream(st):
-                    g.replay()
-            self._done[i].record(st)
-        for i, (_, s, _) in enumerate(self.segments):   # the caller's stream ends behind every segment
-            if s != 0:
-                main.wait_event(self._done[i])
-
-
-def capture_segments(trainer, body):
-    """Like capture_step, for a ``body`` that calls ``trainer._cut(stream, after)`` between segments (every lane joined): each segment
-    becomes its own hipGraph; ``trainer.graph`` is a MultiGraph.  ``after``: indices of earlier segments on the OTHER stream whose results
-    the next segment reads (same-stream order is implicit)."""
-    torch.cuda.synchronize()
-    dev = torch.cuda.current_device()
-    mg = MultiGraph(dev)
-    pool = torch.cuda.graph_pool_handle()
-    cap = torch.cuda.Stream(dev)
-    cap.wait_stream(torch.cuda.current_stream())
-    state = {"g": None, "stream": 0, "after": ()}
-
-    def begin():
-        g = torch.cuda.CUDAGraph()
-        g.capture_begin(pool=pool)
-        state["g"] = g
-
-    def end():
-        state["g"].capture_end()
-        mg.add(state["g"], state["stream"], state["after"])
-        state["g"] = None
-
-    def cut(stream=0, after=()):
-        end()
-        state["stream"], state["after"] = stream, after
-        begin()
-
-    trainer._cut = cut
-    try:
-        with torch.cuda.stream(cap):
-            begin()
-            body()
-            end()
-    except Exception as exc:
-        trainer.graph = None
-        trainer.capture_failed = f"{type(exc).__name__}: {exc}"
-        raise CaptureFailed(trainer.capture_failed) from exc
-    finally:
-        trainer._cut = None
-    torch.cuda.current_stream().wait_stream(cap)
-    trainer.graph = mg
     return trainer
 
 

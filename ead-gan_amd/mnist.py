@@ -182,7 +182,6 @@ class _GenEngine:
                 fn(ws)
             else:
                 side.defer(lane, fn)
-        flush = side.flush if side is not None else (lambda: None)
 
         ops.act_grad_mul_bias_nchw(dimg, self.img, self.dimg_z, B, self.CH, S * S, ACT_TANH, 0.0, ws.small, gof("conv_blocks.9.bias"))
         ops.cast_pad(dt, self.dimg_z, self.p8, B * S * S, self.CH, 8)          # [M][1] fp32 (== NCHW with C=1) -> [M][8]
@@ -196,7 +195,6 @@ class _GenEngine:
             ops.wgrad_reduce(wsw.slab, ns, 8, self.CH, 64, 9, gof("conv_blocks.9.weight"))
         wgrad_side(c3_wgrad, 0)
         ops.conv_bwd_data(self.c3.c, dt, self.p8, self.c3.wp_bwd, self.da2, None)
-        flush()
 
         def bn_bwd(z, da, dz, mod, i, M, C, act, name):
             bn_train_backward(dt, z, da, dz, M, C, mod, self.mean[i], self.invstd[i], act, SLOPE, gof(name + ".weight"), gof(name + ".bias"), ws,
@@ -216,10 +214,8 @@ class _GenEngine:
         wgrad_side(c2_wgrad, 1)
         if self.up3:
             ops.conv_fwd(self.c2.c, dt, self.dz2, self.c2.wp_fwd, self.da1, None)      # the input gradient at the low resolution: no sum-pool
-            flush()
         else:
             ops.conv_bwd_data(self.c2.c, dt, self.dz2, self.c2.wp_bwd, self.dup, None)
-            flush()
             ops.sumpool2x2(dt, self.dup, self.da1, B, 2 * s, 2 * s, 128)
         # conv1 (128 -> 128 on the 2x-upsampled a0)
         bn_bwd(self.z1, self.da1, self.dz1, cb[3], 1, B * 4 * s * s, 128, ACT_LRELU, "conv_blocks.3")
@@ -236,10 +232,8 @@ class _GenEngine:
         wgrad_side(c1_wgrad, 2)
         if self.up3:
             ops.conv_fwd(self.c1.c, dt, self.dz1, self.c1.wp_fwd, self.da0, None)
-            flush()
         else:
             ops.conv_bwd_data(self.c1.c, dt, self.dz1, self.c1.wp_bwd, self.dup, None)     # [B,16,16,128] in the front of dup
-            flush()
             ops.sumpool2x2(dt, self.dup, self.da0, B, s, s, 128)
         bn_bwd(self.h, self.da0, self.dh, cb[0], 0, B * s * s, 128, ACT_NONE, "conv_blocks.0")
         # l1: dW[f][k] = sum_b dh[b][n'(f)] * x[b][k]
@@ -252,7 +246,6 @@ class _GenEngine:
             ops.bias_grad(dt, self.dh, B, self.nl1, wsw.small, self.gb_perm)
             ops.gather_add(gof("l1.0.bias"), self.gb_perm, self.nl1, hw, 1, 128)
         wgrad_side(l1_wgrad, 3)
-        flush()
 
 
 class Generator(_HipModule):
