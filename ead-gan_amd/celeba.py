@@ -788,6 +788,14 @@ class transformation_2D(nn.Module):
         return self.stn(img, matrix_2D)
 
 
+# The regularizer kernels return the gradient of an MSE, gs * (pred - target) * J with gs = 2 * scale / (n B); the drop-in backward gets J^T dpred
+# out of them with target = pred - dpred * (n B / 2).  The kernel then recovers dpred * n B / 2 as a float32 difference of two numbers of size
+# |pred|: relative error 2^-24 * |pred| / (|dpred| n B / 2), 2e-4 for an upstream gradient of 1e-6 at B = 128.  Both the target's offset and
+# 1 / scale therefore carry the factor GRAD_UP, a power of two (exact in both places): the difference is then GRAD_UP times larger than the
+# rounding of pred, and once it exceeds |pred| its error is its own rounding, 2^-24 relative.  Overflow would need |dpred| n B / 2 > 7e28.
+GRAD_UP = 2.0 ** 32
+
+
 class _AffineRegFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, real_code, trans_code):
@@ -800,16 +808,17 @@ class _AffineRegFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dpred):
-        # d/dcode of sum_j dpred_j * pred_j  ==  gradient of the MSE kernel with target = pred - dpred*(5B/2)
+        # d/dcode of sum_j dpred_j * pred_j  ==  gradient of the MSE kernel with target = pred - dpred*(5B/2); target and scale carry the
+        # power of two GRAD_UP (see there)
         real_code, trans_code = ctx.saved_tensors
         B, ld = real_code.shape
         pred = torch.empty(B, 5, device=real_code.device, dtype=torch.float32)
         zero_code = torch.zeros(B, 5, device=real_code.device, dtype=torch.float32)
         ops.loss_affine_rpqxy(real_code, trans_code, ld, 0, B, zero_code, 5, 1.0, None, None, None, pred)
-        tgt = pred - dpred.float() * (5.0 * B / 2.0)
+        tgt = pred - dpred.float() * (GRAD_UP * 5.0 * B / 2.0)
         d_real = torch.empty_like(real_code)
         d_trans = torch.empty_like(trans_code)
-        ops.loss_affine_rpqxy(real_code, trans_code, ld, 0, B, tgt.contiguous(), 5, 1.0, None, d_real, d_trans, None)
+        ops.loss_affine_rpqxy(real_code, trans_code, ld, 0, B, tgt.contiguous(), 5, 1.0 / GRAD_UP, None, d_real, d_trans, None)
         return d_real, d_trans
 
 

@@ -9,7 +9,7 @@ import torch
 
 from . import dsprites as ds
 from . import ops
-from .celeba import _require_cuda, transformation_2D          # noqa: F401
+from .celeba import GRAD_UP, _require_cuda, transformation_2D          # noqa: F401
 from .dsprites import get_matrix, get_matrix_D, get_matrix_pxy_align, mutual_info_loss, to_categorical      # noqa: F401
 
 opt = argparse.Namespace(n_epochs=100, batch_size=128, lr=0.0002, b1=0.5, b2=0.999, n_cpu=8, latent_dim=200, code_dim=7, n_classes=3,
@@ -59,9 +59,9 @@ class _AffineColorFn(torch.autograd.Function):
     def backward(ctx, dpred):
         real_code, trans_code, pred = ctx.saved_tensors
         B, ld = real_code.shape
-        tgt = (pred - dpred.float() * (7.0 * B / 2.0)).contiguous()
+        tgt = (pred - dpred.float() * (GRAD_UP * 7.0 * B / 2.0)).contiguous()
         d_real, d_trans = torch.empty_like(real_code), torch.empty_like(trans_code)
-        ops.loss_affine_rp_color(real_code, trans_code, ld, 0, B, tgt, 7, 1.0, None, d_real, d_trans, None)
+        ops.loss_affine_rp_color(real_code, trans_code, ld, 0, B, tgt, 7, 1.0 / GRAD_UP, None, d_real, d_trans, None)
         return d_real, d_trans
 
 

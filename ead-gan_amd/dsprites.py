@@ -14,7 +14,7 @@ import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
 from . import ops
-from .celeba import FUSE_STATS, IMG_GEMM, _HipModule, _require_cuda, transformation_2D      # noqa: F401
+from .celeba import FUSE_STATS, GRAD_UP, IMG_GEMM, _HipModule, _require_cuda, transformation_2D      # noqa: F401
 from .engine import FUSE_DRAWS, Arena, ConvRec, DeviceSampler, ResidentStep, SideStream, SyncScratch, Workspace, bn_train_backward, bn_train_forward, capture_step, check_usable, parse_dtype
 from .ops import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, EG_F32, OUT_NCHW_F32
 from .trunk import IMG_DIRECT, WGRAD_IMG, Head, TrunkEngine
@@ -493,9 +493,9 @@ class _AffineRegFn(torch.autograd.Function):
     def backward(ctx, dpred):
         real_code, trans_code, pred = ctx.saved_tensors
         B, ld = real_code.shape
-        tgt = (pred - dpred.float() * (4.0 * B / 2.0)).contiguous()
+        tgt = (pred - dpred.float() * (GRAD_UP * 4.0 * B / 2.0)).contiguous()
         d_real, d_trans = torch.empty_like(real_code), torch.empty_like(trans_code)
-        ops.loss_affine_rp(real_code, trans_code, ld, 0, B, tgt, 4, 1.0, None, d_real, d_trans, None)
+        ops.loss_affine_rp(real_code, trans_code, ld, 0, B, tgt, 4, 1.0 / GRAD_UP, None, d_real, d_trans, None)
         return d_real, d_trans
 
 

@@ -15,7 +15,7 @@ import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
 from . import ops
-from .celeba import _HipModule, _require_cuda, transformation_2D      # noqa: F401  (same STN warp in both scripts)
+from .celeba import GRAD_UP, _HipModule, _require_cuda, transformation_2D      # noqa: F401  (same STN warp in both scripts)
 from .engine import (FUSE_DRAWS, Arena, ConvRec, DeviceSampler, ResidentStep, SideStream, SyncScratch, Workspace, bn_train_backward, bn_train_forward, capture_step, check_usable,
                      parse_dtype)
 from .ops import ACT_LRELU, ACT_NONE, ACT_TANH, EG_F32, OUT_NCHW_F32
@@ -470,9 +470,9 @@ class _AffineRegFn(torch.autograd.Function):
         real_code, trans_code, pred = ctx.saved_tensors
         B, ld = real_code.shape
         dev = real_code.device
-        tgt = (pred - dpred.float() * (7.0 * B / 2.0)).contiguous()       # MSE gradient with this target == J^T dpred
+        tgt = (pred - dpred.float() * (GRAD_UP * 7.0 * B / 2.0)).contiguous()       # MSE gradient with this target and scale 1 / GRAD_UP == J^T dpred (celeba.GRAD_UP)
         d_real, d_trans = torch.empty_like(real_code), torch.empty_like(trans_code)
-        ops.loss_affine_rpqmnxy(real_code, trans_code, ld, 0, B, tgt, 7, _approx(dev), 1.0, None, d_real, d_trans, None, torch.empty(B, device=dev))
+        ops.loss_affine_rpqmnxy(real_code, trans_code, ld, 0, B, tgt, 7, _approx(dev), 1.0 / GRAD_UP, None, d_real, d_trans, None, torch.empty(B, device=dev))
         return d_real, d_trans
 
 
