@@ -19,7 +19,7 @@ import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
 from . import ops
-from .engine import Arena, ConvRec, SideStream, Workspace, capture_step, check_usable, parse_dtype
+from .engine import Arena, ConvRec, SideStream, TrainerState, Workspace, capture_step, check_usable, parse_dtype
 from .ops import (ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH, EG_BF16, EG_F32, OUT_NCHW_F32)
 
 # module-level hyper-parameters, mirroring the reference's global ``opt`` (argparse defaults, :39-51)
@@ -961,7 +961,7 @@ class DeviceInputs:
 COMM_GROUPS = {"G": (("G4", "G3", "G2"), ("G1", "G0")), "D": (("D4", "D3"), ("D2", "D1", "D0"))}
 
 
-class CelebATrainer:
+class CelebATrainer(TrainerState):
     """One call of :meth:`train_step` == one iteration of the reference loop body
     (celebA/EAD-GAN_celebA.py:299-401): G adversarial step, D step, info+affine step, three Adams
     (lr 1e-3 / 2e-4 / 2e-4, betas (.5,.999), :211-217) -- hand-scheduled over the C ABI with dead work removed
@@ -1006,6 +1006,7 @@ class CelebATrainer:
         self.labels = torch.empty(B, device=dev, dtype=torch.int64)
         self.graph = None
         self.inputs = None
+        self.log = None
         # weight-gradient chains and re-packing run on a second stream beside the backward-data chain (same arithmetic, same order
         # inside every chain -> bit-identical results with and without)
         self.side = SideStream(dev, Workspace.get(dev), lanes=int(os.environ.get("EG_LANES", "4"))) if overlap else None
@@ -1320,9 +1321,10 @@ class CelebATrainer:
         self.onehot.zero_()
         self.onehot.scatter_(1, self.labels.view(-1, 1), 1.0)
 
-    def capture(self, warmup: bool = False, inputs: "DeviceInputs | None" = None):
+    def capture(self, warmup: bool = False, inputs: "DeviceInputs | None" = None, log=None):
         """Capture the whole iteration into one hipGraph (inputs are read from the static slots; with ``inputs`` -- a DeviceInputs --
-        the graph first draws them on the device, so a replay is a complete loop iteration without host work).
+        the graph first draws them on the device, so a replay is a complete loop iteration without host work; with ``log`` -- an
+        engine.LossLog -- the graph ends with the append of the iteration's loss row).
 
         At least one eager iteration must have run before (it loads every kernel and sizes the workspace);
         ``warmup=True`` runs that iteration here -- note that it IS a real training step on the current inputs."""
@@ -1330,12 +1332,32 @@ class CelebATrainer:
             self._step_body()
         if inputs is not None:
             self.inputs = inputs
+        if log is not None:
+            self.log = log
         return capture_step(self, self._step_with_inputs)
 
     def _step_with_inputs(self):
         if getattr(self, "inputs", None) is not None:
             self.inputs.enqueue(self)
         self._step_body()
+        if self.log is not None:                        # behind the body's join of its lanes, on the main stream
+            self.log.append()
+
+    # -- full state (engine.TrainerState) -------------------------------------------------------------
+    STATE_KIND = "celeba"
+
+    def _state_modules(self):
+        return {"G": self.G, "D": self.D}
+
+    def _state_moments(self):
+        return {"G": (self.mG, self.vG), "D": (self.mD, self.vD), "iG": (self.miG, self.viG), "iD": (self.miD, self.viD)}
+
+    def _state_zero_scratch(self):
+        # scratch whose contract is "left at zero" by every launch that uses it: arrival counters of the fused head and of the
+        # two-launch power iteration.  Zero at every iteration boundary already; cleared so that a load never depends on that.
+        if self.de._head_scratch is not None:
+            self.de._head_scratch[1].zero_()
+        self.de.sn_counters.zero_()
 
     def step_resident(self):
         """Run one iteration on whatever is in the static input slots (or on fresh device-side draws if the trainer was captured /

@@ -81,6 +81,8 @@ class ColoredTrainer(ds.DspritesTrainer):
         self.tmp, self.tmp2 = torch.zeros_like(self.img), torch.zeros_like(self.img)
         self.gains = torch.zeros(batch_size, 3, device=dev)
 
+    STATE_KIND = "colored"
+
     def _align(self):
         B = self.B
         pcode = self.pe.forward(self.img)                                   # [B,6] = p,x,y,r,g,b
@@ -126,6 +128,8 @@ class PxyColorTrainer(ds.PxyTrainer):
         self.gains = torch.ones(batch_size, 3, device=dev, dtype=torch.float32)
         self.warped = torch.zeros(batch_size, 3, 64, 64, device=dev, dtype=torch.float32)
 
+    STATE_KIND = "pxy_color"
+
     def _make_image(self):
         ops.u8_colorize(self.img_u8, self.gains, self.img, self.B, 3, 64 * 64)
 
@@ -156,3 +160,6 @@ class DeviceInputs(ds.DeviceInputs):
         self.end_draws()
         ops.u8_colorize(self.sprites(tr, idx), tr.gains, tr.img, tr.B, 3, 64 * 64)
         self.tick()
+
+
+PxyDeviceInputs = ds.PxyDeviceInputs      # the colour gains are drawn when the trainer has a ``gains`` slot

@@ -584,7 +584,7 @@ class _PxyTrainEngine:
                 ops.wgrad_reduce_perm(ws.slab, ns, TRUNK[0], TRUNK[0], self.kp, 1, gof("conv_block.0.weight"), 0, 0, self.k0)
 
 
-class PxyTrainer:
+class PxyTrainer(ResidentStep):
     """One call == one iteration of dSprites/pxy.py:156-191 (stage-1 trainer): real_code = E(img); trans_img = warp(img,
     get_matrix_pxy(code)); trans_code = E(trans_img); loss = MSE(affine_regularzier_pxy(real_code, trans_code), code); Adam(lr 2e-4,
     betas (.5, .999), :127) on Encoder_pxy.  Its ``state_dict()`` is the ``encoder_pxy_%d.pt`` the stage-2 loop loads (:205)."""
@@ -639,23 +639,25 @@ class PxyTrainer:
         self.img_u8.copy_(img_u8, non_blocking=True)
         self.code.copy_(code, non_blocking=True)
 
-    def capture(self, warmup=False):
-        if warmup:
-            self._step_body()
-        return capture_step(self, self._step_body)
-
-    def step_resident(self):
-        check_usable(self)
-        if self.graph is not None:
-            self.graph.replay()
-        else:
-            self._step_body()
-        return self.losses
+    # capture() / step_resident(): engine.ResidentStep (without ``inputs`` and ``log`` the launches of _step_body alone)
 
     def train_step(self, img_u8, code):
         """train-loop entry: img_u8 uint8 [B,64,64] sprites, code [B,3] ~ U(-1,1) -> {'affine_loss'}"""
         self.load_inputs(img_u8, code)
         return {"affine_loss": float(self.step_resident()[0])}
+
+    # -- full state (engine.TrainerState) -------------------------------------------------------------
+    STATE_KIND = "pxy"
+
+    def _state_modules(self):
+        return {"P": self.P}
+
+    def _state_moments(self):
+        return {"P": (self.m, self.v)}
+
+    def _state_repack(self):
+        self.eng.repack()                                # the training engine is not among the module's inference engines
+        self.P.repack()
 
 
 class DspritesTrainer(ResidentStep):
@@ -765,6 +767,7 @@ class DspritesTrainer(ResidentStep):
             ops.loss_mse(cont[:B], cd, 0, cd, B, self.code2, cd, 0.0, 1.0, L[2:3], self.d_cont[:B])
             self._affine_loss(cont[B:2 * B], cont[2 * B:], L[3:4], self.d_cont[B:2 * B], self.d_cont[2 * B:])
             ops.loss_mutual_info(cat[2 * B:], nc, 0, nc, B, cat[B:2 * B], nc, 0, True, 1.0, L[4:5], self.d_cat[2 * B:])
+            self._log_info_terms(cat, cont)
             dimg_e = ee.backward(0, 3, {"cat_layer.0": self.d_cat, "cont_layer.0": self.d_cont}, ea.grad, need_dimg=True, side=sb)
             e_dimg = mark()
             evs = {}
@@ -840,6 +843,7 @@ class DspritesTrainer(ResidentStep):
         ops.loss_mse(cont[:B], cd, 0, cd, B, self.code2, cd, 0.0, 1.0, L[2:3], self.d_cont[:B])
         self._affine_loss(cont[B:2 * B], cont[2 * B:], L[3:4], self.d_cont[B:2 * B], self.d_cont[2 * B:])
         ops.loss_mutual_info(cat[2 * B:], nc, 0, nc, B, cat[B:2 * B], nc, 0, True, 1.0, L[4:5], self.d_cat[2 * B:])
+        self._log_info_terms(cat, cont)
         dimg_e = ee.backward(0, 3, {"cat_layer.0": self.d_cat, "cont_layer.0": self.d_cont}, ea.grad, need_dimg=True)
         ops.add_f32(self.dimg, dimg_e, dimg_d)
         pending = self.allreduce.start(ea.grad) if (self.allreduce is not None and hasattr(self.allreduce, "start")) else None
@@ -854,6 +858,15 @@ class DspritesTrainer(ResidentStep):
         self._adam(ea, self.miE, self.viE, self.lr[1], 1, False)
         ge.repack()
         ee.repack()
+
+    def _log_info_terms(self, cat, cont):
+        """With a loss log attached only: cat_loss -> losses[5], cont_loss -> losses[6] (loss-only launches, no gradient).  The
+        reference's progress line prints the two terms on their own (rp.py:493-495); losses[2] stays their sum."""
+        if self.log is None:
+            return
+        B, nc, cd, L = self.B, self.nc, self.cd, self.losses
+        ops.loss_mutual_info(cat[:B], nc, 0, nc, B, self.onehot2, nc, 0, False, 1.0, L[5:6], None)
+        ops.loss_mse(cont[:B], cd, 0, cd, B, self.code2, cd, 0.0, 1.0, L[6:7], None)
 
     # -- dataset-specific pieces (overridden by the colored variant) -------------------------------------------------
     def _align(self):
@@ -890,6 +903,17 @@ class DspritesTrainer(ResidentStep):
         l = self.step_resident().tolist()
         return dict(d_loss=l[0], g_loss=l[1], info_loss=l[2], affine_loss=l[3], relative_cat_loss=l[4])
 
+    # -- full state (engine.TrainerState) -------------------------------------------------------------
+    STATE_KIND = "dsprites"
+
+    def _state_modules(self):
+        # the frozen Encoder_pxy too: a run resumes from its own file alone.  Re-packing goes through the modules: the second chain's
+        # engines (``ee``, ``ge2``: own panels over the shared masters) are among ``module._engines``.
+        return {"P": self.P, "G": self.G, "D": self.D, "E": self.E}
+
+    def _state_moments(self):
+        return {"D": (self.mD, self.vD), "iG": (self.miG, self.viG), "iE": (self.miE, self.viE)}
+
 
 class DeviceInputs(DeviceSampler):
     """Device-side replacement of the dSprites loop's host input work (dSprites/rp.py:236-262 the uint8 sprite array + DataLoader; :389-430
@@ -919,4 +943,19 @@ class DeviceInputs(DeviceSampler):
             ops.gather_u8_images(self.data, idx, None, tr.img, tr.B, 1, H, W, 1.0, 0.0, tick=self.step)
             return
         ops.u8_to_f32(self.sprites(tr, idx), tr.img)
+        self.tick()
+
+
+class PxyDeviceInputs(DeviceSampler):
+    """Device-side input work of the stage-1 loops (dSprites/pxy.py:157-168: the uint8 sprite DataLoader and code ~ U(-1,1);
+    colored_dSprites/pxy_color.py:163-187: the colour gains ~ U(.5,1) drawn first).  ``dataset_u8``: uint8 [N,64,64] sprites."""
+
+    def enqueue(self, tr: "PxyTrainer"):
+        self.begin_draws()
+        idx = self.sample_indices(tr.B, 1)
+        if hasattr(tr, "gains"):
+            self.draw(ops.RNG_UNIFORM, tr.gains, 0.5, 1.0, 2)
+        self.draw(ops.RNG_UNIFORM, tr.code, -1.0, 1.0, 3)
+        self.end_draws()
+        torch.index_select(self.data, 0, idx, out=tr.img_u8)
         self.tick()

@@ -365,24 +365,235 @@ class DeviceSampler:
         ops.counter_add(self.step, 1)
 
 
-class ResidentStep:
+def unwrap_ring(ring, head, capacity, since=0):
+    """Rows of the iterations [max(since, head - capacity), head) of a ring filled by eg_runlog_append (row = iteration % capacity), in
+    iteration order: -> (first iteration, array [iterations, n])"""
+    import numpy as np
+    first = max(int(since), int(head) - int(capacity), 0)
+    idx = np.arange(first, int(head)) % int(capacity)
+    return first, np.asarray(ring)[idx].copy()
+
+
+class LossLog:
+    """Loss history of a run kept on the device: ``append()`` enqueues eg_runlog_append on the current stream (row ``head % capacity`` of
+    the ring <- ``trainer.losses``; inside a trainer's captured iteration it is a node of the hipGraph), ``flush_async()`` copies ring,
+    head and the non-finite flag into a pinned host mirror on a copy stream behind an event, so reading losses never drains the
+    queued iterations.  The caller flushes at least once per ``capacity`` appends (train.TrainRun does); rows older than that are
+    overwritten."""
+
+    def __init__(self, trainer, capacity=1024, _host_only_n=None):
+        self.capacity = int(capacity)
+        if self.capacity <= 0:
+            raise ValueError("LossLog: capacity must be positive")
+        self.trainer = trainer
+        self._pending = None
+        self.mirror_head, self.mirror_flag = 0, 0
+        if _host_only_n is not None:                    # a mirror without a device side (reading a saved ring; host tests)
+            import numpy as np
+            self.n = int(_host_only_n)
+            self.mirror = np.zeros((self.capacity, self.n), np.float32)
+            return
+        self.losses = trainer.losses
+        self.n = self.losses.numel()
+        dev = self.losses.device
+        self.ring = torch.zeros(self.capacity, self.n, device=dev, dtype=torch.float32)
+        self.head = torch.zeros(1, device=dev, dtype=torch.int32)
+        self.first_nonfinite = torch.zeros(1, device=dev, dtype=torch.int32)
+        self._ring_host = torch.zeros(self.capacity, self.n, dtype=torch.float32).pin_memory()
+        self._hf_host = torch.zeros(2, dtype=torch.int32).pin_memory()
+        self.mirror = self._ring_host.numpy()
+        self.copy_stream = torch.cuda.Stream(dev)
+
+    @classmethod
+    def host_mirror(cls, n, capacity):
+        return cls(None, capacity, _host_only_n=n)
+
+    def append(self):
+        ops.runlog_append(self.losses, self.n, self.ring, self.capacity, self.head, self.first_nonfinite)
+
+    def landed(self) -> bool:
+        """no copy is in flight (a finished one is taken into the mirror's head / flag here)"""
+        if self._pending is not None and self._pending.query():
+            self._take()
+        return self._pending is None
+
+    def _take(self):
+        self._pending = None
+        self.mirror_head, self.mirror_flag = int(self._hf_host[0]), int(self._hf_host[1])
+
+    def wait(self):
+        """block until the copy in flight (if any) has landed -- the only host wait the log can cause"""
+        if self._pending is not None:
+            self._pending.synchronize()
+            self._take()
+
+    def flush_async(self):
+        """Snapshot behind everything enqueued on the current stream so far.  Head and flag are copied BEFORE the ring: the ring then
+        holds every row below the copied head (appends that run during the copy only touch the slots of the oldest rows)."""
+        self.wait()
+        ev = torch.cuda.Event()
+        ev.record()
+        self.copy_stream.wait_event(ev)
+        with torch.cuda.stream(self.copy_stream):
+            self._hf_host[0:1].copy_(self.head, non_blocking=True)
+            self._hf_host[1:2].copy_(self.first_nonfinite, non_blocking=True)
+            self._ring_host.copy_(self.ring, non_blocking=True)
+            self._pending = torch.cuda.Event()
+            self._pending.record()
+
+    def rows(self, since=0):
+        """the rows that have landed, [iterations, n] in iteration order (the last ``capacity`` at most; from iteration ``since``)"""
+        self.landed()
+        return unwrap_ring(self.mirror, self.mirror_head, self.capacity, since)[1]
+
+    def first_row(self, since=0):
+        return max(int(since), self.mirror_head - self.capacity, 0)
+
+    def load(self, head, first_nonfinite):
+        """continue a saved run's numbering (trainer.load_state_dict): in place, the captured append keeps its addresses"""
+        self.wait()
+        self.head.fill_(int(head))
+        self.first_nonfinite.fill_(int(first_nonfinite))
+        self.mirror_head, self.mirror_flag = int(head), int(first_nonfinite)
+
+
+DTYPE_NAMES = {EG_F32: "f32", EG_BF16: "bf16", EG_F16: "f16"}
+STATE_FORMAT = 1
+
+
+def validate_state(sd, kind, spec):
+    """Checks of ``load_state_dict`` that need no device: ``spec`` maps every expected key to the shape of its tensor (a tuple) or to
+    None for a plain value.  Raises ValueError naming the first offending key; nothing has been written when it does."""
+    if not isinstance(sd, dict):
+        raise ValueError("state: not a dict")
+    if sd.get("meta.kind") != kind:
+        raise ValueError(f"meta.kind: state of a {sd.get('meta.kind')!r} trainer cannot be loaded into a {kind!r} trainer")
+    if sd.get("meta.format") != STATE_FORMAT:
+        raise ValueError(f"meta.format: {sd.get('meta.format')!r} (this build reads format {STATE_FORMAT})")
+    for key, shape in spec.items():
+        if key not in sd:
+            raise ValueError(f"{key}: missing from the state")
+        v = sd[key]
+        if shape is None:
+            if isinstance(v, torch.Tensor):
+                raise ValueError(f"{key}: expected a plain value, found a tensor")
+        else:
+            if not isinstance(v, torch.Tensor):
+                raise ValueError(f"{key}: expected a tensor of shape {tuple(shape)}")
+            if tuple(v.shape) != tuple(shape):
+                raise ValueError(f"{key}: shape {tuple(v.shape)} in the state, {tuple(shape)} in the trainer")
+
+
+class TrainerState:
+    """``state_dict()`` / ``load_state_dict()`` of the fused trainers: everything an iteration reads that an earlier iteration wrote --
+    module parameters and buffers (fp32 masters, BatchNorm running statistics, spectral-norm vectors), Adam moments and the device step
+    counters, the sampler's (seed, step), the loss log's head.  A flat dict of CPU tensors and plain values (``torch.load(...,
+    weights_only=True)`` reads it).  Loading copies IN PLACE -- a captured hipGraph holds the addresses -- and re-packs the engines'
+    weight panels; it works on a trainer that has been captured and used.  Batch size and compute dtype are not state.
+    Subclasses provide ``STATE_KIND``, ``_state_modules()`` ({name: module}), ``_state_moments()`` ({name: (m, v)}) and may add
+    ``_state_extra_tensors()`` ({key: device tensor}), ``_state_repack()``, ``_state_zero_scratch()``."""
+
+    STATE_KIND = None
+    inputs = None
+    log = None
+
+    def _state_extra_tensors(self):
+        return {}
+
+    def _state_repack(self):
+        for mod in self._state_modules().values():
+            mod.repack()
+
+    def _state_zero_scratch(self):
+        pass
+
+    def _state_tensors(self):
+        """{key: device tensor} of every tensor the state holds, in a fixed order"""
+        out = {}
+        for name, mod in self._state_modules().items():
+            for k, v in mod.state_dict().items():
+                out[f"modules.{name}.{k}"] = v
+        out.update(self._state_extra_tensors())
+        for name, (m, v) in self._state_moments().items():
+            out[f"adam.{name}.m"] = m
+            out[f"adam.{name}.v"] = v
+        out["adam.steps"] = self.steps
+        return out
+
+    def _state_spec(self):
+        spec = {k: tuple(v.shape) for k, v in self._state_tensors().items()}
+        if self.inputs is not None:
+            spec.update({"inputs.seed": None, "inputs.step": None, "inputs.sampling": None, "inputs.flip": None})
+        if self.log is not None:
+            spec.update({"log.head": None, "log.first_nonfinite": None})
+        return spec
+
+    def _state_dtype(self):
+        return next(iter(self._state_modules().values())).compute_dtype
+
+    def state_dict(self):
+        torch.cuda.synchronize()
+        sd = {k: v.detach().to("cpu", copy=True) for k, v in self._state_tensors().items()}
+        if self.inputs is not None:
+            sd["inputs.seed"] = int(self.inputs.seed)
+            sd["inputs.step"] = int(self.inputs.step.item())
+            sd["inputs.sampling"] = str(self.inputs.sampling)
+            sd["inputs.flip"] = int(bool(getattr(self.inputs, "flip", False)))
+        if self.log is not None:
+            sd["log.head"] = int(self.log.head.item())
+            sd["log.first_nonfinite"] = int(self.log.first_nonfinite.item())
+        lr = self.lr if isinstance(self.lr, (tuple, list)) else (self.lr,)
+        sd.update({"meta.kind": self.STATE_KIND, "meta.dtype": DTYPE_NAMES[self._state_dtype()], "meta.lr": [float(x) for x in lr],
+                   "meta.betas": [float(x) for x in self.betas], "meta.format": STATE_FORMAT})
+        return sd
+
+    def load_state_dict(self, sd, _skip_repack=False):
+        """``_skip_repack``: test-only -- leaves the packed panels as they are, to show that they are state of their own"""
+        validate_state(sd, self.STATE_KIND, self._state_spec())
+        if self.inputs is not None:
+            # the seed and the sampling mode are host values baked into a captured iteration: they must agree, only the counter moves
+            for key, have in (("inputs.seed", int(self.inputs.seed)), ("inputs.sampling", str(self.inputs.sampling)),
+                              ("inputs.flip", int(bool(getattr(self.inputs, "flip", False))))):
+                if sd[key] != have:
+                    raise ValueError(f"{key}: {sd[key]!r} in the state, {have!r} in the attached sampler")
+        torch.cuda.synchronize()
+        with torch.no_grad():
+            for k, dst in self._state_tensors().items():
+                dst.copy_(sd[k].to(dst.dtype))
+            if self.inputs is not None:
+                self.inputs.step.fill_(int(sd["inputs.step"]))
+            if self.log is not None:
+                self.log.load(sd["log.head"], sd["log.first_nonfinite"])
+            self._state_zero_scratch()
+        if not _skip_repack:
+            self._state_repack()
+        torch.cuda.synchronize()
+
+
+class ResidentStep(TrainerState):
     """capture / replay plumbing shared by the small-network trainers (``_step_body`` = one iteration on the static input slots)"""
 
     inputs = None
     graph = None
+    log = None
 
     def _step_with_inputs(self):
         if self.inputs is not None:
             self.inputs.enqueue(self)
         self._step_body()
+        if self.log is not None:                        # behind the body's joins, on the main stream: the row of THIS iteration
+            self.log.append()
 
-    def capture(self, warmup=False, inputs=None):
+    def capture(self, warmup=False, inputs=None, log=None):
         """Capture the iteration into one hipGraph; with ``inputs`` (a DeviceSampler of this trainer's module) the graph first draws
-        the batch on the device, so a replay is a complete loop iteration without host work."""
+        the batch on the device, so a replay is a complete loop iteration without host work.  ``log`` (a LossLog): the graph ends with
+        the append of the iteration's loss row."""
         if warmup:
             self._step_body()
         if inputs is not None:
             self.inputs = inputs
+        if log is not None:
+            self.log = log
         return capture_step(self, self._step_with_inputs)
 
     def step_resident(self):

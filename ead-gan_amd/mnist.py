@@ -614,6 +614,18 @@ class MnistTrainer(ResidentStep):
         l = self.step_resident().tolist()
         return {"g_loss": l[0], "d_loss": l[1], "info_loss": l[2]}
 
+    # -- full state (engine.TrainerState) -------------------------------------------------------------
+    STATE_KIND = "mnist"
+
+    def _state_modules(self):
+        return {"G": self.G, "D": self.D, "E": self.E}
+
+    def _state_extra_tensors(self):
+        return {"modules.approx.blob": self.mlp}          # the frozen approximator the affine regulariser reads
+
+    def _state_moments(self):
+        return {"G": (self.mG, self.vG), "D": (self.mD, self.vD), "iG": (self.miG, self.viG), "iE": (self.miE, self.viE)}
+
 
 class DeviceInputs(DeviceSampler):
     """Device-side replacement of the MNIST loop's host input work (MNIST/EAD-GAN_rpqmnxy.py:233-246 DataLoader + Resize(32) + ToTensor +

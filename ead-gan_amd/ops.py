@@ -819,3 +819,9 @@ def score_col_std(x, n, ncol, out):
 
 def score_fvae_votes(x, L, M, ncol, eval_std, labels, nlab, predict, votes):
     lib().call("eg_score_fvae_votes", _p(x), L, M, ncol, _p(eval_std), _p(labels), nlab, _p(predict), _p(votes), _stream())
+
+
+# ---- device loss log of a training run (engine.LossLog) ----------------------------------------------
+def runlog_append(losses, n, ring, capacity, head, first_nonfinite):
+    """row head % capacity of ring[capacity][n] <- losses[:n]; head += 1; the first non-finite iteration (1-based) latched"""
+    lib().call("eg_runlog_append", _p(losses), int(n), _p(ring), int(capacity), _p(head), _p(first_nonfinite), _stream())

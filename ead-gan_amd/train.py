@@ -1,0 +1,285 @@
+"""Training runs: the part of the reference's scripts below the loop body -- progress lines, sample grids, checkpoint files
+(celebA/EAD-GAN_celebA.py:403-423, MNIST/EAD-GAN_rpqmnxy.py:451-466, dSprites/rp.py:486-509, colored_dSprites/rp_color.py:518-541,
+dSprites/pxy.py:189-205, colored_dSprites/pxy_color.py:218-234) -- around the fused trainers' ``step_resident()``, with a loss log that
+lives on the device (engine.LossLog, written inside the captured iteration) and a full-state checkpoint from which a run continues bit
+for bit (``trainer.state_dict()``).  The loop only enqueues; every blocking wait goes through ``TrainRun._wait`` and is recorded.
+Single process only."""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+import torch
+
+from . import ops, sampling
+from .engine import LossLog
+
+# One row per script.  print: the progress line's cadence; fmt: its format string, character for character; cols: which entries of the
+# trainer's loss row fill it; sample / ckpt: multiples of ``sample_interval`` (None: the script's sample_image is not restated);
+# minmax: labels of the four extra print lines of the dSprites scripts; interval: the script's --sample_interval default.
+_HEAD = "[Epoch %d/%d] [Batch %d/%d] "
+_RUNS = {
+    "celeba": dict(print=10, fmt=_HEAD + "[D loss: %f] [G loss: %f]", cols=(1, 0), sample=1, ckpt=15, grid="celeba_train", interval=4000,
+                   minmax=None),                                                                    # celebA/EAD-GAN_celebA.py:404-414
+    "mnist": dict(print=100, fmt=_HEAD + "[D loss: %f] [G loss: %f] [info loss: %f]", cols=(1, 0, 2), sample=1, ckpt=10, grid="mnist_train",
+                  interval=4000, minmax=None),                                                      # MNIST/EAD-GAN_rpqmnxy.py:453-462
+    "dsprites": dict(print=100, fmt=_HEAD + "[D loss: %f] [G loss: %f] [info cat loss: %f] [info cont loss: %f] [affine loss: %f] "
+                                            "[relative_cat_loss: %f] ", cols=(0, 1, 5, 6, 3, 4), sample=2, ckpt=500, grid="dsprites_train",
+                     interval=1000, minmax="trans_img_affine"),                                     # dSprites/rp.py:491-507
+    "colored": dict(print=100, fmt=_HEAD + "[D loss: %f] [G loss: %f] [info cat loss: %f] [info cont loss: %f] [affine_color loss: %f] "
+                                           "[relative_cat_loss: %f] ", cols=(0, 1, 5, 6, 3, 4), sample=2, ckpt=50, grid="colored_train",
+                    interval=1000, minmax="trans_img_affine_color"),                                # colored_dSprites/rp_color.py:523-539
+    "pxy": dict(print=100, fmt=_HEAD + "[D loss: %f]", cols=(0,), sample=None, ckpt=50, grid=None, interval=1000, minmax=None),   # dSprites/pxy.py:194-204
+    "pxy_color": dict(print=100, fmt=_HEAD + "[D loss: %f]", cols=(0,), sample=None, ckpt=10, grid=None, interval=1000,
+                      minmax=None),                                                                 # colored_dSprites/pxy_color.py:223-233
+}
+KINDS = tuple(_RUNS)
+WAIT_REASONS = ("ring-full", "sample", "checkpoint", "end")
+
+
+class NonFiniteLoss(RuntimeError):
+    """a loss of iteration ``iteration`` (1-based, as the device log latches it) was NaN or infinite; nothing was saved afterwards"""
+
+    def __init__(self, iteration):
+        super().__init__(f"non-finite loss first seen at iteration {iteration}")
+        self.iteration = int(iteration)
+
+
+def _plan(kind):
+    if kind not in _RUNS:
+        raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
+    return _RUNS[kind]
+
+
+def cadence(kind, batches_done, sample_interval=None):
+    """-> (print?, sample?, checkpoint?) for the iteration that has just run: the scripts' ``batches_done % k == 0`` tests, so iteration
+    0 prints, samples and saves"""
+    p = _plan(kind)
+    si = p["interval"] if sample_interval is None else int(sample_interval)
+    return (batches_done % p["print"] == 0,
+            p["sample"] is not None and batches_done % (si * p["sample"]) == 0,
+            batches_done % (si * p["ckpt"]) == 0)
+
+
+def loader_len(n_images, batch_size):
+    """len(DataLoader(dataset, batch_size)) with drop_last=False"""
+    return -(-int(n_images) // int(batch_size))
+
+
+def progress_line(kind, batches_done, n_epochs, n_images, batch_size, row):
+    """the script's progress line for the iteration ``batches_done`` with the loss row the trainer wrote in it"""
+    p = _plan(kind)
+    L = loader_len(n_images, batch_size)
+    return p["fmt"] % ((batches_done // L, n_epochs, batches_done % L, L) + tuple(float(row[c]) for c in p["cols"]))
+
+
+def minmax_lines(kind, vals):
+    """the four extra lines of the dSprites scripts (rp.py:498-501): ``vals`` = (trans min, trans max, gen min, gen max).  The values
+    print as torch prints a 0-dim device tensor (the reference's gen_imgs lines also carry a grad_fn, which is not restated)."""
+    name = _plan(kind)["minmax"]
+    t = lambda v: str(torch.tensor(float(v), dtype=torch.float32))[:-1] + ", device='cuda:0')"
+    return [f"{name} max {t(vals[1])}", f"gen_imgs max {t(vals[3])}", f"{name} min {t(vals[0])}", f"gen_imgs min {t(vals[2])}"]
+
+
+_FILES = {"celeba": ("checkpoint_%d.tar",), "mnist": ("generator_%d.pt", "encoder_%d.pt"), "dsprites": ("encoder_%d.pt", "generator_%d.pt"),
+          "colored": ("encoder_%d.pt", "generator_%d.pt"), "pxy": ("encoder_pxy_%d.pt",), "pxy_color": ("encoder_pxy_color_%d.pt",)}
+
+
+def checkpoint_files(kind, batches_done):
+    """names of the reference-format files one checkpoint iteration writes (celebA.py:415, rpqmnxy.py:465-466, rp.py:508-509,
+    rp_color.py:540-541, pxy.py:205, pxy_color.py:234)"""
+    _plan(kind)
+    return [n % batches_done for n in _FILES[kind]]
+
+
+def sample_seed(seed, batches_done):
+    """seed of the sample grids' numpy draws: a function of (run seed, iteration), so a resumed run writes the same PNG bytes"""
+    return (int(seed) * 1000003 + int(batches_done) * 7919 + 12345) % (2 ** 32)
+
+
+class TrainRun:
+    """``run(max_iters=None)`` continues from ``batches_done`` until ``n_epochs`` epochs of ``ceil(N / B)`` iterations are done or
+    ``max_iters`` more iterations ran; ``save()`` writes ``run_state_<batches_done>.pt``; ``TrainRun.resume(path, ...)`` continues such a
+    file on a fresh trainer.  ``graph=True``: the iteration (input draws, step, log append) is captured into one hipGraph;
+    engine.CaptureFailed propagates (no in-process fallback).  ``log_in_graph=False``: the trainer runs without the log (its
+    graph is node for node the one ``capture(inputs=...)`` alone gives) and the loop enqueues the append after every iteration -- the
+    trade for the small-network steps, where the log's launches are measurable; the dSprites lines then print 0 for the two
+    separate info terms, which only a trainer with a log computes."""
+
+    def __init__(self, kind, trainer, inputs, out_dir, n_epochs, sample_interval=None, seed=0, graph=True, log_capacity=1024, log_in_graph=True):
+        self.plan = _plan(kind)
+        if getattr(trainer, "STATE_KIND", None) != kind:
+            raise ValueError(f"a {kind!r} run needs a {kind!r} trainer, got {type(trainer).__name__}")
+        if getattr(trainer, "allreduce", None) is not None or getattr(trainer, "sync_bn", None) is not None:
+            raise NotImplementedError("training runs are single process: a trainer with allreduce / sync_bn is not supported (DESIGN 5)")
+        self.kind, self.trainer, self.inputs, self.out_dir = kind, trainer, inputs, str(out_dir)
+        self.n_epochs = int(n_epochs)
+        self.sample_interval = self.plan["interval"] if sample_interval is None else int(sample_interval)
+        self.seed, self.graph, self.log_in_graph = int(seed), bool(graph), bool(log_in_graph)
+        self.log = LossLog(trainer, log_capacity)
+        self.n_images = int(inputs.data.shape[0])
+        self.L = loader_len(self.n_images, trainer.B)
+        self.batches_done = 0
+        self.history = np.zeros((0, self.log.n), np.float32)       # loss rows of the iterations [0, len)
+        self.lines = []                                             # every line printed so far
+        self.waits = []
+        self.files = []                                             # reference-format files and run states written by this object
+        self._prints = []                                           # (iteration, slot of its min / max values or None) not printed yet
+        self._prepared = False
+        self._enqueued = 0
+        os.makedirs(self.out_dir, exist_ok=True)
+        trainer.inputs, trainer.log = inputs, (self.log if self.log_in_graph else None)
+        if self.plan["minmax"]:
+            dev = trainer.losses.device
+            self._mm_dev = torch.zeros(4, device=dev, dtype=torch.float32)
+            self._mm_ws = torch.empty(ops.minmax_ws_floats(), device=dev, dtype=torch.float32)
+            self._mm_host = torch.zeros(256, 4, dtype=torch.float32).pin_memory()
+            self._mm_n = 0
+
+    # -- host discipline ----------------------------------------------------------------------------
+    def _wait(self, reason):
+        """THE blocking wait of a run: drains the device, brings the loss log up to date, prints what is due"""
+        assert reason in WAIT_REASONS, reason
+        self.waits.append(reason)
+        torch.cuda.synchronize()
+        self.log.flush_async()
+        self.log.wait()
+        self._collect()
+
+    def _collect(self):
+        """take the rows of a landed copy (never blocks), print the lines whose rows are there, end the run on a non-finite loss"""
+        if not self.log.landed():
+            return
+        head = self.log.mirror_head
+        have = len(self.history)
+        if head > have:
+            if head - have > self.log.capacity:
+                raise RuntimeError(f"loss log overrun: {head - have} rows since the last flush, capacity {self.log.capacity}")
+            self.history = np.concatenate((self.history, self.log.rows(since=have)), 0)
+        while self._prints and self._prints[0][0] < len(self.history):
+            it, slot = self._prints.pop(0)
+            out = [progress_line(self.kind, it, self.n_epochs, self.n_images, self.trainer.B, self.history[it])]
+            if slot is not None:
+                out += minmax_lines(self.kind, self._mm_host[slot].tolist())
+            for ln in out:
+                print(ln, flush=True)
+            self.lines += out
+        if self.log.mirror_flag:
+            raise NonFiniteLoss(self.log.mirror_flag)
+
+    # -- pieces of an iteration's tail ----------------------------------------------------------------
+    def _queue_print(self, it):
+        slot = None
+        if self.plan["minmax"]:
+            tr = self.trainer
+            slot = self._mm_n % self._mm_host.shape[0]
+            self._mm_n += 1
+            ops.minmax_f32(tr.trans2, tr.trans2.numel(), self._mm_ws, self._mm_dev[0:2])
+            ops.minmax_f32(tr.ge2.img, tr.ge2.img.numel(), self._mm_ws, self._mm_dev[2:4])
+            self._mm_host[slot].copy_(self._mm_dev, non_blocking=True)        # lands before the flush that brings this iteration's row
+        self._prints.append((it, slot))
+
+    def _sample(self, it):
+        tr = self.trainer
+        real, trans = {"celeba": lambda: (tr.real, tr.scaled), "mnist": lambda: (tr.real, tr.scaled),
+                       "dsprites": lambda: (tr.align, tr.trans2), "colored": lambda: (tr.align, tr.trans2)}[self.kind]()
+        rng = np.random.RandomState(sample_seed(self.seed, it))
+        self.files += sampling.sample_image(self.plan["grid"], tr.G, n=10, batches_done=it, real=real[:100], trans=trans[:100],
+                                            out_dir=self.out_dir, rng=rng, device=tr.losses.device)
+
+    def _checkpoint(self, it):
+        tr, od = self.trainer, self.out_dir
+        names = [os.path.join(od, n) for n in checkpoint_files(self.kind, it)]
+        if self.kind == "celeba":
+            sampling.save_checkpoint(names[0], tr.G, tr.D, it // self.L, it)
+        elif self.kind == "mnist":
+            torch.save(tr.G.state_dict(), names[0])
+            torch.save(tr.E.state_dict(), names[1])
+        elif self.kind in ("dsprites", "colored"):
+            torch.save(tr.E.state_dict(), names[0])
+            torch.save(tr.G.state_dict(), names[1])
+        else:
+            torch.save(tr.P.state_dict(), names[0])
+        self.files += names
+
+    def _prepare(self):
+        tr = self.trainer
+        tr.inputs, tr.log = self.inputs, (self.log if self.log_in_graph else None)
+        if self.graph and tr.graph is None:
+            # capture(warmup=True) is a real training step on the current slots: run it on a saved state and put that state back
+            sd = tr.state_dict()
+            self.inputs.enqueue(tr)                      # a real batch in the slots for the warm-up iteration
+            tr.capture(warmup=True, inputs=self.inputs, log=tr.log)
+            tr.load_state_dict(sd)
+        # the log numbers its rows like the run numbers its iterations
+        if len(self.history) < self.batches_done:
+            self.history = np.concatenate((self.history, np.zeros((self.batches_done - len(self.history), self.log.n), np.float32)), 0)
+        self.log.load(self.batches_done, int(self.log.first_nonfinite.item()))
+        self._enqueued = self.batches_done
+        self._prepared = True
+
+    # -- public ---------------------------------------------------------------------------------------
+    def run(self, max_iters=None):
+        if not self._prepared or self._enqueued != self.batches_done or len(self.history) > self.batches_done:
+            self.history = self.history[:self.batches_done]
+            self._prepare()
+        tr, log = self.trainer, self.log
+        total = self.n_epochs * self.L
+        done = 0
+        while self.batches_done < total and (max_iters is None or done < max_iters):
+            it = self.batches_done
+            if self._enqueued - len(self.history) >= log.capacity:       # the next append would overwrite a row not yet taken
+                self._wait("ring-full")
+            tr.step_resident()
+            if not self.log_in_graph:
+                log.append()
+            self._enqueued += 1
+            do_print, do_sample, do_ckpt = cadence(self.kind, it, self.sample_interval)
+            if do_print:
+                self._queue_print(it)
+            if log.landed() and (do_print or self._enqueued - log.mirror_head >= log.capacity // 2):
+                log.flush_async()
+            self._collect()
+            if do_sample:
+                self._wait("sample")
+                self._sample(it)
+            if do_ckpt:
+                self._wait("checkpoint")
+                self._checkpoint(it)
+            self.batches_done = it + 1
+            done += 1
+            if do_ckpt:
+                self._write_state()
+        self._wait("end")
+        self.save()
+        return self
+
+    def _write_state(self):
+        sd = self.trainer.state_dict()
+        sd["run.kind"] = self.kind
+        sd["run.batches_done"] = int(self.batches_done)
+        sd["run.losses"] = torch.from_numpy(self.history[:self.batches_done].copy())
+        path = os.path.join(self.out_dir, f"run_state_{self.batches_done}.pt")
+        torch.save(sd, path)
+        np.save(os.path.join(self.out_dir, "losses.npy"), self.history[:self.batches_done])
+        self.files.append(path)
+        return path
+
+    def save(self):
+        """``out_dir/run_state_<batches_done>.pt``: the trainer's full state, ``batches_done`` and the loss rows so far; and
+        ``out_dir/losses.npy``"""
+        if len(self.history) < self.batches_done:
+            self._wait("end")
+        return self._write_state()
+
+    @classmethod
+    def resume(cls, path, kind, trainer, inputs, out_dir, n_epochs, **kw):
+        """continue the run saved in ``path`` on a (fresh or used) trainer of the same kind with a sampler of the same seed"""
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        if sd.get("run.kind") != kind:
+            raise ValueError(f"run.kind: {sd.get('run.kind')!r} in the file, {kind!r} asked for")
+        run = cls(kind, trainer, inputs, out_dir, n_epochs, **kw)
+        trainer.load_state_dict(sd)
+        run.batches_done = int(sd["run.batches_done"])
+        run.history = sd["run.losses"].numpy().astype(np.float32).reshape(-1, run.log.n)
+        return run

@@ -584,6 +584,13 @@ int eg_score_col_std(const double* x, int n, int ncol, double* out, eg_stream_t 
 int eg_score_fvae_votes(const double* x, int L, int M, int ncol, const double* eval_std, const int* labels, int nlab, int* predict,
                         long long* votes, eg_stream_t s);
 
+/* --- device loss log of a training run: replaces the `.item()` calls of the reference's progress lines --
+ * celebA/EAD-GAN_celebA.py:404-408, MNIST/EAD-GAN_rpqmnxy.py:453-457, dSprites/rp.py:491-496, colored_dSprites/rp_color.py:523-528,
+ * dSprites/pxy.py:194-198, colored_dSprites/pxy_color.py:223-227 -- with one small launch inside the (captured) iteration:
+ * row head[0] % capacity of ring[capacity][n] <- losses[0..n), then head[0] += 1 (head counts the iterations ever logged); if a value is
+ * NaN or +-Inf and first_nonfinite[0] == 0, first_nonfinite[0] <- the 1-based iteration (sticky).  1 <= n <= 64.  No allocation, no sync. */
+int eg_runlog_append(const float* losses, int n, float* ring, int capacity, int* head, int* first_nonfinite, eg_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
