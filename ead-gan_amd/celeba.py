@@ -10,7 +10,6 @@ parameter containers so that ``state_dict()`` keys, shapes and default initialis
 from __future__ import annotations
 
 import argparse
-import os
 
 import numpy as np
 
@@ -19,34 +18,19 @@ import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
 from . import ops
-from .engine import Arena, ConvRec, SideStream, TrainerState, Workspace, capture_step, check_usable, parse_dtype
+from .engine import FUSE_DRAWS, Arena, ConvRec, SideStream, TrainerState, Workspace, capture_step, check_usable, parse_dtype
 from .ops import (ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH, EG_BF16, EG_F32, OUT_NCHW_F32)
 
 # module-level hyper-parameters, mirroring the reference's global ``opt`` (argparse defaults, :39-51)
 opt = argparse.Namespace(n_epochs=50, batch_size=16, lr=0.0002, b1=0.5, b2=0.999, n_cpu=8, latent_dim=200, code_dim=8,
                          n_classes=10, img_size=64, channels=3, sample_interval=4000)
 
-# image-side transposed convolutions (128 -> C) as one GEMM + col2im gather (1) or as the 4-phase implicit GEMM (0)
-IMG_GEMM = os.environ.get("EG_IMG_GEMM", "1") == "1"
-
-# the iteration's head (device-side draws, gather, affine matrix + warp) as 3 launches instead of 11 (same values)
-FUSE_INPUTS = os.environ.get("EG_FUSE_INPUTS", "1") != "0"
-
-# image-side convolutions (first D layer forward, input gradient of G's last layer) straight from the fp32 images on the MFMA units
-# (ops.conv_img_mfma) instead of patch rows in HBM + a K = 64 GEMM; the patch rows remain for the weight gradients, off the main chain
-IMG_DIRECT = os.environ.get("EG_IMG_DIRECT", "1") != "0"
-
-# column statistics (BatchNorm batch statistics / backward sums, bias gradient + spectral-norm coefficient) taken from the epilogue of the
-# convolution that produces the tensor (eg_epilogue.stat_mode) instead of by kernels that re-read it; 0: the stand-alone kernels (A/B runs)
-FUSE_STATS = os.environ.get("EG_FUSE_STATS", "1") != "0"
-
-# the discriminator's head with the sub-step's losses and the head's input gradient in two launches (K-sliced dense head; eg_head_fused: slice
-# combine + losses + dense backward, the affine term's Jacobian spread over lanes) instead of four or five on the main chain; same bits;
-# EG_FUSE_HEAD=0: the separate launches
-FUSE_HEAD = os.environ.get("EG_FUSE_HEAD", "1") != "0"
+# Reference paths the tests compare the production ones against (they monkeypatch these; nothing else changes them).
+# image-side transposed convolutions (128 -> C) as one GEMM + col2im gather (True) or as the 4-phase implicit GEMM (False)
+IMG_GEMM = True
 # optimizer.step() of a convolution weight and the refresh of its packed panels as ONE launch per layer (ops.adam_pack_conv / adam_pack_rows);
-# 0: one Adam launch over the arena (or bucket) followed by the re-packing launches (A/B runs; same bits either way)
-FUSE_ADAM = os.environ.get("EG_FUSE_ADAM", "1") != "0"
+# False: one Adam launch over the arena (or bucket) followed by the re-packing launches (same bits either way)
+FUSE_ADAM = True
 
 
 def adam_bucket(eng, arena, tag, lo, hi, m, v, lr, betas, step, zero):
@@ -145,7 +129,7 @@ class _GenEngine:
         """(nrb, buffer) if the launch described by (c, bwd, ep) can take its column statistics in the epilogue, else (0, None).  Asked
         once per layer with the very epilogue the launch uses (same hints, same split-K scratch)."""
         if key not in self._stat:
-            nrb = ops.conv_stat_blocks(c, self.dtype, bwd, ep) if FUSE_STATS else 0
+            nrb = ops.conv_stat_blocks(c, self.dtype, bwd, ep)
             self._stat[key] = (nrb, torch.empty(2 * C * nrb, device=self.inp.device, dtype=torch.float32) if nrb else None)
         return self._stat[key]
 
@@ -223,7 +207,7 @@ class _GenEngine:
             else:
                 ops.bn_fwd_eval(dt, self.z[i], self.a[i], M, W[i + 1], bn.weight, bn.bias, bn.eps, bn.running_mean, bn.running_var, small, ACT_RELU)
             x = self.a[i]
-        if IMG_GEMM and IMG_DIRECT and ops.convt_img_mfma_ok(dt, self.gen.channels, self.l4g.H, self.l4g.W, G_WIDTHS[3], 4, 2, 1):
+        if IMG_GEMM and ops.convt_img_mfma_ok(dt, self.gen.channels, self.l4g.H, self.l4g.W, G_WIDTHS[3], 4, 2, 1):
             # the last transposed convolution + Tanh in one launch: the GEMM's 48 columns per pixel stay in LDS
             ops.convt_img_mfma(dt, x, self.l4g.wp_fwd, self._p(10, "bias"), self.img, B, self.gen.channels, self.l4g.H, self.l4g.W, ACT_TANH, 0.0)
         elif IMG_GEMM:
@@ -247,7 +231,7 @@ class _GenEngine:
             else:
                 side.defer(lane, fn, tag)
 
-        direct = IMG_DIRECT and ops.conv_img_mfma_ok(dt, C, S, S, W[3], 4, 2, 1)
+        direct = ops.conv_img_mfma_ok(dt, C, S, S, W[3], 4, 2, 1)
         if not direct:
             # tanh backward fused with the bias gradient of the last ConvTranspose2d
             ops.act_grad_mul_bias_nchw(dimg, self.img, self.dimg_z, B, C, S * S, ACT_TANH, 0.0, ws.small, gof("conv_blocks.10.bias"))
@@ -266,7 +250,7 @@ class _GenEngine:
             # d(a) = Conv2d(C -> 128, 4, 2, 1) of d(img) * tanh'(img): straight from the two fp32 images, no patch rows -- and, in the same
             # launch, dy = da * relu'(bn(z)) with the two sums of the last BatchNorm layer's backward
             ep4 = None
-            if FUSE_STATS and sync is None:
+            if sync is None:
                 if "bwd2" not in self._stat:
                     nrb = ops.conv_img_mfma_stat_blocks(B, S, S)
                     self._stat["bwd2"] = (nrb, torch.empty(2 * W[3] * nrb, device=self.inp.device, dtype=torch.float32))
@@ -485,7 +469,7 @@ class _DiscEngine:
         self.coef = [torch.zeros(4, device=dev, dtype=torch.float32) for _ in range(4)]
         self.imgs = [None] * NT
         self.patch_ok = [False] * NT                    # tape has its patch rows (the weight gradient of layer 0 reads them)
-        self.img_direct = IMG_DIRECT and ops.conv_img_mfma_ok(dtype, C, S, S, W[0], 4, 2, 1)
+        self.img_direct = ops.conv_img_mfma_ok(dtype, C, S, S, W[0], 4, 2, 1)
         self._stat = {}                                 # (layer, T) -> (row blocks, buffer) of the fused bias-gradient / coefficient sums
         self._sn_arrays = None
         self._sn(0)
@@ -501,7 +485,6 @@ class _DiscEngine:
                 self._sn_arrays.append(ops.sn_layers(ent))
             # own scratch: the power iterations may run on a side stream while the main stream uses the shared workspace
             self.sn_scratch = torch.empty(ops.sn_multi_ws_floats(self._sn_arrays[0]), device=self.ws.device, dtype=torch.float32)
-            self.sn_counters = torch.zeros(16, device=self.ws.device, dtype=torch.int32)      # arrival counters of the two-launch iteration
         return self._sn_arrays[t]
 
     def _m(self, i):
@@ -543,14 +526,14 @@ class _DiscEngine:
         (row blocks, buffer), (0, None) where that launch cannot take them (see _GenEngine._stat_buf)"""
         key = (i, T)
         if key not in self._stat:
-            ok = FUSE_STATS and self.rows(i + 1) % 256 == 0
+            ok = self.rows(i + 1) % 256 == 0
             nrb = ops.conv_stat_blocks(c, self.dtype, True, ep) if ok else 0
             N = D_WIDTHS[i]
             self._stat[key] = (nrb, torch.empty(N * nrb + nrb * (N // 128), device=self.out.device, dtype=torch.float32) if nrb else None)
         return self._stat[key]
 
     def _sn_tape(self, t, training=True):
-        ops.sn_power_iter_multi(self._sn(t), self.sn_scratch, training, SN_EPS, self.sn_counters)
+        ops.sn_power_iter_multi(self._sn(t), self.sn_scratch, training, SN_EPS)
         if not training:
             for i in range(4):
                 self.u[i][t].copy_(self._m(i).weight_u)
@@ -605,7 +588,7 @@ class _DiscEngine:
         return out
 
     def head_fused_ok(self, T):
-        return FUSE_HEAD and ops.head_fused_ok(self.dtype, T, 16 * D_WIDTHS[3], self.nout)
+        return ops.head_fused_ok(self.dtype, T, 16 * D_WIDTHS[3], self.nout)
 
     def head_losses(self, t0, T, dout, loss, targets=None, scales=None, info=None):
         """The head of tapes t0..t0+T-1 (after ``forward(..., head=False)``), their losses (added to ``loss[0]``), ``dout`` = d(loss)/d(head
@@ -682,7 +665,7 @@ class _DiscEngine:
                     kw.update(stat_mode=ops.STAT_SN_BIAS, stat_out=fused[1], stat_p=(self._m(i - 1).bias,), stat_slope=LRELU_SLOPE)
                 ops.conv_bwd_data(geo, dt, sl(self.dz[i]), self.mid[i - 1].wp_bwd, sl(self.dz[i - 1]), ops.epilogue(**kw))
         if need_dimg:
-            if IMG_GEMM and IMG_DIRECT and ops.convt_img_mfma_ok(dt, self.C, self.S // 2, self.S // 2, W[0], 4, 2, 1):
+            if IMG_GEMM and ops.convt_img_mfma_ok(dt, self.C, self.S // 2, self.S // 2, W[0], 4, 2, 1):
                 ops.convt_img_mfma(dt, sl(self.dz[0]), self.l1g.wp_fwd, None, self.dimg, B, self.C, self.S // 2, self.S // 2, ACT_NONE, 0.0)
             elif IMG_GEMM:
                 ops.conv_fwd(self.l1g.c, dt, sl(self.dz[0]), self.l1g.wp_fwd, self.cols1, None)
@@ -929,7 +912,7 @@ class DeviceInputs:
         if self.idx is None or self.idx.numel() != B:
             self.idx = torch.empty(B, device=self.data.device, dtype=torch.int64)
             self.flips = torch.empty(B, device=self.data.device, dtype=torch.uint8)
-        if FUSE_INPUTS:
+        if FUSE_DRAWS:
             # the five draws + the one-hot labels as one launch, the counter tick inside the gather: 3 launches instead of 8 at the head of
             # the iteration's critical chain (the same values: a draw depends on (element, step, stream id, seed) only)
             first = (ops.RNG_EPOCH_PERM, self.idx, N, 0, 1) if self.sampling == "permutation" else (ops.RNG_RANDINT, self.idx, 0, N, 1)
@@ -1009,7 +992,7 @@ class CelebATrainer(TrainerState):
         self.log = None
         # weight-gradient chains and re-packing run on a second stream beside the backward-data chain (same arithmetic, same order
         # inside every chain -> bit-identical results with and without)
-        self.side = SideStream(dev, Workspace.get(dev), lanes=int(os.environ.get("EG_LANES", "4"))) if overlap else None
+        self.side = SideStream(dev, Workspace.get(dev), lanes=4) if overlap else None
 
     # -- the hot path ---------------------------------------------------------------------------------
     def _buckets(self, arena):
@@ -1045,7 +1028,7 @@ class CelebATrainer(TrainerState):
     def _inputs_head(self):
         G, B = self.G, self.B
         # A = get_matrix(code[:, :5]); scaled = trans_2D(real, A[:, 0:2])           (:325-327)
-        if FUSE_INPUTS and (G.img_size * G.img_size) % 256 == 0:
+        if FUSE_DRAWS and (G.img_size * G.img_size) % 256 == 0:
             ops.warp_affine_rpqxy(self.real, self.code, G.code_dim, self.theta, self.scaled, B, G.channels, G.img_size, G.img_size, zero=self.losses)
             return
         ops.fill_f32(self.losses)
@@ -1263,7 +1246,7 @@ class CelebATrainer(TrainerState):
         de.backward(0, 2, self.dout[:2 * B], da.grad, side=side, head_done=fh1)
         update(da, self.mD, self.vD, self.lr[1], 1, True, True, de, key_w="dw")             # beside step 3's generator forward
 
-        # the first layer reads the images themselves (IMG_DIRECT): the patch rows are only the weight gradient's operand and are built by
+        # the first layer reads the images themselves (ops.conv_img_mfma): the patch rows are only the weight gradient's operand and are built by
         # its own chain in step 3's backward -- not here, on the chain step 3's discriminator forward waits for
         lazy = de.img_direct
 
@@ -1353,11 +1336,10 @@ class CelebATrainer(TrainerState):
         return {"G": (self.mG, self.vG), "D": (self.mD, self.vD), "iG": (self.miG, self.viG), "iD": (self.miD, self.viD)}
 
     def _state_zero_scratch(self):
-        # scratch whose contract is "left at zero" by every launch that uses it: arrival counters of the fused head and of the
-        # two-launch power iteration.  Zero at every iteration boundary already; cleared so that a load never depends on that.
+        # scratch whose contract is "left at zero" by every launch that uses it: arrival counters of the fused head.  Zero at every
+        # iteration boundary already; cleared so that a load never depends on that.
         if self.de._head_scratch is not None:
             self.de._head_scratch[1].zero_()
-        self.de.sn_counters.zero_()
 
     def step_resident(self):
         """Run one iteration on whatever is in the static input slots (or on fresh device-side draws if the trainer was captured /

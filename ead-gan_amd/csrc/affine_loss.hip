@@ -753,7 +753,7 @@ __global__ __launch_bounds__(1024) void affine_reg_rp_kernel(const float* __rest
 extern "C" int eg_loss_affine_rp(const float* o_real, const float* o_trans, int ld, int c0, int B, const float* code, int ldc, float scale,
                                  float* loss, float* d_real, float* d_trans, float* pred_out, eg_stream_t s) {
     EG_REQUIRE(o_real && o_trans && code && B > 0, "eg_loss_affine_rp: bad argument");
-    static const int cap = [] { const char* e = getenv("EG_AFFINE_THREADS"); const int v = e ? atoi(e) : 0; return v >= 64 && v <= 1024 ? v : 1024; }();
+    constexpr int cap = 1024;
     const int threads = B * 8 >= cap ? cap : ((B * 8 + 63) / 64) * 64;
     hipLaunchKernelGGL(affine_reg_rp_kernel, dim3(1), dim3(threads), 0, (hipStream_t)s, o_real, o_trans, ld, c0, B, code, ldc, scale, loss, d_real, d_trans, pred_out);
     EG_LAUNCH_CHECK();

@@ -7,7 +7,6 @@
 // Both run in fp32 (v_mfma_f32_16x16x4_f32, exact fp32) or bf16 (v_mfma_f32_16x16x32_bf16, fp32
 // accumulate).  K rows in LDS are always 128 bytes (32 fp32 / 64 bf16) and XOR-swizzled in 16-byte
 // chunks so that ds_read_b128 fragment reads are bank-conflict free without padding.
-#include <stdlib.h>
 #include <algorithm>
 #include <vector>
 #include <type_traits>
@@ -889,21 +888,19 @@ static NtPlan nt_plan_auto(const NtParams& p, int nphase, const NtFacts& f, size
     const long long wgs256 = (long long)cdiv(p.M, 256) * (p.N / 128) * nphase;
     const long long rounds = (wgs256 + 255) / 256;
     // Measured in the whole (overlapped) step, the big tile wins beyond the shapes where it wins back to back: S8 wherever it can run
-    // 4.70 ms, this rule set 4.76, 128 x 128 everywhere 4.93 (profiles/r02_r_ab_nt_variant.txt; EG_NT_AUTO_S8=0 restores the rule set)
-    static const bool all_s8 = [] { const char* e = getenv("EG_NT_AUTO_S8"); return !(e && atoi(e) == 0); }();
+    // 4.70 ms, this rule set 4.76, 128 x 128 everywhere 4.93 (profiles/r02_r_ab_nt_variant.txt)
     // (16-bit launches of at least 48 such tiles: below that -- the small networks' layers -- and in fp32 the rule set below stays ahead,
     //  profiles/r02_r_ab_auto_s8.txt)
     // fewer than ~200 tiles of 256 x 128 (the single-tape layers: 64 or 128 such tiles on 256 CUs): the same 8-wave design on 128 x 128
-    // tiles (igemm_nt8h) -- whole K loops in place of one K split level (profiles/r03_n_nt8h_layers.txt; EG_NT_AUTO_S8H=0: igemm_nt8s)
-    static const bool use_h = [] { const char* e = getenv("EG_NT_AUTO_S8H"); return !(e && atoi(e) == 0); }();
-    static const int h_below = [] { const char* e = getenv("EG_NT_S8H_BELOW"); return e ? atoi(e) : 200; }();
-    if (all_s8 && use_h && f.half && wgs256 >= 48 && wgs256 < h_below && f.nk_min >= 8)
+    // tiles (igemm_nt8h) -- whole K loops in place of one K split level (profiles/r03_n_nt8h_layers.txt)
+    constexpr int h_below = 200;
+    if (f.half && wgs256 >= 48 && wgs256 < h_below && f.nk_min >= 8)
         return {EG_NT_S8H, nt_splits(f.tiles128, 224, f.nk_min, part128, ws_bytes, splitk)};
-    if (all_s8 && f.half && wgs256 >= 48) return {EG_NT_S8, nt_splits(wgs256, 224, f.nk_min, part256, ws_bytes, splitk)};
+    if (f.half && wgs256 >= 48) return {EG_NT_S8, nt_splits(wgs256, 224, f.nk_min, part256, ws_bytes, splitk)};
     if (splitk <= 1 && f.nk_min >= 32 && wgs256 >= 200 && wgs256 * 100 >= rounds * 256 * 85) return {EG_NT_S8, 1};
     // split K only below one workgroup per CU: at 256..511 tiles the unsplit launch wins or ties (M=8192 N=512 K=4096: 52 vs 58 us,
     // the 4-phase M=2048 N=512 K=4096: 50 vs 48 us -- profiles/r02_i_t1_splits.txt) and saves the slab round trip and the epilogue launch
-    static const int split_below = [] { const char* e = getenv("EG_NT_SPLIT_BELOW"); return e ? atoi(e) : 256; }();
+    constexpr int split_below = 256;
     // ... except very long K loops (>= 128 K tiles: the 512 -> 1024 layer, K = 8192), which still gain from two splits at 256 tiles
     // (in-step 110 -> 79 us, profiles/r02_q_step_detail.txt)
     const bool long_k = f.nk_min >= 128 && f.tiles128 <= 256;         // (at 384 tiles the split loses: 143 vs 116 us)
@@ -938,14 +935,12 @@ static void launch_nt_cfg(const NtParams& p, int nphase, hipStream_t st) {
 }
 
 // K splits of the register-staged kernel (N = 32 / 64, NHWC output): few tiles and a deep K loop
-// EXPERIMENT, default off (EG_NT_REG_SPLIT=1 or eg_epilogue.nt_splitk > 1 turn it on): correct (tested) but slower in the small networks'
+// EXPERIMENT, off unless eg_epilogue.nt_splitk > 1 asks for it: correct (tested) but slower in the small networks'
 // steps -- dSprites 1.415 -> 1.503 ms, colored / MNIST +0.2-0.8 % (profiles/r03_zg_ab_reg_split.txt): the 16-48-tile launches it targets
 // are not the ~22 us the profiler shows for them once the profiler is off, and the split adds partial-tile traffic and a serial finish.
 template <typename T>
 static int nt_reg_splits(const NtParams& p, int nphase, int forced) {
-    static const bool env_on = [] { const char* e = getenv("EG_NT_REG_SPLIT"); return e && atoi(e) != 0; }();
-    const bool on = env_on || forced > 1;
-    if (!on || p.out_mode != EG_OUT_NHWC || !(p.N == 64 || p.N == 32) || (p.N % Elt<T>::VEC) != 0 || !p.part || p.part_bytes <= EG_SPLIT_CNT_BYTES) return 1;
+    if (forced <= 1 || p.out_mode != EG_OUT_NHWC || !(p.N == 64 || p.N == 32) || (p.N % Elt<T>::VEC) != 0 || !p.part || p.part_bytes <= EG_SPLIT_CNT_BYTES) return 1;
     const long long tiles = (long long)cdiv(p.M, 128) * nphase;
     int nk = 1 << 30;
     for (int i = 0; i < nphase; ++i) nk = std::min(nk, p.ph[i].Kpad / (8 * Elt<T>::VEC));
@@ -968,7 +963,6 @@ static void launch_splitk_epilogue(const NtParams& q, int nphase, int Mpad, hipS
     hipLaunchKernelGGL((nt_splitk_epilogue_kernel<T>), dim3(blocks, nphase), dim3(256), 0, st, q, nphase, Mpad, lvpr);
 }
 
-static bool nt_split_inkernel();
 static int nt_stat_blocks(const NtParams& p, int nphase, const NtPlan& plan, bool half);
 
 template <typename T>
@@ -978,7 +972,7 @@ static int launch_nt(const NtParams& p, int nphase, int variant, int splitk, hip
     EG_REQUIRE(plan.kind > 0, "eg_epilogue.nt_variant %d cannot run this problem (M=%d N=%d C=%d)", variant, p.M, p.N, p.C);
     const int stat_nrb = nt_stat_blocks(p, nphase, plan, sizeof(T) == 2);
     EG_REQUIRE(p.stat_mode == EG_STAT_NONE || stat_nrb > 0, "eg_epilogue.stat_mode is set but this launch cannot fuse column statistics (eg_conv_stat_blocks() == 0: M=%d N=%d C=%d)", p.M, p.N, p.C);
-    static const int xcd = [] { const char* e = getenv("EG_XCD_REMAP"); return e ? atoi(e) : 1; }();   // default on (7: + diagnostic piece skipping in PROF builds)
+    constexpr int xcd = 1;
     if (plan.kind == EG_NT_S8 || plan.kind == EG_NT_S8P) {
         NtParams q = p;
         q.nsplit = plan.ns;
@@ -987,10 +981,8 @@ static int launch_nt(const NtParams& p, int nphase, int variant, int splitk, hip
         Nt8pGeom g;
         memset(&g, 0, sizeof(g));
         if (plan.kind == EG_NT_S8P) EG_REQUIRE(eg_nt8p_geometry(p, nphase, g), "patch geometry");
-        const bool inkernel = nt_split_inkernel();
-        q.split_cnt = (plan.ns > 1 && inkernel) ? reinterpret_cast<unsigned*>(reinterpret_cast<char*>(p.part) + p.part_bytes - EG_SPLIT_CNT_BYTES) : nullptr;
+        q.split_cnt = plan.ns > 1 ? reinterpret_cast<unsigned*>(reinterpret_cast<char*>(p.part) + p.part_bytes - EG_SPLIT_CNT_BYTES) : nullptr;
         eg_launch_nt8s<T>(q, g, plan.kind == EG_NT_S8P, nphase, plan.ns, st);      // K splits are reduced inside the launch (last-arriving workgroup)
-        if (plan.ns > 1 && !inkernel) launch_splitk_epilogue<T>(q, nphase, cdiv(p.M, 256) * 256, st);
         return 0;
     }
     if (plan.kind == EG_NT_S8H) {
@@ -998,7 +990,6 @@ static int launch_nt(const NtParams& p, int nphase, int variant, int splitk, hip
         q.nsplit = plan.ns;
         q.xcd_remap = xcd;
         q.stat_nrb = stat_nrb;
-        EG_REQUIRE(plan.ns == 1 || nt_split_inkernel(), "igemm_nt8h reduces its K splits inside the launch only (EG_NT_SPLIT_INKERNEL=0 is an igemm_nt8s experiment)");
         q.split_cnt = plan.ns > 1 ? reinterpret_cast<unsigned*>(reinterpret_cast<char*>(p.part) + p.part_bytes - EG_SPLIT_CNT_BYTES) : nullptr;
         eg_launch_nt8h<T>(q, nphase, plan.ns, st);
         return 0;
@@ -1025,10 +1016,10 @@ static int launch_nt(const NtParams& p, int nphase, int variant, int splitk, hip
         NtParams q = p;
         q.nsplit = ns;
         q.xcd_remap = xcd;
-        // diagnostic (EG_NT_PROF=1 in the environment): run the instrumented instantiation synchronously and print the per-wave averages of
-        // its phase timers (wait+barrier / LDS-DMA issue / ds_read+MFMA / epilogue) -- how DESIGN.md section 6's round-1 breakdown was measured
-        static const char* prof_env = getenv("EG_NT_PROF");
-        if (prof_env && ns == 1) {
+#ifdef EG_PROF
+        // diagnostic build (make PROF=1): run the instrumented instantiation synchronously and print the per-wave averages of its phase
+        // timers (wait+barrier / LDS-DMA issue / ds_read+MFMA / epilogue) -- how DESIGN.md section 6's round-1 breakdown was measured
+        if (ns == 1) {
             const dim3 grid(cdiv(p.M, 128), p.N / 128, nphase);
             const size_t nw = (size_t)grid.x * grid.y * grid.z * 4;
             unsigned long long* dbuf = nullptr;
@@ -1046,6 +1037,7 @@ static int launch_nt(const NtParams& p, int nphase, int variant, int splitk, hip
                     grid.x, grid.y, grid.z, nk, tot / nw, wt / nw, wt / nw / nk, is / nw, is / nw / nk, cp / nw, cp / nw / nk, ep / nw);
             return 0;
         }
+#endif
         if (ns > 1) {
             static bool attr_split = false;
             if (!attr_split) {
@@ -1123,18 +1115,12 @@ static void fill_epilogue(NtParams& p, const eg_epilogue* ep) {
 
 // row blocks of the fused column statistics if this plan can produce them (the 8-wave kernel on whole 256-row tiles, K splits reduced
 // inside the launch), else 0
-static bool nt_split_inkernel() {
-    static const bool inkernel = [] { const char* e = getenv("EG_NT_SPLIT_INKERNEL"); return !(e && atoi(e) == 0); }();
-    return inkernel;
-}
 static int nt_stat_blocks(const NtParams& p, int nphase, const NtPlan& plan, bool half) {
     if (!half || p.out_mode != EG_OUT_NHWC) return 0;
     if (plan.kind == EG_NT_S8H) return (p.M % 128) == 0 ? nphase * (p.M / 128) : 0;          // row blocks of 128
     // the register-staged kernel on 128 x 64 / 128 x 32 tiles (the small networks' layers): one column tile, whole row tiles
-    static const bool reg_stat = [] { const char* e = getenv("EG_NT_REG_STAT"); return !(e && atoi(e) == 0); }();
-    if (plan.kind == EG_NT_REG) return (reg_stat && (p.N == 64 || p.N == 32) && (p.M % 128) == 0) ? nphase * (p.M / 128) : 0;
+    if (plan.kind == EG_NT_REG) return ((p.N == 64 || p.N == 32) && (p.M % 128) == 0) ? nphase * (p.M / 128) : 0;
     if (plan.kind != EG_NT_S8 || (p.M % 256) != 0) return 0;
-    if (plan.ns > 1 && !nt_split_inkernel()) return 0;
     return nphase * (p.M / 256);
 }
 static int check_stat(const NtParams& p) {
@@ -1352,7 +1338,7 @@ extern "C" int eg_pack_bwd(const eg_conv* c, int dtype, const float* w, void* wp
 // panel and [c][tap'][n] rows of every backward (sub-pixel phase) panel.  The per-element gather above reads the master with a
 // 64-byte (forward) or Cin*64-byte (backward) stride and was 5-9 % of a CelebA iteration.
 // ------------------------------------------------------------------------------------------------
-#define EG_PACKM_TC 8       // Cin tile of the tile jobs inside pack_multi_kernel (the stand-alone tile kernel uses 32)
+#define EG_PACKM_TC 8       // Cin tile of the tile jobs inside pack_multi_kernel (and of the stand-alone tile kernels)
 struct PackTileParams {
     const float* w;
     void* wp_fwd;          // may be null
@@ -1365,7 +1351,7 @@ struct PackTileParams {
 };
 
 // TTC: taps (k*k) as a compile-time constant (16 for every 4x4 layer; 0 = run time): the index arithmetic below divides by it per element
-template <typename T, int TTC, int TC = 32>
+template <typename T, int TTC, int TC>
 __device__ __forceinline__ void pack_conv_tile_body(const PackTileParams& p, float* tile, int bx, int by) {
     constexpr int VEC = Elt<T>::VEC;
     constexpr int TN = 16;
@@ -1405,7 +1391,7 @@ __device__ __forceinline__ void pack_conv_tile_body(const PackTileParams& p, flo
         }
     }
 }
-template <typename T, int TTC, int TC = 32>
+template <typename T, int TTC, int TC>
 __global__ __launch_bounds__(256) void pack_conv_tile_kernel(const PackTileParams p) {
     extern __shared__ float tile[];                 // [TN][TC][T + 1]
     pack_conv_tile_body<T, TTC, TC>(p, tile, blockIdx.x, blockIdx.y);
@@ -1452,16 +1438,14 @@ extern "C" int eg_pack_conv(const eg_conv* c, int dtype, const float* w, void* w
         if (wp_bwd) if (int e = eg_pack_bwd(c, dtype, w, wp_bwd, s)) return e;
         return 0;
     }
-    // Cin tile: 32 (64-byte panel stores, 34 KiB of LDS) or 8 (16-byte stores, 8.5 KiB: fits on a CU beside a resident 8-wave GEMM workgroup:
-    // the re-packing on the optimizer lane then runs beside the next sub-step's GEMMs; EG_PACK_TC, A/B in profiles/r03_zm_ab_pack_tc.txt)
-    static const int tc = [] { const char* e = getenv("EG_PACK_TC"); return (e && atoi(e) == 32) ? 32 : 8; }();
+    // Cin tile 8 (16-byte panel stores, 8.5 KiB of LDS: fits on a CU beside a resident 8-wave GEMM workgroup: the re-packing on the optimizer
+    // lane then runs beside the next sub-step's GEMMs), not 32 (64-byte stores, 34 KiB); A/B in profiles/r03_zm_ab_pack_tc.txt
+    constexpr int tc = 8;
     const dim3 grid(c->Cout / 16, c->Cin / tc);
     const size_t lds = (size_t)16 * tc * (T + 1) * sizeof(float);
     if (pack_record_tile(p, dtype, grid.x, c->Cin / EG_PACKM_TC)) return 0;     // (the joint launch tiles Cin by EG_PACKM_TC)
-#define EG_PACK_TILE(TY) do { if (tc == 32) { if (T == 16) hipLaunchKernelGGL((pack_conv_tile_kernel<TY, 16>), grid, dim3(256), lds, (hipStream_t)s, p); \
-                                              else hipLaunchKernelGGL((pack_conv_tile_kernel<TY, 0>), grid, dim3(256), lds, (hipStream_t)s, p); } \
-                              else { if (T == 16) hipLaunchKernelGGL((pack_conv_tile_kernel<TY, 16, 8>), grid, dim3(256), lds, (hipStream_t)s, p); \
-                                     else hipLaunchKernelGGL((pack_conv_tile_kernel<TY, 0, 8>), grid, dim3(256), lds, (hipStream_t)s, p); } } while (0)
+#define EG_PACK_TILE(TY) do { if (T == 16) hipLaunchKernelGGL((pack_conv_tile_kernel<TY, 16, tc>), grid, dim3(256), lds, (hipStream_t)s, p); \
+                              else hipLaunchKernelGGL((pack_conv_tile_kernel<TY, 0, tc>), grid, dim3(256), lds, (hipStream_t)s, p); } while (0)
     if (dtype == EG_F32) EG_PACK_TILE(float);
     else if (dtype == EG_F16) EG_PACK_TILE(f16_t);
     else EG_PACK_TILE(bf16_t);
@@ -1577,21 +1561,18 @@ extern "C" int eg_adam_pack_conv(const eg_conv* c, int dtype, float* w, float* g
     const int T = c->k * c->k;
     PackTileParams p;
     EG_REQUIRE(pack_tile_params(c, dtype, wp_fwd, wp_bwd, p), "eg_adam_pack_conv: this layer needs the gather kernels (eg_adam_pack_conv_ok() == 0): run eg_adam_step_zero + eg_pack_conv");
-    // tile width along Cin: 32 (64-byte panel stores, 34 KiB of LDS) or 8 (16-byte stores, 8.5 KiB: fits beside a resident 147-KiB GEMM
-    // workgroup, so the update can share CUs with the main chain's convolutions like the LDS-free flat Adam kernel does)
-    static const int tc_env = [] { const char* e = getenv("EG_ADAM_PACK_TC"); return e ? atoi(e) : 8; }();
-    const int tc = tc_env == 32 ? 32 : 8;
+    // tile width along Cin: 8 (16-byte panel stores, 8.5 KiB of LDS: fits beside a resident 147-KiB GEMM workgroup, so the update can share
+    // CUs with the main chain's convolutions like the LDS-free flat Adam kernel does), not 32 (64-byte stores, 34 KiB)
+    constexpr int tc = 8;
     const dim3 grid(c->Cout / 16, c->Cin / tc);
     const size_t lds = (size_t)16 * tc * (T + 1) * sizeof(float);
     const bool v4 = T == 16 && ((((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
-#define EG_AP_TC(TY, Z, TCC) do { if (v4) hipLaunchKernelGGL((adam_pack_conv_tile_kernel<TY, 16, Z, true, TCC>), grid, dim3(256), lds, (hipStream_t)s, p, w, g, m, v, lr, b1, b2, eps, step); \
-                               else if (T == 16) hipLaunchKernelGGL((adam_pack_conv_tile_kernel<TY, 16, Z, false, TCC>), grid, dim3(256), lds, (hipStream_t)s, p, w, g, m, v, lr, b1, b2, eps, step); \
-                               else hipLaunchKernelGGL((adam_pack_conv_tile_kernel<TY, 0, Z, false, TCC>), grid, dim3(256), lds, (hipStream_t)s, p, w, g, m, v, lr, b1, b2, eps, step); } while (0)
-#define EG_AP_TILE(TY, Z) do { if (tc == 32) EG_AP_TC(TY, Z, 32); else EG_AP_TC(TY, Z, 8); } while (0)
+#define EG_AP_TILE(TY, Z) do { if (v4) hipLaunchKernelGGL((adam_pack_conv_tile_kernel<TY, 16, Z, true, tc>), grid, dim3(256), lds, (hipStream_t)s, p, w, g, m, v, lr, b1, b2, eps, step); \
+                               else if (T == 16) hipLaunchKernelGGL((adam_pack_conv_tile_kernel<TY, 16, Z, false, tc>), grid, dim3(256), lds, (hipStream_t)s, p, w, g, m, v, lr, b1, b2, eps, step); \
+                               else hipLaunchKernelGGL((adam_pack_conv_tile_kernel<TY, 0, Z, false, tc>), grid, dim3(256), lds, (hipStream_t)s, p, w, g, m, v, lr, b1, b2, eps, step); } while (0)
 #define EG_AP_TYPE(Z) do { if (dtype == EG_F32) EG_AP_TILE(float, Z); else if (dtype == EG_F16) EG_AP_TILE(f16_t, Z); else EG_AP_TILE(bf16_t, Z); } while (0)
     if (zero_grad) EG_AP_TYPE(true);
     else EG_AP_TYPE(false);
-#undef EG_AP_TC
 #undef EG_AP_TYPE
 #undef EG_AP_TILE
     EG_LAUNCH_CHECK();
@@ -2044,7 +2025,7 @@ static void tn_plan(const eg_conv* c, int* nsplit, int* rps) {
     int bnt, bct;
     tn_tiles(c, &bnt, &bct);
     const long long base = (long long)cdiv(c->Cout, bnt) * cdiv(c->Cin, bct) * c->k * c->k;
-    static const int target = [] { const char* e = getenv("EG_TN_TARGET"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 768; }();   // workgroups per launch
+    constexpr int target = 768;      // workgroups per launch
     long long want = base >= target ? 1 : (target + base - 1) / base;
     long long cap = M / 256 > 0 ? M / 256 : 1;
     if (want > cap) want = cap;
@@ -2052,9 +2033,8 @@ static void tn_plan(const eg_conv* c, int* nsplit, int* rps) {
     // the grid: 128 workgroups of a 32 x 64 tile keep ~1.5 MB in flight and stream the 100-134 MB of the small networks' image-side layers at
     // ~1 TB/s; 512 of them: colored dSprites 3.08 -> 2.98 ms, dSprites 1.39 -> 1.38, MNIST neutral (profiles/r03_zv_tn_maxsplit_small.txt).
     // Big tiles (CelebA's 128-channel image-side layer, on a lane beside the main chain's GEMMs) keep 128: more took CUs from the main chain
-    // (5.50 -> 5.65 ms at 512, profiles/r01_timeline_notes.md item 14).  EG_TN_MAXSPLIT overrides both.
-    static const int max_split_env = [] { const char* e = getenv("EG_TN_MAXSPLIT"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 0; }();
-    const int max_split = max_split_env ? max_split_env : (bnt * bct <= 64 * 64 ? 512 : 128);
+    // (5.50 -> 5.65 ms at 512, profiles/r01_timeline_notes.md item 14).
+    const int max_split = bnt * bct <= 64 * 64 ? 512 : 128;
     if (want > max_split) want = max_split;
     int r = round_up((int)((M + want - 1) / want), 32);
     *rps = r;
@@ -2100,10 +2080,8 @@ static void launch_tn_cfg(TnParams& p, int nsplit, hipStream_t st) {
     dim3 grid(p.ntn * p.ntc, p.ntaps, nsplit);
     // 32 rows per pipeline step; 64 (half the barriers) measured 10-20 % slower on the CelebA layers.  Launches with ONE output tile (the
     // image-side layers: the grid is just the split count, <= 128 workgroups streaming the whole activation) are latency-bound on bytes in
-    // flight per workgroup: those get 64 rows per step (colored dSprites B=512: 5.22 -> 5.00 ms; CelebA, dSprites, MNIST neutral to +1 %;
-    // EG_TN_KR64=0 restores 32).
-    static const bool kr64 = [] { const char* e = getenv("EG_TN_KR64"); return !(e && atoi(e) == 0); }();
-    if (kr64 && p.ntn * p.ntc * p.ntaps == 1 && sizeof(T) == 2 && BNT + BCT <= 192)
+    // flight per workgroup: those get 64 rows per step (colored dSprites B=512: 5.22 -> 5.00 ms; CelebA, dSprites, MNIST neutral to +1 %).
+    if (p.ntn * p.ntc * p.ntaps == 1 && sizeof(T) == 2 && BNT + BCT <= 192)
         launch_tn_kr<T, BNT, BCT, 64>(p, grid, st);
     else
         launch_tn_kr<T, BNT, BCT, 32>(p, grid, st);
@@ -2169,7 +2147,6 @@ extern "C" int eg_conv_wgrad_target(const eg_conv* c, int dtype, const void* X, 
 // the rank-1 spectral-norm terms, transposes through LDS and read-modify-writes the master-layout gradient [n][c][t] as
 // one contiguous run of 64*T floats.  MODE 0: out += a; MODE 1: out = a (gtmp) + <a,W> partials; MODE 2: out += a - rank1.
 #define EG_RC 64
-__device__ int eg_reduce_chain_flag;                    // EG_REDUCE_RAGGED=0 (A/B runs): the one-chain loop for ragged channel counts
 // LEAN: the instantiation for launches with < 16 splits (every big layer: 2-8 slabs): no split-group scratch (4.4 KiB of LDS instead of
 // 24) and four loads in flight instead of eight (<= 48 VGPRs) -- its workgroups then fit on a CU beside a resident 8-wave GEMM workgroup
 // (147 KiB of LDS, 2 x 232 VGPRs per SIMD lane), so a reduction forked beside the main chain's GEMMs no longer waits for their tiles to
@@ -2257,7 +2234,7 @@ __global__ __launch_bounds__(LEAN ? 256 : 1024) void wgrad_reduce_kernel(const f
             }
             tile[c * (T + 1) + t] = a.x; tile[(c + 1) * (T + 1) + t] = a.y; tile[(c + 2) * (T + 1) + t] = a.z; tile[(c + 3) * (T + 1) + t] = a.w;
         }
-    } else if (!LEAN && nsplit >= 16 && T * EG_RC * 2 <= NTH && !eg_reduce_chain_flag) {
+    } else if (!LEAN && nsplit >= 16 && T * EG_RC * 2 <= NTH) {
         // many splits of a small tile whose channel count is not a multiple of 64 (the image-side layers: 48 = 3 x 16 gathered channels,
         // 128 splits): the loop below is ONE chain of nsplit dependent loads per thread (39 us for a 6 K-parameter gradient, at the end
         // of every sub-step's backward pass).  As above: thread groups take every G-th split, eight loads in flight, added in group order.
@@ -2342,13 +2319,6 @@ __global__ void sn_grad_apply_kernel(const float* __restrict__ gtmp, const float
 }
 
 static inline int reduce_blocks(int n_rows, int C) {
-    static const bool once = [] {
-        const char* e = getenv("EG_REDUCE_RAGGED");
-        const int v = (e && atoi(e) == 0) ? 1 : 0;
-        if (v) (void)hipMemcpyToSymbol(HIP_SYMBOL(eg_reduce_chain_flag), &v, sizeof(v));
-        return true;
-    }();
-    (void)once;
     return n_rows * ((C + EG_RC - 1) / EG_RC);
 }
 // threads per workgroup: 1024 (several split groups per tile vector) where a launch has many splits and few, small tiles
@@ -2357,10 +2327,7 @@ static inline int reduce_threads(int nsplit, int n_rows, int C, int T) {
     return (nsplit >= 16 && nv * 2 <= 1024 && nv * 2 > 256 && reduce_blocks(n_rows, C) <= 2048) ? 1024 : 256;
 }
 static inline size_t reduce_lds(int T) { return (size_t)EG_RC * (T + 1) * sizeof(float); }
-static inline bool reduce_lean(int nsplit) {
-    static const bool on = [] { const char* e = getenv("EG_REDUCE_LEAN"); return !(e && atoi(e) == 0); }();
-    return on && nsplit < 16;
-}
+static inline bool reduce_lean(int nsplit) { return nsplit < 16; }
 
 extern "C" int eg_wgrad_reduce(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad, int accumulate, eg_stream_t s) {
     EG_REQUIRE(slab && grad && nsplit > 0 && n_rows <= n_slab && T > 0 && T <= 64, "eg_wgrad_reduce: bad argument");

@@ -8,7 +8,6 @@
 // Per K tile and wave: 16 MFMAs (4 groups of 4: k half g >> 1, row tile g & 1, four column tiles), 12 ds_read_b128 of K tile t + 1 into
 // the other fragment set, 4 LDS-DMA pieces of K tile t + 3 (A rows 8w + 64j, B rows 8w + 64j; j = 0, 1), one counted wait, ONE barrier.
 // Hazards as in igemm_nt8s.hip with one more stage of slack: K tile t + 3 goes into stage (t + 3) % 4, last read in iteration t - 2.
-#include <stdlib.h>
 #include <string.h>
 
 #include "eg_common.h"

@@ -18,7 +18,6 @@
 // s_waitcnt vmcnt(pieces issued in this iteration) lgkmcnt(0) ; s_barrier }.  RAW: K tile t+2 (issued in iteration t-1) has landed for
 // every wave before the barrier that ends iteration t, its first read is in iteration t+1.  WAR: stage t % 3 was last read in iteration
 // t-1 (fragments of K tile t), retired by that iteration's lgkmcnt(0) in front of its barrier.
-#include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 #include <vector>
@@ -52,7 +51,7 @@ __device__ __forceinline__ void eg_wait_vm_dyn_lgkm0(int n) {      // wave-unifo
     }
 }
 
-// PROF (diagnostic instantiation, EG_NT8_PROF=1): wave 0 of every workgroup stamps s_memtime (shader clock) and s_memrealtime (100 MHz)
+// PROF (diagnostic instantiation, built with make PROF=1): wave 0 of every workgroup stamps s_memtime (shader clock) and s_memrealtime (100 MHz)
 // at kernel entry, after the prologue, after the K loop and at the end: where a workgroup's time goes and at which clock it ran.
 // STAT: its own instantiation for launches with eg_epilogue.stat_mode set (column statistics of the stored tile in the epilogue): the
 // plain kernels keep their register allocation (230 VGPRs, no scratch; with the statistics epilogue inlined behind a branch they spilled)
@@ -444,7 +443,7 @@ __global__ __launch_bounds__(512) void igemm_nt8s_kernel(const NtParams p, const
         const size_t slab = (size_t)nphase * ((size_t)tiles_m * BM) * p.N;       // floats per split
         float* part = p.part + ((size_t)phase * ((size_t)tiles_m * BM) + m0) * p.N + n0;
         float* mine = part + (size_t)split * slab;
-        if (p.split_cnt == nullptr) {                  // A/B path (EG_NT_SPLIT_INKERNEL=0): plain partial stores, a second launch sums them
+        if (p.split_cnt == nullptr) {                  // no counters given: plain partial stores for a reduction by the caller (no host path passes none)
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 const int row = (wm * TM + i) * 16 + frow;
@@ -590,41 +589,40 @@ static void launch_s(const NtParams& p, const Nt8pGeom& g, int nphase, int ns, h
         attr_set = true;
     }
     const int tm = (p.M + 255) / 256, tn = p.N / 128;
+#ifdef EG_PROF
     if constexpr (std::is_same<T, bf16_t>::value && !SPLITK) {
-        static const char* prof_env = getenv("EG_NT8_PROF");
-        if (prof_env) {
-            // diagnostic: synchronous instrumented launch, prints medians over workgroups (ticks of the shader clock; 100 MHz real time)
-            const size_t nwg = (size_t)tm * tn * nphase;
-            unsigned long long* dbuf = nullptr;
-            (void)hipMalloc(&dbuf, nwg * 208);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_nt8s_kernel<T, PATCH, SPLITK, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL((igemm_nt8s_kernel<T, PATCH, SPLITK, true>), dim3(tm * tn, 1, nphase), dim3(512), lds, st, p, g, tm, tn, dbuf);
-            (void)hipStreamSynchronize(st);
-            std::vector<unsigned long long> h(nwg * 26);
-            (void)hipMemcpy(h.data(), dbuf, nwg * 208, hipMemcpyDeviceToHost);
-            (void)hipFree(dbuf);
-            std::vector<double> pro, loop, epi, clk, start, endt, e_pf, e_st, e_dr, l_g, l_w, l_b, l7_g, l7_w, l7_b;
-            unsigned long long r0 = ~0ull, r1 = 0;
-            for (size_t w = 0; w < nwg; ++w) {
-                const unsigned long long* o = &h[w * 26];
-                const unsigned long long* o7 = &h[w * 26 + 13];
-                l7_g.push_back((double)o7[10]); l7_w.push_back((double)o7[11]); l7_b.push_back((double)o7[12]);
-                l_g.push_back((double)o[10]); l_w.push_back((double)o[11]); l_b.push_back((double)o[12]);
-                e_pf.push_back((double)(o[8] - o[2])); e_st.push_back((double)(o[9] - o[8])); e_dr.push_back((double)(o[3] - o[9]));
-                pro.push_back((double)(o[1] - o[0])); loop.push_back((double)(o[2] - o[1])); epi.push_back((double)(o[3] - o[2]));
-                clk.push_back((double)(o[3] - o[0]) / (double)(o[7] - o[4]) * 100.0);
-                r0 = std::min(r0, o[4]); r1 = std::max(r1, o[7]);
-            }
-            for (size_t w = 0; w < nwg; ++w) { start.push_back((double)(h[w * 26 + 4] - r0) / 100.0); endt.push_back((double)(h[w * 26 + 7] - r0) / 100.0); }
-            auto med = [](std::vector<double>& v) { std::sort(v.begin(), v.end()); return v[v.size() / 2]; };
-            auto mx = [](std::vector<double>& v) { return *std::max_element(v.begin(), v.end()); };
-            const int nk = p.ph[0].Kpad / (8 * Elt<T>::VEC);
-            fprintf(stderr, "[nt8s_prof] patch %d wgs %zu nk %d | median ticks: prologue %.0f  K loop %.0f (%.0f per K tile: wave 0 groups %.0f, counted wait %.0f, barrier %.0f; wave 7 %.0f / %.0f / %.0f)  epilogue %.0f (operand fetch %.0f, staging + store issue %.0f, store drain %.0f) | clock %.0f MHz | "
-                    "first->last wave-0 stamp %.1f us, median WG start %.1f us, median end %.1f us, last end %.1f us\n",
-                    (int)PATCH, nwg, nk, med(pro), med(loop), med(loop) / nk, med(l_g) / nk, med(l_w) / nk, med(l_b) / nk, med(l7_g) / nk, med(l7_w) / nk, med(l7_b) / nk, med(epi), med(e_pf), med(e_st), med(e_dr), med(clk), (double)(r1 - r0) / 100.0, med(start), med(endt), mx(endt));
-            return;
+        // diagnostic: synchronous instrumented launch, prints medians over workgroups (ticks of the shader clock; 100 MHz real time)
+        const size_t nwg = (size_t)tm * tn * nphase;
+        unsigned long long* dbuf = nullptr;
+        (void)hipMalloc(&dbuf, nwg * 208);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_nt8s_kernel<T, PATCH, SPLITK, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL((igemm_nt8s_kernel<T, PATCH, SPLITK, true>), dim3(tm * tn, 1, nphase), dim3(512), lds, st, p, g, tm, tn, dbuf);
+        (void)hipStreamSynchronize(st);
+        std::vector<unsigned long long> h(nwg * 26);
+        (void)hipMemcpy(h.data(), dbuf, nwg * 208, hipMemcpyDeviceToHost);
+        (void)hipFree(dbuf);
+        std::vector<double> pro, loop, epi, clk, start, endt, e_pf, e_st, e_dr, l_g, l_w, l_b, l7_g, l7_w, l7_b;
+        unsigned long long r0 = ~0ull, r1 = 0;
+        for (size_t w = 0; w < nwg; ++w) {
+            const unsigned long long* o = &h[w * 26];
+            const unsigned long long* o7 = &h[w * 26 + 13];
+            l7_g.push_back((double)o7[10]); l7_w.push_back((double)o7[11]); l7_b.push_back((double)o7[12]);
+            l_g.push_back((double)o[10]); l_w.push_back((double)o[11]); l_b.push_back((double)o[12]);
+            e_pf.push_back((double)(o[8] - o[2])); e_st.push_back((double)(o[9] - o[8])); e_dr.push_back((double)(o[3] - o[9]));
+            pro.push_back((double)(o[1] - o[0])); loop.push_back((double)(o[2] - o[1])); epi.push_back((double)(o[3] - o[2]));
+            clk.push_back((double)(o[3] - o[0]) / (double)(o[7] - o[4]) * 100.0);
+            r0 = std::min(r0, o[4]); r1 = std::max(r1, o[7]);
         }
+        for (size_t w = 0; w < nwg; ++w) { start.push_back((double)(h[w * 26 + 4] - r0) / 100.0); endt.push_back((double)(h[w * 26 + 7] - r0) / 100.0); }
+        auto med = [](std::vector<double>& v) { std::sort(v.begin(), v.end()); return v[v.size() / 2]; };
+        auto mx = [](std::vector<double>& v) { return *std::max_element(v.begin(), v.end()); };
+        const int nk = p.ph[0].Kpad / (8 * Elt<T>::VEC);
+        fprintf(stderr, "[nt8s_prof] patch %d wgs %zu nk %d | median ticks: prologue %.0f  K loop %.0f (%.0f per K tile: wave 0 groups %.0f, counted wait %.0f, barrier %.0f; wave 7 %.0f / %.0f / %.0f)  epilogue %.0f (operand fetch %.0f, staging + store issue %.0f, store drain %.0f) | clock %.0f MHz | "
+                "first->last wave-0 stamp %.1f us, median WG start %.1f us, median end %.1f us, last end %.1f us\n",
+                (int)PATCH, nwg, nk, med(pro), med(loop), med(loop) / nk, med(l_g) / nk, med(l_w) / nk, med(l_b) / nk, med(l7_g) / nk, med(l7_w) / nk, med(l7_b) / nk, med(epi), med(e_pf), med(e_st), med(e_dr), med(clk), (double)(r1 - r0) / 100.0, med(start), med(endt), mx(endt));
+        return;
     }
+#endif
     if constexpr (!PATCH && !std::is_same<T, float>::value) {
         if (p.stat_mode != EG_STAT_NONE) {
             static bool attr_stat = false;

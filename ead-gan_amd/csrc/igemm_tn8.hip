@@ -16,7 +16,6 @@
 //     barrier; both operands are K-major in memory, fragments come from `ds_read_b64_tr_b16` (transposed LDS reads);
 //   * both operands staged by LDS-DMA (buffer descriptors, 256-byte rows, 32-byte blocks XOR-swizzled on the source side) into a ring
 //     of three stages, two K steps in flight behind a counted vmcnt, one barrier per K step.
-#include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 
@@ -208,11 +207,9 @@ __global__ __launch_bounds__(512) void igemm_tn8_kernel(const Tn8Params p) {
 // ------------------------------------------------------------------------------------------------
 // geometry + split plan; false if this convolution is not a 16-bit 4x4 / stride-2 / pad-1 layer of the supported sizes
 bool eg_tn8_plan(const eg_conv* c, int dtype, Tn8Params& p, int* nsplit, int wgs_target) {
-    static const bool enabled = [] { const char* e = getenv("EG_TN8"); return !(e && atoi(e) == 0); }();
-    if (!enabled || dtype == EG_F32 || c->k != 4 || c->stride != 2 || c->pad != 1 || c->up != 0) return false;
-    static const bool ch32 = [] { const char* e = getenv("EG_TN8_CH32"); return !(e && atoi(e) == 0); }();
+    if (dtype == EG_F32 || c->k != 4 || c->stride != 2 || c->pad != 1 || c->up != 0) return false;
     const int ch = ((c->Cin % 128) == 0 && (c->Cout % 128) == 0) ? 128 : (((c->Cin % 64) == 0 && (c->Cout % 64) == 0) ? 64
-                   : ((ch32 && (c->Cin % 32) == 0 && (c->Cout % 32) == 0) ? 32 : 0));
+                   : (((c->Cin % 32) == 0 && (c->Cout % 32) == 0) ? 32 : 0));
     if (ch == 0 || (c->H & 1) || (c->W & 1)) return false;
     const int OH = c->H / 2, OW = c->W / 2;
     const int lOH = ilog2_exact(OH), lOW = ilog2_exact(OW);
@@ -240,8 +237,7 @@ bool eg_tn8_plan(const eg_conv* c, int dtype, Tn8Params& p, int* nsplit, int wgs
     const long long base = (long long)p.ntn * p.ntc * 4;
     // (wgs_target: the caller's share of the chip -- a launch forked beside the main chain's GEMMs runs the step fastest at 128: half the
     //  slab bytes to write and reduce, and the other CUs stay with the main chain; profiles/r02_i_ab_tn8_target.txt)
-    static const int env_target = [] { const char* e = getenv("EG_TN8_TARGET"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 0; }();
-    const int target = env_target ? env_target : (wgs_target > 0 ? wgs_target : 256);
+    const int target = wgs_target > 0 ? wgs_target : 256;
     long long want = base >= target ? 1 : (target + base - 1) / base;
     const long long steps = M / 64;
     want = std::min(want, std::max(1LL, steps / 4));

@@ -12,7 +12,6 @@
 // lives in registers, 16 MFMAs per 16 pixels, and the tile leaves through LDS as whole 256-byte pixel rows.
 // Same operands in the same MFMA slots as the patch-row GEMM (K order = master weight order (c, ky, kx), zero padded to 64; k halves in
 // order) and the same epilogue arithmetic -> bit-identical outputs (tests/test_gpu_img_conv.py).
-#include <stdlib.h>
 
 #include "eg_common.h"
 #include "igemm_nt.h"
@@ -247,8 +246,7 @@ extern "C" int eg_conv_img_mfma_n(int dtype, const float* img0, const float* img
         p.stat_p[0] = ep->stat_p0; p.stat_p[1] = ep->stat_p1; p.stat_p[2] = ep->stat_p2; p.stat_p[3] = ep->stat_p3;
     }
     const int ntiles = (H / 4) * (W / 64) * B * ntapes;  // 2 output rows x 32 columns each
-    static const int wgs = [] { const char* e = getenv("EG_IMG_CONV_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 256 * EG_IMG_CONV_OCC; }();
-    const int wgs_n = N == 128 ? wgs : 256 * img_conv_occ(N);
+    const int wgs_n = N == 128 ? 256 * EG_IMG_CONV_OCC : 256 * img_conv_occ(N);
     const dim3 grid(ntiles < wgs_n ? ntiles : wgs_n);     // persistent: a few workgroups per CU walk the tiles with the weight panel in registers
     if (stat) {
         const dim3 gs(ntiles < 512 ? ntiles : 512);      // two workgroups per CU: the sums take the registers
@@ -404,17 +402,10 @@ extern "C" int eg_convt_img_mfma_k(int dtype, const void* a, const void* wp, con
         EG_LAUNCH_CHECK();
         return 0;
     }
-    // input rows per workgroup: 8 (+ 2 halo rows: 25 % of the GEMM done twice, 36 KiB of LDS, several workgroups per CU) or 16
-    static const int rows = [] { const char* e = getenv("EG_CONVT_IMG_ROWS"); return e && atoi(e) == 16 ? 16 : 8; }();
-    if (rows == 16) {
-        const dim3 grid(B * (Hin / 16));
-        if (dtype == EG_F16) hipLaunchKernelGGL((convt_img_mfma_kernel<f16_t, 16>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((convt_img_mfma_kernel<bf16_t, 16>), grid, dim3(256), 0, st, p);
-    } else {
-        const dim3 grid(B * (Hin / 8));
-        if (dtype == EG_F16) hipLaunchKernelGGL((convt_img_mfma_kernel<f16_t, 8>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((convt_img_mfma_kernel<bf16_t, 8>), grid, dim3(256), 0, st, p);
-    }
+    // input rows per workgroup: 8 (+ 2 halo rows: 25 % of the GEMM done twice, 36 KiB of LDS, several workgroups per CU), not 16
+    const dim3 grid(B * (Hin / 8));
+    if (dtype == EG_F16) hipLaunchKernelGGL((convt_img_mfma_kernel<f16_t, 8>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((convt_img_mfma_kernel<bf16_t, 8>), grid, dim3(256), 0, st, p);
     EG_LAUNCH_CHECK();
     return 0;
 }

@@ -188,125 +188,13 @@ __global__ void snm_u_final_kernel(const SnMulti p, int training) {
     if (threadIdx.x == 0) p.sigma[l][0] = sg;
 }
 
-// ---- the same iteration in TWO launches: each stage's per-layer finish by the last workgroup of the layer to arrive ---------------------
-// (W^T u partial sums + the norm of v; W v + the norm of u and sigma).  On the chains that wait for a power iteration -- step 3 of the
-// CelebA iteration runs three in a row on freshly updated weights, the small networks six per iteration -- every launch is a dependent
-// ~5-10 us.  The finishing code is the 1024-thread code of snm_v_final / snm_u_final: stage one runs 1024-thread workgroups (each k's
-// partial sum does not depend on the workgroup shape), stage two's 256-thread workgroup walks the 16 "virtual waves" of that code in
-// order, so u, v and sigma keep their bits.  Hand-off: partial results are written through (agent-scope stores), vmcnt(0), a relaxed
-// counter per layer and stage (caller-owned, zeroed once, left at zero).
-__global__ __launch_bounds__(1024) void snm2_wtu_v_kernel(const SnMulti p, unsigned* __restrict__ cnt) {
-    __shared__ float sm[16];
-    __shared__ unsigned flag;
-    const int l = blockIdx.z, R = p.R[l], Kd = p.Kd[l];
-    if ((int)blockIdx.x * 1024 >= Kd) return;           // (uniform: this layer has fewer column blocks than the widest one)
-    const int k = blockIdx.x * 1024 + threadIdx.x;
-    float* partial = p.ws + p.ws_off[l];
-    if (k < Kd) {
-        const int rb = (R + SN_NRB - 1) / SN_NRB;
-        const int r0 = blockIdx.y * rb, r1 = min(R, r0 + rb);
-        const float* __restrict__ W = p.w[l];
-        const float* __restrict__ u = p.u[l];
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        int r = r0;
-        for (; r + 3 < r1; r += 4) {
-            a0 += W[(size_t)r * Kd + k] * u[r];
-            a1 += W[(size_t)(r + 1) * Kd + k] * u[r + 1];
-            a2 += W[(size_t)(r + 2) * Kd + k] * u[r + 2];
-            a3 += W[(size_t)(r + 3) * Kd + k] * u[r + 3];
-        }
-        for (; r < r1; ++r) a0 += W[(size_t)r * Kd + k] * u[r];
-        __hip_atomic_store(partial + (size_t)blockIdx.y * Kd + k, (a0 + a1) + (a2 + a3), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const unsigned total = (unsigned)((Kd + 1023) / 1024) * SN_NRB;
-    if (threadIdx.x == 0) flag = __hip_atomic_fetch_add(cnt + 2 * l, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (flag != total - 1) return;
-    if (threadIdx.x == 0) __hip_atomic_store(cnt + 2 * l, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // snm_v_final_kernel's body (1024 threads)
-    float* v = p.v[l];
-    float* v_snap = p.v_snap[l];
-    float ss = 0.f;
-    for (int kk = threadIdx.x; kk < Kd; kk += 1024) {
-        float t = 0.f;
-        for (int r = 0; r < SN_NRB; ++r) t += __hip_atomic_load(partial + (size_t)r * Kd + kk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        v[kk] = t;
-        ss += t * t;
-    }
-    const float nrm = sqrtf(block_sum(ss, sm));
-    const float inv = 1.f / fmaxf(nrm, p.eps);
-    for (int kk = threadIdx.x; kk < Kd; kk += 1024) {
-        const float vn = v[kk] * inv;
-        v[kk] = vn;
-        if (v_snap) v_snap[kk] = vn;
-    }
-}
-
-// block_sum of a 1024-thread workgroup, computed by 256 threads: virtual thread vt = 64 * vw + lane of virtual wave vw = w, w + 4, w + 8,
-// w + 12 belongs to physical wave w; wave sums go to sm[vw], then the 16 are added in order (block_sum's order)
-template <typename F>
-__device__ __forceinline__ float block_sum_as_1024(F&& value_of_virtual_thread, float* sm) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int vw = w + 4 * q;
-        const float s = wave_sum(value_of_virtual_thread(64 * vw + lane));
-        if (lane == 0) sm[vw] = s;
-    }
-    __syncthreads();
-    float r = 0.f;
-    for (int i = 0; i < 16; ++i) r += sm[i];
-    return r;
-}
-
-__global__ __launch_bounds__(256) void snm2_wv_u_kernel(const SnMulti p, unsigned* __restrict__ cnt) {
-    __shared__ float sm[16];
-    __shared__ unsigned flag;
-    const int l = blockIdx.z, R = p.R[l], Kd = p.Kd[l];
-    const int r = blockIdx.x;
-    if (r >= R) return;
-    const float* __restrict__ W = p.w[l] + (size_t)r * Kd;
-    const float* __restrict__ v = p.v[l];
-    float* s = p.ws + p.ws_off[l] + (size_t)SN_NRB * Kd;
-    float a = 0.f;
-    for (int k = threadIdx.x; k < Kd; k += blockDim.x) a += W[k] * v[k];
-    const float tot = block_sum(a, sm);
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(s + r, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        flag = __hip_atomic_fetch_add(cnt + 2 * l + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (flag != (unsigned)(R - 1)) return;
-    if (threadIdx.x == 0) __hip_atomic_store(cnt + 2 * l + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // snm_u_final_kernel's training body as its 1024 threads would run it
-    float* u = p.u[l];
-    auto sr = [&](int i) { return __hip_atomic_load(s + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    const float nrm = sqrtf(block_sum_as_1024([&](int vt) { float ss = 0.f; for (int i = vt; i < R; i += 1024) { const float x = sr(i); ss += x * x; } return ss; }, sm));
-    const float inv = 1.f / fmaxf(nrm, p.eps);
-    const float sg = block_sum_as_1024([&](int vt) {
-        float d = 0.f;
-        for (int i = vt; i < R; i += 1024) {
-            const float x = sr(i), un = x * inv;
-            u[i] = un;
-            if (p.u_snap[l]) p.u_snap[l][i] = un;
-            d += un * x;
-        }
-        return d; }, sm);
-    if (threadIdx.x == 0) p.sigma[l][0] = sg;
-}
-
 extern "C" size_t eg_sn_multi_ws_floats(const eg_sn_layer* layers, int nlayers) {
     size_t tot = 0;
     for (int i = 0; i < nlayers; ++i) tot += (size_t)SN_NRB * layers[i].Kd + layers[i].R;
     return tot;
 }
 
-extern "C" int eg_sn_power_iter_multi2(const eg_sn_layer* layers, int nlayers, float* ws, unsigned int* counters, int training, float eps,
-                                       eg_stream_t s) {
+extern "C" int eg_sn_power_iter_multi(const eg_sn_layer* layers, int nlayers, float* ws, int training, float eps, eg_stream_t s) {
     EG_REQUIRE(layers && ws && nlayers > 0 && nlayers <= SN_MAXL, "eg_sn_power_iter_multi: bad argument");
     SnMulti p;
     memset(&p, 0, sizeof(p));
@@ -323,12 +211,6 @@ extern "C" int eg_sn_power_iter_multi2(const eg_sn_layer* layers, int nlayers, f
     }
     p.ws = ws; p.eps = eps;
     hipStream_t st = (hipStream_t)s;
-    if (training && counters) {
-        hipLaunchKernelGGL(snm2_wtu_v_kernel, dim3(cdiv(maxK, 1024), SN_NRB, nlayers), dim3(1024), 0, st, p, counters);
-        hipLaunchKernelGGL(snm2_wv_u_kernel, dim3(maxR, 1, nlayers), dim3(256), 0, st, p, counters);
-        EG_LAUNCH_CHECK();
-        return 0;
-    }
     if (training) {
         hipLaunchKernelGGL(snm_wtu_partial_kernel, dim3(cdiv(maxK, 256), SN_NRB, nlayers), dim3(256), 0, st, p);
         hipLaunchKernelGGL(snm_v_final_kernel, dim3(1, 1, nlayers), dim3(1024), 0, st, p);
@@ -339,10 +221,6 @@ extern "C" int eg_sn_power_iter_multi2(const eg_sn_layer* layers, int nlayers, f
     return 0;
 }
 
-extern "C" int eg_sn_power_iter_multi(const eg_sn_layer* layers, int nlayers, float* ws, int training, float eps, eg_stream_t s) {
-    return eg_sn_power_iter_multi2(layers, nlayers, ws, nullptr, training, eps, s);
-}
-
 // ---- Adam -----------------------------------------------------------------------------------------
 __global__ void adam_tick_kernel(int* step) { step[0] += 1; }
 
@@ -351,7 +229,7 @@ __global__ void adam_tick_kernel(int* step) { step[0] += 1; }
 // elements [0, head) and [head + 4*nvec, n) one per thread (the unaligned ends of an arena slice), the middle as float4; the four arrays
 // are slices of sibling arenas at the same element offset, so one `head` aligns all of them.  ZERO: the gradient is cleared in the
 // same pass (optimizer.zero_grad() of the next backward pass that accumulates into it).
-template <bool ZERO, bool V2>
+template <bool ZERO>
 __global__ void adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n, size_t head,
                             size_t nvec, float lr, float b1, float b2, float eps, const int* __restrict__ step) {
     const AdamCoef c = adam_coef(lr, b1, b2, eps, step);
@@ -359,24 +237,6 @@ __global__ void adam_kernel(float* __restrict__ p, float* __restrict__ g, float*
     // 8-byte vectors (two per 16-byte slot `nvec` counts): with 16-byte ones the kernel needs 50-54 VGPRs, with these 48 -- what a wave
     // may use on a SIMD beside the two 232-register waves of a resident 8-wave GEMM workgroup: the updates on the optimizer
     // lane run beside the next sub-step's GEMMs.  Same element arithmetic.
-    if constexpr (!V2) {                                 // (the 16-byte form: A/B runs, EG_ADAM_V2=0)
-        float4* p4 = reinterpret_cast<float4*>(p + head);
-        float4* g4 = reinterpret_cast<float4*>(g + head);
-        float4* m4 = reinterpret_cast<float4*>(m + head);
-        float4* v4 = reinterpret_cast<float4*>(v + head);
-        for (size_t i = tid; i < nvec; i += nth) {
-            float4 pi = p4[i], mi = m4[i], vi = v4[i];
-            const float4 gi = g4[i];
-            adam_elem(pi.x, gi.x, mi.x, vi.x, c);
-            adam_elem(pi.y, gi.y, mi.y, vi.y, c);
-            adam_elem(pi.z, gi.z, mi.z, vi.z, c);
-            adam_elem(pi.w, gi.w, mi.w, vi.w, c);
-            m4[i] = mi;
-            v4[i] = vi;
-            p4[i] = pi;
-            if (ZERO) g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    } else {
     float2* p2 = reinterpret_cast<float2*>(p + head);
     float2* g2 = reinterpret_cast<float2*>(g + head);
     float2* m2 = reinterpret_cast<float2*>(m + head);
@@ -390,7 +250,6 @@ __global__ void adam_kernel(float* __restrict__ p, float* __restrict__ g, float*
         v2[i] = vi;
         p2[i] = pi;
         if (ZERO) g2[i] = make_float2(0.f, 0.f);
-    }
     }
     const size_t tail0 = head + 4 * nvec, nends = head + (n - tail0);
     for (size_t e = tid; e < nends; e += nth) {
@@ -414,14 +273,8 @@ static void launch_adam(float* p, float* g, float* m, float* v, size_t n, float 
     if (!same) head = 0;
     const size_t work = same ? (nvec > 8 ? nvec : 8) : n;          // differently aligned slices: every element through the scalar loop
     const int blocks = (int)((work + 255) / 256 > 2048 ? 2048 : (work + 255) / 256);
-    static const bool v2 = [] { const char* e = getenv("EG_ADAM_V2"); return !(e && atoi(e) == 0); }();
-    if (v2) {
-        if (zero) hipLaunchKernelGGL((adam_kernel<true, true>), dim3(blocks), dim3(256), 0, st, p, g, m, v, n, head, nvec, lr, b1, b2, eps, step);
-        else hipLaunchKernelGGL((adam_kernel<false, true>), dim3(blocks), dim3(256), 0, st, p, g, m, v, n, head, nvec, lr, b1, b2, eps, step);
-    } else {
-        if (zero) hipLaunchKernelGGL((adam_kernel<true, false>), dim3(blocks), dim3(256), 0, st, p, g, m, v, n, head, nvec, lr, b1, b2, eps, step);
-        else hipLaunchKernelGGL((adam_kernel<false, false>), dim3(blocks), dim3(256), 0, st, p, g, m, v, n, head, nvec, lr, b1, b2, eps, step);
-    }
+    if (zero) hipLaunchKernelGGL(adam_kernel<true>, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, head, nvec, lr, b1, b2, eps, step);
+    else hipLaunchKernelGGL(adam_kernel<false>, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, head, nvec, lr, b1, b2, eps, step);
 }
 
 /* In-place Adam over a flat fp32 arena.  `step` is a device int32 incremented by this call (so a captured

@@ -5,7 +5,6 @@ entry :class:`DspritesTrainer` (loop body rp.py:365-482).  torch modules are par
 """
 from __future__ import annotations
 
-import os
 import argparse
 
 import numpy as np
@@ -14,19 +13,19 @@ import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
 from . import ops
-from .celeba import FUSE_STATS, GRAD_UP, IMG_GEMM, _HipModule, _require_cuda, transformation_2D      # noqa: F401
+from .celeba import GRAD_UP, IMG_GEMM, _HipModule, _require_cuda, transformation_2D      # noqa: F401
 from .engine import FUSE_DRAWS, Arena, ConvRec, DeviceSampler, ResidentStep, SideStream, SyncScratch, Workspace, bn_train_backward, bn_train_forward, capture_step, check_usable, parse_dtype
 from .ops import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, EG_F32, OUT_NCHW_F32
-from .trunk import IMG_DIRECT, WGRAD_IMG, Head, TrunkEngine
+from .trunk import Head, TrunkEngine
 
 opt = argparse.Namespace(n_epochs=100, batch_size=128, lr=0.0001, b1=0.5, b2=0.999, n_cpu=8, latent_dim=200, code_dim=4, n_classes=3,
                          img_size=64, channels=1, sample_interval=1000)           # argparse defaults rp.py:40-51
 TRUNK = (32, 32, 64, 64)
-# EXPERIMENT (default off): the generator's last-layer backward straight from the image gradient -- eg_wgrad_img (N = 64) for the weight
+# The generator's last-layer backward straight from the image gradient -- eg_wgrad_img (N = 64) for the weight
 # gradient, eg_conv_img_mfma (N = 64) with the BatchNorm-backward sums in its epilogue for the input gradient -- instead of patch rows + the
 # two GEMMs over them.  Same results within fp32 summation order (tests), one launch fewer, but SLOWER in the step: dSprites 1.305 -> 1.32 ms,
-# colored 2.50 -> 2.53 (profiles/r03_zzo_ab_l4_direct.txt): the statistics instantiation of the image kernel runs two workgroups per CU
-L4_DIRECT = os.environ.get("EG_L4_DIRECT", "0") != "0"
+# colored 2.50 -> 2.53 (profiles/r03_zzo_ab_l4_direct.txt): the statistics instantiation of the image kernel runs two workgroups per CU.
+# So no engine takes it by itself (``_GenEngine.l4_direct`` starts False); the layer-wise tests set the attribute to check this form of the layer too.
 
 
 def to_categorical(y, num_columns, device=None):
@@ -74,7 +73,7 @@ class _PxyEngine:
     def forward(self, img):
         dt, B, cb = self.dtype, self.B, self.mod.conv_block
         ep0 = ops.epilogue(bias=cb[0].bias, act=ACT_LRELU, slope=0.1)
-        if IMG_DIRECT and self.l0.Kpad_fwd == 64 and ops.conv_img_mfma_ok(dt, self.C, self.S, self.S, TRUNK[0], 4, 2, 1):
+        if self.l0.Kpad_fwd == 64 and ops.conv_img_mfma_ok(dt, self.C, self.S, self.S, TRUNK[0], 4, 2, 1):
             ops.conv_img_mfma(dt, [img], self.l0.wp_fwd, self.a[0], B, self.C, self.S, self.S, ep0, N=TRUNK[0])      # no patch rows (frozen: no weight gradient)
         else:
             ops.im2col_img(dt, img, self.patches, B, self.C, self.S, self.S, 4, 2, 1, self.kp)
@@ -217,10 +216,7 @@ class _GenEngine:
         # forward of the last ConvTranspose2d(64 -> C) as ONE GEMM over the 32x32 lattice with N = 16 taps x C columns + the col2im gather
         # (eg_col2im_img): every activation read once instead of 16 times (see celeba._GenEngine.l4g)
         self.l4g = ConvRec(dtype, B, 32, 32, 64, self.k0, 1, 1, 0, device=dev, want_bwd=False, want_wgrad=False, ws=ws)
-        self.l4_direct = (IMG_DIRECT and WGRAD_IMG and L4_DIRECT and self.kp == self.k0 and self.l4p.Kpad_fwd == 64
-                          and ops.conv_img_mfma_ok(dtype, self.CH, 64, 64, 64, 4, 2, 1) and ops.wgrad_img_ok(dtype, self.CH, 64, 64, 64, 4, 2, 1))
-        if self.l4_direct:
-            ws.need_slab(ops.wgrad_img_splits(B, 64) * 64 * self.kp * 4)
+        self.l4_direct = False                          # the image-direct backward of the last layer: measured slower, set by tests only (module comment)
         self.cols4 = torch.empty(B * 32 * 32, self.k0, device=dev, dtype=tdt)
         e = lambda *s, dt=tdt: torch.empty(s, device=dev, dtype=dt)
         f = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)
@@ -250,7 +246,7 @@ class _GenEngine:
     def _stat_buf(self, key, c, bwd, ep, C):
         """(nrb, buffer) if the launch described by (c, bwd, ep) can take its column statistics in the epilogue, else (0, None)"""
         if key not in self._stat:
-            nrb = ops.conv_stat_blocks(c, self.dtype, bwd, ep) if FUSE_STATS else 0
+            nrb = ops.conv_stat_blocks(c, self.dtype, bwd, ep)
             self._stat[key] = (nrb, torch.empty(2 * C * nrb, device=self.inp.device, dtype=torch.float32) if nrb else None)
         return self._stat[key]
 
@@ -299,7 +295,7 @@ class _GenEngine:
             else:
                 ops.bn_fwd_eval(dt, self.z[i], self.a[i], B * (8 << i) ** 2, 64, bn.weight, bn.bias, bn.eps, bn.running_mean, bn.running_var, ws.small, ACT_RELU)
             x = self.a[i]
-        if IMG_GEMM and IMG_DIRECT and self.l4g.Kpad_fwd == 64 and ops.convt_img_mfma_ok(dt, self.CH, 32, 32, 64, 4, 2, 1):
+        if IMG_GEMM and self.l4g.Kpad_fwd == 64 and ops.convt_img_mfma_ok(dt, self.CH, 32, 32, 64, 4, 2, 1):
             # GEMM + col2im gather as ONE launch (the columns stay in LDS; celeba._GenEngine.forward): same bits
             ops.convt_img_mfma(dt, x, self.l4g.wp_fwd, cb[9].bias, self.img, B, self.CH, 32, 32, ACT_SIGMOID, 0.0, K=64)
         elif IMG_GEMM:
@@ -325,7 +321,7 @@ class _GenEngine:
         ops.act_grad_mul_bias_nchw(dimg, self.img, self.dimg_z, B, self.CH, 64 * 64, ACT_SIGMOID, 0.0, ws.small, gof("conv_block.9.bias"))
         # the last layer's backward straight from the image gradient (no patch rows in HBM): weight gradient by eg_wgrad_img, input gradient by
         # eg_conv_img_mfma with the BatchNorm-backward sums of the layer below in its epilogue (celeba._GenEngine.backward)
-        direct = self.l4_direct and sync is None and FUSE_STATS
+        direct = self.l4_direct and sync is None
         if not direct:
             ops.im2col_img(dt, self.dimg_z, self.patches, B, self.CH, 64, 64, 4, 2, 1, self.kp)
 
@@ -684,15 +680,10 @@ class DspritesTrainer(ResidentStep):
             # for the joint step's forward (and backward), so that it does not wait for the D step to release the first one's buffers
             self.ws2 = Workspace(dev, register=False)
             self.chain = torch.cuda.Stream(dev)
-            # weight-gradient side lanes under the two chains: slower (profiles/r02_n_ab_small_lanes.txt), off.  "tailN": N lanes for the
-            # generator backward only -- the one phase in which a single chain is active
-            # (colored dSprites B = 512: 3.47 -> 3.34 ms with tail2; dSprites B = 128: 1.71 -> 1.73: on from batch 256 up,
-            #  profiles/r02_z_ab_tail_lanes.txt)
-            env = os.environ.get("EG_SMALL_LANES", "tail2" if B >= 256 else "0")
-            self.tail_lanes = env.startswith("tail")
-            nl = int(env[4:] or 2) if self.tail_lanes else int(env)
-            self.side_a = SideStream(dev, Workspace.get(dev), lanes=nl) if nl else None     # weight-gradient lanes of the main chain
-            self.side_b = SideStream(dev, self.ws2, lanes=nl) if (nl and not self.tail_lanes) else None    # ... and of the second chain
+            # weight-gradient side lanes under the two chains are slower (profiles/r02_n_ab_small_lanes.txt): two lanes for the generator
+            # backward only -- the one phase in which a single chain is active -- and from batch 256 up
+            # (colored dSprites B = 512: 3.47 -> 3.34 ms; dSprites B = 128: 1.71 -> 1.73, profiles/r02_z_ab_tail_lanes.txt)
+            self.side_a = SideStream(dev, Workspace.get(dev), lanes=2) if B >= 256 else None
             with Workspace.scope(self.ws2):
                 self.ee, self.ge2 = encoder.engine(B, slot=1), generator.engine(B, slot=1)
         else:
@@ -745,9 +736,7 @@ class DspritesTrainer(ResidentStep):
         L = self.losses
         mark = SideStream.mark
         main, chain = torch.cuda.current_stream(), self.chain
-        sa, sb = self.side_a, self.side_b
-        sa_d = None if getattr(self, "tail_lanes", False) else sa          # lanes of the D step's backward
-        join = lambda sd: sd.join_lanes() if sd is not None else None
+        sa = self.side_a                                  # weight-gradient lanes of the generator backward
         ops.fill_f32(L)
         # the alignment pass in front of BOTH chains: the second chain forks from a point with no main-chain work queued behind it
         # (behind the first generator forward the replayed step ran the two chains one after the other, profiles/r03_zzh_ab_align_late.txt)
@@ -768,30 +757,19 @@ class DspritesTrainer(ResidentStep):
             self._affine_loss(cont[B:2 * B], cont[2 * B:], L[3:4], self.d_cont[B:2 * B], self.d_cont[2 * B:])
             ops.loss_mutual_info(cat[2 * B:], nc, 0, nc, B, cat[B:2 * B], nc, 0, True, 1.0, L[4:5], self.d_cat[2 * B:])
             self._log_info_terms(cat, cont)
-            dimg_e = ee.backward(0, 3, {"cat_layer.0": self.d_cat, "cont_layer.0": self.d_cont}, ea.grad, need_dimg=True, side=sb)
+            dimg_e = ee.backward(0, 3, {"cat_layer.0": self.d_cat, "cont_layer.0": self.d_cont}, ea.grad, need_dimg=True)
             e_dimg = mark()
-            evs = {}
-
-            def update_e(_ws):
-                # optimizer_info's step counter is shared by G and E: it ticks here, G's update (main chain, behind this event) reads it
-                self._adam(ea, self.miE, self.viE, self.lr[1], 1, True)
-                ee.repack()
-                evs["chain"] = mark()
-            if sb is not None:
-                # behind the encoder's weight-gradient lanes, on the lanes' optimizer stream: the second chain itself must never wait for
-                # its lanes (hipStreamEndCapture crashes on a stream-level cycle that does not pass through the capture's origin stream)
-                sb.defer_opt(update_e)
-            else:
-                update_e(None)
-            e_chain = evs["chain"]
+            # optimizer_info's step counter is shared by G and E: it ticks here, G's update (main chain, behind this event) reads it
+            self._adam(ea, self.miE, self.viE, self.lr[1], 1, True)
+            ee.repack()
+            e_chain = mark()
         # ---- D step (:404-419): D(trans) then D(gen.detach()) ----
         self._transform(self.code1, self.trans1)                                             # :396-400
         ops.fill_f32(da.grad)
         out = de.forward([self.trans1, gen])["fc2"]
         ops.loss_bce_sigmoid(out[:B], 1, 0, B, 1.0, 0.5, L[0:1], self.dout_d[:B])
         ops.loss_bce_sigmoid(out[B:], 1, 0, B, 0.0, 0.5, L[0:1], self.dout_d[B:])
-        de.backward(0, 2, {"fc2": self.dout_d}, da.grad, side=sa_d)
-        join(sa_d)
+        de.backward(0, 2, {"fc2": self.dout_d}, da.grad)
         self._adam(da, self.mD, self.vD, self.lr[0], 0, True)
         de.repack()
         # ---- joint step (:424-482): the generator's adversarial term needs the UPDATED discriminator ----
@@ -802,7 +780,8 @@ class DspritesTrainer(ResidentStep):
         main.wait_event(e_dimg)
         ops.add_f32(self.dimg, dimg_e, dimg_d)
         ge2.backward(self.dimg, ga.grad, side=sa)
-        join(sa)
+        if sa is not None:
+            sa.join_lanes()
         main.wait_event(e_chain)
         self._adam(ga, self.miG, self.viG, self.lr[1], 1, False)
         ge.repack()

@@ -127,7 +127,8 @@ class Workspace:
         self._grow("sums", floats)
 
 
-LANE_WGS_TARGET = int(os.environ.get("EG_LANE_WGS", "64"))      # 64: profiles/r03_o_lane_wgs_sweep.txt (128 in round 2)
+# workgroups the weight-gradient GEMMs of a side lane aim for (tests set 0 -- the whole chip -- for their reference run)
+LANE_WGS_TARGET = 64      # 64: profiles/r03_o_lane_wgs_sweep.txt (128 in round 2)
 
 
 class _Lane:
@@ -297,7 +298,9 @@ def bn_train_backward(dt, z, da, dz, M, C, bn, mean, invstd, act, slope, dgamma,
     ops.bn_bwd_from_sums(dt, z, da, dz, M, C, sums, M * sync.world, bn.weight, bn.bias, mean, invstd, act, slope, ws.small)
 
 
-FUSE_DRAWS = os.environ.get("EG_FUSE_INPUTS", "1") != "0"      # (the switch of celeba.FUSE_INPUTS)
+# an iteration's device-side draws as one launch and the counter tick inside the gather (same values); False: one launch per draw, the
+# reference the tests compare against
+FUSE_DRAWS = True
 
 
 class DeviceSampler:

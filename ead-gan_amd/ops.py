@@ -6,7 +6,6 @@ torch is used for device memory and streams only.  No function here has a CPU or
 from __future__ import annotations
 
 import ctypes
-import os
 
 import torch
 
@@ -59,13 +58,8 @@ def conv_splitk_ws_bytes(c, dtype, bwd):
     return lib().query("eg_conv_splitk_ws_bytes", ctypes.byref(c), dtype, int(bwd))
 
 
-# experiment switches (A/B runs of a whole step): default hints of every launch that does not pass its own
-_ENV_VARIANT = int(os.environ.get("EG_NT_VARIANT", "0"))
-_ENV_SPLITK = int(os.environ.get("EG_NT_SPLITK", "0"))
-
-
 def epilogue(bias=None, bias_mod=0, sigma=None, act=ACT_NONE, slope=0.0, mask=None, mask_act=ACT_NONE,
-             mask_slope=0.0, out_mode=OUT_NHWC, sigma_rows=0, nt_variant=_ENV_VARIANT, nt_splitk=_ENV_SPLITK, splitk_ws="default",
+             mask_slope=0.0, out_mode=OUT_NHWC, sigma_rows=0, nt_variant=0, nt_splitk=0, splitk_ws="default",
              stat_mode=STAT_NONE, stat_out=None, stat_aux=None, stat_p=(), stat_act=ACT_NONE, stat_slope=0.0) -> EgEpilogue:
     """``nt_variant`` / ``nt_splitk``: per-call kernel hints (NT_* in _lib.py; 0 = the planner decides).  ``splitk_ws``: scratch
     tensor lent for K splits (default: the device's registered workspace; None = never split).  ``stat_*``: column statistics of
@@ -368,9 +362,6 @@ def head_fused_ok(dtype, T, K, N):
     return bool(lib().cdll.eg_head_fused_ok(dtype, T, K, N))
 
 
-PACK_BATCH = os.environ.get("EG_PACK_BATCH", "1") != "0"      # 0: every pack its own launch (A/B runs)
-
-
 class PackBatch:
     """The pack launches issued by ``fn()`` as ONE launch (eg_pack_record_begin / _end / eg_pack_multi).  Eager calls record again (host
     work only) and re-upload the job table if a pointer or a geometry changed; inside a hipGraph capture the table of the last eager call
@@ -383,8 +374,6 @@ class PackBatch:
         self.n = self.nb = 0
 
     def run(self, fn):
-        if not PACK_BATCH:
-            return fn()
         if not (self.dev is not None and torch.cuda.is_current_stream_capturing()):
             jb = lib().cdll.eg_pack_job_bytes()
             cap = self.MAX_JOBS * jb
@@ -560,19 +549,8 @@ def sn_multi_ws_floats(arr):
     return lib().query("eg_sn_multi_ws_floats", arr, len(arr))
 
 
-# EXPERIMENT (default off): the power iteration of a network's layers as two launches instead of four (eg_sn_power_iter_multi2: each stage's
-# per-layer finish by the last workgroup to arrive).  Same bits, but slower in the step: CelebA 4.33 -> 4.38 ms, dSprites 1.413 -> 1.424
-# (profiles/r03_zf_ab_sn2.txt) -- the wide first stage runs 1024-thread workgroups and every layer's finish waits for its last row.
-SN_TWO_LAUNCHES = os.environ.get("EG_SN2", "0") != "0"
-
-
-def sn_power_iter_multi(arr, ws, training=True, eps=1e-12, counters=None):
-    """``counters``: int32 tensor of >= 2 * len(arr) zeros owned by the caller (one per engine and stream of use): the iteration runs as two
-    launches instead of four, same bits (eg_sn_power_iter_multi2)"""
-    if counters is None or not SN_TWO_LAUNCHES:
-        lib().call("eg_sn_power_iter_multi", arr, len(arr), _p(ws), int(training), eps, _stream())
-    else:
-        lib().call("eg_sn_power_iter_multi2", arr, len(arr), _p(ws), _p(counters), int(training), eps, _stream())
+def sn_power_iter_multi(arr, ws, training=True, eps=1e-12):
+    lib().call("eg_sn_power_iter_multi", arr, len(arr), _p(ws), int(training), eps, _stream())
 
 
 def adam_step(p, g, m, v, n, lr, b1, b2, eps, step, tick=True):

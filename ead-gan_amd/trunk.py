@@ -8,27 +8,14 @@ ONE weight-gradient GEMM covers all tapes and the spectral-norm rank-1 terms are
 """
 from __future__ import annotations
 
-import os
 from dataclasses import dataclass, field
 
 import torch
 
 from . import ops
+from .celeba import IMG_GEMM
 from .engine import ConvRec, Workspace
 from .ops import ACT_LRELU, ACT_NONE, EG_F32, OUT_NCHW_F32
-
-IMG_GEMM = os.environ.get("EG_IMG_GEMM", "1") == "1"     # as in celeba.py
-FUSE_STATS = os.environ.get("EG_FUSE_STATS", "1") != "0"  # as in celeba.py
-# the first layer straight from the fp32 images (ops.conv_img_mfma: 4x4 / stride-2 first layers with 32 / 64 / 128 channels, 16-bit types) instead
-# of patch rows + a K = 64 GEMM over them; the patch rows are then only the weight gradient's operand (``forward(..., patches=False)`` skips
-# them where no weight gradient follows).  Same bits.  EG_IMG_DIRECT=0: patch rows + GEMM
-IMG_DIRECT = os.environ.get("EG_IMG_DIRECT", "1") != "0"
-# ... and its weight gradient straight from the images too (ops.wgrad_img: patch rows expanded in LDS): no patch rows in HBM at all for the
-# first layer.  EG_WGRAD_IMG=0: patch rows (eg_im2col_img at forward time) + the per-tap GEMM
-WGRAD_IMG = os.environ.get("EG_WGRAD_IMG", "1") != "0"
-# trunks with BatchNorm (the MNIST discriminator / encoder): the forward's convolutions, hidden layers and heads once over all T tapes with one
-# BatchNorm pass per tape in between, instead of T whole passes.  EG_BN_BATCH_TAPES=0: one pass per tape
-BN_BATCH_TAPES = os.environ.get("EG_BN_BATCH_TAPES", "1") != "0"
 
 SN_EPS = 1e-12
 
@@ -147,12 +134,15 @@ class TrunkEngine:
                     for h in heads if h.sn]
             self._sn_arrays.append(ops.sn_layers(ent))
         ws.need_small(ops.sn_multi_ws_floats(self._sn_arrays[0]))
-        self.sn_counters = torch.zeros(16, device=dev, dtype=torch.int32)       # arrival counters of the two-launch power iteration
         self.imgs = [None] * NT
         self.patch_ok = [False] * NT
-        self.img_direct = (IMG_DIRECT and NT <= 3 and self.l0p.Kpad_fwd == 64 and self.kp <= 64
+        # the first layer straight from the fp32 images (ops.conv_img_mfma: 4x4 / stride-2 first layers with 32 / 64 / 128 channels, 16-bit types)
+        # instead of patch rows + a K = 64 GEMM over them; the patch rows are then only the weight gradient's operand (``forward(...,
+        # patches=False)`` skips them where no weight gradient follows).  Same bits.
+        self.img_direct = (NT <= 3 and self.l0p.Kpad_fwd == 64 and self.kp <= 64
                            and ops.conv_img_mfma_ok(dtype, in_ch, size, size, self.W[0], k, 2, pad))
-        self.wgrad_direct = (self.img_direct and WGRAD_IMG and self.kp == self.k0
+        # ... and its weight gradient straight from the images too (ops.wgrad_img: patch rows expanded in LDS): no patch rows in HBM at all
+        self.wgrad_direct = (self.img_direct and self.kp == self.k0
                              and ops.wgrad_img_ok(dtype, in_ch, size, size, self.W[0], k, 2, pad))
         if self.wgrad_direct:
             ws.need_slab(ops.wgrad_img_splits(NT * B, self.W[0]) * self.W[0] * self.kp * 4)
@@ -247,7 +237,7 @@ class TrunkEngine:
         for kk, img in enumerate(imgs):
             t = t0 + kk
             self.imgs[t] = img
-            ops.sn_power_iter_multi(self._sn_arrays[t], self.ws.small, training, SN_EPS, self.sn_counters)
+            ops.sn_power_iter_multi(self._sn_arrays[t], self.ws.small, training, SN_EPS)
             if not training:
                 for i, c in enumerate(self.convs):
                     self.u[i][t].copy_(c.weight_u)
@@ -268,11 +258,8 @@ class TrunkEngine:
                 if patches and not self.wgrad_direct:
                     ops.im2col_img(dt, img, self.patches[(t0 + kk) * npix:(t0 + kk + 1) * npix], B, self.in_ch, self.S, self.S, self.k, 2, 1, self.kp)
                 self.patch_ok[t0 + kk] = bool(patches) and not self.wgrad_direct
-        if self.has_bn and not BN_BATCH_TAPES:
-            for kk in range(T):
-                self._fwd_pass(t0 + kk, 1, training, self.img_direct)
-        else:
-            self._fwd_pass(t0, T, training, self.img_direct)
+        # (trunks with BatchNorm too: convolutions, hidden layers and heads once over all T tapes, one BatchNorm pass per tape in between)
+        self._fwd_pass(t0, T, training, self.img_direct)
         return {h.name: self.outs[h.name][t0 * B:(t0 + T) * B] for h in self.heads if h.compute}
 
     # ------------------------------------------------------------------------------------------------------------------
@@ -281,7 +268,7 @@ class TrunkEngine:
         blocks, buffer), (0, None) where that launch cannot take them (4x4 stride-2 layers, whole 128-row tiles per tape and phase)"""
         key = (i, T)
         if key not in self._stat:
-            ok = FUSE_STATS and self.taps == 16 and self.rows(i + 1) % 128 == 0 and self.dtype != EG_F32
+            ok = self.taps == 16 and self.rows(i + 1) % 128 == 0 and self.dtype != EG_F32
             nrb = ops.conv_stat_blocks(c, self.dtype, True, ep) if ok else 0
             if nrb % (4 * T):
                 nrb = 0
@@ -406,11 +393,4 @@ class TrunkEngine:
         """douts: {head name: d(loss)/d(head output) [T*B, N] fp32} for every computed head (zeros where a head carries no
         loss).  Accumulates into flat ``grad``; returns d(loss)/d(img) of tape t0 if ``need_dimg``.  ``side`` (engine.SideStream): each
         layer's weight- / bias-gradient chain runs on a side lane; the caller joins the lanes before it reads ``grad``."""
-        if self.has_bn and T > 1 and not BN_BATCH_TAPES:
-            dimg = None
-            for kk in range(T):
-                sub = {k: v[kk * self.B:(kk + 1) * self.B] for k, v in douts.items()}
-                r = self._bwd_pass(t0 + kk, 1, sub, grad, need_wgrad, need_dimg and kk == 0, side)
-                dimg = r if kk == 0 else dimg
-            return dimg
         return self._bwd_pass(t0, T, douts, grad, need_wgrad, need_dimg, side)

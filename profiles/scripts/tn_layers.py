@@ -1,5 +1,6 @@
 """Weight-gradient GEMM timings on the CelebA B=128 layers (conv k4 s2 p1; T tapes batched along M): TFLOP/s of eg_conv_wgrad alone and
-with its slab reduction.  EG_TN8=0 in the environment selects the per-tap kernel (igemm_tn_kernel) for an A/B in two processes.
+with its slab reduction.  EG_TN8=0 in the environment selects the per-tap kernel (igemm_tn_kernel) for an A/B in two processes.  (That switch
+was removed from the code after this measurement; kept as the record of how it was measured.)
 usage: python profiles/scripts/tn_layers.py [--T 1,2,3]"""
 import argparse
 import importlib

@@ -66,6 +66,28 @@ def test_no_oracle_import_in_product_path():
             assert "oracle" not in src.replace("# oracle", ""), fn
 
 
+def test_no_environment_switches_in_library_or_package():
+    """One configuration exists: the library reads no environment variable, the package reads the launcher's variables in dp.py only, and
+    the module constants that tests patch to reach their reference paths are each defined in one module (the others import them)."""
+    import re
+    for d in (os.path.join(ROOT, "ead-gan_amd", "csrc"), os.path.join(ROOT, "include")):
+        for fn in sorted(os.listdir(d)):
+            assert "getenv" not in open(os.path.join(d, fn), errors="replace").read(), fn
+    owners = {name: [] for name in ("IMG_GEMM", "FUSE_STATS", "IMG_DIRECT", "FUSE_DRAWS", "FUSE_INPUTS")}
+    for fn in sorted(os.listdir(os.path.join(ROOT, "ead-gan_amd"))):
+        if not fn.endswith(".py"):
+            continue
+        src = open(os.path.join(ROOT, "ead-gan_amd", fn)).read()
+        if fn != "dp.py":
+            assert "os.environ" not in src and "os.getenv" not in src and not re.search(r"\bfrom os import\b.*\b(environ|getenv)\b", src), fn
+        for name in owners:
+            if re.search(rf"^{name}\s*(:[^=\n]*)?=[^=]", src, re.M):
+                owners[name].append(fn)
+    for name, files in owners.items():
+        assert len(files) <= 1, (name, files)
+    assert len(owners["FUSE_DRAWS"]) + len(owners["FUSE_INPUTS"]) <= 1, owners      # one draws switch under one name
+
+
 DP_WORKER = r"""
 import importlib, os, sys, torch
 sys.path.insert(0, sys.argv[1])

@@ -503,7 +503,7 @@ def test_ragged_batch_sizes_through_the_drop_in_modules(B):
 @pytest.mark.parametrize("dtype,tol", [("f32", 2e-6), ("bf16", 2e-2)])
 def test_image_side_layers_both_formulations_agree(dtype, tol, monkeypatch):
     """The 128 -> 3 transposed convolutions (G's last layer forward, D's first-layer backward-to-image) as one GEMM + col2im gather (the
-    default) and as the 4-phase implicit GEMM (EG_IMG_GEMM=0, kept as an A/B switch) are the same function: fp32 up to summation order,
+    default) and as the 4-phase implicit GEMM (celeba.IMG_GEMM = False, kept as this test's reference) are the same function: fp32 up to summation order,
     bf16 up to one extra rounding of the per-tap partial sums."""
     B = 4
     orc, G, D = build_pair(2, dtype)

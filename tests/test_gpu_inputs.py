@@ -132,7 +132,7 @@ def test_fused_iteration_head_draws_the_same_batches(monkeypatch):
     data = (co.synthetic_real(64, seed=9) * 127.5 + 127.5).clamp(0, 255).to(torch.uint8).to(DEV)
     runs = []
     for fuse in (False, True):
-        monkeypatch.setattr(eg.celeba, "FUSE_INPUTS", fuse)
+        monkeypatch.setattr(eg.celeba, "FUSE_DRAWS", fuse)
         orc = co.CelebAOracle(seed=2)
         G = eg.celeba.Generator(dtype="bf16").to(DEV)
         D = eg.celeba.Discriminator(dtype="bf16").to(DEV)
