@@ -218,11 +218,16 @@ class _GenEngine:
                               ops.epilogue(bias=self._p(10, "bias"), act=ACT_TANH, out_mode=OUT_NCHW_F32))
         return self.img
 
-    def backward(self, dimg, grad, side=None, sync=None):
+    def backward(self, dimg, grad, side=None, sync=None, store=False):
         """Accumulates d(loss)/d(params) into the flat gradient tensor ``grad`` (arena layout).  ``sync``: as in forward.  With ``side`` (an
         engine.SideStream) the weight/bias-gradient work of every layer is enqueued there, behind a fork taken right after
-        the layer's output gradient exists; the caller joins before it reads ``grad``."""
+        the layer's output gradient exists; the caller joins before it reads ``grad``.
+        ``store``: every slot of ``grad`` has exactly ONE writer in this pass (weights: the slab reduction; convolution biases: the column
+        sums; BatchNorm affine: the statistics' final launch), so a caller that wants the gradient of this pass alone -- the trainer --
+        lets each of them store instead of add: ``grad`` need not be cleared first and is never read.  The default keeps autograd's
+        accumulate contract (the drop-in modules)."""
         dt, B, W, ws, gen = self.dtype, self.B, G_WIDTHS, self.ws, self.gen
+        acc = not store
         gof = lambda name: gen.arena.grad_of(name, grad)
         C, S = gen.channels, self.img.shape[-1]
         def wgrad_side(fn, lane, tag=None):
@@ -234,16 +239,17 @@ class _GenEngine:
         direct = ops.conv_img_mfma_ok(dt, C, S, S, W[3], 4, 2, 1)
         if not direct:
             # tanh backward fused with the bias gradient of the last ConvTranspose2d
-            ops.act_grad_mul_bias_nchw(dimg, self.img, self.dimg_z, B, C, S * S, ACT_TANH, 0.0, ws.small, gof("conv_blocks.10.bias"))
+            ops.act_grad_mul_bias_nchw(dimg, self.img, self.dimg_z, B, C, S * S, ACT_TANH, 0.0, ws.small, gof("conv_blocks.10.bias"), accumulate=acc)
             # L4 = ConvTranspose2d(128 -> C): weight / input gradients as 1x1-conv GEMMs over im2col patches of d(img)
             ops.im2col_img(dt, self.dimg_z, self.patches, B, C, S, S, 4, 2, 1, self.kp)
 
         def l4_wgrad(wsw):
             if direct:                                  # the patch rows only feed the weight gradient: built here, beside the main chain
-                ops.act_grad_mul_bias_nchw(dimg, self.img, self.dimg_z, B, C, S * S, ACT_TANH, 0.0, wsw.small, gof("conv_blocks.10.bias"))
+                ops.act_grad_mul_bias_nchw(dimg, self.img, self.dimg_z, B, C, S * S, ACT_TANH, 0.0, wsw.small, gof("conv_blocks.10.bias"),
+                                           accumulate=acc)
                 ops.im2col_img(dt, self.dimg_z, self.patches, B, C, S, S, 4, 2, 1, self.kp)
             ns = ops.conv_wgrad(self.l4p.c, dt, self.patches, self.a[2], wsw.slab, wsw.wgs_target)
-            ops.wgrad_reduce(wsw.slab, ns, W[3], W[3], self.kp, 1, gof("conv_blocks.10.weight"))
+            ops.wgrad_reduce(wsw.slab, ns, W[3], W[3], self.kp, 1, gof("conv_blocks.10.weight"), accumulate=acc)
         wgrad_side(l4_wgrad, 0, "G4")
         fused = (0, None)                               # (row blocks, sums) if da[i] came with its BatchNorm backward sums (then it holds dy)
         if direct:
@@ -268,22 +274,23 @@ class _GenEngine:
             M = self.z[i].numel() // W[i + 1]
             if fused[0]:
                 ops.bn_bwd_fused(dt, self.z[i], self.da[i], self.dz[i], M, W[i + 1], fused[1], fused[0], bn.weight, bn.bias, self.mean[i], self.invstd[i],
-                                 gof(f"conv_blocks.{idx + 1}.weight"), gof(f"conv_blocks.{idx + 1}.bias"), ws.sums, ws.small)
+                                 gof(f"conv_blocks.{idx + 1}.weight"), gof(f"conv_blocks.{idx + 1}.bias"), ws.sums, ws.small, accumulate=acc)
             elif sync is not None:
                 ops.bn_bwd_sums_local(dt, self.z[i], self.da[i], M, W[i + 1], bn.weight, bn.bias, self.mean[i], self.invstd[i], ACT_RELU, 0.0,
-                                      gof(f"conv_blocks.{idx + 1}.weight"), gof(f"conv_blocks.{idx + 1}.bias"), self.bn_sums[i], ws.small)
+                                      gof(f"conv_blocks.{idx + 1}.weight"), gof(f"conv_blocks.{idx + 1}.bias"), self.bn_sums[i], ws.small,
+                                      accumulate=acc)
                 sync.reduce_sums(self.bn_sums[i])
                 ops.bn_bwd_from_sums(dt, self.z[i], self.da[i], self.dz[i], M, W[i + 1], self.bn_sums[i], M * sync.world, bn.weight, bn.bias,
                                      self.mean[i], self.invstd[i], ACT_RELU, 0.0, ws.small)
             else:
                 ops.bn_bwd(dt, self.z[i], self.da[i], self.dz[i], M, W[i + 1], bn.weight, bn.bias, self.mean[i], self.invstd[i], ACT_RELU, 0.0,
-                           gof(f"conv_blocks.{idx + 1}.weight"), gof(f"conv_blocks.{idx + 1}.bias"), ws.sums, ws.small)
+                           gof(f"conv_blocks.{idx + 1}.weight"), gof(f"conv_blocks.{idx + 1}.bias"), ws.sums, ws.small, accumulate=acc)
             x_in = self.a[i - 1] if i > 0 else self.h0
 
             def mid_wgrad(wsw, i=i, idx=idx, r=r, M=M, x_in=x_in):
                 ns = ops.conv_wgrad(r.c, dt, self.dz[i], x_in, wsw.slab, wsw.wgs_target)
-                ops.wgrad_reduce(wsw.slab, ns, r.Cout, r.Cout, r.Cin, 16, gof(f"conv_blocks.{idx}.weight"))
-                ops.bias_grad(dt, self.dz[i], M, W[i + 1], wsw.small, gof(f"conv_blocks.{idx}.bias"))
+                ops.wgrad_reduce(wsw.slab, ns, r.Cout, r.Cout, r.Cin, 16, gof(f"conv_blocks.{idx}.weight"), accumulate=acc)
+                ops.bias_grad(dt, self.dz[i], M, W[i + 1], wsw.small, gof(f"conv_blocks.{idx}.bias"), accumulate=acc)
             wgrad_side(mid_wgrad, i + 1, f"G{i + 1}")
             fused = (0, None)
             if i > 0 and sync is None:
@@ -300,8 +307,8 @@ class _GenEngine:
         # L0
         def l0_wgrad(wsw):
             ns = ops.conv_wgrad(self.l0w.c, dt, self.dh0, self.inp, wsw.slab, wsw.wgs_target)
-            ops.wgrad_reduce(wsw.slab, ns, self.cpad, self.cin, W[0], 16, gof("conv_blocks.0.weight"))
-            ops.bias_grad(dt, self.dh0, B * 16, W[0], wsw.small, gof("conv_blocks.0.bias"))
+            ops.wgrad_reduce(wsw.slab, ns, self.cpad, self.cin, W[0], 16, gof("conv_blocks.0.weight"), accumulate=acc)
+            ops.bias_grad(dt, self.dh0, B * 16, W[0], wsw.small, gof("conv_blocks.0.bias"), accumulate=acc)
         wgrad_side(l0_wgrad, 0, "G0")
 
 
@@ -606,11 +613,14 @@ class _DiscEngine:
                        B, T, K, self.head.Kpad_fwd, self.nout, loss, terms, counter, ACT_LRELU, LRELU_SLOPE, targets=targets, scales=scales, info=info)
         return out
 
-    def backward(self, t0, T, dout, grad, need_wgrad=True, need_dimg=False, side=None, head_done=False):
+    def backward(self, t0, T, dout, grad, need_wgrad=True, need_dimg=False, side=None, head_done=False, store=False):
         """``dout``: d(loss)/d(head output) of tapes t0..t0+T-1, [T*B,19] fp32.  Accumulates into flat ``grad`` (arena
         layout); returns d(loss)/d(img) of tape t0 when ``need_dimg``.  With ``side`` (engine.SideStream) the weight- and
-        bias-gradient work is enqueued there (see _GenEngine.backward); the caller joins before it reads ``grad``."""
+        bias-gradient work is enqueued there (see _GenEngine.backward); the caller joins before it reads ``grad``.
+        ``store``: as in _GenEngine.backward -- the T tapes are batched into ONE weight-gradient GEMM, one rank-1 reduction and one column-sum
+        launch per layer, so with ``need_wgrad`` every slot of ``grad`` has exactly one writer here too (without it nothing is written)."""
         dt, B, W, ws, disc = self.dtype, self.B, D_WIDTHS, self.ws, self.disc
+        acc = not store
         gof = lambda name: disc.arena.grad_of(name, grad)
         g = self.geo[T]
         sl = lambda buf: buf[t0 * (buf.shape[0] // self.NT):]
@@ -625,8 +635,8 @@ class _DiscEngine:
             def head_wgrad(wsw):
                 ops.cast_pad(dt, dout, self.dout_t, T * B, self.nout, 32)
                 ns = ops.conv_wgrad(g["headw"], dt, sl(self.a[3]), self.dout_t, wsw.slab, wsw.wgs_target)
-                ops.wgrad_reduce(wsw.slab, ns, 32, self.nout, W[3], 16, gof("main.8.weight"))
-                ops.dense_small_bgrad(dout, gof("main.8.bias"), T * B, self.nout)
+                ops.wgrad_reduce(wsw.slab, ns, 32, self.nout, W[3], 16, gof("main.8.weight"), accumulate=acc)
+                ops.dense_small_bgrad(dout, gof("main.8.bias"), T * B, self.nout, accumulate=acc)
             wgrad_side(head_wgrad, 0, "D4")
         # dzs_3 = (W5^T dout) * lrelu'(a3) / sigma_3[tape]
         if not head_done:
@@ -648,13 +658,14 @@ class _DiscEngine:
                     ns = ops.conv_wgrad(geo, dt, x_in, sl(self.dz[i]), wsw.slab, wsw.wgs_target)
                     if fused[0]:
                         tiles_m = fused[0] // 4         # row blocks (of 256 or 128 lattice rows: the kernel's tile height) per sub-pixel phase
-                        ops.bias_grad_sn_fused(fused[1], fused[0], W[i], tiles_m, tiles_m // T, T, self.sigma[i][t0:], gof(f"main.{2 * i}.bias"), self.coef[i])
+                        ops.bias_grad_sn_fused(fused[1], fused[0], W[i], tiles_m, tiles_m // T, T, self.sigma[i][t0:], gof(f"main.{2 * i}.bias"), self.coef[i],
+                                               accumulate=acc)
                     else:
                         ops.bias_grad_sn(dt, sl(self.dz[i]), sl(self.a[i]), m.bias, T * self.rows(i), W[i], self.rows(i), self.sigma[i][t0:], LRELU_SLOPE,
-                                         wsw.small, gof(f"main.{2 * i}.bias"), self.coef[i])
+                                         wsw.small, gof(f"main.{2 * i}.bias"), self.coef[i], accumulate=acc)
                     taps = 16 if i > 0 else 1
                     ops.wgrad_reduce_rank1(wsw.slab, ns, W[i], W[i], self.cin[i], taps, gof(f"main.{2 * i}.weight_orig"), T, self.coef[i],
-                                           self.u[i][t0:], self.v[i][t0:])
+                                           self.u[i][t0:], self.v[i][t0:], accumulate=acc)
                 wgrad_side(layer_wgrad, i + 1, f"D{i}")
             if i > 0:
                 # dzs_{i-1} = conv^T(dzs_i, W_i) * lrelu'(a_{i-1}) / sigma_{i-1}[tape]
@@ -990,11 +1001,45 @@ class CelebATrainer(TrainerState):
         self.graph = None
         self.inputs = None
         self.log = None
+        # test hook: callable(k) run on the main stream in front of the backward pass of sub-step k = 1, 2, 3, at a point where no launch of
+        # an earlier pass still reads either gradient arena (tests/test_gpu_grad_store.py poisons them there).  To give it that point the
+        # pipelined body adds ONE wait in front of step 2's hook (for step 1's generator update, which otherwise runs beside step 2): a run
+        # with the hook set is the shipped iteration with that extra edge -- same launches, same operands, same bits.  None in production
+        # and in every capture (bench.py, train.py): the branch is then never taken.
+        self.before_backward = None
         # weight-gradient chains and re-packing run on a second stream beside the backward-data chain (same arithmetic, same order
         # inside every chain -> bit-identical results with and without)
         self.side = SideStream(dev, Workspace.get(dev), lanes=4) if overlap else None
+        # the iteration never clears the gradient arenas (WRITER TABLE below): once here, so that whatever an earlier user of the modules
+        # left in them is gone before anybody reads `.grad`
+        ops.fill_f32(ga.grad)
+        ops.fill_f32(da.grad)
 
     # -- the hot path ---------------------------------------------------------------------------------
+    # WRITER TABLE of the two gradient arenas (optimizer.zero_grad() of the reference loop, :334,353,375).  A backward pass of _GenEngine /
+    # _DiscEngine has exactly ONE launch per parameter slice, and every slice has one (Arena: the parameters tile it, no padding):
+    #
+    #   slice                                  writer (launch)                                   stream, pipelined body (SideStream.defer index)
+    #   G conv_blocks.10.weight / .bias        wgrad_reduce / act_grad_mul_bias_nchw             chain G4, lane 0 (bias: main stream without conv_img_mfma)
+    #   G conv_blocks.{7,4,1}.weight / .bias   wgrad_reduce / bias_grad                          chains G3,G2,G1, lanes 3,2,1: both on the layer's chain
+    #   G conv_blocks.{8,5,2}.weight / .bias   bn_bwd_fused | bn_bwd | bn_bwd_sums_local         main stream
+    #   G conv_blocks.0.weight / .bias         wgrad_reduce / bias_grad                          chain G0, lane 0
+    #   D main.8.weight / .bias                wgrad_reduce / dense_small_bgrad                  chain D4, lane 0
+    #   D main.{6,4,2,0}.weight_orig / .bias   wgrad_reduce_rank1 / bias_grad_sn[_fused]         chains D3..D0, lanes 4,3,2,1: both on the layer's chain
+    #
+    #   pass                      G arena                                        D arena
+    #   step 1 (G adversarial)    every slice: first and only writer -> STORE    no writer (need_wgrad=False) and no reader: untouched
+    #   step 2 (D)                no writer, no reader: untouched                every slice: first and only writer -> STORE
+    #   step 3 (info + affine)    every slice: first and only writer -> STORE    every slice: first and only writer -> STORE
+    #
+    # No slice has a second writer behind the first (nothing keeps accumulate), none collects contributions from lanes that are not ordered
+    # against each other (the three tapes of step 3 are batched into one GEMM and one reduction per layer), and the only slices without a
+    # writer in a pass -- D's in step 1, G's in step 2 -- have no reader in it either (no all-reduce, no Adam): they keep the gradients of
+    # the last pass that wrote them, as the reference's do between zero_grad() calls of the OTHER optimizer.  So the iteration has no
+    # arena fill at all and no Adam launch clears its gradients.
+    # Hazards a store must respect are those the read-modify-write had: a writer of pass k+1 runs behind the Adam launch (and, data
+    # parallel, the all-reduce) that read the slice in pass k -- step 3's generator forward waits for evs["g"], its discriminator forward
+    # joins every lane, and the iteration ends with a join.  The gradients of step 3 stay in place afterwards: callers and tests read them.
     def _buckets(self, arena):
         """(tag, lo, hi) element ranges of `arena` per layer bucket, in completion order; the ranges tile the arena"""
         eng = self.ge if arena is self.G.arena else self.de
@@ -1019,6 +1064,10 @@ class CelebATrainer(TrainerState):
             ops.adam_tick(self.steps[slot:slot + 1])
         for tag, lo, hi in self._buckets(arena):
             adam_bucket(eng, arena, tag, lo, hi, m, v, lr, self.betas, self.steps[slot:slot + 1], False)
+
+    def _pre_backward(self, k):
+        if self.before_backward is not None:
+            self.before_backward(k)
 
     def _step_body(self):
         if self.side is not None:
@@ -1055,31 +1104,29 @@ class CelebATrainer(TrainerState):
         fh3 = de.head_fused_ok(3) and cd >= 5            # ... of the info step
         self._inputs_head()
         # ---- 1) generator adversarial step (:334-345) ----
-        ops.fill_f32(ga.grad)
         gen = ge.forward(self.z, self.onehot, self.code, sync=self.sync_bn)
         out = de.forward([gen], 2, head=not fh1)
         if fh1:
             de.head_losses(2, 1, self.dout[2 * B:], self.losses[0:1], targets=(1.0,), scales=(1.0,))
         else:
             ops.loss_bce_sigmoid(out, 19, 0, B, 1.0, 1.0, self.losses[0:1], self.dout[2 * B:])
+        self._pre_backward(1)
         dimg = de.backward(2, 1, self.dout[2 * B:], da.grad, need_wgrad=False, need_dimg=True, head_done=fh1)
-        ge.backward(dimg, ga.grad, None, sync=self.sync_bn)
+        ge.backward(dimg, ga.grad, None, sync=self.sync_bn, store=True)
         self._reduce(ga.grad)
         self._adam(ga, self.mG, self.vG, self.lr[0], 0, True)
         # ---- 2) discriminator step (:353-366); gen is the (detached) output of step 1; D(scaled) then D(gen), batched ----
-        ops.fill_f32(da.grad)
         out = de.forward([self.scaled, gen], 0, head=not fh1)
         if fh1:
             de.head_losses(0, 2, self.dout[:2 * B], self.losses[1:2], targets=(1.0, 0.0), scales=(0.5, 0.5))
         else:
             ops.loss_bce_sigmoid(out[:B], 19, 0, B, 1.0, 0.5, self.losses[1:2], self.dout[:B])
             ops.loss_bce_sigmoid(out[B:], 19, 0, B, 0.0, 0.5, self.losses[1:2], self.dout[B:2 * B])
-        de.backward(0, 2, self.dout[:2 * B], da.grad, head_done=fh1)
+        self._pre_backward(2)
+        de.backward(0, 2, self.dout[:2 * B], da.grad, head_done=fh1, store=True)
         self._reduce(da.grad)
         self._adam(da, self.mD, self.vD, self.lr[1], 1, True)
-        ops.fill_f32(da.grad)
         # ---- 3) info + affine step (:375-401): D(gen), D(scaled), D(real) batched as tapes 0,1,2 ----
-        ops.fill_f32(ga.grad)
         gen = ge.forward(self.z, self.onehot, self.code, sync=self.sync_bn)
         out = de.forward([gen, self.scaled, self.real], 0, head=not fh3)
         if fh3:
@@ -1089,8 +1136,9 @@ class CelebATrainer(TrainerState):
             ops.loss_mse(o_gen, 19, 1, cd, B, self.code, cd, 0.0, lcon, self.losses[2:3], self.dout[:B])
             ops.loss_ce_softmaxed(o_gen, 19, cd + 1, nc, B, self.labels, lcat, self.losses[2:3], self.dout[:B])
             ops.loss_affine_rpqxy(o_real, o_trans, 19, 1, B, self.code, cd, laff, self.losses[2:3], self.dout[2 * B:], self.dout[B:2 * B])
-        dimg = de.backward(0, 3, self.dout, da.grad, need_dimg=True, head_done=fh3)
-        ge.backward(dimg, ga.grad, None, sync=self.sync_bn)
+        self._pre_backward(3)
+        dimg = de.backward(0, 3, self.dout, da.grad, need_dimg=True, head_done=fh3, store=True)
+        ge.backward(dimg, ga.grad, None, sync=self.sync_bn, store=True)
         self._reduce(da.grad)
         self._reduce(ga.grad)
         self._adam(da, self.miD, self.viD, self.lr[2], 2, True)     # optimizer_info's step counter is shared by both arenas
@@ -1100,7 +1148,8 @@ class CelebATrainer(TrainerState):
         """The same iteration on five streams.  Main stream: the forward / backward-data chain of the three sub-steps, back to back.
         Lanes 0,1: weight-gradient GEMMs with their reductions.  Preparation lane: the next sub-step's power iterations and patch
         rows.  Optimizer lane:
-        per network, behind ALL of its weight-gradient chains: (all-reduce over the ranks ->) Adam -> gradient zeroing -> re-packing.
+        per network, behind ALL of its weight-gradient chains: (all-reduce over the ranks ->) Adam -> re-packing.  No gradient is cleared:
+        every backward pass stores (WRITER TABLE above).
         The main stream never waits for an optimizer update it does not need: step 2 neither reads nor writes G, step 3 starts with
         the generator forward, which does not read D; it waits for single events (``mark`` / ``wait``) instead of joining every lane."""
         G, D, ge, de, B = self.G, self.D, self.ge, self.de, self.B
@@ -1115,11 +1164,11 @@ class CelebATrainer(TrainerState):
         ar = self.allreduce
         ar_async = ar is not None and hasattr(ar, "start")
 
-        def update(arena, m, v, lr, slot, tick, zero, eng, key=None, key_w=None, bucketed=False):
+        def update(arena, m, v, lr, slot, tick, eng, key=None, key_w=None, bucketed=False):
             """Queue one network's optimizer update on the optimizer lane.  Default: the whole arena in one update behind ALL of its weight-
             gradient chains (engine.SideStream.defer_opt).  ``bucketed`` (the info step's generator update, the last of the iteration,
-            profiles/r02_h_ab_bucket_opt.txt): bucket by bucket in the order the backward pass completes them -- a bucket's Adam (+ gradient
-            zeroing in the same pass) and panel re-packing wait only for the lane chain that completes the bucket's gradients and for the
+            profiles/r02_h_ab_bucket_opt.txt): bucket by bucket in the order the backward pass completes them -- a bucket's Adam
+            and panel re-packing wait only for the lane chain that completes the bucket's gradients and for the
             main-stream kernels that still read its parameters (engine.SideStream.free), so the update of the upper layers runs beside the
             backward pass of the lower ones and only the last bucket's update is behind all of it.
             Data parallel: each bucket's all-reduce is STARTED once its chain is done (RCCL's stream must only ever wait for the capture's
@@ -1173,12 +1222,12 @@ class CelebATrainer(TrainerState):
                     for tag in hs:
                         finish(tag)
                     ops.adam_step_zero(arena.flat, arena.grad, m, v, arena.numel, lr, self.betas[0], self.betas[1], 1e-8, self.steps[slot:slot + 1],
-                                       tick, zero)
+                                       tick, False)
                     if key_w:
                         evs[key_w] = side.mark()        # master weights are new
                     eng.repack()
                     if key:
-                        evs[key] = side.mark()          # panels are new, gradients zeroed
+                        evs[key] = side.mark()          # panels are new, the gradients have been read
                 side.done.clear()
                 side.free.clear()
                 side.defer_opt(whole)
@@ -1190,17 +1239,17 @@ class CelebATrainer(TrainerState):
                     if FUSE_ADAM:
                         if tick and first:
                             ops.adam_tick(self.steps[slot:slot + 1])
-                        adam_bucket(eng, arena, tag, lo, hi, m, v, lr, self.betas, self.steps[slot:slot + 1], zero)
+                        adam_bucket(eng, arena, tag, lo, hi, m, v, lr, self.betas, self.steps[slot:slot + 1], False)
                         if key_w and tag == last:
                             evs[key_w] = side.mark()    # master weights are new
                     else:
                         ops.adam_step_zero(arena.flat[lo:hi], arena.grad[lo:hi], m[lo:hi], v[lo:hi], hi - lo, lr, self.betas[0], self.betas[1], 1e-8,
-                                           self.steps[slot:slot + 1], tick and first, zero)
+                                           self.steps[slot:slot + 1], tick and first, False)
                         if key_w and tag == last:
                             evs[key_w] = side.mark()    # master weights are new
                         eng.repack_bucket(tag)
                     if key and tag == last:
-                        evs[key] = side.mark()          # panels are new, gradients zeroed
+                        evs[key] = side.mark()          # panels are new, the gradients have been read
                 side.defer_opt_after((tag,), fn)
 
         # the generator forward needs the draws only: the image gather (DeviceInputs) and the warp go to the preparation lane, in front of
@@ -1214,10 +1263,6 @@ class CelebATrainer(TrainerState):
                 tail()
             self._inputs_head()
             de._sn_tape(2)
-            # optimizer.zero_grad() of the generator and discriminator steps (the last updates of an iteration leave their gradients in
-            # place: callers and tests read them): here, beside the generator forward -- the first gradient write is a backward pass away
-            ops.fill_f32(ga.grad)
-            ops.fill_f32(da.grad)
             evs["sn1"] = side.mark()
         side.defer_prep(sn1)
         gen = ge.forward(self.z, self.onehot, self.code, sync=self.sync_bn)
@@ -1232,9 +1277,10 @@ class CelebATrainer(TrainerState):
             de.head_losses(2, 1, self.dout[2 * B:], self.losses[0:1], targets=(1.0,), scales=(1.0,))
         else:
             ops.loss_bce_sigmoid(out, 19, 0, B, 1.0, 1.0, self.losses[0:1], self.dout[2 * B:])
+        self._pre_backward(1)
         dimg = de.backward(2, 1, self.dout[2 * B:], da.grad, need_wgrad=False, need_dimg=True, head_done=fh1)
-        ge.backward(dimg, ga.grad, side, sync=self.sync_bn)
-        update(ga, self.mG, self.vG, self.lr[0], 0, True, True, ge, key="g")                # beside the whole of step 2
+        ge.backward(dimg, ga.grad, side, sync=self.sync_bn, store=True)
+        update(ga, self.mG, self.vG, self.lr[0], 0, True, ge, key="g")                # beside the whole of step 2
         # ---- 2) discriminator step (:353-366); gen is the (detached) output of step 1; D(scaled) then D(gen), batched ----
         side.wait(evs["prep2"])
         out = de.forward([self.scaled, gen], 0, prepared=(True, True), head=not fh1)
@@ -1243,8 +1289,11 @@ class CelebATrainer(TrainerState):
         else:
             ops.loss_bce_sigmoid(out[:B], 19, 0, B, 1.0, 0.5, self.losses[1:2], self.dout[:B])
             ops.loss_bce_sigmoid(out[B:], 19, 0, B, 0.0, 0.5, self.losses[1:2], self.dout[B:2 * B])
-        de.backward(0, 2, self.dout[:2 * B], da.grad, side=side, head_done=fh1)
-        update(da, self.mD, self.vD, self.lr[1], 1, True, True, de, key_w="dw")             # beside step 3's generator forward
+        if self.before_backward is not None:
+            side.wait(evs["g"])                         # test hook only (see __init__): step 1's generator update still reads G's gradients
+        self._pre_backward(2)
+        de.backward(0, 2, self.dout[:2 * B], da.grad, side=side, head_done=fh1, store=True)
+        update(da, self.mD, self.vD, self.lr[1], 1, True, de, key_w="dw")             # beside step 3's generator forward
 
         # the first layer reads the images themselves (ops.conv_img_mfma): the patch rows are only the weight gradient's operand and are built by
         # its own chain in step 3's backward -- not here, on the chain step 3's discriminator forward waits for
@@ -1255,7 +1304,7 @@ class CelebATrainer(TrainerState):
             de.prepare(0, [None, None, None] if lazy else [None, self.scaled, self.real])
         side.defer_prep(prep3)
         # ---- 3) info + affine step (:375-401): D(gen), D(scaled), D(real) batched as tapes 0,1,2 ----
-        side.wait(evs["g"])                             # G's panels and zeroed gradients (optimizer lane, step 1)
+        side.wait(evs["g"])                             # G's panels; its gradients have been read (optimizer lane, step 1): step 3 may store
         gen = ge.forward(self.z, self.onehot, self.code, sync=self.sync_bn)
         side.join()                                     # D's panels, power iterations, patch rows
         out = de.forward([gen, self.scaled, self.real], 0, prepared=(False, False, False) if lazy else (False, True, True), head=not fh3)
@@ -1265,11 +1314,12 @@ class CelebATrainer(TrainerState):
             o_gen, o_trans, o_real = out[:B], out[B:2 * B], out[2 * B:]
             ops.loss_info_rpqxy(o_gen, o_trans, o_real, 19, 1, cd, nc, B, self.code, cd, self.labels, lcat, lcon, laff, self.losses[2:3], self.dout[:B],
                                 self.dout[B:2 * B], self.dout[2 * B:])           # the three losses in one launch
-        dimg = de.backward(0, 3, self.dout, da.grad, need_dimg=True, side=side, head_done=fh3)
+        self._pre_backward(3)
+        dimg = de.backward(0, 3, self.dout, da.grad, need_dimg=True, side=side, head_done=fh3, store=True)
         # D's update beside the generator backward; it ticks optimizer_info's counter (shared by both arenas), G's does not
-        update(da, self.miD, self.viD, self.lr[2], 2, True, False, de)
-        ge.backward(dimg, ga.grad, side, sync=self.sync_bn)
-        update(ga, self.miG, self.viG, self.lr[2], 2, False, False, ge, bucketed=True)
+        update(da, self.miD, self.viD, self.lr[2], 2, True, de)
+        ge.backward(dimg, ga.grad, side, sync=self.sync_bn, store=True)
+        update(ga, self.miG, self.viG, self.lr[2], 2, False, ge, bucketed=True)
         side.join()
 
     # -- public API -----------------------------------------------------------------------------------
@@ -1310,9 +1360,17 @@ class CelebATrainer(TrainerState):
         engine.LossLog -- the graph ends with the append of the iteration's loss row).
 
         At least one eager iteration must have run before (it loads every kernel and sizes the workspace);
-        ``warmup=True`` runs that iteration here -- note that it IS a real training step on the current inputs."""
+        ``warmup=True`` runs that iteration here -- note that it IS a real training step on the current inputs.
+
+        Gradients: an iteration never clears the gradient arenas (every backward pass stores), so ``capture(warmup=False)`` clears them
+        once, outside the graph -- the gradients a previous eager iteration left in ``.grad`` are gone after this call; read them before
+        capturing.  With ``warmup=True`` nothing is cleared: the arenas hold the warm-up iteration's gradients, as after any iteration."""
         if warmup:
             self._step_body()
+        else:
+            # a replay clears nothing (WRITER TABLE): the arenas enter the graph's first replay cleared, as they enter the first eager iteration
+            ops.fill_f32(self.G.arena.grad)
+            ops.fill_f32(self.D.arena.grad)
         if inputs is not None:
             self.inputs = inputs
         if log is not None:

@@ -2145,7 +2145,9 @@ extern "C" int eg_conv_wgrad_target(const eg_conv* c, int dtype, const void* X, 
 
 // One block per (n, chunk of 64 gathered channels): reads the [t][c] slab rows coalesced along c, sums the splits, subtracts
 // the rank-1 spectral-norm terms, transposes through LDS and read-modify-writes the master-layout gradient [n][c][t] as
-// one contiguous run of 64*T floats.  MODE 0: out += a; MODE 1: out = a (gtmp) + <a,W> partials; MODE 2: out += a - rank1.
+// one contiguous run of 64*T floats.  MODE 0: out (+)= a; MODE 1: out = a (gtmp) + <a,W> partials; MODE 2: out (+)= a - rank1.
+// `accumulate` (uniform, MODES 0 and 2): 1 = read-modify-write, 0 = store -- the first writer of a gradient slot in a backward pass stores
+// the very value it would have added to a cleared slot and never reads the slot.
 #define EG_RC 64
 // LEAN: the instantiation for launches with < 16 splits (every big layer: 2-8 slabs): no split-group scratch (4.4 KiB of LDS instead of
 // 24) and four loads in flight instead of eight (<= 48 VGPRs) -- its workgroups then fit on a CU beside a resident 8-wave GEMM workgroup
@@ -2294,7 +2296,7 @@ __global__ __launch_bounds__(LEAN ? 256 : 1024) void wgrad_reduce_kernel(const f
             out[obase + e] = a;
             dot += a * w_orig[obase + e];
         } else {
-            out[obase + e] = (MODE == 2 || accumulate) ? out[obase + e] + a : a;
+            out[obase + e] = accumulate ? out[obase + e] + a : a;
         }
     }
     if (MODE == 1) {
@@ -2305,7 +2307,7 @@ __global__ __launch_bounds__(LEAN ? 256 : 1024) void wgrad_reduce_kernel(const f
 
 __global__ void sn_grad_apply_kernel(const float* __restrict__ gtmp, const float* __restrict__ partials, int npart,
                                      const float* __restrict__ sigma, const float* __restrict__ u, const float* __restrict__ v,
-                                     long long total, int Kdim, float* __restrict__ grad) {
+                                     long long total, int Kdim, float* __restrict__ grad, int accumulate) {
     __shared__ float sm[16];
     float d = 0.f;
     for (int i = threadIdx.x; i < npart; i += blockDim.x) d += partials[i];
@@ -2314,7 +2316,8 @@ __global__ void sn_grad_apply_kernel(const float* __restrict__ gtmp, const float
     const float inv = 1.f / sg, coef = dot / (sg * sg);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int n = (int)(i / Kdim), kk = (int)(i % Kdim);
-        grad[i] += gtmp[i] * inv - coef * u[n] * v[kk];
+        const float a = gtmp[i] * inv - coef * u[n] * v[kk];
+        grad[i] = accumulate ? grad[i] + a : a;
     }
 }
 
@@ -2341,32 +2344,40 @@ extern "C" int eg_wgrad_reduce(const float* slab, int nsplit, int n_slab, int n_
     return 0;
 }
 
-extern "C" int eg_wgrad_reduce_perm(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad, int row_div, int row_mul, int c_row, eg_stream_t s) {
+extern "C" int eg_wgrad_reduce_perm_store(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad, int row_div, int row_mul, int c_row,
+                                          int accumulate, eg_stream_t s) {
     EG_REQUIRE(slab && grad && nsplit > 0 && n_rows <= n_slab && T > 0 && T <= 64 && row_div >= 0 && c_row >= 0 && c_row <= C, "eg_wgrad_reduce_perm: bad argument");
     hipLaunchKernelGGL(wgrad_reduce_kernel<0>, dim3(reduce_blocks(n_rows, C)), dim3(reduce_threads(nsplit, n_rows, C, T)), reduce_lds(T), (hipStream_t)s, slab, nsplit, n_slab, n_rows, C, T,
-                       grad, 1, (const float*)nullptr, (float*)nullptr, 0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, row_div, row_mul, c_row);
+                       grad, accumulate != 0, (const float*)nullptr, (float*)nullptr, 0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, row_div, row_mul, c_row);
     EG_LAUNCH_CHECK();
     return 0;
 }
+extern "C" int eg_wgrad_reduce_perm(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad, int row_div, int row_mul, int c_row, eg_stream_t s) {
+    return eg_wgrad_reduce_perm_store(slab, nsplit, n_slab, n_rows, C, T, grad, row_div, row_mul, c_row, 1, s);
+}
 
-extern "C" int eg_wgrad_reduce_rank1(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad, int ntapes,
-                                     const float* coef, const float* u, const float* v, int c_row, eg_stream_t s) {
+extern "C" int eg_wgrad_reduce_rank1_store(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad, int ntapes,
+                                           const float* coef, const float* u, const float* v, int c_row, int accumulate, eg_stream_t s) {
     EG_REQUIRE(slab && grad && nsplit > 0 && n_rows <= n_slab && ntapes >= 0 && ntapes <= 4 && (ntapes == 0 || (coef && u && v)) && T > 0 && T <= 64,
                "eg_wgrad_reduce_rank1: bad argument");
     if (reduce_lean(nsplit))
         hipLaunchKernelGGL((wgrad_reduce_kernel<2, true>), dim3(reduce_blocks(n_rows, C)), dim3(256), reduce_lds(T), (hipStream_t)s, slab, nsplit, n_slab, n_rows, C, T,
-                           grad, 1, (const float*)nullptr, (float*)nullptr, ntapes, coef, u, v, 0, 0, c_row);
+                           grad, accumulate != 0, (const float*)nullptr, (float*)nullptr, ntapes, coef, u, v, 0, 0, c_row);
     else
     hipLaunchKernelGGL(wgrad_reduce_kernel<2>, dim3(reduce_blocks(n_rows, C)), dim3(reduce_threads(nsplit, n_rows, C, T)), reduce_lds(T), (hipStream_t)s, slab, nsplit, n_slab, n_rows, C, T,
-                       grad, 1, (const float*)nullptr, (float*)nullptr, ntapes, coef, u, v, 0, 0, c_row);
+                       grad, accumulate != 0, (const float*)nullptr, (float*)nullptr, ntapes, coef, u, v, 0, 0, c_row);
     EG_LAUNCH_CHECK();
     return 0;
+}
+extern "C" int eg_wgrad_reduce_rank1(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad, int ntapes,
+                                     const float* coef, const float* u, const float* v, int c_row, eg_stream_t s) {
+    return eg_wgrad_reduce_rank1_store(slab, nsplit, n_slab, n_rows, C, T, grad, ntapes, coef, u, v, c_row, 1, s);
 }
 
 extern "C" int eg_sn_partials(void) { return 1 << 17; }
 
-extern "C" int eg_wgrad_reduce_sn(const eg_conv* c, const float* slab, int nsplit, const float* w_orig, const float* sigma,
-                                  const float* u, const float* v, float* gtmp, float* partials, float* grad, eg_stream_t s) {
+extern "C" int eg_wgrad_reduce_sn_store(const eg_conv* c, const float* slab, int nsplit, const float* w_orig, const float* sigma,
+                                        const float* u, const float* v, float* gtmp, float* partials, float* grad, int accumulate, eg_stream_t s) {
     EG_REQUIRE(c && slab && w_orig && sigma && u && v && gtmp && partials && grad && nsplit > 0, "eg_wgrad_reduce_sn: bad argument");
     const int T = c->k * c->k;
     const int blocks = reduce_blocks(c->Cout, c->Cin);
@@ -2376,9 +2387,13 @@ extern "C" int eg_wgrad_reduce_sn(const eg_conv* c, const float* slab, int nspli
     const long long total = (long long)c->Cout * c->Cin * T;
     const int blocks2 = (int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
     hipLaunchKernelGGL(sn_grad_apply_kernel, dim3(blocks2), dim3(256), 0, (hipStream_t)s, gtmp, partials, blocks, sigma, u, v, total,
-                       c->Cin * T, grad);
+                       c->Cin * T, grad, accumulate != 0);
     EG_LAUNCH_CHECK();
     return 0;
+}
+extern "C" int eg_wgrad_reduce_sn(const eg_conv* c, const float* slab, int nsplit, const float* w_orig, const float* sigma,
+                                  const float* u, const float* v, float* gtmp, float* partials, float* grad, eg_stream_t s) {
+    return eg_wgrad_reduce_sn_store(c, slab, nsplit, w_orig, sigma, u, v, gtmp, partials, grad, 1, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2430,8 +2445,9 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const T* __restrict
     }
 }
 
-// gb[j] += scale * sum_{n == j mod nb} sum_r partials[r][n]; one wave per output j
-__global__ void colsum_final_kernel(const float* __restrict__ partials, int nrb, int N, int nb, const float* __restrict__ scale, float* __restrict__ gb) {
+// gb[j] (+)= scale * sum_{n == j mod nb} sum_r partials[r][n]; one wave per output j
+__global__ void colsum_final_kernel(const float* __restrict__ partials, int nrb, int N, int nb, const float* __restrict__ scale, float* __restrict__ gb,
+                                    int accumulate) {
     const int j = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (j >= nb) return;
@@ -2439,7 +2455,10 @@ __global__ void colsum_final_kernel(const float* __restrict__ partials, int nrb,
     for (int n = j; n < N; n += nb)
         for (int r = lane; r < nrb; r += 64) a += partials[(size_t)r * N + n];
     a = wave_sum(a);
-    if (lane == 0) gb[j] += a * (scale ? scale[0] : 1.f);
+    if (lane == 0) {
+        const float t = a * (scale ? scale[0] : 1.f);
+        gb[j] = accumulate ? gb[j] + t : t;
+    }
 }
 
 extern "C" size_t eg_bias_grad_ws_floats(int rows, int N) {
@@ -2448,7 +2467,7 @@ extern "C" size_t eg_bias_grad_ws_floats(int rows, int N) {
     return (size_t)std::max(cdiv(rows, 256), 1024) * N;
 }
 
-extern "C" int eg_bias_grad(int dtype, const void* dY, int rows, int N, int bias_mod, float* partials, float* gb, eg_stream_t s) {
+extern "C" int eg_bias_grad_store(int dtype, const void* dY, int rows, int N, int bias_mod, float* partials, float* gb, int accumulate, eg_stream_t s) {
     EG_REQUIRE(dY && partials && gb && rows > 0 && N > 0, "eg_bias_grad: bad argument");
     const int vecw = dtype == EG_F32 ? 4 : 8;
     EG_REQUIRE(N % vecw == 0, "eg_bias_grad: N must be a multiple of the 16-byte vector width");
@@ -2462,9 +2481,12 @@ extern "C" int eg_bias_grad(int dtype, const void* dY, int rows, int N, int bias
     else if (dtype == EG_F16) hipLaunchKernelGGL(colsum_partial_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)s, (const f16_t*)dY, rows, N, rpb, partials);
     else hipLaunchKernelGGL(colsum_partial_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)s, (const bf16_t*)dY, rows, N, rpb, partials);
     const int nb = bias_mod > 0 ? bias_mod : N;
-    hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(nb, 4)), dim3(256), 0, (hipStream_t)s, partials, nrb, N, nb, (const float*)nullptr, gb);
+    hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(nb, 4)), dim3(256), 0, (hipStream_t)s, partials, nrb, N, nb, (const float*)nullptr, gb, accumulate != 0);
     EG_LAUNCH_CHECK();
     return 0;
+}
+extern "C" int eg_bias_grad(int dtype, const void* dY, int rows, int N, int bias_mod, float* partials, float* gb, eg_stream_t s) {
+    return eg_bias_grad_store(dtype, dY, rows, N, bias_mod, partials, gb, 1, s);
 }
 
 // ---- tape-segmented bias gradient + <G,W>/sigma^2 coefficient from activations (spectrally normalised layers) --------
@@ -2517,16 +2539,17 @@ __global__ __launch_bounds__(256) void colsum_sn_partial_kernel(const T* __restr
     if (threadIdx.x == 0) dots[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = dtot;
 }
 
-// gb[n] += sum_rb sigma[tape(rb)] * partials[rb][n]   (one wave per n);  coef[t] = sum of the tape's dot partials (block z)
+// gb[n] (+)= sum_rb sigma[tape(rb)] * partials[rb][n]   (one wave per n);  coef[t] = sum of the tape's dot partials (block z)
 __global__ void colsum_sn_final_kernel(const float* __restrict__ partials, const float* __restrict__ dots, int nrb, int N, int blocks_per_tape,
-                                       int ndot_per_rb, int ntapes, const float* __restrict__ sigma, float* __restrict__ gb, float* __restrict__ coef) {
+                                       int ndot_per_rb, int ntapes, const float* __restrict__ sigma, float* __restrict__ gb, float* __restrict__ coef,
+                                       int accumulate) {
     const int lane = threadIdx.x & 63;
     const int j = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (j < N) {
         float a = 0.f;
         for (int r = lane; r < nrb; r += 64) a += partials[(size_t)r * N + j] * sigma[r / blocks_per_tape];
         a = wave_sum(a);
-        if (lane == 0) gb[j] += a;
+        if (lane == 0) gb[j] = accumulate ? gb[j] + a : a;
     } else if (j < N + ntapes) {
         const int t = j - N;
         float a = 0.f;
@@ -2543,8 +2566,8 @@ extern "C" size_t eg_bias_grad_sn_ws_floats(int rows, int N, int rows_per_tape) 
     return (size_t)std::max(ntapes * cdiv(rows_per_tape, 256), 1024 + ntapes) * (N + 64);
 }
 
-extern "C" int eg_bias_grad_sn(int dtype, const void* dzs, const void* a, const float* bias, int rows, int N, int rows_per_tape,
-                               const float* sigma, float slope, float* ws, float* gb, float* coef, eg_stream_t s) {
+extern "C" int eg_bias_grad_sn_store(int dtype, const void* dzs, const void* a, const float* bias, int rows, int N, int rows_per_tape,
+                                     const float* sigma, float slope, float* ws, float* gb, float* coef, int accumulate, eg_stream_t s) {
     EG_REQUIRE(dzs && a && bias && sigma && ws && gb && coef && rows_per_tape > 0 && rows % rows_per_tape == 0 && slope > 0.f, "eg_bias_grad_sn: bad argument");
     const int vecw = dtype == EG_F32 ? 4 : 8;
     EG_REQUIRE(N % vecw == 0, "eg_bias_grad_sn: N must be a multiple of the 16-byte vector width");
@@ -2563,20 +2586,24 @@ extern "C" int eg_bias_grad_sn(int dtype, const void* dzs, const void* a, const 
     if (dtype == EG_F32) hipLaunchKernelGGL(colsum_sn_partial_kernel<float>, grid, dim3(256), 0, (hipStream_t)s, (const float*)dzs, (const float*)a, bias, N, rows_per_tape, bpt, rpb, 1.f / slope, partials, dots);
     else if (dtype == EG_F16) hipLaunchKernelGGL(colsum_sn_partial_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)s, (const f16_t*)dzs, (const f16_t*)a, bias, N, rows_per_tape, bpt, rpb, 1.f / slope, partials, dots);
     else hipLaunchKernelGGL(colsum_sn_partial_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)s, (const bf16_t*)dzs, (const bf16_t*)a, bias, N, rows_per_tape, bpt, rpb, 1.f / slope, partials, dots);
-    hipLaunchKernelGGL(colsum_sn_final_kernel, dim3(cdiv(N + ntapes, 4)), dim3(256), 0, (hipStream_t)s, partials, dots, nrb, N, bpt, gx, ntapes, sigma, gb, coef);
+    hipLaunchKernelGGL(colsum_sn_final_kernel, dim3(cdiv(N + ntapes, 4)), dim3(256), 0, (hipStream_t)s, partials, dots, nrb, N, bpt, gx, ntapes, sigma, gb, coef, accumulate != 0);
     EG_LAUNCH_CHECK();
     return 0;
 }
+extern "C" int eg_bias_grad_sn(int dtype, const void* dzs, const void* a, const float* bias, int rows, int N, int rows_per_tape,
+                               const float* sigma, float slope, float* ws, float* gb, float* coef, eg_stream_t s) {
+    return eg_bias_grad_sn_store(dtype, dzs, a, bias, rows, N, rows_per_tape, sigma, slope, ws, gb, coef, 1, s);
+}
 
 // ---- the same sums from the epilogue of the convolution that produced dzs (eg_epilogue.stat_mode = EG_STAT_SN_BIAS) -----------------
-// stat: [N][nrb] column sums, then [nrb][tiles_n] tile dots.  gb[n] += sum_rb sigma[tape(rb)] * stat[n][rb] (one wave per n, contiguous
+// stat: [N][nrb] column sums, then [nrb][tiles_n] tile dots.  gb[n] (+)= sum_rb sigma[tape(rb)] * stat[n][rb] (one wave per n, contiguous
 // reads); coef[t] = sum of the dots of tape t's row blocks (waves N .. N + ntapes - 1).  tape(rb) = (rb % tiles_m) / tiles_per_tape.
 // WIDE: one 256-thread workgroup per sum instead of one wave (>= 1024 row blocks: the small networks' 32 / 64-channel layers at B = 128 .. 512
 // have up to 12288 of them; one wave walked 192 partials per lane with an integer division each: 25 us per launch in the colored dSprites step);
 // fewer row blocks keep the wave form and its bits
 template <bool WIDE>
 __global__ void colsum_sn_final_t_kernel(const float* __restrict__ stat, int nrb, int N, int tiles_m, int tiles_per_tape, int tiles_n, int ntapes,
-                                         const float* __restrict__ sigma, float* __restrict__ gb, float* __restrict__ coef) {
+                                         const float* __restrict__ sigma, float* __restrict__ gb, float* __restrict__ coef, int accumulate) {
     __shared__ float sh[4];
     const int lane = WIDE ? threadIdx.x : threadIdx.x & 63, step = WIDE ? 256 : 64;
     const int j = WIDE ? blockIdx.x : blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -2600,21 +2627,25 @@ __global__ void colsum_sn_final_t_kernel(const float* __restrict__ stat, int nrb
         acc = ((sh[0] + sh[1]) + sh[2]) + sh[3];
     }
     if (lane != 0) return;
-    if (j < N) gb[j] += acc;
+    if (j < N) gb[j] = accumulate ? gb[j] + acc : acc;
     else if (j < N + ntapes) coef[j - N] = acc;
 }
 
-extern "C" int eg_bias_grad_sn_fused(const float* stat, int nrb, int N, int tiles_m, int tiles_per_tape, int ntapes, const float* sigma, float* gb,
-                                     float* coef, eg_stream_t s) {
+extern "C" int eg_bias_grad_sn_fused_store(const float* stat, int nrb, int N, int tiles_m, int tiles_per_tape, int ntapes, const float* sigma, float* gb,
+                                           float* coef, int accumulate, eg_stream_t s) {
     EG_REQUIRE(stat && sigma && gb && coef && nrb > 0 && N > 0 && ((N % 128) == 0 || N == 64 || N == 32) && tiles_m > 0 && (nrb % tiles_m) == 0 &&
                tiles_per_tape > 0 && ntapes > 0 && ntapes <= 4 && tiles_per_tape * ntapes == tiles_m, "eg_bias_grad_sn_fused: bad argument");
     // (column tiles of the producing launch: 128 wide for the 8-wave kernels, the whole row for the register-staged kernel's N = 32 / 64)
     if (nrb >= 1024)
         hipLaunchKernelGGL(colsum_sn_final_t_kernel<true>, dim3(N + ntapes), dim3(256), 0, (hipStream_t)s, stat, nrb, N, tiles_m, tiles_per_tape,
-                           N >= 128 ? N / 128 : 1, ntapes, sigma, gb, coef);
+                           N >= 128 ? N / 128 : 1, ntapes, sigma, gb, coef, accumulate != 0);
     else
         hipLaunchKernelGGL(colsum_sn_final_t_kernel<false>, dim3(cdiv(N + ntapes, 4)), dim3(256), 0, (hipStream_t)s, stat, nrb, N, tiles_m, tiles_per_tape,
-                           N >= 128 ? N / 128 : 1, ntapes, sigma, gb, coef);
+                           N >= 128 ? N / 128 : 1, ntapes, sigma, gb, coef, accumulate != 0);
     EG_LAUNCH_CHECK();
     return 0;
+}
+extern "C" int eg_bias_grad_sn_fused(const float* stat, int nrb, int N, int tiles_m, int tiles_per_tape, int ntapes, const float* sigma, float* gb,
+                                     float* coef, eg_stream_t s) {
+    return eg_bias_grad_sn_fused_store(stat, nrb, N, tiles_m, tiles_per_tape, ntapes, sigma, gb, coef, 1, s);
 }

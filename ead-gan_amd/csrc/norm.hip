@@ -412,7 +412,7 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const T* __restrict
 // dz = A*dy - Bz*z - Cc  with  A = g*is, Bz = g*is*is*s2/M, Cc = g*is*(s1/M - mean*is*s2/M);  mask: z*P + Q > 0
 __global__ void bn_bwd_final_kernel(const float* __restrict__ partial, int nrb, int C, float* sums, float* dgamma, float* dbeta,
                                     const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
-                                    const float* __restrict__ invstd, int M, float* __restrict__ coef) {
+                                    const float* __restrict__ invstd, int M, float* __restrict__ coef, int accumulate) {
     const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (c >= C) return;
@@ -426,8 +426,9 @@ __global__ void bn_bwd_final_kernel(const float* __restrict__ partial, int nrb, 
     if (lane != 0) return;
     sums[c] = s1;
     sums[C + c] = s2;
-    if (dbeta) dbeta[c] += s1;
-    if (dgamma) dgamma[c] += s2;
+    // accumulate = 0: the first writer of the two parameter gradients in a backward pass stores (and never reads the slots)
+    if (dbeta) dbeta[c] = accumulate ? dbeta[c] + s1 : s1;
+    if (dgamma) dgamma[c] = accumulate ? dgamma[c] + s2 : s2;
     const float g = gamma[c], is = invstd[c], mu = mean[c], invM = 1.f / (float)M;
     coef[c] = g * is;
     coef[C + c] = g * is * is * s2 * invM;
@@ -471,7 +472,7 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ z, const T* __restrict
 // ws: >= eg_bn_ws_floats(M,C) floats; sums: 2*C floats
 static int bn_bwd_impl(int dtype, const void* z, const void* da, void* dz, int M, int C, const float* gamma, const float* beta,
                        const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta, float* sums, float* ws,
-                       int post_act, float post_slope, const float* post_sigma, hipStream_t st) {
+                       int post_act, float post_slope, const float* post_sigma, int accumulate, hipStream_t st) {
     const int gx = bn_gx(C, dtype), rpb = bn_rpb(M, gx);
     const int nrb = cdiv(M, rpb);
     dim3 g1(gx, nrb);
@@ -480,7 +481,7 @@ static int bn_bwd_impl(int dtype, const void* z, const void* da, void* dz, int M
     else hipLaunchKernelGGL(bn_bwd_partial_kernel<bf16_t>, g1, dim3(256), 0, st, (const bf16_t*)z, (const bf16_t*)da, M, C, rpb, gamma, beta, save_mean, save_invstd, act, slope, ws);
     const int cpr = C / (dtype == EG_F32 ? 4 : 8);
     float* coef = ws + (size_t)nrb * 3 * C;
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(cdiv(C, 4)), dim3(256), 0, st, ws, nrb, C, sums, dgamma, dbeta, gamma, beta, save_mean, save_invstd, M, coef);
+    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(cdiv(C, 4)), dim3(256), 0, st, ws, nrb, C, sums, dgamma, dbeta, gamma, beta, save_mean, save_invstd, M, coef, accumulate != 0);
     const int blocks = bn_apply_blocks((size_t)M, cpr);
     if (dtype == EG_F32) hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)z, (const float*)da, (float*)dz, (size_t)M, C, coef, act, slope, post_act, post_slope, post_sigma);
     else if (dtype == EG_F16) hipLaunchKernelGGL(bn_bwd_apply_kernel<f16_t>, dim3(blocks), dim3(256), 0, st, (const f16_t*)z, (const f16_t*)da, (f16_t*)dz, (size_t)M, C, coef, act, slope, post_act, post_slope, post_sigma);
@@ -489,9 +490,9 @@ static int bn_bwd_impl(int dtype, const void* z, const void* da, void* dz, int M
 }
 
 // synchronised backward, stage 1: this rank's sums (also added to dbeta / dgamma), no dz yet
-extern "C" int eg_bn_bwd_sums_local(int dtype, const void* z, const void* da, int M, int C, const float* gamma, const float* beta,
-                                    const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta,
-                                    float* sums, float* ws, eg_stream_t s) {
+extern "C" int eg_bn_bwd_sums_local_store(int dtype, const void* z, const void* da, int M, int C, const float* gamma, const float* beta,
+                                          const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta,
+                                          float* sums, float* ws, int accumulate, eg_stream_t s) {
     EG_REQUIRE(z && da && gamma && beta && save_mean && save_invstd && sums && ws && M > 0 && C > 0, "eg_bn_bwd_sums_local: bad argument");
     hipStream_t st = (hipStream_t)s;
     const int gx = bn_gx(C, dtype), rpb = bn_rpb(M, gx);
@@ -501,9 +502,15 @@ extern "C" int eg_bn_bwd_sums_local(int dtype, const void* z, const void* da, in
     else if (dtype == EG_F16) hipLaunchKernelGGL(bn_bwd_partial_kernel<f16_t>, g1, dim3(256), 0, st, (const f16_t*)z, (const f16_t*)da, M, C, rpb, gamma, beta, save_mean, save_invstd, act, slope, ws);
     else hipLaunchKernelGGL(bn_bwd_partial_kernel<bf16_t>, g1, dim3(256), 0, st, (const bf16_t*)z, (const bf16_t*)da, M, C, rpb, gamma, beta, save_mean, save_invstd, act, slope, ws);
     float* coef = ws + (size_t)nrb * 3 * C;             // written but unused here (local M): stage 2 recomputes it from the global sums
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(cdiv(C, 4)), dim3(256), 0, st, ws, nrb, C, sums, dgamma, dbeta, gamma, beta, save_mean, save_invstd, M, coef);
+    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(cdiv(C, 4)), dim3(256), 0, st, ws, nrb, C, sums, dgamma, dbeta, gamma, beta, save_mean, save_invstd, M, coef, accumulate != 0);
     EG_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int eg_bn_bwd_sums_local(int dtype, const void* z, const void* da, int M, int C, const float* gamma, const float* beta,
+                                    const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta,
+                                    float* sums, float* ws, eg_stream_t s) {
+    return eg_bn_bwd_sums_local_store(dtype, z, da, M, C, gamma, beta, save_mean, save_invstd, act, slope, dgamma, dbeta, sums, ws, 1, s);
 }
 
 __global__ void bn_bwd_coef_kernel(const float* __restrict__ sums, int C, int M, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -541,7 +548,7 @@ extern "C" int eg_bn_bwd_from_sums(int dtype, const void* z, const void* da, voi
 template <bool WIDE>       // (WIDE: a workgroup per channel, as bn_stats_final_eq_kernel)
 __global__ void bn_bwd_final_t_kernel(const float* __restrict__ stat, int nrb, int C, float* sums, float* dgamma, float* dbeta,
                                       const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
-                                      const float* __restrict__ invstd, int M, float* __restrict__ coef) {
+                                      const float* __restrict__ invstd, int M, float* __restrict__ coef, int accumulate) {
     __shared__ float sh[2][4];
     const int c = WIDE ? blockIdx.x : blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int lane = WIDE ? threadIdx.x : threadIdx.x & 63, step = WIDE ? 256 : 64;
@@ -561,8 +568,9 @@ __global__ void bn_bwd_final_t_kernel(const float* __restrict__ stat, int nrb, i
     if (lane != 0) return;
     sums[c] = s1;
     sums[C + c] = s2;
-    if (dbeta) dbeta[c] += s1;
-    if (dgamma) dgamma[c] += s2;
+    // accumulate = 0: the first writer of the two parameter gradients in a backward pass stores (and never reads the slots)
+    if (dbeta) dbeta[c] = accumulate ? dbeta[c] + s1 : s1;
+    if (dgamma) dgamma[c] = accumulate ? dgamma[c] + s2 : s2;
     const float g = gamma[c], is = invstd[c], mu = mean[c], invM = 1.f / (float)M;
     coef[c] = g * is;
     coef[C + c] = g * is * is * s2 * invM;
@@ -571,17 +579,17 @@ __global__ void bn_bwd_final_t_kernel(const float* __restrict__ stat, int nrb, i
     coef[4 * C + c] = beta[c] - mu * g * is;
 }
 
-extern "C" int eg_bn_bwd_fused(int dtype, const void* z, const void* dy, void* dz, int M, int C, const float* stat, int nrb,
-                               const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta,
-                               float* sums, float* ws, eg_stream_t s) {
+extern "C" int eg_bn_bwd_fused_store(int dtype, const void* z, const void* dy, void* dz, int M, int C, const float* stat, int nrb,
+                                     const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta,
+                                     float* sums, float* ws, int accumulate, eg_stream_t s) {
     EG_REQUIRE(z && dy && dz && stat && gamma && beta && save_mean && save_invstd && sums && ws && M > 0 && C > 0 && nrb > 0, "eg_bn_bwd_fused: bad argument");
     EG_REQUIRE(C % (dtype == EG_F32 ? 4 : 8) == 0, "eg_bn_bwd_fused: C must be a multiple of the 16-byte vector width");
     hipStream_t st = (hipStream_t)s;
     float* coef = ws;                                   // 5*C floats
     if (nrb >= EG_FINAL_WIDE_NRB)
-        hipLaunchKernelGGL(bn_bwd_final_t_kernel<true>, dim3(C), dim3(256), 0, st, stat, nrb, C, sums, dgamma, dbeta, gamma, beta, save_mean, save_invstd, M, coef);
+        hipLaunchKernelGGL(bn_bwd_final_t_kernel<true>, dim3(C), dim3(256), 0, st, stat, nrb, C, sums, dgamma, dbeta, gamma, beta, save_mean, save_invstd, M, coef, accumulate != 0);
     else
-        hipLaunchKernelGGL(bn_bwd_final_t_kernel<false>, dim3(cdiv(C, 4)), dim3(256), 0, st, stat, nrb, C, sums, dgamma, dbeta, gamma, beta, save_mean, save_invstd, M, coef);
+        hipLaunchKernelGGL(bn_bwd_final_t_kernel<false>, dim3(cdiv(C, 4)), dim3(256), 0, st, stat, nrb, C, sums, dgamma, dbeta, gamma, beta, save_mean, save_invstd, M, coef, accumulate != 0);
     const int cpr = C / (dtype == EG_F32 ? 4 : 8);
     const int blocks = bn_apply_blocks((size_t)M, cpr);
     // dy already carries the activation gradient (act = NONE here)
@@ -592,20 +600,31 @@ extern "C" int eg_bn_bwd_fused(int dtype, const void* z, const void* dy, void* d
     return 0;
 }
 
+extern "C" int eg_bn_bwd_fused(int dtype, const void* z, const void* dy, void* dz, int M, int C, const float* stat, int nrb,
+                               const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta,
+                               float* sums, float* ws, eg_stream_t s) {
+    return eg_bn_bwd_fused_store(dtype, z, dy, dz, M, C, stat, nrb, gamma, beta, save_mean, save_invstd, dgamma, dbeta, sums, ws, 1, s);
+}
+
+extern "C" int eg_bn_bwd_store(int dtype, const void* z, const void* da, void* dz, int M, int C, const float* gamma, const float* beta,
+                               const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta,
+                               float* sums, float* ws, int accumulate, eg_stream_t s) {
+    EG_REQUIRE(z && da && dz && gamma && beta && save_mean && save_invstd && sums && ws, "eg_bn_bwd: null pointer");
+    bn_bwd_impl(dtype, z, da, dz, M, C, gamma, beta, save_mean, save_invstd, act, slope, dgamma, dbeta, sums, ws, EG_ACT_NONE, 0.f, nullptr, accumulate, (hipStream_t)s);
+    EG_LAUNCH_CHECK();
+    return 0;
+}
 extern "C" int eg_bn_bwd(int dtype, const void* z, const void* da, void* dz, int M, int C, const float* gamma, const float* beta,
                          const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta,
                          float* sums, float* ws, eg_stream_t s) {
-    EG_REQUIRE(z && da && dz && gamma && beta && save_mean && save_invstd && sums && ws, "eg_bn_bwd: null pointer");
-    bn_bwd_impl(dtype, z, da, dz, M, C, gamma, beta, save_mean, save_invstd, act, slope, dgamma, dbeta, sums, ws, EG_ACT_NONE, 0.f, nullptr, (hipStream_t)s);
-    EG_LAUNCH_CHECK();
-    return 0;
+    return eg_bn_bwd_store(dtype, z, da, dz, M, C, gamma, beta, save_mean, save_invstd, act, slope, dgamma, dbeta, sums, ws, 1, s);
 }
 
 extern "C" int eg_bn_bwd_post(int dtype, const void* z, const void* da, void* dz, int M, int C, const float* gamma, const float* beta,
                               const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta, float* sums, float* ws,
                               int post_act, float post_slope, const float* post_sigma, eg_stream_t s) {
     EG_REQUIRE(z && da && dz && gamma && beta && save_mean && save_invstd && sums && ws, "eg_bn_bwd_post: null pointer");
-    bn_bwd_impl(dtype, z, da, dz, M, C, gamma, beta, save_mean, save_invstd, EG_ACT_NONE, 0.f, dgamma, dbeta, sums, ws, post_act, post_slope, post_sigma, (hipStream_t)s);
+    bn_bwd_impl(dtype, z, da, dz, M, C, gamma, beta, save_mean, save_invstd, EG_ACT_NONE, 0.f, dgamma, dbeta, sums, ws, post_act, post_slope, post_sigma, 1, (hipStream_t)s);
     EG_LAUNCH_CHECK();
     return 0;
 }

@@ -233,9 +233,9 @@ __global__ void act_grad_mul_rowsum_kernel(const float* __restrict__ g, const fl
     const float tot = block_sum(acc, sm);
     if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
-// gb[c] += sum_b partial[b][c]: 256 threads = Cp (C rounded up to a power of two) channels x 256/Cp batch lanes, combined through LDS in lane
+// gb[c] (+)= sum_b partial[b][c] (accumulate = 0: store, the slot is not read): 256 threads = Cp (C rounded up to a power of two) channels x 256/Cp batch lanes, combined through LDS in lane
 // order (deterministic).  One thread per channel walking all B partials was a chain of B dependent loads (40 us at B = 512).
-__global__ __launch_bounds__(256) void rowsum_final_kernel(const float* __restrict__ partial, int B, int C, float* __restrict__ gb) {
+__global__ __launch_bounds__(256) void rowsum_final_kernel(const float* __restrict__ partial, int B, int C, float* __restrict__ gb, int accumulate) {
     __shared__ float cs[256];
     int Cp = 1;
     while (Cp < C) Cp <<= 1;
@@ -248,16 +248,20 @@ __global__ __launch_bounds__(256) void rowsum_final_kernel(const float* __restri
     if (threadIdx.x < C) {
         float t = 0.f;
         for (int q = 0; q < L; ++q) t += cs[q * Cp + threadIdx.x];
-        gb[threadIdx.x] += t;
+        gb[threadIdx.x] = accumulate ? gb[threadIdx.x] + t : t;
     }
+}
+extern "C" int eg_act_grad_mul_bias_nchw_store(const float* g, const float* a, float* out, int B, int C, int HW, int act, float slope, float* partial,
+                                               float* gb, int accumulate, eg_stream_t s) {
+    EG_REQUIRE(g && a && out && partial && gb && C <= 64, "eg_act_grad_mul_bias_nchw: bad argument");
+    hipLaunchKernelGGL(act_grad_mul_rowsum_kernel, dim3(B * C), dim3(256), 0, (hipStream_t)s, g, a, out, HW, act, slope, partial);
+    hipLaunchKernelGGL(rowsum_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, partial, B, C, gb, accumulate != 0);
+    EG_LAUNCH_CHECK();
+    return 0;
 }
 extern "C" int eg_act_grad_mul_bias_nchw(const float* g, const float* a, float* out, int B, int C, int HW, int act, float slope, float* partial,
                                          float* gb, eg_stream_t s) {
-    EG_REQUIRE(g && a && out && partial && gb && C <= 64, "eg_act_grad_mul_bias_nchw: bad argument");
-    hipLaunchKernelGGL(act_grad_mul_rowsum_kernel, dim3(B * C), dim3(256), 0, (hipStream_t)s, g, a, out, HW, act, slope, partial);
-    hipLaunchKernelGGL(rowsum_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, partial, B, C, gb);
-    EG_LAUNCH_CHECK();
-    return 0;
+    return eg_act_grad_mul_bias_nchw_store(g, a, out, B, C, HW, act, slope, partial, gb, 1, s);
 }
 
 // per-channel sum of an NCHW fp32 tensor with few channels: gb[c] += sum_{b,hw} x[b][c][hw]
@@ -681,8 +685,8 @@ extern "C" int eg_dense_small_bwd(int dtype, const float* dy, const void* wp, co
     return 0;
 }
 
-/* gw (master [N][Cin][taps], accumulate) and gb[n] += sum_b dy[b][n] */
-__global__ __launch_bounds__(512) void dense_small_bgrad_kernel(const float* dy, float* gb, int B, int N) {
+/* gw (master [N][Cin][taps], accumulate) and gb[n] (+)= sum_b dy[b][n]  (accumulate = 0: store, gb is not read) */
+__global__ __launch_bounds__(512) void dense_small_bgrad_kernel(const float* dy, float* gb, int B, int N, int accumulate) {
     // 8 row groups x 64 columns: independent loads in flight instead of one dependent chain per column; fixed-order combine
     __shared__ float part[8][64];
     const int n = threadIdx.x & 63, g = threadIdx.x >> 6;
@@ -695,15 +699,18 @@ __global__ __launch_bounds__(512) void dense_small_bgrad_kernel(const float* dy,
         float t = 0.f;
 #pragma unroll
         for (int q = 0; q < 8; ++q) t += part[q][n];
-        gb[n] += t;
+        gb[n] = accumulate ? gb[n] + t : t;
     }
 }
 
-extern "C" int eg_dense_small_bgrad(const float* dy, float* gb, int B, int N, eg_stream_t s) {
+extern "C" int eg_dense_small_bgrad_store(const float* dy, float* gb, int B, int N, int accumulate, eg_stream_t s) {
     EG_REQUIRE(dy && gb && N <= 64, "eg_dense_small_bgrad: bad argument");
-    hipLaunchKernelGGL(dense_small_bgrad_kernel, dim3(1), dim3(512), 0, (hipStream_t)s, dy, gb, B, N);
+    hipLaunchKernelGGL(dense_small_bgrad_kernel, dim3(1), dim3(512), 0, (hipStream_t)s, dy, gb, B, N, accumulate != 0);
     EG_LAUNCH_CHECK();
     return 0;
+}
+extern "C" int eg_dense_small_bgrad(const float* dy, float* gb, int B, int N, eg_stream_t s) {
+    return eg_dense_small_bgrad_store(dy, gb, B, N, 1, s);
 }
 
 extern "C" int eg_dense_small_wgrad(int dtype, const float* dy, const void* x, float* gw, float* gb, int B, int K, int N, int Cin, int taps,
@@ -713,7 +720,7 @@ extern "C" int eg_dense_small_wgrad(int dtype, const float* dy, const void* x, f
     if (dtype == EG_F32) hipLaunchKernelGGL(dense_small_wgrad_kernel<float>, dim3(cdiv(K, 256)), dim3(256), lds, (hipStream_t)s, dy, (const float*)x, gw, B, K, N, Cin, taps);
     else if (dtype == EG_F16) hipLaunchKernelGGL(dense_small_wgrad_kernel<f16_t>, dim3(cdiv(K, 256)), dim3(256), lds, (hipStream_t)s, dy, (const f16_t*)x, gw, B, K, N, Cin, taps);
     else hipLaunchKernelGGL(dense_small_wgrad_kernel<bf16_t>, dim3(cdiv(K, 256)), dim3(256), lds, (hipStream_t)s, dy, (const bf16_t*)x, gw, B, K, N, Cin, taps);
-    if (gb) hipLaunchKernelGGL(dense_small_bgrad_kernel, dim3(1), dim3(512), 0, (hipStream_t)s, dy, gb, B, N);
+    if (gb) hipLaunchKernelGGL(dense_small_bgrad_kernel, dim3(1), dim3(512), 0, (hipStream_t)s, dy, gb, B, N, 1);
     EG_LAUNCH_CHECK();
     return 0;
 }

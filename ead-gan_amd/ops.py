@@ -217,12 +217,14 @@ def conv_wgrad_variant(c, dtype) -> int:
     return lib().query("eg_conv_wgrad_variant", ctypes.byref(c), dtype)
 
 
+# Gradient writers take ``accumulate``: True adds to the slot (autograd's .grad contract, the default), False stores the value that would
+# have been added and never reads the slot (include/eadgan_hip.h, "gradient writers with a store mode").
 def wgrad_reduce(slab, nsplit, n_slab, n_rows, C, T, grad, accumulate=True):
     lib().call("eg_wgrad_reduce", _p(slab), nsplit, n_slab, n_rows, C, T, _p(grad), int(accumulate), _stream())
 
 
-def wgrad_reduce_perm(slab, nsplit, n_slab, n_rows, C, T, grad, row_div=0, row_mul=0, c_row=0):
-    lib().call("eg_wgrad_reduce_perm", _p(slab), nsplit, n_slab, n_rows, C, T, _p(grad), row_div, row_mul, c_row, _stream())
+def wgrad_reduce_perm(slab, nsplit, n_slab, n_rows, C, T, grad, row_div=0, row_mul=0, c_row=0, accumulate=True):
+    lib().call("eg_wgrad_reduce_perm_store", _p(slab), nsplit, n_slab, n_rows, C, T, _p(grad), row_div, row_mul, c_row, int(accumulate), _stream())
 
 
 def gather_add(out, src, n, div, s_div, s_mod):
@@ -262,32 +264,35 @@ def sn_partials():
     return lib().query("eg_sn_partials")
 
 
-def wgrad_reduce_sn(c, slab, nsplit, w_orig, sigma, u, v, gtmp, partials, grad):
-    lib().call("eg_wgrad_reduce_sn", ctypes.byref(c), _p(slab), nsplit, _p(w_orig), _p(sigma), _p(u), _p(v), _p(gtmp), _p(partials), _p(grad), _stream())
+def wgrad_reduce_sn(c, slab, nsplit, w_orig, sigma, u, v, gtmp, partials, grad, accumulate=True):
+    lib().call("eg_wgrad_reduce_sn_store", ctypes.byref(c), _p(slab), nsplit, _p(w_orig), _p(sigma), _p(u), _p(v), _p(gtmp), _p(partials), _p(grad),
+               int(accumulate), _stream())
 
 
 def bias_grad_ws_floats(rows, N):
     return lib().query("eg_bias_grad_ws_floats", rows, N)
 
 
-def bias_grad(dtype, dY, rows, N, partials, gb, bias_mod=0):
-    lib().call("eg_bias_grad", dtype, _p(dY), rows, N, bias_mod, _p(partials), _p(gb), _stream())
+def bias_grad(dtype, dY, rows, N, partials, gb, bias_mod=0, accumulate=True):
+    lib().call("eg_bias_grad_store", dtype, _p(dY), rows, N, bias_mod, _p(partials), _p(gb), int(accumulate), _stream())
 
 
 def bias_grad_sn_ws_floats(rows, N, rows_per_tape):
     return lib().query("eg_bias_grad_sn_ws_floats", rows, N, rows_per_tape)
 
 
-def bias_grad_sn(dtype, dzs, a, bias, rows, N, rows_per_tape, sigma, slope, ws, gb, coef):
-    lib().call("eg_bias_grad_sn", dtype, _p(dzs), _p(a), _p(bias), rows, N, rows_per_tape, _p(sigma), slope, _p(ws), _p(gb), _p(coef), _stream())
+def bias_grad_sn(dtype, dzs, a, bias, rows, N, rows_per_tape, sigma, slope, ws, gb, coef, accumulate=True):
+    lib().call("eg_bias_grad_sn_store", dtype, _p(dzs), _p(a), _p(bias), rows, N, rows_per_tape, _p(sigma), slope, _p(ws), _p(gb), _p(coef),
+               int(accumulate), _stream())
 
 
-def bias_grad_sn_fused(stat, nrb, N, tiles_m, tiles_per_tape, ntapes, sigma, gb, coef):
-    lib().call("eg_bias_grad_sn_fused", _p(stat), nrb, N, tiles_m, tiles_per_tape, ntapes, _p(sigma), _p(gb), _p(coef), _stream())
+def bias_grad_sn_fused(stat, nrb, N, tiles_m, tiles_per_tape, ntapes, sigma, gb, coef, accumulate=True):
+    lib().call("eg_bias_grad_sn_fused_store", _p(stat), nrb, N, tiles_m, tiles_per_tape, ntapes, _p(sigma), _p(gb), _p(coef), int(accumulate), _stream())
 
 
-def wgrad_reduce_rank1(slab, nsplit, n_slab, n_rows, C, T, grad, ntapes, coef, u, v, c_row=0):
-    lib().call("eg_wgrad_reduce_rank1", _p(slab), nsplit, n_slab, n_rows, C, T, _p(grad), ntapes, _p(coef), _p(u), _p(v), c_row, _stream())
+def wgrad_reduce_rank1(slab, nsplit, n_slab, n_rows, C, T, grad, ntapes, coef, u, v, c_row=0, accumulate=True):
+    lib().call("eg_wgrad_reduce_rank1_store", _p(slab), nsplit, n_slab, n_rows, C, T, _p(grad), ntapes, _p(coef), _p(u), _p(v), c_row, int(accumulate),
+               _stream())
 
 
 # ---- image side / heads ----------------------------------------------------------------------------
@@ -354,8 +359,8 @@ def cast_pad(dtype, src, dst, rows, n, npad):
     lib().call("eg_cast_pad", dtype, _p(src), _p(dst), rows, n, npad, _stream())
 
 
-def act_grad_mul_bias_nchw(g, a, out, B, C, HW, act, slope, partial, gb):
-    lib().call("eg_act_grad_mul_bias_nchw", _p(g), _p(a), _p(out), B, C, HW, act, slope, _p(partial), _p(gb), _stream())
+def act_grad_mul_bias_nchw(g, a, out, B, C, HW, act, slope, partial, gb, accumulate=True):
+    lib().call("eg_act_grad_mul_bias_nchw_store", _p(g), _p(a), _p(out), B, C, HW, act, slope, _p(partial), _p(gb), int(accumulate), _stream())
 
 
 def head_fused_ok(dtype, T, K, N):
@@ -434,8 +439,8 @@ def head_fused(dtype, x, wp, bias, partials, nslice, y, dout, dx, sigma, B, T, K
     lib().call("eg_head_fused", dtype, ctypes.byref(h), _stream())
 
 
-def dense_small_bgrad(dy, gb, B, N):
-    lib().call("eg_dense_small_bgrad", _p(dy), _p(gb), B, N, _stream())
+def dense_small_bgrad(dy, gb, B, N, accumulate=True):
+    lib().call("eg_dense_small_bgrad_store", _p(dy), _p(gb), B, N, int(accumulate), _stream())
 
 
 def flat_reduce(slab, nslab, total, grad, accumulate=True):
@@ -493,9 +498,9 @@ def bn_fwd_from_stats(dtype, x, y, M_local, C, stats_all, nranks, M_global, gamm
                _stream())
 
 
-def bn_bwd_sums_local(dtype, z, da, M, C, gamma, beta, save_mean, save_invstd, act, slope, dgamma, dbeta, sums, ws):
-    lib().call("eg_bn_bwd_sums_local", dtype, _p(z), _p(da), M, C, _p(gamma), _p(beta), _p(save_mean), _p(save_invstd), act, float(slope),
-               _p(dgamma), _p(dbeta), _p(sums), _p(ws), _stream())
+def bn_bwd_sums_local(dtype, z, da, M, C, gamma, beta, save_mean, save_invstd, act, slope, dgamma, dbeta, sums, ws, accumulate=True):
+    lib().call("eg_bn_bwd_sums_local_store", dtype, _p(z), _p(da), M, C, _p(gamma), _p(beta), _p(save_mean), _p(save_invstd), act, float(slope),
+               _p(dgamma), _p(dbeta), _p(sums), _p(ws), int(accumulate), _stream())
 
 
 def bn_bwd_from_sums(dtype, z, da, dz, M_local, C, sums_global, M_global, gamma, beta, save_mean, save_invstd, act, slope, ws):
@@ -514,14 +519,14 @@ def bn_fwd_train_fused(dtype, x, y, M, C, stat, nrb, rows_per_block, gamma, beta
                _p(nbt), _p(save_mean), _p(save_invstd), _p(ws), act, slope, _stream())
 
 
-def bn_bwd_fused(dtype, z, dy, dz, M, C, stat, nrb, gamma, beta, save_mean, save_invstd, dgamma, dbeta, sums, ws):
-    lib().call("eg_bn_bwd_fused", dtype, _p(z), _p(dy), _p(dz), M, C, _p(stat), nrb, _p(gamma), _p(beta), _p(save_mean), _p(save_invstd),
-               _p(dgamma), _p(dbeta), _p(sums), _p(ws), _stream())
+def bn_bwd_fused(dtype, z, dy, dz, M, C, stat, nrb, gamma, beta, save_mean, save_invstd, dgamma, dbeta, sums, ws, accumulate=True):
+    lib().call("eg_bn_bwd_fused_store", dtype, _p(z), _p(dy), _p(dz), M, C, _p(stat), nrb, _p(gamma), _p(beta), _p(save_mean), _p(save_invstd),
+               _p(dgamma), _p(dbeta), _p(sums), _p(ws), int(accumulate), _stream())
 
 
-def bn_bwd(dtype, z, da, dz, M, C, gamma, beta, save_mean, save_invstd, act, slope, dgamma, dbeta, sums, ws):
-    lib().call("eg_bn_bwd", dtype, _p(z), _p(da), _p(dz), M, C, _p(gamma), _p(beta), _p(save_mean), _p(save_invstd), act, slope,
-               _p(dgamma), _p(dbeta), _p(sums), _p(ws), _stream())
+def bn_bwd(dtype, z, da, dz, M, C, gamma, beta, save_mean, save_invstd, act, slope, dgamma, dbeta, sums, ws, accumulate=True):
+    lib().call("eg_bn_bwd_store", dtype, _p(z), _p(da), _p(dz), M, C, _p(gamma), _p(beta), _p(save_mean), _p(save_invstd), act, slope,
+               _p(dgamma), _p(dbeta), _p(sums), _p(ws), int(accumulate), _stream())
 
 
 def bn_bwd_post(dtype, z, da, dz, M, C, gamma, beta, save_mean, save_invstd, dgamma, dbeta, sums, ws, post_act, post_slope, post_sigma):

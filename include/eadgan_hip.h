@@ -359,6 +359,38 @@ int eg_bn_bwd_post(int dtype, const void* z, const void* da, void* dz, int M, in
                    const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta, float* sums, float* ws,
                    int post_act, float post_slope, const float* post_sigma, eg_stream_t s);
 
+/* --- gradient writers with a store mode --------------------------------------------------------------------
+ * Every entry point above that writes a parameter gradient adds to it (autograd's .grad contract).  The `_store` forms take one more
+ * argument in front of the stream: accumulate != 0 is the entry point without the suffix, accumulate == 0 STORES the value that would
+ * have been added (same kernel, same summation order: the result is the one of accumulating into a cleared slot, up to the sign of a
+ * zero) and never reads the slot.  A trainer whose backward pass has exactly one writer per gradient slot needs neither the
+ * zero-fill of the gradient arena nor the read of the zeros (celeba.CelebATrainer; eg_wgrad_reduce has had the argument all along). */
+int eg_wgrad_reduce_perm_store(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad,
+                               int row_div, int row_mul, int c_row, int accumulate, eg_stream_t s);
+int eg_wgrad_reduce_rank1_store(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad,
+                                int ntapes, const float* coef, const float* u, const float* v, int c_row, int accumulate, eg_stream_t s);
+int eg_wgrad_reduce_sn_store(const eg_conv* c, const float* slab, int nsplit, const float* w_orig,
+                             const float* sigma, const float* u, const float* v, float* gtmp, float* partials,
+                             float* grad, int accumulate, eg_stream_t s);
+int eg_bias_grad_store(int dtype, const void* dY, int rows, int N, int bias_mod, float* partials, float* gb,
+                       int accumulate, eg_stream_t s);
+int eg_bias_grad_sn_store(int dtype, const void* dzs, const void* a, const float* bias, int rows, int N, int rows_per_tape,
+                          const float* sigma, float slope, float* ws, float* gb, float* coef, int accumulate, eg_stream_t s);
+int eg_bias_grad_sn_fused_store(const float* stat, int nrb, int N, int tiles_m, int tiles_per_tape, int ntapes, const float* sigma,
+                                float* gb, float* coef, int accumulate, eg_stream_t s);
+int eg_act_grad_mul_bias_nchw_store(const float* g, const float* a, float* out, int B, int C, int HW, int act, float slope,
+                                    float* partial, float* gb, int accumulate, eg_stream_t s);
+int eg_dense_small_bgrad_store(const float* dy, float* gb, int B, int N, int accumulate, eg_stream_t s);
+int eg_bn_bwd_store(int dtype, const void* z, const void* da, void* dz, int M, int C, const float* gamma, const float* beta,
+                    const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta,
+                    float* sums, float* ws, int accumulate, eg_stream_t s);
+int eg_bn_bwd_fused_store(int dtype, const void* z, const void* dy, void* dz, int M, int C, const float* stat, int nrb,
+                          const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, float* dgamma,
+                          float* dbeta, float* sums, float* ws, int accumulate, eg_stream_t s);
+int eg_bn_bwd_sums_local_store(int dtype, const void* z, const void* da, int M, int C, const float* gamma, const float* beta,
+                               const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta,
+                               float* sums, float* ws, int accumulate, eg_stream_t s);
+
 /* --- spectral norm power iteration (torch.nn.utils.spectral_norm, celebA/EAD-GAN_celebA.py:110-120) -------- */
 size_t eg_sn_ws_floats(int R, int Kd);
 int eg_sn_power_iter(const float* w_orig, int R, int Kd, float* u, float* v, float* sigma, float* u_snap,
