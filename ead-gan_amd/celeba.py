@@ -33,23 +33,23 @@ IMG_GEMM = True
 FUSE_ADAM = True
 
 
-def adam_bucket(eng, arena, tag, lo, hi, m, v, lr, betas, step, zero):
-    """optimizer.step() (+ zero_grad) on one gradient bucket [lo, hi) of ``arena`` and the refresh of the packed panels of its layers.  The
+def adam_bucket(eng, arena, tag, lo, hi, m, v, lr, betas, step):
+    """optimizer.step() on one gradient bucket [lo, hi) of ``arena`` and the refresh of the packed panels of its layers.  The
     bucket's big convolution weight (``eng.fused_weight(tag)``) is updated AND re-packed by one launch; the remaining parameters of the
     bucket (biases, BatchNorm affine) by plain Adam launches on their slices.  The step counter has been ticked by the caller."""
     b1, b2 = betas
     fw = eng.fused_weight(tag) if FUSE_ADAM else None
     if fw is None:
-        ops.adam_step_zero(arena.flat[lo:hi], arena.grad[lo:hi], m[lo:hi], v[lo:hi], hi - lo, lr, b1, b2, 1e-8, step, False, zero)
+        ops.adam_step_zero(arena.flat[lo:hi], arena.grad[lo:hi], m[lo:hi], v[lo:hi], hi - lo, lr, b1, b2, 1e-8, step, False, False)
         eng.repack_bucket(tag)
         return
     name, launch = fw
     off, k = arena.slices[name]
     assert lo <= off and off + k <= hi
-    launch(arena.flat[off:off + k], arena.grad[off:off + k], m[off:off + k], v[off:off + k], lr, b1, b2, step, zero)
+    launch(arena.flat[off:off + k], arena.grad[off:off + k], m[off:off + k], v[off:off + k], lr, b1, b2, step)
     for a, b in ((lo, off), (off + k, hi)):
         if b > a:
-            ops.adam_step_zero(arena.flat[a:b], arena.grad[a:b], m[a:b], v[a:b], b - a, lr, b1, b2, 1e-8, step, False, zero)
+            ops.adam_step_zero(arena.flat[a:b], arena.grad[a:b], m[a:b], v[a:b], b - a, lr, b1, b2, 1e-8, step, False, False)
 
 
 G_WIDTHS = (1024, 512, 256, 128)
@@ -149,13 +149,13 @@ class _GenEngine:
         dt = self.dtype
         if tag == "G0":
             # [cin][1024][4][4] seen as [cin][16384]: panel row (t, co) = column co * 16 + t
-            return ("conv_blocks.0.weight", lambda p, g, m, v, lr, b1, b2, step, zero: ops.adam_pack_rows(
-                dt, p, g, m, v, self.l0.wp_fwd, self.cin, 16 * G_WIDTHS[0], self.l0.Kpad_fwd, 16, G_WIDTHS[0], lr, b1, b2, 1e-8, step, zero))
+            return ("conv_blocks.0.weight", lambda p, g, m, v, lr, b1, b2, step: ops.adam_pack_rows(
+                dt, p, g, m, v, self.l0.wp_fwd, self.cin, 16 * G_WIDTHS[0], self.l0.Kpad_fwd, 16, G_WIDTHS[0], lr, b1, b2, 1e-8, step))
         if tag in ("G1", "G2", "G3"):
             r = self.mid[int(tag[1]) - 1]
             if ops.adam_pack_conv_ok(r.c, dt, True, True):
-                return (f"conv_blocks.{(1, 4, 7)[int(tag[1]) - 1]}.weight", lambda p, g, m, v, lr, b1, b2, step, zero: ops.adam_pack_conv(
-                    r.c, dt, p, g, m, v, lr, b1, b2, 1e-8, step, zero, r.wp_fwd, r.wp_bwd))
+                return (f"conv_blocks.{(1, 4, 7)[int(tag[1]) - 1]}.weight", lambda p, g, m, v, lr, b1, b2, step: ops.adam_pack_conv(
+                    r.c, dt, p, g, m, v, lr, b1, b2, 1e-8, step, r.wp_fwd, r.wp_bwd))
         return None
 
     def repack_bucket(self, tag):
@@ -507,8 +507,8 @@ class _DiscEngine:
             i = int(tag[1])
             r = self.mid[i - 1]
             if ops.adam_pack_conv_ok(r.c, self.dtype, True, True):
-                return (f"main.{2 * i}.weight_orig", lambda p, g, m, v, lr, b1, b2, step, zero: ops.adam_pack_conv(
-                    r.c, self.dtype, p, g, m, v, lr, b1, b2, 1e-8, step, zero, r.wp_fwd, r.wp_bwd))
+                return (f"main.{2 * i}.weight_orig", lambda p, g, m, v, lr, b1, b2, step: ops.adam_pack_conv(
+                    r.c, self.dtype, p, g, m, v, lr, b1, b2, 1e-8, step, r.wp_fwd, r.wp_bwd))
         return None
 
     def repack_bucket(self, tag):
@@ -1063,7 +1063,7 @@ class CelebATrainer(TrainerState):
         if tick:
             ops.adam_tick(self.steps[slot:slot + 1])
         for tag, lo, hi in self._buckets(arena):
-            adam_bucket(eng, arena, tag, lo, hi, m, v, lr, self.betas, self.steps[slot:slot + 1], False)
+            adam_bucket(eng, arena, tag, lo, hi, m, v, lr, self.betas, self.steps[slot:slot + 1])
 
     def _pre_backward(self, k):
         if self.before_backward is not None:
@@ -1239,7 +1239,7 @@ class CelebATrainer(TrainerState):
                     if FUSE_ADAM:
                         if tick and first:
                             ops.adam_tick(self.steps[slot:slot + 1])
-                        adam_bucket(eng, arena, tag, lo, hi, m, v, lr, self.betas, self.steps[slot:slot + 1], False)
+                        adam_bucket(eng, arena, tag, lo, hi, m, v, lr, self.betas, self.steps[slot:slot + 1])
                         if key_w and tag == last:
                             evs[key_w] = side.mark()    # master weights are new
                     else:

@@ -1457,10 +1457,10 @@ extern "C" int eg_pack_conv(const eg_conv* c, int dtype, const float* w, void* w
 // ------------------------------------------------------------------------------------------------
 // Adam + re-packing in one pass (torch.optim.Adam.step() on a convolution's weight, celebA/EAD-GAN_celebA.py:344,365,400, followed by
 // the panel refresh every consumer of the weight needs): the pack_conv_tile tiling with the optimizer update applied while the master
-// tile is on its way into LDS -- p, g, m, v are read once, p, m, v (and the cleared g) written once, both panels written from the tile.
+// tile is on its way into LDS -- p, g, m, v are read once, p, m, v written once, both panels written from the tile.
 // Same element update as adam_kernel (adam.h), same panel bytes as eg_pack_conv of the updated master.
 // ------------------------------------------------------------------------------------------------
-template <typename T, int TTC, bool ZERO, bool V4, int TC>
+template <typename T, int TTC, bool V4, int TC>
 __global__ __launch_bounds__(256) void adam_pack_conv_tile_kernel(const PackTileParams p, float* __restrict__ w, float* __restrict__ g,
                                                                   float* __restrict__ m, float* __restrict__ v, float lr, float b1, float b2,
                                                                   float eps, const int* __restrict__ step) {
@@ -1500,7 +1500,6 @@ __global__ __launch_bounds__(256) void adam_pack_conv_tile_kernel(const PackTile
                 *reinterpret_cast<float4*>(w + idx[u]) = pi[u];
                 *reinterpret_cast<float4*>(m + idx[u]) = mi[u];
                 *reinterpret_cast<float4*>(v + idx[u]) = vi[u];
-                if (ZERO) *reinterpret_cast<float4*>(g + idx[u]) = make_float4(0.f, 0.f, 0.f, 0.f);
                 const int e = (e0 + u * 256) * 4;
                 const int n = e / (TC * TT), rem = e - n * (TC * TT);
                 const int c = rem / TT, t = rem - c * TT;
@@ -1516,7 +1515,6 @@ __global__ __launch_bounds__(256) void adam_pack_conv_tile_kernel(const PackTile
         float pi = w[i], mi = m[i], vi = v[i];
         adam_elem(pi, g[i], mi, vi, ac);
         w[i] = pi; m[i] = mi; v[i] = vi;
-        if (ZERO) g[i] = 0.f;
         tile[(n * TC + c) * TP + t] = pi;
     }
     __syncthreads();
@@ -1555,7 +1553,7 @@ extern "C" int eg_adam_pack_conv_ok(const eg_conv* c, int dtype, int has_fwd, in
 }
 
 extern "C" int eg_adam_pack_conv(const eg_conv* c, int dtype, float* w, float* g, float* m, float* v, float lr, float b1, float b2, float eps,
-                                 const int* step, int zero_grad, void* wp_fwd, void* wp_bwd, eg_stream_t s) {
+                                 const int* step, void* wp_fwd, void* wp_bwd, eg_stream_t s) {
     EG_REQUIRE(c && w && g && m && v && step && (wp_fwd || wp_bwd), "eg_adam_pack_conv: null pointer");
     EG_REQUIRE(dtype == EG_F32 || dtype == EG_BF16 || dtype == EG_F16, "dtype must be EG_F32, EG_BF16 or EG_F16");
     const int T = c->k * c->k;
@@ -1567,13 +1565,10 @@ extern "C" int eg_adam_pack_conv(const eg_conv* c, int dtype, float* w, float* g
     const dim3 grid(c->Cout / 16, c->Cin / tc);
     const size_t lds = (size_t)16 * tc * (T + 1) * sizeof(float);
     const bool v4 = T == 16 && ((((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
-#define EG_AP_TILE(TY, Z) do { if (v4) hipLaunchKernelGGL((adam_pack_conv_tile_kernel<TY, 16, Z, true, tc>), grid, dim3(256), lds, (hipStream_t)s, p, w, g, m, v, lr, b1, b2, eps, step); \
-                               else if (T == 16) hipLaunchKernelGGL((adam_pack_conv_tile_kernel<TY, 16, Z, false, tc>), grid, dim3(256), lds, (hipStream_t)s, p, w, g, m, v, lr, b1, b2, eps, step); \
-                               else hipLaunchKernelGGL((adam_pack_conv_tile_kernel<TY, 0, Z, false, tc>), grid, dim3(256), lds, (hipStream_t)s, p, w, g, m, v, lr, b1, b2, eps, step); } while (0)
-#define EG_AP_TYPE(Z) do { if (dtype == EG_F32) EG_AP_TILE(float, Z); else if (dtype == EG_F16) EG_AP_TILE(f16_t, Z); else EG_AP_TILE(bf16_t, Z); } while (0)
-    if (zero_grad) EG_AP_TYPE(true);
-    else EG_AP_TYPE(false);
-#undef EG_AP_TYPE
+#define EG_AP_TILE(TY) do { if (v4) hipLaunchKernelGGL((adam_pack_conv_tile_kernel<TY, 16, true, tc>), grid, dim3(256), lds, (hipStream_t)s, p, w, g, m, v, lr, b1, b2, eps, step); \
+                            else if (T == 16) hipLaunchKernelGGL((adam_pack_conv_tile_kernel<TY, 16, false, tc>), grid, dim3(256), lds, (hipStream_t)s, p, w, g, m, v, lr, b1, b2, eps, step); \
+                            else hipLaunchKernelGGL((adam_pack_conv_tile_kernel<TY, 0, false, tc>), grid, dim3(256), lds, (hipStream_t)s, p, w, g, m, v, lr, b1, b2, eps, step); } while (0)
+    if (dtype == EG_F32) EG_AP_TILE(float); else if (dtype == EG_F16) EG_AP_TILE(f16_t); else EG_AP_TILE(bf16_t);
 #undef EG_AP_TILE
     EG_LAUNCH_CHECK();
     return 0;
@@ -1583,7 +1578,7 @@ extern "C" int eg_adam_pack_conv(const eg_conv* c, int dtype, float* w, float* g
 // a 1x1 input, celebA/EAD-GAN_celebA.py:76: K = input channels, N = Cout * 16), panel wp[n'][Kpad] with n' = (n % n_mod) * n_mul + n / n_mod
 // and k < K (the K padding keeps the zeros of the first eg_pack_strided).  A workgroup takes 32 master rows x 256 columns: coalesced
 // reads along N, the update, 16-byte panel stores along K.
-template <typename T, bool ZERO>
+template <typename T>
 __global__ __launch_bounds__(256) void adam_pack_rows_kernel(float* __restrict__ w, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                              T* __restrict__ wp, int K, int N, int Kpad, int n_mod, int n_mul, float lr, float b1,
                                                              float b2, float eps, const int* __restrict__ step) {
@@ -1613,7 +1608,6 @@ __global__ __launch_bounds__(256) void adam_pack_rows_kernel(float* __restrict__
                 const size_t i = (size_t)k * N + n;
                 adam_elem(pi[u], gi[u], mi[u], vi[u], ac);
                 w[i] = pi[u]; m[i] = mi[u]; v[i] = vi[u];
-                if (ZERO) g[i] = 0.f;
             }
             tile[kk + u][tid] = pi[u];
         }
@@ -1639,14 +1633,13 @@ __global__ __launch_bounds__(256) void adam_pack_rows_kernel(float* __restrict__
 }
 
 extern "C" int eg_adam_pack_rows(int dtype, float* w, float* g, float* m, float* v, void* wp, int K, int N, int Kpad, int n_mod, int n_mul,
-                                 float lr, float b1, float b2, float eps, const int* step, int zero_grad, eg_stream_t s) {
+                                 float lr, float b1, float b2, float eps, const int* step, eg_stream_t s) {
     EG_REQUIRE(w && g && m && v && wp && step && K > 0 && N > 0 && Kpad >= K && n_mod > 0 && n_mul > 0 && (N % n_mod) == 0, "eg_adam_pack_rows: bad argument");
     EG_REQUIRE(dtype == EG_F32 || dtype == EG_BF16 || dtype == EG_F16, "dtype must be EG_F32, EG_BF16 or EG_F16");
     EG_REQUIRE((Kpad % vec_of(dtype)) == 0, "eg_adam_pack_rows: Kpad must be a multiple of the 16-byte vector width");
     const dim3 grid(cdiv(N, 256), cdiv(K, 8));
-#define EG_APR(TY, Z) hipLaunchKernelGGL((adam_pack_rows_kernel<TY, Z>), grid, dim3(256), 0, (hipStream_t)s, w, g, m, v, (TY*)wp, K, N, Kpad, n_mod, n_mul, lr, b1, b2, eps, step)
-    if (zero_grad) { if (dtype == EG_F32) EG_APR(float, true); else if (dtype == EG_F16) EG_APR(f16_t, true); else EG_APR(bf16_t, true); }
-    else { if (dtype == EG_F32) EG_APR(float, false); else if (dtype == EG_F16) EG_APR(f16_t, false); else EG_APR(bf16_t, false); }
+#define EG_APR(TY) hipLaunchKernelGGL((adam_pack_rows_kernel<TY>), grid, dim3(256), 0, (hipStream_t)s, w, g, m, v, (TY*)wp, K, N, Kpad, n_mod, n_mul, lr, b1, b2, eps, step)
+    if (dtype == EG_F32) EG_APR(float); else if (dtype == EG_F16) EG_APR(f16_t); else EG_APR(bf16_t);
 #undef EG_APR
     EG_LAUNCH_CHECK();
     return 0;
@@ -2097,12 +2090,7 @@ static void launch_tn(TnParams& p, int bnt, int bct, int nsplit, hipStream_t st)
 }
 
 extern "C" int eg_conv_wgrad(const eg_conv* c, int dtype, const void* X, const void* dY, float* slab, int* nsplit_out,
-                             eg_stream_t s) {
-    return eg_conv_wgrad_target(c, dtype, X, dY, slab, nsplit_out, 0, s);
-}
-
-extern "C" int eg_conv_wgrad_target(const eg_conv* c, int dtype, const void* X, const void* dY, float* slab, int* nsplit_out,
-                                    int wgs_target, eg_stream_t s) {
+                             int wgs_target, eg_stream_t s) {
     if (int e = check_conv(c, dtype, NEED_CIN | NEED_COUT)) return e;
     EG_REQUIRE(X && dY && slab && nsplit_out && wgs_target >= 0, "eg_conv_wgrad: bad argument");
     const int OH = conv_out_dim(c, c->H), OW = conv_out_dim(c, c->W);
@@ -2344,20 +2332,17 @@ extern "C" int eg_wgrad_reduce(const float* slab, int nsplit, int n_slab, int n_
     return 0;
 }
 
-extern "C" int eg_wgrad_reduce_perm_store(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad, int row_div, int row_mul, int c_row,
-                                          int accumulate, eg_stream_t s) {
+extern "C" int eg_wgrad_reduce_perm(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad, int row_div, int row_mul, int c_row,
+                                    int accumulate, eg_stream_t s) {
     EG_REQUIRE(slab && grad && nsplit > 0 && n_rows <= n_slab && T > 0 && T <= 64 && row_div >= 0 && c_row >= 0 && c_row <= C, "eg_wgrad_reduce_perm: bad argument");
     hipLaunchKernelGGL(wgrad_reduce_kernel<0>, dim3(reduce_blocks(n_rows, C)), dim3(reduce_threads(nsplit, n_rows, C, T)), reduce_lds(T), (hipStream_t)s, slab, nsplit, n_slab, n_rows, C, T,
                        grad, accumulate != 0, (const float*)nullptr, (float*)nullptr, 0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, row_div, row_mul, c_row);
     EG_LAUNCH_CHECK();
     return 0;
 }
-extern "C" int eg_wgrad_reduce_perm(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad, int row_div, int row_mul, int c_row, eg_stream_t s) {
-    return eg_wgrad_reduce_perm_store(slab, nsplit, n_slab, n_rows, C, T, grad, row_div, row_mul, c_row, 1, s);
-}
 
-extern "C" int eg_wgrad_reduce_rank1_store(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad, int ntapes,
-                                           const float* coef, const float* u, const float* v, int c_row, int accumulate, eg_stream_t s) {
+extern "C" int eg_wgrad_reduce_rank1(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad, int ntapes,
+                                     const float* coef, const float* u, const float* v, int c_row, int accumulate, eg_stream_t s) {
     EG_REQUIRE(slab && grad && nsplit > 0 && n_rows <= n_slab && ntapes >= 0 && ntapes <= 4 && (ntapes == 0 || (coef && u && v)) && T > 0 && T <= 64,
                "eg_wgrad_reduce_rank1: bad argument");
     if (reduce_lean(nsplit))
@@ -2369,15 +2354,11 @@ extern "C" int eg_wgrad_reduce_rank1_store(const float* slab, int nsplit, int n_
     EG_LAUNCH_CHECK();
     return 0;
 }
-extern "C" int eg_wgrad_reduce_rank1(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad, int ntapes,
-                                     const float* coef, const float* u, const float* v, int c_row, eg_stream_t s) {
-    return eg_wgrad_reduce_rank1_store(slab, nsplit, n_slab, n_rows, C, T, grad, ntapes, coef, u, v, c_row, 1, s);
-}
 
 extern "C" int eg_sn_partials(void) { return 1 << 17; }
 
-extern "C" int eg_wgrad_reduce_sn_store(const eg_conv* c, const float* slab, int nsplit, const float* w_orig, const float* sigma,
-                                        const float* u, const float* v, float* gtmp, float* partials, float* grad, int accumulate, eg_stream_t s) {
+extern "C" int eg_wgrad_reduce_sn(const eg_conv* c, const float* slab, int nsplit, const float* w_orig, const float* sigma,
+                                  const float* u, const float* v, float* gtmp, float* partials, float* grad, int accumulate, eg_stream_t s) {
     EG_REQUIRE(c && slab && w_orig && sigma && u && v && gtmp && partials && grad && nsplit > 0, "eg_wgrad_reduce_sn: bad argument");
     const int T = c->k * c->k;
     const int blocks = reduce_blocks(c->Cout, c->Cin);
@@ -2390,10 +2371,6 @@ extern "C" int eg_wgrad_reduce_sn_store(const eg_conv* c, const float* slab, int
                        c->Cin * T, grad, accumulate != 0);
     EG_LAUNCH_CHECK();
     return 0;
-}
-extern "C" int eg_wgrad_reduce_sn(const eg_conv* c, const float* slab, int nsplit, const float* w_orig, const float* sigma,
-                                  const float* u, const float* v, float* gtmp, float* partials, float* grad, eg_stream_t s) {
-    return eg_wgrad_reduce_sn_store(c, slab, nsplit, w_orig, sigma, u, v, gtmp, partials, grad, 1, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2467,7 +2444,7 @@ extern "C" size_t eg_bias_grad_ws_floats(int rows, int N) {
     return (size_t)std::max(cdiv(rows, 256), 1024) * N;
 }
 
-extern "C" int eg_bias_grad_store(int dtype, const void* dY, int rows, int N, int bias_mod, float* partials, float* gb, int accumulate, eg_stream_t s) {
+extern "C" int eg_bias_grad(int dtype, const void* dY, int rows, int N, int bias_mod, float* partials, float* gb, int accumulate, eg_stream_t s) {
     EG_REQUIRE(dY && partials && gb && rows > 0 && N > 0, "eg_bias_grad: bad argument");
     const int vecw = dtype == EG_F32 ? 4 : 8;
     EG_REQUIRE(N % vecw == 0, "eg_bias_grad: N must be a multiple of the 16-byte vector width");
@@ -2484,9 +2461,6 @@ extern "C" int eg_bias_grad_store(int dtype, const void* dY, int rows, int N, in
     hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(nb, 4)), dim3(256), 0, (hipStream_t)s, partials, nrb, N, nb, (const float*)nullptr, gb, accumulate != 0);
     EG_LAUNCH_CHECK();
     return 0;
-}
-extern "C" int eg_bias_grad(int dtype, const void* dY, int rows, int N, int bias_mod, float* partials, float* gb, eg_stream_t s) {
-    return eg_bias_grad_store(dtype, dY, rows, N, bias_mod, partials, gb, 1, s);
 }
 
 // ---- tape-segmented bias gradient + <G,W>/sigma^2 coefficient from activations (spectrally normalised layers) --------
@@ -2566,8 +2540,8 @@ extern "C" size_t eg_bias_grad_sn_ws_floats(int rows, int N, int rows_per_tape) 
     return (size_t)std::max(ntapes * cdiv(rows_per_tape, 256), 1024 + ntapes) * (N + 64);
 }
 
-extern "C" int eg_bias_grad_sn_store(int dtype, const void* dzs, const void* a, const float* bias, int rows, int N, int rows_per_tape,
-                                     const float* sigma, float slope, float* ws, float* gb, float* coef, int accumulate, eg_stream_t s) {
+extern "C" int eg_bias_grad_sn(int dtype, const void* dzs, const void* a, const float* bias, int rows, int N, int rows_per_tape,
+                               const float* sigma, float slope, float* ws, float* gb, float* coef, int accumulate, eg_stream_t s) {
     EG_REQUIRE(dzs && a && bias && sigma && ws && gb && coef && rows_per_tape > 0 && rows % rows_per_tape == 0 && slope > 0.f, "eg_bias_grad_sn: bad argument");
     const int vecw = dtype == EG_F32 ? 4 : 8;
     EG_REQUIRE(N % vecw == 0, "eg_bias_grad_sn: N must be a multiple of the 16-byte vector width");
@@ -2589,10 +2563,6 @@ extern "C" int eg_bias_grad_sn_store(int dtype, const void* dzs, const void* a, 
     hipLaunchKernelGGL(colsum_sn_final_kernel, dim3(cdiv(N + ntapes, 4)), dim3(256), 0, (hipStream_t)s, partials, dots, nrb, N, bpt, gx, ntapes, sigma, gb, coef, accumulate != 0);
     EG_LAUNCH_CHECK();
     return 0;
-}
-extern "C" int eg_bias_grad_sn(int dtype, const void* dzs, const void* a, const float* bias, int rows, int N, int rows_per_tape,
-                               const float* sigma, float slope, float* ws, float* gb, float* coef, eg_stream_t s) {
-    return eg_bias_grad_sn_store(dtype, dzs, a, bias, rows, N, rows_per_tape, sigma, slope, ws, gb, coef, 1, s);
 }
 
 // ---- the same sums from the epilogue of the convolution that produced dzs (eg_epilogue.stat_mode = EG_STAT_SN_BIAS) -----------------
@@ -2631,8 +2601,8 @@ __global__ void colsum_sn_final_t_kernel(const float* __restrict__ stat, int nrb
     else if (j < N + ntapes) coef[j - N] = acc;
 }
 
-extern "C" int eg_bias_grad_sn_fused_store(const float* stat, int nrb, int N, int tiles_m, int tiles_per_tape, int ntapes, const float* sigma, float* gb,
-                                           float* coef, int accumulate, eg_stream_t s) {
+extern "C" int eg_bias_grad_sn_fused(const float* stat, int nrb, int N, int tiles_m, int tiles_per_tape, int ntapes, const float* sigma, float* gb,
+                                     float* coef, int accumulate, eg_stream_t s) {
     EG_REQUIRE(stat && sigma && gb && coef && nrb > 0 && N > 0 && ((N % 128) == 0 || N == 64 || N == 32) && tiles_m > 0 && (nrb % tiles_m) == 0 &&
                tiles_per_tape > 0 && ntapes > 0 && ntapes <= 4 && tiles_per_tape * ntapes == tiles_m, "eg_bias_grad_sn_fused: bad argument");
     // (column tiles of the producing launch: 128 wide for the 8-wave kernels, the whole row for the register-staged kernel's N = 32 / 64)
@@ -2644,8 +2614,4 @@ extern "C" int eg_bias_grad_sn_fused_store(const float* stat, int nrb, int N, in
                            N >= 128 ? N / 128 : 1, ntapes, sigma, gb, coef, accumulate != 0);
     EG_LAUNCH_CHECK();
     return 0;
-}
-extern "C" int eg_bias_grad_sn_fused(const float* stat, int nrb, int N, int tiles_m, int tiles_per_tape, int ntapes, const float* sigma, float* gb,
-                                     float* coef, eg_stream_t s) {
-    return eg_bias_grad_sn_fused_store(stat, nrb, N, tiles_m, tiles_per_tape, ntapes, sigma, gb, coef, 1, s);
 }

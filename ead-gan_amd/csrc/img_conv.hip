@@ -220,9 +220,9 @@ extern "C" int eg_conv_img_mfma_ok(int dtype, int C, int H, int W, int N, int k,
     return dtype != EG_F32 && C >= 1 && C <= 4 && (N == 128 || N == 64 || N == 32) && k == 4 && stride == 2 && pad == 1 && H >= 4 && (H % 4) == 0 && (W % 64) == 0;
 }
 
-extern "C" int eg_conv_img_mfma_n(int dtype, const float* img0, const float* img1, const float* img2, const float* gate0, const float* gate1,
-                                  const float* gate2, int ntapes, const void* wp, void* out, int B, int C, int H, int W, int N, const eg_epilogue* ep,
-                                  int gate_act, float gate_slope, eg_stream_t s) {
+extern "C" int eg_conv_img_mfma(int dtype, const float* img0, const float* img1, const float* img2, const float* gate0, const float* gate1,
+                                const float* gate2, int ntapes, const void* wp, void* out, int B, int C, int H, int W, int N, const eg_epilogue* ep,
+                                int gate_act, float gate_slope, eg_stream_t s) {
     EG_REQUIRE(img0 && wp && out && ntapes >= 1 && ntapes <= 3 && B > 0, "eg_conv_img_mfma: bad argument");
     EG_REQUIRE(eg_conv_img_mfma_ok(dtype, C, H, W, N, 4, 2, 1), "eg_conv_img_mfma: 16-bit types, C <= 4, N = 32 / 64 / 128, H %% 4 == 0, W %% 64 == 0 only (use eg_im2col_img + eg_conv_fwd)");
     EG_REQUIRE((ntapes < 2 || img1) && (ntapes < 3 || img2), "eg_conv_img_mfma: one image pointer per tape");
@@ -267,12 +267,6 @@ extern "C" int eg_conv_img_mfma_n(int dtype, const float* img0, const float* img
     }
     EG_LAUNCH_CHECK();
     return 0;
-}
-
-extern "C" int eg_conv_img_mfma(int dtype, const float* img0, const float* img1, const float* img2, const float* gate0, const float* gate1,
-                                const float* gate2, int ntapes, const void* wp, void* out, int B, int C, int H, int W, const eg_epilogue* ep,
-                                int gate_act, float gate_slope, eg_stream_t s) {
-    return eg_conv_img_mfma_n(dtype, img0, img1, img2, gate0, gate1, gate2, ntapes, wp, out, B, C, H, W, 128, ep, gate_act, gate_slope, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -387,8 +381,8 @@ extern "C" int eg_convt_img_mfma_ok(int dtype, int C, int Hin, int Win, int K, i
     return dtype != EG_F32 && C >= 1 && C <= 3 && (K == 128 || K == 64) && k == 4 && stride == 2 && pad == 1 && Hin >= 16 && (Hin % 16) == 0 && (Win == 16 || Win == 32);
 }
 
-extern "C" int eg_convt_img_mfma_k(int dtype, const void* a, const void* wp, const float* bias, float* out, int B, int C, int Hin, int Win, int K, int act,
-                                   float slope, eg_stream_t s) {
+extern "C" int eg_convt_img_mfma(int dtype, const void* a, const void* wp, const float* bias, float* out, int B, int C, int Hin, int Win, int K, int act,
+                                 float slope, eg_stream_t s) {
     EG_REQUIRE(a && wp && out && B > 0, "eg_convt_img_mfma: bad argument");
     EG_REQUIRE(eg_convt_img_mfma_ok(dtype, C, Hin, Win, K, 4, 2, 1), "eg_convt_img_mfma: 16-bit types, C <= 3, K = 64 / 128, Hin %% 16 == 0, Win 16 or 32 only (use eg_conv_fwd + eg_col2im_img)");
     ImgTParams p;
@@ -408,10 +402,6 @@ extern "C" int eg_convt_img_mfma_k(int dtype, const void* a, const void* wp, con
     else hipLaunchKernelGGL((convt_img_mfma_kernel<bf16_t, 8>), grid, dim3(256), 0, st, p);
     EG_LAUNCH_CHECK();
     return 0;
-}
-extern "C" int eg_convt_img_mfma(int dtype, const void* a, const void* wp, const float* bias, float* out, int B, int C, int Hin, int Win, int act,
-                                 float slope, eg_stream_t s) {
-    return eg_convt_img_mfma_k(dtype, a, wp, bias, out, B, C, Hin, Win, 128, act, slope, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -539,11 +529,10 @@ extern "C" int eg_wgrad_img_ok(int dtype, int C, int H, int W, int N, int k, int
     return dtype != EG_F32 && C >= 1 && C <= 4 && (N == 32 || N == 64 || N == 128) && k == 4 && stride == 2 && pad == 1 && H == 64 && W == 64;
 }
 /* workgroups (= slabs of N x 16 C floats) an eg_wgrad_img launch over `images` images (all tapes) with N output channels uses */
-extern "C" int eg_wgrad_img_splits_n(int images, int N) {
+extern "C" int eg_wgrad_img_splits(int images, int N) {
     const long long tiles = (long long)images * 8, cap = N >= 128 ? 256 : 1024;      // (wide slabs: fewer of them to reduce)
     return (int)(tiles < cap ? tiles : cap);
 }
-extern "C" int eg_wgrad_img_splits(int images) { return eg_wgrad_img_splits_n(images, 32); }
 extern "C" int eg_wgrad_img(int dtype, const float* img0, const float* img1, const float* img2, int ntapes, const void* P, float* slab, int B, int C,
                             int H, int W, int N, int* nsplit_out, eg_stream_t s) {
     EG_REQUIRE(img0 && P && slab && nsplit_out && ntapes >= 1 && ntapes <= 3 && B > 0, "eg_wgrad_img: bad argument");
@@ -553,7 +542,7 @@ extern "C" int eg_wgrad_img(int dtype, const float* img0, const float* img1, con
     memset(&p, 0, sizeof(p));
     p.img[0] = img0; p.img[1] = img1; p.img[2] = img2;
     p.P = P; p.slab = slab; p.B = B; p.C = C; p.ntiles = ntapes * B * 8;
-    const int grid = eg_wgrad_img_splits_n(ntapes * B, N);
+    const int grid = eg_wgrad_img_splits(ntapes * B, N);
     hipStream_t st = (hipStream_t)s;
     if (N == 128) {
         if (dtype == EG_F16) hipLaunchKernelGGL((wgrad_img_kernel<f16_t, 128>), dim3(grid), dim3(256), 0, st, p);

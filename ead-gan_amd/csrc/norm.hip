@@ -490,9 +490,9 @@ static int bn_bwd_impl(int dtype, const void* z, const void* da, void* dz, int M
 }
 
 // synchronised backward, stage 1: this rank's sums (also added to dbeta / dgamma), no dz yet
-extern "C" int eg_bn_bwd_sums_local_store(int dtype, const void* z, const void* da, int M, int C, const float* gamma, const float* beta,
-                                          const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta,
-                                          float* sums, float* ws, int accumulate, eg_stream_t s) {
+extern "C" int eg_bn_bwd_sums_local(int dtype, const void* z, const void* da, int M, int C, const float* gamma, const float* beta,
+                                    const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta,
+                                    float* sums, float* ws, int accumulate, eg_stream_t s) {
     EG_REQUIRE(z && da && gamma && beta && save_mean && save_invstd && sums && ws && M > 0 && C > 0, "eg_bn_bwd_sums_local: bad argument");
     hipStream_t st = (hipStream_t)s;
     const int gx = bn_gx(C, dtype), rpb = bn_rpb(M, gx);
@@ -505,12 +505,6 @@ extern "C" int eg_bn_bwd_sums_local_store(int dtype, const void* z, const void* 
     hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(cdiv(C, 4)), dim3(256), 0, st, ws, nrb, C, sums, dgamma, dbeta, gamma, beta, save_mean, save_invstd, M, coef, accumulate != 0);
     EG_LAUNCH_CHECK();
     return 0;
-}
-
-extern "C" int eg_bn_bwd_sums_local(int dtype, const void* z, const void* da, int M, int C, const float* gamma, const float* beta,
-                                    const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta,
-                                    float* sums, float* ws, eg_stream_t s) {
-    return eg_bn_bwd_sums_local_store(dtype, z, da, M, C, gamma, beta, save_mean, save_invstd, act, slope, dgamma, dbeta, sums, ws, 1, s);
 }
 
 __global__ void bn_bwd_coef_kernel(const float* __restrict__ sums, int C, int M, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -579,9 +573,9 @@ __global__ void bn_bwd_final_t_kernel(const float* __restrict__ stat, int nrb, i
     coef[4 * C + c] = beta[c] - mu * g * is;
 }
 
-extern "C" int eg_bn_bwd_fused_store(int dtype, const void* z, const void* dy, void* dz, int M, int C, const float* stat, int nrb,
-                                     const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta,
-                                     float* sums, float* ws, int accumulate, eg_stream_t s) {
+extern "C" int eg_bn_bwd_fused(int dtype, const void* z, const void* dy, void* dz, int M, int C, const float* stat, int nrb,
+                               const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta,
+                               float* sums, float* ws, int accumulate, eg_stream_t s) {
     EG_REQUIRE(z && dy && dz && stat && gamma && beta && save_mean && save_invstd && sums && ws && M > 0 && C > 0 && nrb > 0, "eg_bn_bwd_fused: bad argument");
     EG_REQUIRE(C % (dtype == EG_F32 ? 4 : 8) == 0, "eg_bn_bwd_fused: C must be a multiple of the 16-byte vector width");
     hipStream_t st = (hipStream_t)s;
@@ -600,24 +594,13 @@ extern "C" int eg_bn_bwd_fused_store(int dtype, const void* z, const void* dy, v
     return 0;
 }
 
-extern "C" int eg_bn_bwd_fused(int dtype, const void* z, const void* dy, void* dz, int M, int C, const float* stat, int nrb,
-                               const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta,
-                               float* sums, float* ws, eg_stream_t s) {
-    return eg_bn_bwd_fused_store(dtype, z, dy, dz, M, C, stat, nrb, gamma, beta, save_mean, save_invstd, dgamma, dbeta, sums, ws, 1, s);
-}
-
-extern "C" int eg_bn_bwd_store(int dtype, const void* z, const void* da, void* dz, int M, int C, const float* gamma, const float* beta,
-                               const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta,
-                               float* sums, float* ws, int accumulate, eg_stream_t s) {
+extern "C" int eg_bn_bwd(int dtype, const void* z, const void* da, void* dz, int M, int C, const float* gamma, const float* beta,
+                         const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta,
+                         float* sums, float* ws, int accumulate, eg_stream_t s) {
     EG_REQUIRE(z && da && dz && gamma && beta && save_mean && save_invstd && sums && ws, "eg_bn_bwd: null pointer");
     bn_bwd_impl(dtype, z, da, dz, M, C, gamma, beta, save_mean, save_invstd, act, slope, dgamma, dbeta, sums, ws, EG_ACT_NONE, 0.f, nullptr, accumulate, (hipStream_t)s);
     EG_LAUNCH_CHECK();
     return 0;
-}
-extern "C" int eg_bn_bwd(int dtype, const void* z, const void* da, void* dz, int M, int C, const float* gamma, const float* beta,
-                         const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta,
-                         float* sums, float* ws, eg_stream_t s) {
-    return eg_bn_bwd_store(dtype, z, da, dz, M, C, gamma, beta, save_mean, save_invstd, act, slope, dgamma, dbeta, sums, ws, 1, s);
 }
 
 extern "C" int eg_bn_bwd_post(int dtype, const void* z, const void* da, void* dz, int M, int C, const float* gamma, const float* beta,

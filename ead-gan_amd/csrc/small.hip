@@ -204,21 +204,6 @@ __global__ void flat_reduce_kernel(const float* __restrict__ slab, int nslab, si
     }
 }
 
-__global__ void sn_grad_apply_kernel2(const float* __restrict__ gtmp, const float* __restrict__ partials, int npart,
-                                      const float* __restrict__ sigma, const float* __restrict__ u, const float* __restrict__ v,
-                                      long long total, int Kdim, float* __restrict__ grad) {
-    __shared__ float sm[16];
-    float d = 0.f;
-    for (int i = threadIdx.x; i < npart; i += blockDim.x) d += partials[i];
-    const float dot = block_sum(d, sm);
-    const float sg = sigma[0];
-    const float inv = 1.f / sg, coef = dot / (sg * sg);
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int n = (int)(i / Kdim), kk = (int)(i % Kdim);
-        grad[i] += gtmp[i] * inv - coef * u[n] * v[kk];
-    }
-}
-
 // out = g * act'(a) on NCHW fp32 tensors, plus partial[b*C+c] = sum_hw out  (bias gradient of the layer that produced a)
 __global__ void act_grad_mul_rowsum_kernel(const float* __restrict__ g, const float* __restrict__ a, float* __restrict__ out, int HW, int act,
                                            float slope, float* __restrict__ partial) {
@@ -251,34 +236,11 @@ __global__ __launch_bounds__(256) void rowsum_final_kernel(const float* __restri
         gb[threadIdx.x] = accumulate ? gb[threadIdx.x] + t : t;
     }
 }
-extern "C" int eg_act_grad_mul_bias_nchw_store(const float* g, const float* a, float* out, int B, int C, int HW, int act, float slope, float* partial,
-                                               float* gb, int accumulate, eg_stream_t s) {
+extern "C" int eg_act_grad_mul_bias_nchw(const float* g, const float* a, float* out, int B, int C, int HW, int act, float slope, float* partial,
+                                         float* gb, int accumulate, eg_stream_t s) {
     EG_REQUIRE(g && a && out && partial && gb && C <= 64, "eg_act_grad_mul_bias_nchw: bad argument");
     hipLaunchKernelGGL(act_grad_mul_rowsum_kernel, dim3(B * C), dim3(256), 0, (hipStream_t)s, g, a, out, HW, act, slope, partial);
     hipLaunchKernelGGL(rowsum_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, partial, B, C, gb, accumulate != 0);
-    EG_LAUNCH_CHECK();
-    return 0;
-}
-extern "C" int eg_act_grad_mul_bias_nchw(const float* g, const float* a, float* out, int B, int C, int HW, int act, float slope, float* partial,
-                                         float* gb, eg_stream_t s) {
-    return eg_act_grad_mul_bias_nchw_store(g, a, out, B, C, HW, act, slope, partial, gb, 1, s);
-}
-
-// per-channel sum of an NCHW fp32 tensor with few channels: gb[c] += sum_{b,hw} x[b][c][hw]
-__global__ void bias_grad_nchw_kernel(const float* __restrict__ x, int B, int C, int HW, float* __restrict__ gb) {
-    __shared__ float sm[16];
-    const int c = blockIdx.x;
-    float a = 0.f;
-    for (int b = 0; b < B; ++b) {
-        const float* p = x + ((size_t)b * C + c) * HW;
-        for (int i = threadIdx.x; i < HW; i += blockDim.x) a += p[i];
-    }
-    const float tot = block_sum(a, sm);
-    if (threadIdx.x == 0) gb[c] += tot;
-}
-extern "C" int eg_bias_grad_nchw(const float* x, int B, int C, int HW, float* gb, eg_stream_t s) {
-    EG_REQUIRE(x && gb, "eg_bias_grad_nchw: null pointer");
-    hipLaunchKernelGGL(bias_grad_nchw_kernel, dim3(C), dim3(1024), 0, (hipStream_t)s, x, B, C, HW, gb);
     EG_LAUNCH_CHECK();
     return 0;
 }
@@ -288,18 +250,6 @@ extern "C" int eg_flat_reduce(const float* slab, int nslab, size_t total, float*
     EG_REQUIRE(slab && grad && nslab > 0, "eg_flat_reduce: bad argument");
     const int blocks = (int)((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256);
     hipLaunchKernelGGL(flat_reduce_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)s, slab, nslab, total, grad, accumulate, (const float*)nullptr, (float*)nullptr);
-    EG_LAUNCH_CHECK();
-    return 0;
-}
-
-/* spectral-norm variant: rows = Cout, Kdim = elements per row; partials >= 1024 floats */
-extern "C" int eg_flat_reduce_sn(const float* slab, int nslab, int rows, int Kdim, const float* w_orig, const float* sigma, const float* u,
-                                 const float* v, float* gtmp, float* partials, float* grad, eg_stream_t s) {
-    EG_REQUIRE(slab && w_orig && sigma && u && v && gtmp && partials && grad && nslab > 0, "eg_flat_reduce_sn: bad argument");
-    const size_t total = (size_t)rows * Kdim;
-    const int blocks = (int)((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256);
-    hipLaunchKernelGGL(flat_reduce_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)s, slab, nslab, total, gtmp, 0, w_orig, partials);
-    hipLaunchKernelGGL(sn_grad_apply_kernel2, dim3(blocks), dim3(256), 0, (hipStream_t)s, gtmp, partials, blocks, sigma, u, v, (long long)total, Kdim, grad);
     EG_LAUNCH_CHECK();
     return 0;
 }
@@ -703,14 +653,11 @@ __global__ __launch_bounds__(512) void dense_small_bgrad_kernel(const float* dy,
     }
 }
 
-extern "C" int eg_dense_small_bgrad_store(const float* dy, float* gb, int B, int N, int accumulate, eg_stream_t s) {
+extern "C" int eg_dense_small_bgrad(const float* dy, float* gb, int B, int N, int accumulate, eg_stream_t s) {
     EG_REQUIRE(dy && gb && N <= 64, "eg_dense_small_bgrad: bad argument");
     hipLaunchKernelGGL(dense_small_bgrad_kernel, dim3(1), dim3(512), 0, (hipStream_t)s, dy, gb, B, N, accumulate != 0);
     EG_LAUNCH_CHECK();
     return 0;
-}
-extern "C" int eg_dense_small_bgrad(const float* dy, float* gb, int B, int N, eg_stream_t s) {
-    return eg_dense_small_bgrad_store(dy, gb, B, N, 1, s);
 }
 
 extern "C" int eg_dense_small_wgrad(int dtype, const float* dy, const void* x, float* gw, float* gb, int B, int K, int N, int Cin, int taps,

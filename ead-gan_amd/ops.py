@@ -80,6 +80,11 @@ def nt_tile(c, dtype, bwd, ep=None) -> int:
     return lib().query("eg_igemm_nt_tile_ep", ctypes.byref(c), dtype, int(bwd), ctypes.byref(ep))
 
 
+def nt_tile_hinted(c, dtype, bwd, variant=0, splitk=0) -> int:
+    """the same label for the bare hints, with unlimited split-K scratch (profiling labels and the kernel tests); -1 = ``variant`` cannot run it"""
+    return lib().query("eg_igemm_nt_tile", ctypes.byref(c), dtype, int(bwd), variant, splitk)
+
+
 def conv_stat_blocks(c, dtype, bwd, ep=None) -> int:
     """row blocks of the fused column statistics this exact call (geometry, hints, scratch of ``ep``) would write; 0 = it cannot fuse them"""
     if ep is None:
@@ -204,7 +209,7 @@ def conv_wgrad_ws_bytes(c, dtype):
 def conv_wgrad(c, dtype, X, dY, slab, wgs_target=0) -> int:
     """``wgs_target``: workgroups the parity-class kernel aims for (0: one per CU; 128 for launches forked beside the main chain)"""
     ns = ctypes.c_int(0)
-    args = ("eg_conv_wgrad_target", ctypes.byref(c), dtype, _p(X), _p(dY), _p(slab), ctypes.addressof(ns), wgs_target)
+    args = ("eg_conv_wgrad", ctypes.byref(c), dtype, _p(X), _p(dY), _p(slab), ctypes.addressof(ns), wgs_target)
     if RECORDER is not None:
         _timed("tn", c, dtype, args)
     else:
@@ -224,7 +229,7 @@ def wgrad_reduce(slab, nsplit, n_slab, n_rows, C, T, grad, accumulate=True):
 
 
 def wgrad_reduce_perm(slab, nsplit, n_slab, n_rows, C, T, grad, row_div=0, row_mul=0, c_row=0, accumulate=True):
-    lib().call("eg_wgrad_reduce_perm_store", _p(slab), nsplit, n_slab, n_rows, C, T, _p(grad), row_div, row_mul, c_row, int(accumulate), _stream())
+    lib().call("eg_wgrad_reduce_perm", _p(slab), nsplit, n_slab, n_rows, C, T, _p(grad), row_div, row_mul, c_row, int(accumulate), _stream())
 
 
 def gather_add(out, src, n, div, s_div, s_mod):
@@ -265,7 +270,7 @@ def sn_partials():
 
 
 def wgrad_reduce_sn(c, slab, nsplit, w_orig, sigma, u, v, gtmp, partials, grad, accumulate=True):
-    lib().call("eg_wgrad_reduce_sn_store", ctypes.byref(c), _p(slab), nsplit, _p(w_orig), _p(sigma), _p(u), _p(v), _p(gtmp), _p(partials), _p(grad),
+    lib().call("eg_wgrad_reduce_sn", ctypes.byref(c), _p(slab), nsplit, _p(w_orig), _p(sigma), _p(u), _p(v), _p(gtmp), _p(partials), _p(grad),
                int(accumulate), _stream())
 
 
@@ -274,7 +279,7 @@ def bias_grad_ws_floats(rows, N):
 
 
 def bias_grad(dtype, dY, rows, N, partials, gb, bias_mod=0, accumulate=True):
-    lib().call("eg_bias_grad_store", dtype, _p(dY), rows, N, bias_mod, _p(partials), _p(gb), int(accumulate), _stream())
+    lib().call("eg_bias_grad", dtype, _p(dY), rows, N, bias_mod, _p(partials), _p(gb), int(accumulate), _stream())
 
 
 def bias_grad_sn_ws_floats(rows, N, rows_per_tape):
@@ -282,16 +287,16 @@ def bias_grad_sn_ws_floats(rows, N, rows_per_tape):
 
 
 def bias_grad_sn(dtype, dzs, a, bias, rows, N, rows_per_tape, sigma, slope, ws, gb, coef, accumulate=True):
-    lib().call("eg_bias_grad_sn_store", dtype, _p(dzs), _p(a), _p(bias), rows, N, rows_per_tape, _p(sigma), slope, _p(ws), _p(gb), _p(coef),
+    lib().call("eg_bias_grad_sn", dtype, _p(dzs), _p(a), _p(bias), rows, N, rows_per_tape, _p(sigma), slope, _p(ws), _p(gb), _p(coef),
                int(accumulate), _stream())
 
 
 def bias_grad_sn_fused(stat, nrb, N, tiles_m, tiles_per_tape, ntapes, sigma, gb, coef, accumulate=True):
-    lib().call("eg_bias_grad_sn_fused_store", _p(stat), nrb, N, tiles_m, tiles_per_tape, ntapes, _p(sigma), _p(gb), _p(coef), int(accumulate), _stream())
+    lib().call("eg_bias_grad_sn_fused", _p(stat), nrb, N, tiles_m, tiles_per_tape, ntapes, _p(sigma), _p(gb), _p(coef), int(accumulate), _stream())
 
 
 def wgrad_reduce_rank1(slab, nsplit, n_slab, n_rows, C, T, grad, ntapes, coef, u, v, c_row=0, accumulate=True):
-    lib().call("eg_wgrad_reduce_rank1_store", _p(slab), nsplit, n_slab, n_rows, C, T, _p(grad), ntapes, _p(coef), _p(u), _p(v), c_row, int(accumulate),
+    lib().call("eg_wgrad_reduce_rank1", _p(slab), nsplit, n_slab, n_rows, C, T, _p(grad), ntapes, _p(coef), _p(u), _p(v), c_row, int(accumulate),
                _stream())
 
 
@@ -325,7 +330,7 @@ def conv_img_mfma(dtype, imgs, wp, out, B, C, H, W, ep=None, gates=None, gate_ac
     """Conv2d(C -> N = 128 / 64 / 32, 4, 2, 1) of up to three fp32 NCHW image tensors (tapes) straight on the MFMA units, no patch rows in HBM"""
     im = [_p(t) for t in imgs] + [None] * (3 - len(imgs))
     ga = [_p(t) for t in (gates or [])] + [None] * (3 - len(gates or []))
-    lib().call("eg_conv_img_mfma_n", dtype, im[0], im[1], im[2], ga[0], ga[1], ga[2], len(imgs), _p(wp), _p(out), B, C, H, W, N,
+    lib().call("eg_conv_img_mfma", dtype, im[0], im[1], im[2], ga[0], ga[1], ga[2], len(imgs), _p(wp), _p(out), B, C, H, W, N,
                ctypes.byref(ep) if ep is not None else None, gate_act, gate_slope, _stream())
 
 
@@ -334,7 +339,7 @@ def wgrad_img_ok(dtype, C, H, W, N, k, stride, pad) -> bool:
 
 
 def wgrad_img_splits(images, N=32) -> int:
-    return lib().query("eg_wgrad_img_splits_n", images, N)
+    return lib().query("eg_wgrad_img_splits", images, N)
 
 
 def wgrad_img(dtype, imgs, P, slab, B, C, H, W, N) -> int:
@@ -352,7 +357,7 @@ def convt_img_mfma_ok(dtype, C, Hin, Win, K, k, stride, pad) -> bool:
 
 def convt_img_mfma(dtype, a, wp, bias, out, B, C, Hin, Win, act=ACT_NONE, slope=0.0, K=128):
     """ConvTranspose2d(K = 128 / 64 -> C <= 3, 4, 2, 1) (+ bias + activation) from 16-bit NHWC activations to an fp32 NCHW image in one launch"""
-    lib().call("eg_convt_img_mfma_k", dtype, _p(a), _p(wp), _p(bias), _p(out), B, C, Hin, Win, K, act, slope, _stream())
+    lib().call("eg_convt_img_mfma", dtype, _p(a), _p(wp), _p(bias), _p(out), B, C, Hin, Win, K, act, slope, _stream())
 
 
 def cast_pad(dtype, src, dst, rows, n, npad):
@@ -360,7 +365,7 @@ def cast_pad(dtype, src, dst, rows, n, npad):
 
 
 def act_grad_mul_bias_nchw(g, a, out, B, C, HW, act, slope, partial, gb, accumulate=True):
-    lib().call("eg_act_grad_mul_bias_nchw_store", _p(g), _p(a), _p(out), B, C, HW, act, slope, _p(partial), _p(gb), int(accumulate), _stream())
+    lib().call("eg_act_grad_mul_bias_nchw", _p(g), _p(a), _p(out), B, C, HW, act, slope, _p(partial), _p(gb), int(accumulate), _stream())
 
 
 def head_fused_ok(dtype, T, K, N):
@@ -440,19 +445,11 @@ def head_fused(dtype, x, wp, bias, partials, nslice, y, dout, dx, sigma, B, T, K
 
 
 def dense_small_bgrad(dy, gb, B, N, accumulate=True):
-    lib().call("eg_dense_small_bgrad_store", _p(dy), _p(gb), B, N, int(accumulate), _stream())
+    lib().call("eg_dense_small_bgrad", _p(dy), _p(gb), B, N, int(accumulate), _stream())
 
 
 def flat_reduce(slab, nslab, total, grad, accumulate=True):
     lib().call("eg_flat_reduce", _p(slab), nslab, total, _p(grad), int(accumulate), _stream())
-
-
-def flat_reduce_sn(slab, nslab, rows, Kdim, w_orig, sigma, u, v, gtmp, partials, grad):
-    lib().call("eg_flat_reduce_sn", _p(slab), nslab, rows, Kdim, _p(w_orig), _p(sigma), _p(u), _p(v), _p(gtmp), _p(partials), _p(grad), _stream())
-
-
-def bias_grad_nchw(x, B, C, HW, gb):
-    lib().call("eg_bias_grad_nchw", _p(x), B, C, HW, _p(gb), _stream())
 
 
 def dense_small_fwd(dtype, x, wp, bias, y, B, K, Kpad, N, ws=None):
@@ -499,7 +496,7 @@ def bn_fwd_from_stats(dtype, x, y, M_local, C, stats_all, nranks, M_global, gamm
 
 
 def bn_bwd_sums_local(dtype, z, da, M, C, gamma, beta, save_mean, save_invstd, act, slope, dgamma, dbeta, sums, ws, accumulate=True):
-    lib().call("eg_bn_bwd_sums_local_store", dtype, _p(z), _p(da), M, C, _p(gamma), _p(beta), _p(save_mean), _p(save_invstd), act, float(slope),
+    lib().call("eg_bn_bwd_sums_local", dtype, _p(z), _p(da), M, C, _p(gamma), _p(beta), _p(save_mean), _p(save_invstd), act, float(slope),
                _p(dgamma), _p(dbeta), _p(sums), _p(ws), int(accumulate), _stream())
 
 
@@ -520,12 +517,12 @@ def bn_fwd_train_fused(dtype, x, y, M, C, stat, nrb, rows_per_block, gamma, beta
 
 
 def bn_bwd_fused(dtype, z, dy, dz, M, C, stat, nrb, gamma, beta, save_mean, save_invstd, dgamma, dbeta, sums, ws, accumulate=True):
-    lib().call("eg_bn_bwd_fused_store", dtype, _p(z), _p(dy), _p(dz), M, C, _p(stat), nrb, _p(gamma), _p(beta), _p(save_mean), _p(save_invstd),
+    lib().call("eg_bn_bwd_fused", dtype, _p(z), _p(dy), _p(dz), M, C, _p(stat), nrb, _p(gamma), _p(beta), _p(save_mean), _p(save_invstd),
                _p(dgamma), _p(dbeta), _p(sums), _p(ws), int(accumulate), _stream())
 
 
 def bn_bwd(dtype, z, da, dz, M, C, gamma, beta, save_mean, save_invstd, act, slope, dgamma, dbeta, sums, ws, accumulate=True):
-    lib().call("eg_bn_bwd_store", dtype, _p(z), _p(da), _p(dz), M, C, _p(gamma), _p(beta), _p(save_mean), _p(save_invstd), act, slope,
+    lib().call("eg_bn_bwd", dtype, _p(z), _p(da), _p(dz), M, C, _p(gamma), _p(beta), _p(save_mean), _p(save_invstd), act, slope,
                _p(dgamma), _p(dbeta), _p(sums), _p(ws), int(accumulate), _stream())
 
 
@@ -575,14 +572,13 @@ def adam_pack_conv_ok(c, dtype, has_fwd, has_bwd) -> bool:
     return bool(lib().query("eg_adam_pack_conv_ok", ctypes.byref(c), dtype, int(has_fwd), int(has_bwd)))
 
 
-def adam_pack_conv(c, dtype, p, g, m, v, lr, b1, b2, eps, step, zero_grad, wp_fwd, wp_bwd):
+def adam_pack_conv(c, dtype, p, g, m, v, lr, b1, b2, eps, step, wp_fwd, wp_bwd):
     """optimizer.step() on one convolution weight (slices of the four arenas) + refresh of its packed panels, one launch"""
-    lib().call("eg_adam_pack_conv", ctypes.byref(c), dtype, _p(p), _p(g), _p(m), _p(v), lr, b1, b2, eps, _p(step), int(zero_grad), _p(wp_fwd), _p(wp_bwd),
-               _stream())
+    lib().call("eg_adam_pack_conv", ctypes.byref(c), dtype, _p(p), _p(g), _p(m), _p(v), lr, b1, b2, eps, _p(step), _p(wp_fwd), _p(wp_bwd), _stream())
 
 
-def adam_pack_rows(dtype, p, g, m, v, wp, K, N, Kpad, n_mod, n_mul, lr, b1, b2, eps, step, zero_grad):
-    lib().call("eg_adam_pack_rows", dtype, _p(p), _p(g), _p(m), _p(v), _p(wp), K, N, Kpad, n_mod, n_mul, lr, b1, b2, eps, _p(step), int(zero_grad), _stream())
+def adam_pack_rows(dtype, p, g, m, v, wp, K, N, Kpad, n_mod, n_mul, lr, b1, b2, eps, step):
+    lib().call("eg_adam_pack_rows", dtype, _p(p), _p(g), _p(m), _p(v), _p(wp), K, N, Kpad, n_mod, n_mul, lr, b1, b2, eps, _p(step), _stream())
 
 
 def clear_errors():
@@ -599,18 +595,6 @@ def concat_cast(dtype, a, b, c, out, B, Cpad):
     wb = b.shape[1] if b is not None else 0
     wc = c.shape[1] if c is not None else 0
     lib().call("eg_concat_cast", dtype, _p(a), wa, _p(b), wb, _p(c), wc, B, Cpad, _p(out), _stream())
-
-
-def act_grad_mul_f32(g, a, out, act, slope=0.0):
-    lib().call("eg_act_grad_mul_f32", _p(g), _p(a), _p(out), g.numel(), act, slope, _stream())
-
-
-def nchw_to_nhwc(dtype, x, y, B, C, HW, Cpad):
-    lib().call("eg_nchw_to_nhwc", dtype, _p(x), _p(y), B, C, HW, Cpad, _stream())
-
-
-def nhwc_to_nchw(dtype, x, y, B, C, HW, Cpad):
-    lib().call("eg_nhwc_to_nchw", dtype, _p(x), _p(y), B, C, HW, Cpad, _stream())
 
 
 # ---- affine / warp / losses --------------------------------------------------------------------------------

@@ -138,13 +138,14 @@ size_t eg_conv_splitk_ws_bytes(const eg_conv* c, int dtype, int bwd);
  * one input patch and one tile of dY per K step), everything else on the per-tap kernel; eg_conv_wgrad_variant tells which (2 / 1). */
 int eg_conv_wgrad_variant(const eg_conv* c, int dtype);
 size_t eg_conv_wgrad_ws_bytes(const eg_conv* c, int dtype);
+/* wgs_target: the caller's share of the chip = workgroups the parity-class kernel should aim for (0 = one per CU).  A launch forked onto
+ * a side stream beside the main chain's GEMMs passes 128 (half the slab to write and reduce, the other CUs stay with the main chain);
+ * never more splits than eg_conv_wgrad_ws_bytes provides for. */
 int eg_conv_wgrad(const eg_conv* c, int dtype, const void* X, const void* dY, float* slab, int* nsplit,
-                  eg_stream_t s);
-/* the same with the caller's share of the chip: wgs_target = workgroups the parity-class kernel should aim for (0 = one per CU).  A
- * launch forked onto a side stream beside the main chain's GEMMs passes 128 (half the slab to write and reduce, the other CUs stay
- * with the main chain); never more splits than eg_conv_wgrad_ws_bytes provides for. */
-int eg_conv_wgrad_target(const eg_conv* c, int dtype, const void* X, const void* dY, float* slab, int* nsplit,
-                         int wgs_target, eg_stream_t s);
+                  int wgs_target, eg_stream_t s);
+/* Gradient writers.  Every entry point from here on that writes a parameter gradient ("(+)=" below) takes `accumulate` in front of the
+ * stream: accumulate != 0 adds to the slot (autograd's .grad contract), accumulate == 0 stores the same sum without reading the slot
+ * (what accumulating into a cleared slot gives, up to the sign of a zero). */
 /* grad[n][c][t] (+)= sum_split slab[split][n][t][c]  for n < n_rows (slab rows: n_slab >= n_rows);
  * C = gathered channels, T = taps.  Master layouts [Cout][Cin][k][k] / [Cin_T][Cout_T][k][k] are both [n][c][t]. */
 int eg_wgrad_reduce(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad,
@@ -152,7 +153,7 @@ int eg_wgrad_reduce(const float* slab, int nsplit, int n_slab, int n_rows, int C
 /* same with a row permutation: slab row n lands in gradient row (n % row_div) * row_mul + n / row_div
  * (Linear whose output is viewed [B,C,H,W] and kept NHWC on device: MNIST/EAD-GAN_rpqmnxy.py:77,95-96) */
 int eg_wgrad_reduce_perm(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad,
-                         int row_div, int row_mul, int c_row /* destination row length in channels, 0 = C */, eg_stream_t s);
+                         int row_div, int row_mul, int c_row /* destination row length in channels, 0 = C */, int accumulate, eg_stream_t s);
 /* out[i] += src[(i / div) * s_div + (i % div) * s_mod]   (un-permute a bias gradient) */
 int eg_gather_add(float* out, const float* src, int n, int div, int s_div, int s_mod, eg_stream_t s);
 /* y[B,H,W,C] = 2x2 sum-pool of x[B,2H,2W,C]  (backward of nn.Upsample(scale_factor=2), MNIST/EAD-GAN_rpqmnxy.py:81,85) */
@@ -171,33 +172,33 @@ int eg_wgrad_c1(int dtype, const void* x, const float* dy, float* slab, int B, i
 int eg_up3_expand(const float* w3, float* w4t, int Cout, int Cin, eg_stream_t s);
 int eg_up3_contract(const float* dw4t, float* dw3, int Cout, int Cin, int accumulate, eg_stream_t s);
 /* spectral-norm variant (torch.nn.utils.spectral_norm backward, celebA/EAD-GAN_celebA.py:110-120):
- * G = sum slab ;  grad += G/sigma - (<G,W_orig>/sigma^2) u v^T.  gtmp: Cout*Cin*k*k floats,
+ * G = sum slab ;  grad (+)= G/sigma - (<G,W_orig>/sigma^2) u v^T.  gtmp: Cout*Cin*k*k floats,
  * partials: >= eg_sn_partials() floats. */
 int eg_sn_partials(void);
 int eg_wgrad_reduce_sn(const eg_conv* c, const float* slab, int nsplit, const float* w_orig,
                        const float* sigma, const float* u, const float* v, float* gtmp, float* partials,
-                       float* grad, eg_stream_t s);
-/* per-output-channel bias gradient: gb[n % bias_mod] += sum_rows dY[row][n]  (dY is [rows][N] dtype T) */
+                       float* grad, int accumulate, eg_stream_t s);
+/* per-output-channel bias gradient: gb[n % bias_mod] (+)= sum_rows dY[row][n]  (dY is [rows][N] dtype T) */
 size_t eg_bias_grad_ws_floats(int rows, int N);
 int eg_bias_grad(int dtype, const void* dY, int rows, int N, int bias_mod, float* partials, float* gb,
-                 eg_stream_t s);
+                 int accumulate, eg_stream_t s);
 /* Batched-tape form for spectrally normalised layers.  dzs holds dL/dz ALREADY divided by the tape's sigma
  * (dzs = dz / sigma[tape]); a = activation output (LeakyReLU), bias = the layer's bias.  Computes
- *   gb[n]   += sum_tape sigma[tape] * sum_{rows of tape} dzs[row][n]
+ *   gb[n]  (+)= sum_tape sigma[tape] * sum_{rows of tape} dzs[row][n]
  *   coef[t]  = sum_{rows of tape t, n} dzs[row][n] * (lrelu^-1(a[row][n]) - bias[n])      (== <G_t, W_orig> / sigma_t^2)
  * ws: eg_bias_grad_sn_ws_floats(rows, N, rows_per_tape) floats. */
 size_t eg_bias_grad_sn_ws_floats(int rows, int N, int rows_per_tape);
 int eg_bias_grad_sn(int dtype, const void* dzs, const void* a, const float* bias, int rows, int N, int rows_per_tape,
-                    const float* sigma, float slope, float* ws, float* gb, float* coef, eg_stream_t s);
+                    const float* sigma, float slope, float* ws, float* gb, float* coef, int accumulate, eg_stream_t s);
 /* eg_bias_grad_sn with the per-tile sums taken from the epilogue of the convolution that produced dzs (EG_STAT_SN_BIAS): stat = its
  * stat_out (nrb = nphase * tiles_m row blocks of 256 lattice rows; tape of a row block = (rb % tiles_m) / tiles_per_tape) */
 int eg_bias_grad_sn_fused(const float* stat, int nrb, int N, int tiles_m, int tiles_per_tape, int ntapes, const float* sigma, float* gb,
-                          float* coef, eg_stream_t s);
-/* grad[n][c][t] += sum_split slab[split][n][t][c] - sum_tape coef[tape] * u[tape][n] * v[tape][c*T + t]
+                          float* coef, int accumulate, eg_stream_t s);
+/* grad[n][c][t] (+)= sum_split slab[split][n][t][c] - sum_tape coef[tape] * u[tape][n] * v[tape][c*T + t]
  * (u: [ntapes][n_rows], v: [ntapes][c_row*T]); single pass, deterministic.  c_row: destination row length in channels
  * (0 = C; < C when the gathered operand was zero padded, e.g. 9 of 16 im2col columns). */
 int eg_wgrad_reduce_rank1(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad,
-                          int ntapes, const float* coef, const float* u, const float* v, int c_row, eg_stream_t s);
+                          int ntapes, const float* coef, const float* u, const float* v, int c_row, int accumulate, eg_stream_t s);
 /* wp[n][k] = w[(n / n_div) * s_hi + (n % n_div) * s_lo + k * s_k], zero for K <= k < Kpad
  * (ConvTranspose2d on a 1x1 input as a GEMM: celebA/EAD-GAN_celebA.py:76; view-permuted Linear outputs) */
 int eg_pack_strided(int dtype, const float* w, void* wp, int N, int K, int Kpad, int n_div, long long s_hi,
@@ -228,23 +229,19 @@ int eg_conv_img_mfma_ok(int dtype, int C, int H, int W, int N, int k, int stride
 /* ep->stat_mode == EG_STAT_BN_BWD is honoured too (the output feeds a BatchNorm backward: dy stored, the two sums per tile of 64 pixels
  * to ep->stat_out[(which * 128 + n) * nrb + tile]); nrb = eg_conv_img_mfma_stat_blocks() */
 int eg_conv_img_mfma_stat_blocks(int B, int H, int W, int ntapes);
-int eg_conv_img_mfma(int dtype, const float* img0, const float* img1, const float* img2, const float* gate0, const float* gate1,
-                     const float* gate2, int ntapes, const void* wp, void* out, int B, int C, int H, int W, const eg_epilogue* ep,
-                     int gate_act, float gate_slope, eg_stream_t s);
-/* ... with N = 32, 64 or 128 output channels (wp: the [N][64] panel; out [ntapes*B][H/2][W/2][N]): the first trunk layer of the dSprites
+/* N = 32, 64 or 128 output channels (wp: the [N][64] panel; out [ntapes*B][H/2][W/2][N]): 32 is the first trunk layer of the dSprites
  * networks, Conv2d(C -> 32, 4, 2, 1) (dSprites/rp.py:95-97, 165-167; rp_color.py likewise).  EG_STAT_BN_BWD: N = 128 only. */
-int eg_conv_img_mfma_n(int dtype, const float* img0, const float* img1, const float* img2, const float* gate0, const float* gate1,
-                       const float* gate2, int ntapes, const void* wp, void* out, int B, int C, int H, int W, int N, const eg_epilogue* ep,
-                       int gate_act, float gate_slope, eg_stream_t s);
+int eg_conv_img_mfma(int dtype, const float* img0, const float* img1, const float* img2, const float* gate0, const float* gate1,
+                     const float* gate2, int ntapes, const void* wp, void* out, int B, int C, int H, int W, int N, const eg_epilogue* ep,
+                     int gate_act, float gate_slope, eg_stream_t s);
 /* weight gradient of the image-side 4x4 / stride-2 / pad-1 layers of the dSprites networks WITHOUT patch rows in HBM (16-bit types, 64 x 64
  * images, C <= 4): S[n][c*16 + ky*4 + kx] = sum over output pixels of P[pixel][n] * img[b][c][2 oy - 1 + ky][2 ox - 1 + kx] for up to three
  * tapes (img_t fp32 NCHW; P [ntapes*B*1024][N] dtype T, tape-major rows) -- Conv2d(C -> 32, 4, 2, 1) of the trunks (dSprites/rp.py:95-97,
  * 165-167; N = 32, P = d(loss)/d(pre-activation)) and ConvTranspose2d(64 -> C, 4, 2, 1) of the generator (:139-140; N = 64, img = the image
- * gradient, P = the layer's input).  Writes *nsplit_out = eg_wgrad_img_splits_n(ntapes * B, N) slabs [N][16 C] (the per-tap kernel's layout over
+ * gradient, P = the layer's input).  Writes *nsplit_out = eg_wgrad_img_splits(ntapes * B, N) slabs [N][16 C] (the per-tap kernel's layout over
  * patch rows: finish with eg_wgrad_reduce / _rank1 / _perm as after eg_im2col_img + eg_conv_wgrad, which this replaces). */
 int eg_wgrad_img_ok(int dtype, int C, int H, int W, int N, int k, int stride, int pad);
-int eg_wgrad_img_splits(int images);                 /* N = 32 / 64 */
-int eg_wgrad_img_splits_n(int images, int N);        /* ... and N = 128: the first Discriminator layer of the CelebA script (celebA/EAD-GAN_celebA.py:110) */
+int eg_wgrad_img_splits(int images, int N);          /* N = 32 / 64, and 128: the first Discriminator layer of the CelebA script (celebA/EAD-GAN_celebA.py:110) */
 int eg_wgrad_img(int dtype, const float* img0, const float* img1, const float* img2, int ntapes, const void* P, float* slab, int B, int C,
                  int H, int W, int N, int* nsplit_out, eg_stream_t s);
 /* ConvTranspose2d(128 -> C <= 3, 4, 2, 1) from 16-bit NHWC activations a [B][Hin][Win][128] to an fp32 NCHW image [B][C][2 Hin][2 Win] in ONE
@@ -252,11 +249,9 @@ int eg_wgrad_img(int dtype, const float* img0, const float* img1, const float* i
  * eg_pack_strided.  The Generator's last layer + Tanh (celebA.py:90-91) and the backward-to-image of the first Discriminator layer (:110).
  * Bit-identical to eg_conv_fwd (N = 16 C columns) + eg_col2im_img. */
 int eg_convt_img_mfma_ok(int dtype, int C, int Hin, int Win, int K, int k, int stride, int pad);
-/* ... with K = 64 or 128 input channels (a [B][Hin][Win][K], wp [16 * C][K]): the dSprites generators' last layer ConvTranspose2d(64 -> C, 4, 2, 1) +
+/* K = 64 or 128 input channels (a [B][Hin][Win][K], wp [16 * C][K]): 64 is the dSprites generators' last layer ConvTranspose2d(64 -> C, 4, 2, 1) +
  * Sigmoid (dSprites/rp.py:139-141) */
-int eg_convt_img_mfma_k(int dtype, const void* a, const void* wp, const float* bias, float* out, int B, int C, int Hin, int Win, int K, int act,
-                        float slope, eg_stream_t s);
-int eg_convt_img_mfma(int dtype, const void* a, const void* wp, const float* bias, float* out, int B, int C, int Hin, int Win, int act,
+int eg_convt_img_mfma(int dtype, const void* a, const void* wp, const float* bias, float* out, int B, int C, int Hin, int Win, int K, int act,
                       float slope, eg_stream_t s);
 int eg_cast_pad(int dtype, const float* src, void* dst, int rows, int n, int npad, eg_stream_t s);
 /* col2im of a transposed convolution with C = 1 or 3 output channels (ConvTranspose2d(128 -> 3, 4, 2, 1): celebA/EAD-GAN_celebA.py:90-91; the
@@ -266,13 +261,10 @@ int eg_cast_pad(int dtype, const float* src, void* dst, int rows, int n, int npa
  * out: fp32 NCHW [B][C][(Hin-1)*stride - 2*pad + k][(Win-1)*stride - 2*pad + k]; bias may be NULL. */
 int eg_col2im_img(int dtype, const void* cols, int B, int C, int Hin, int Win, int k, int stride, int pad, const float* bias, int act,
                   float slope, float* out, eg_stream_t s);
-/* out = g * act'(a) over an NCHW fp32 tensor and gb[c] += sum_{b,hw} out  (partial: B*C floats) */
+/* out = g * act'(a) over an NCHW fp32 tensor and gb[c] (+)= sum_{b,hw} out  (partial: B*C floats) */
 int eg_act_grad_mul_bias_nchw(const float* g, const float* a, float* out, int B, int C, int HW, int act, float slope,
-                              float* partial, float* gb, eg_stream_t s);
+                              float* partial, float* gb, int accumulate, eg_stream_t s);
 int eg_flat_reduce(const float* slab, int nslab, size_t total, float* grad, int accumulate, eg_stream_t s);
-int eg_flat_reduce_sn(const float* slab, int nslab, int rows, int Kdim, const float* w_orig, const float* sigma,
-                      const float* u, const float* v, float* gtmp, float* partials, float* grad, eg_stream_t s);
-int eg_bias_grad_nchw(const float* x, int B, int C, int HW, float* gb, eg_stream_t s);
 
 /* --- small-N dense heads (celebA/EAD-GAN_celebA.py:122; MNIST/EAD-GAN_rpqmnxy.py:124,161-163; dSprites/rp.py:109-110,180-183)
  * y[b][n] = sum_k x[b][k] Wp[n][k] + bias[n];  x dtype T [B][K]; Wp dtype T [N][Kpad] (eg_pack_fwd order);  y fp32
@@ -308,7 +300,7 @@ int eg_dense_small_bwd(int dtype, const float* dy, const void* wp, const void* m
                        eg_stream_t s);
 int eg_dense_small_wgrad(int dtype, const float* dy, const void* x, float* gw, float* gb, int B, int K, int N,
                          int Cin, int taps, eg_stream_t s);
-int eg_dense_small_bgrad(const float* dy, float* gb, int B, int N, eg_stream_t s);   /* gb[n] += sum_b dy[b][n] */
+int eg_dense_small_bgrad(const float* dy, float* gb, int B, int N, int accumulate, eg_stream_t s);   /* gb[n] (+)= sum_b dy[b][n] */
 
 /* --- BatchNorm2d, training mode (celebA/EAD-GAN_celebA.py:79,83,87; MNIST/EAD-GAN_rpqmnxy.py:80,83,87,145) ----
  * x,y: [M][C] dtype T; updates running stats (momentum, unbiased var) and num_batches_tracked; fused activation */
@@ -324,15 +316,15 @@ int eg_bn_fwd_train_fused(int dtype, const void* x, void* y, int M, int C, const
                           long long* num_batches_tracked, float* save_mean, float* save_invstd, float* ws, int act, float slope,
                           eg_stream_t s);
 /* backward with the two sums taken from the epilogue of the convolution that produced dy (EG_STAT_BN_BWD: dy already carries the
- * activation gradient): dz = gamma * invstd * (dy - sum(dy)/M - xhat * sum(dy*xhat)/M); dgamma / dbeta accumulate.  ws: 5*C floats. */
+ * activation gradient): dz = gamma * invstd * (dy - sum(dy)/M - xhat * sum(dy*xhat)/M); dgamma / dbeta (+)= their sums.  ws: 5*C floats. */
 int eg_bn_bwd_fused(int dtype, const void* z, const void* dy, void* dz, int M, int C, const float* stat, int nrb,
                     const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta,
-                    float* sums, float* ws, eg_stream_t s);
+                    float* sums, float* ws, int accumulate, eg_stream_t s);
 /* synchronised BatchNorm for data parallel runs (statistics over the global batch: N ranks x B/N images == 1 rank x B images).
  * Forward: eg_bn_stats_local writes this rank's (count, mean, M2) per channel to stats[3*C]; the host gathers every rank's block
  * (stats_all[nranks][3*C]); eg_bn_fwd_from_stats combines them (Chan, fp64), updates the running statistics with the GLOBAL
  * batch (M_global rows) and normalises the local rows.  Backward: eg_bn_bwd_sums_local writes the local sum(dy), sum(dy*xhat)
- * to sums[2*C] and adds them to dbeta / dgamma (parameter gradients stay local; the gradient all-reduce averages them); the host
+ * to sums[2*C] and dbeta / dgamma (+)= them (parameter gradients stay local; the gradient all-reduce averages them); the host
  * all-reduces sums; eg_bn_bwd_from_sums produces dz of the local rows.  ws: eg_bn_ws_floats(M, C) floats. */
 int eg_bn_stats_local(int dtype, const void* x, int M, int C, float* ws, float* stats, eg_stream_t s);
 int eg_bn_fwd_from_stats(int dtype, const void* x, void* y, int M_local, int C, const float* stats_all, int nranks, int M_global,
@@ -341,7 +333,7 @@ int eg_bn_fwd_from_stats(int dtype, const void* x, void* y, int M_local, int C, 
                          eg_stream_t s);
 int eg_bn_bwd_sums_local(int dtype, const void* z, const void* da, int M, int C, const float* gamma, const float* beta,
                          const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta,
-                         float* sums, float* ws, eg_stream_t s);
+                         float* sums, float* ws, int accumulate, eg_stream_t s);
 int eg_bn_bwd_from_sums(int dtype, const void* z, const void* da, void* dz, int M_local, int C, const float* sums_global, int M_global,
                         const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, int act, float slope,
                         float* ws, eg_stream_t s);
@@ -349,47 +341,15 @@ int eg_bn_bwd_from_sums(int dtype, const void* z, const void* da, void* dz, int 
  * sqrt(running_var + eps) * gamma + beta); nothing is updated; ws: 2*C floats */
 int eg_bn_fwd_eval(int dtype, const void* x, void* y, int M, int C, const float* gamma, const float* beta, float eps,
                    const float* running_mean, const float* running_var, float* ws, int act, float slope, eg_stream_t s);
-/* dz from da (gradient w.r.t. the activation output); dgamma/dbeta accumulate; sums: 2*C floats scratch */
+/* dz from da (gradient w.r.t. the activation output); dgamma / dbeta (+)= their sums; sums: 2*C floats scratch */
 int eg_bn_bwd(int dtype, const void* z, const void* da, void* dz, int M, int C, const float* gamma, const float* beta,
               const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta,
-              float* sums, float* ws, eg_stream_t s);
+              float* sums, float* ws, int accumulate, eg_stream_t s);
 /* as eg_bn_bwd, then dz *= act'(z as an activation OUTPUT) / post_sigma  -- for blocks ordered conv -> LeakyReLU -> BN
  * (MNIST/EAD-GAN_rpqmnxy.py:143-146): the BN input IS the LeakyReLU output, so its backward mask is fused here */
 int eg_bn_bwd_post(int dtype, const void* z, const void* da, void* dz, int M, int C, const float* gamma, const float* beta,
                    const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta, float* sums, float* ws,
                    int post_act, float post_slope, const float* post_sigma, eg_stream_t s);
-
-/* --- gradient writers with a store mode --------------------------------------------------------------------
- * Every entry point above that writes a parameter gradient adds to it (autograd's .grad contract).  The `_store` forms take one more
- * argument in front of the stream: accumulate != 0 is the entry point without the suffix, accumulate == 0 STORES the value that would
- * have been added (same kernel, same summation order: the result is the one of accumulating into a cleared slot, up to the sign of a
- * zero) and never reads the slot.  A trainer whose backward pass has exactly one writer per gradient slot needs neither the
- * zero-fill of the gradient arena nor the read of the zeros (celeba.CelebATrainer; eg_wgrad_reduce has had the argument all along). */
-int eg_wgrad_reduce_perm_store(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad,
-                               int row_div, int row_mul, int c_row, int accumulate, eg_stream_t s);
-int eg_wgrad_reduce_rank1_store(const float* slab, int nsplit, int n_slab, int n_rows, int C, int T, float* grad,
-                                int ntapes, const float* coef, const float* u, const float* v, int c_row, int accumulate, eg_stream_t s);
-int eg_wgrad_reduce_sn_store(const eg_conv* c, const float* slab, int nsplit, const float* w_orig,
-                             const float* sigma, const float* u, const float* v, float* gtmp, float* partials,
-                             float* grad, int accumulate, eg_stream_t s);
-int eg_bias_grad_store(int dtype, const void* dY, int rows, int N, int bias_mod, float* partials, float* gb,
-                       int accumulate, eg_stream_t s);
-int eg_bias_grad_sn_store(int dtype, const void* dzs, const void* a, const float* bias, int rows, int N, int rows_per_tape,
-                          const float* sigma, float slope, float* ws, float* gb, float* coef, int accumulate, eg_stream_t s);
-int eg_bias_grad_sn_fused_store(const float* stat, int nrb, int N, int tiles_m, int tiles_per_tape, int ntapes, const float* sigma,
-                                float* gb, float* coef, int accumulate, eg_stream_t s);
-int eg_act_grad_mul_bias_nchw_store(const float* g, const float* a, float* out, int B, int C, int HW, int act, float slope,
-                                    float* partial, float* gb, int accumulate, eg_stream_t s);
-int eg_dense_small_bgrad_store(const float* dy, float* gb, int B, int N, int accumulate, eg_stream_t s);
-int eg_bn_bwd_store(int dtype, const void* z, const void* da, void* dz, int M, int C, const float* gamma, const float* beta,
-                    const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta,
-                    float* sums, float* ws, int accumulate, eg_stream_t s);
-int eg_bn_bwd_fused_store(int dtype, const void* z, const void* dy, void* dz, int M, int C, const float* stat, int nrb,
-                          const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, float* dgamma,
-                          float* dbeta, float* sums, float* ws, int accumulate, eg_stream_t s);
-int eg_bn_bwd_sums_local_store(int dtype, const void* z, const void* da, int M, int C, const float* gamma, const float* beta,
-                               const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta,
-                               float* sums, float* ws, int accumulate, eg_stream_t s);
 
 /* --- spectral norm power iteration (torch.nn.utils.spectral_norm, celebA/EAD-GAN_celebA.py:110-120) -------- */
 size_t eg_sn_ws_floats(int R, int Kd);
@@ -422,21 +382,18 @@ int eg_adam_step_zero(float* p, float* g, float* m, float* v, size_t n, float lr
  * eg_adam_pack_conv_ok() accepts (channel counts in multiples of 16 / 32, no K padding); either panel may be NULL. */
 int eg_adam_pack_conv_ok(const eg_conv* c, int dtype, int has_fwd, int has_bwd);
 int eg_adam_pack_conv(const eg_conv* c, int dtype, float* p, float* g, float* m, float* v, float lr, float b1, float b2, float eps,
-                      const int* step, int zero_grad, void* wp_fwd, void* wp_bwd, eg_stream_t s);
+                      const int* step, void* wp_fwd, void* wp_bwd, eg_stream_t s);
 /* the same for a weight whose panel is a row-permuted transpose of the master: master p[K][N] (N contiguous; the ConvTranspose2d on a
  * 1x1 input, celebA/EAD-GAN_celebA.py:76), panel wp[n'][Kpad], n' = (n % n_mod) * n_mul + n / n_mod, columns k < K (the padding keeps
  * the zeros eg_pack_strided wrote once) */
 int eg_adam_pack_rows(int dtype, float* p, float* g, float* m, float* v, void* wp, int K, int N, int Kpad, int n_mod, int n_mul,
-                      float lr, float b1, float b2, float eps, const int* step, int zero_grad, eg_stream_t s);
+                      float lr, float b1, float b2, float eps, const int* step, eg_stream_t s);
 int eg_adam_tick(int* step, eg_stream_t s);            /* step[0] += 1 (once per optimizer.step(), before its slice-wise updates) */
 int eg_fill_f32(float* p, size_t n, float val, eg_stream_t s);
 
-/* --- utility: generator input concat+cast, elementwise activation gradient, layout conversion -------------- */
+/* --- utility: generator input concat+cast ---------------------------------------------------------------- */
 int eg_concat_cast(int dtype, const float* a, int wa, const float* b, int wb, const float* c, int wc, int B,
                    int Cpad, void* out, eg_stream_t s);
-int eg_act_grad_mul_f32(const float* g, const float* a, float* out, size_t n, int act, float slope, eg_stream_t s);
-int eg_nchw_to_nhwc(int dtype, const float* x, void* y, int B, int C, int HW, int Cpad, eg_stream_t s);
-int eg_nhwc_to_nchw(int dtype, const void* x, float* y, int B, int C, int HW, int Cpad, eg_stream_t s);
 
 /* --- affine codes, warp and loss heads ---------------------------------------------------------------------
  * eg_theta_rpqxy : celebA/utils_rpqxy.py:59-80 (rows 0,1 of R*Z*T) ;  eg_warp_affine : transformation_2D,

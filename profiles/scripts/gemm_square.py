@@ -2,7 +2,6 @@
 each variant gets when prologue, epilogue and round quantisation are amortised (the microarchitecture guide's GEMM numbers are for 8192^3).
 usage: python profiles/scripts/gemm_square.py [--sizes 4096,8192] [--configs 4:1,2:1]"""
 import argparse
-import ctypes
 import importlib
 import os
 import statistics
@@ -22,7 +21,6 @@ def main():
     a = ap.parse_args()
     dt, dev = 1, "cuda"
     tdt = ops.torch_dtype(dt)
-    lib = eg._lib.lib()
     g = torch.Generator(device=dev).manual_seed(1)
     for n in [int(v) for v in a.sizes.split(",")]:
         c = ops.make_conv(n // 1024, 32, 32, n, n, 1, 1, 0)          # M = n rows
@@ -34,7 +32,7 @@ def main():
         flops = 2.0 * n * n * n
         cells = []
         for v, s in [tuple(int(t) for t in cfg.split(":")) for cfg in a.configs.split(",")]:
-            lab = lib.query("eg_igemm_nt_tile", ctypes.byref(c), dt, 0, v, s)
+            lab = ops.nt_tile_hinted(c, dt, 0, v, s)
             if lab < 0:
                 cells.append(f"v{v}: n/a")
                 continue

@@ -1,5 +1,5 @@
 """first trunk layer of the dSprites networks (Conv2d(C -> 32, 4, 2, 1) + LeakyReLU): eg_im2col_img + the K = 64 GEMM over patch rows against
-eg_conv_img_mfma_n, and whether a TrunkEngine dispatches to it.  usage: python profiles/scripts/img_conv_small_bench.py"""
+eg_conv_img_mfma with N < 128, and whether a TrunkEngine dispatches to it.  usage: python profiles/scripts/img_conv_small_bench.py"""
 import importlib
 import os
 import sys

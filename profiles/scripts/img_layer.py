@@ -1,7 +1,6 @@
 """The image-side layer as a 1x1 convolution over im2col patches (K = 48 padded to 64, N = 128; celebA/EAD-GAN_celebA.py:110 first D conv):
 forced NT variants back to back.  usage: python profiles/scripts/img_layer.py [--T 1,2,3]"""
 import argparse
-import ctypes
 import importlib
 import os
 import statistics
@@ -21,7 +20,6 @@ def main():
     a = ap.parse_args()
     dt, dev = 1, "cuda"
     tdt = ops.torch_dtype(dt)
-    lib = eg._lib.lib()
     g = torch.Generator(device=dev).manual_seed(1)
     cfgs = [tuple(int(v) for v in c.split(":")) for c in a.configs.split(",")]
     for T in [int(t) for t in a.T.split(",")]:
@@ -37,7 +35,7 @@ def main():
         ref = None
         cells = []
         for v, s in cfgs:
-            lab = lib.query("eg_igemm_nt_tile", ctypes.byref(c), dt, 0, v, s)
+            lab = ops.nt_tile_hinted(c, dt, 0, v, s)
             if lab < 0:
                 cells.append(f"v{v}: n/a")
                 continue

@@ -12,7 +12,6 @@ usage: python profiles/scripts/nt_layers.py [--shapes ABCDEF] [--T 1,2,3] [--con
        config v:s = nt_variant : nt_splitk   (0:0 = planner; 2 = 128x128, 4 waves; 4 = 256x128, 8 waves (igemm_nt8s); 5 = 4 + input patch)
 """
 import argparse
-import ctypes
 import importlib
 import os
 import statistics
@@ -45,7 +44,6 @@ def main():
     dev = "cuda"
     ws = torch.zeros(96 << 20, device=dev, dtype=torch.float32)        # 384 MiB of split-K scratch (zeroed: its tail holds arrival counters)
     cfgs = [tuple(int(v) for v in c.split(":")) for c in a.configs.split(",")]
-    lib = eg._lib.lib()
     g = torch.Generator(device=dev).manual_seed(1)
     print(f"{'shape':8s} " + " ".join(f"{'v%d:s%d' % c:>22s}" for c in cfgs))
     for name in a.shapes:
@@ -80,7 +78,7 @@ def main():
                     ops.conv_bwd_data(c, dt, x, wp, out, ops.epilogue(sigma=sig, sigma_rows=rows, mask=mask, mask_act=ops.ACT_LRELU,
                                                                       mask_slope=0.1, nt_variant=v, nt_splitk=s, splitk_ws=ws))
             flops = 2.0 * M * N * K * nph
-            labels = [lib.query("eg_igemm_nt_tile", ctypes.byref(c), dt, int(kind == "bwd"), v, s) for v, s in cfgs]
+            labels = [ops.nt_tile_hinted(c, dt, kind == "bwd", v, s) for v, s in cfgs]
             if a.check:
                 ref = torch.empty_like(y)
                 run(1, 1, ref)

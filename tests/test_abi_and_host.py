@@ -88,6 +88,25 @@ def test_no_environment_switches_in_library_or_package():
     assert len(owners["FUSE_DRAWS"]) + len(owners["FUSE_INPUTS"]) <= 1, owners      # one draws switch under one name
 
 
+def test_one_entry_point_per_operation():
+    """An operation that gains an argument keeps its name: no declared entry point is another one's name plus a suffix."""
+    names = set(_pkg()._lib.parse_header())
+    twins = [n + suffix for n in names for suffix in ("_store", "_target", "_n", "_k") if n + suffix in names]
+    assert not twins, sorted(twins)
+
+
+def test_every_declared_entry_point_is_bound_in_the_package():
+    """An entry point that no module of the package binds has no caller: the header declares what the package binds, nothing else.
+    A binding is the name as a quoted string (lib().call / lib().query) or as an attribute of the loaded library; a mention in a
+    comment or a docstring is none."""
+    import re
+    pkg = os.path.join(ROOT, "ead-gan_amd")
+    src = "\n".join(open(os.path.join(pkg, fn)).read() for fn in sorted(os.listdir(pkg)) if fn.endswith(".py"))
+    words = {m.group(2) or m.group(3) for m in re.finditer(r"""(["'])(eg_\w+)\1|\.(eg_\w+)\b""", src)}
+    unbound = [n for n in _pkg()._lib.parse_header() if n != "eg_version" and n not in words]
+    assert not unbound, sorted(unbound)
+
+
 DP_WORKER = r"""
 import importlib, os, sys, torch
 sys.path.insert(0, sys.argv[1])

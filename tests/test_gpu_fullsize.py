@@ -15,7 +15,6 @@ and fp32 accumulation against the fp32 oracle: losses 3e-2 relative; gradients 0
 four 16-bit discriminator layers and four generator layers) and 0.1 (discriminator / encoder) -- the 16-bit rounding itself, not the
 batch size or the kernel variant: B = 8 measures the same 0.15 / 0.05 as B = 128 (profiles/scripts/diag_fullsize_grad_error.py), and
 the CelebA configuration is therefore also run in fp32 at full size, where the same planner choices must meet the tight bound."""
-import ctypes
 import importlib
 
 import pytest
@@ -52,8 +51,7 @@ def arena_rel_err(mod, ref, skip=()):
 
 def nt_labels(convs, dtype):
     """planner labels (kernel code = label % 1000) of a list of (eg_conv, bwd) launches"""
-    lib = eg._lib.lib()
-    return {lib.query("eg_igemm_nt_tile", ctypes.byref(c), dtype, int(bwd), 0, 0) % 1000 for c, bwd in convs}
+    return {eg.ops.nt_tile_hinted(c, dtype, bwd) % 1000 for c, bwd in convs}
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "f32"])

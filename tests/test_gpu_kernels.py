@@ -260,7 +260,7 @@ def test_conv_wgrad_parity_class_kernel(case, dtype):
     ops.conv_wgrad(c, dtype, nhwc(x, dtype), nhwc(dy, dtype), slab2)
     torch.cuda.synchronize()
     assert torch.equal(slab, slab2)
-    # chip-share hint of the side lanes (eg_conv_wgrad_target): fewer, longer K splits, the same gradient
+    # chip-share hint of the side lanes (the wgs_target of eg_conv_wgrad): fewer, longer K splits, the same gradient
     slab3 = torch.full_like(slab, float("nan"))
     ns3 = ops.conv_wgrad(c, dtype, nhwc(x, dtype), nhwc(dy, dtype), slab3, 16)
     assert 1 <= ns3 <= ns
@@ -632,8 +632,7 @@ NT_VARIANTS = [(NT_BUF128, 128131), (NT_PERS, 128135), (NT_S8, 256147), (NT_S8P,
 
 
 def nt_tile(c, dtype, bwd, variant, splitk):
-    import ctypes
-    return eg._lib.lib().query("eg_igemm_nt_tile", ctypes.byref(c), dtype, bwd, variant, splitk)
+    return eg.ops.nt_tile_hinted(c, dtype, bwd, variant, splitk)
 
 
 def same(got, ref, variant, dtype, K):
