@@ -61,7 +61,7 @@ class EgHead(ctypes.Structure):
                 ("mask_slope", ctypes.c_float)]
 
 
-_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t,
             "long long": ctypes.c_longlong, "unsigned long long": ctypes.c_ulonglong, "unsigned int": ctypes.c_uint,
             "eg_stream_t": ctypes.c_void_p}
 

@@ -788,6 +788,27 @@ def score_fvae_votes(x, L, M, ncol, eval_std, labels, nlab, predict, votes):
     lib().call("eg_score_fvae_votes", _p(x), L, M, ncol, _p(eval_std), _p(labels), nlab, _p(predict), _p(votes), _stream())
 
 
+def score_pair_absdiff_mean(x, L, M, ncol, feat):
+    lib().call("eg_score_pair_absdiff_mean", _p(x), L, M, ncol, _p(feat), _stream())
+
+
+# info[3] of eg_score_logreg_fit
+LOGREG_STATUS = {0: "converged", 1: "max_iter reached", 2: "line search failed", 3: "Hessian not positive definite",
+                 4: "a label outside 0..K-1", 5: "non-finite gradient"}
+
+
+def score_logreg_ws_bytes(n, K):
+    return lib().query("eg_score_logreg_ws_bytes", n, K)
+
+
+def score_logreg_fit(X, y, n, d, K, inv_C, max_iter, gtol, ws, W, info):
+    lib().call("eg_score_logreg_fit", _p(X), _p(y), n, d, K, inv_C, max_iter, gtol, _p(ws), _p(W), _p(info), _stream())
+
+
+def score_logreg_accuracy(X, y, n, d, K, W, predict, correct):
+    lib().call("eg_score_logreg_accuracy", _p(X), _p(y), n, d, K, _p(W), _p(predict), _p(correct), _stream())
+
+
 # ---- device loss log of a training run (engine.LossLog) ----------------------------------------------
 def runlog_append(losses, n, ring, capacity, head, first_nonfinite):
     """row head % capacity of ring[capacity][n] <- losses[:n]; head += 1; the first non-finite iteration (1-based) latched"""

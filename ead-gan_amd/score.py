@@ -1,5 +1,5 @@
-"""Disentanglement scores of a trained dSprites / colored-dSprites encoder pair on the MI355X: MIG and FactorVAE
-(dSprites/score/MIG.py, FactorVAE.py; colored_dSprites/score/MIG.py, FactorVAE.py).
+"""Disentanglement scores of a trained dSprites / colored-dSprites encoder pair on the MI355X: MIG, FactorVAE and BetaVAE
+(dSprites/score/MIG.py, FactorVAE.py, BetVAE.py; colored_dSprites/score/MIG.py, FactorVAE.py, BetVAE.py).
 
 The reference pushes every sampled image through Encoder_pxy -> inverse translation -> grid_sample(padding_mode='zeros') [-> divide by
 the colour gains] -> Encoder (eval) on the CPU and scores the rows [argmax(cat), cont0, cont1, pxy1, pxy2] with numpy / sklearn.  Here the
@@ -50,11 +50,9 @@ def latents_bases(latents_sizes):
     return np.concatenate((s[::-1].cumprod()[::-1][1:], np.array([1, ])))
 
 
-def factor_vae_plan(latents_sizes, N, colored=False, rng=None, L=100, M=500):
-    """load_data's plan (FactorVAE.py:36-97): group i fixes latent i % 5 + 1 (one randint per latent for L samples, then the fixed latent
-    redrawn once), then the eval set ``permutation(N)[:N/10]``; colored, evaluate() then draws the eval set's gains and each group's, in
-    group order.  -> {"group_idx" int64 [M,L], "labels" int64 [M], "eval_idx" int64 [N/10] (+ "eval_gains", "group_gains" float64)}"""
-    r = _rs(rng)
+def _group_draws(r, latents_sizes, L, M):
+    """The group loop load_data runs in FactorVAE.py:36-69 and BetVAE.py:27-69 (the same code): group i fixes latent i % 5 + 1 (one randint
+    per latent for L samples, then the fixed latent redrawn once).  -> (group_idx int64 [M,L], labels int64 [M])"""
     sizes = np.asarray(latents_sizes)
     bases = latents_bases(sizes)
     group_idx = np.empty((M, L), dtype=np.int64)
@@ -67,11 +65,38 @@ def factor_vae_plan(latents_sizes, N, colored=False, rng=None, L=100, M=500):
         samples[:, fixed] = r.randint(sizes[fixed], size=1)
         group_idx[i] = np.dot(samples, bases).astype(int)
         labels[i] = fixed - 1
+    return group_idx, labels
+
+
+def _group_gains(r, L, M):
+    """evaluate()'s add_color_2_img draw of each group, in group order -> float64 [M,L,3]"""
+    return np.stack([r.uniform(0.5, 1, [L, 3, 1, 1]).reshape(L, 3) for _ in range(M)])
+
+
+def factor_vae_plan(latents_sizes, N, colored=False, rng=None, L=100, M=500):
+    """load_data's plan (FactorVAE.py:36-97): the group draws, then the eval set ``permutation(N)[:N/10]``; colored, evaluate() then draws
+    the eval set's gains and each group's, in group order.
+    -> {"group_idx" int64 [M,L], "labels" int64 [M], "eval_idx" int64 [N/10] (+ "eval_gains", "group_gains" float64)}"""
+    r = _rs(rng)
+    group_idx, labels = _group_draws(r, latents_sizes, L, M)
     eval_idx = r.permutation(range(N))[0:int(N / 10)]
     plan = {"group_idx": group_idx, "labels": labels, "eval_idx": eval_idx}
     if colored:
         plan["eval_gains"] = r.uniform(0.5, 1, [eval_idx.size, 3, 1, 1]).reshape(-1, 3)
-        plan["group_gains"] = np.stack([r.uniform(0.5, 1, [L, 3, 1, 1]).reshape(L, 3) for _ in range(M)])
+        plan["group_gains"] = _group_gains(r, L, M)
+    return plan
+
+
+def beta_vae_plan(latents_sizes, N, colored=False, rng=None, L=100, M=500):
+    """load_data's plan (BetVAE.py:27-82): FactorVAE's group draws, then the ``permutation(N)`` the script draws and never uses (consumed
+    here so that the stream stands where the script's does); colored, evaluate() then draws each group's gains in group order -- no eval
+    set comes before them, so they are not factor_vae_plan's.  -> {"group_idx" int64 [M,L], "labels" int64 [M] (+ "group_gains" [M,L,3])}"""
+    r = _rs(rng)
+    group_idx, labels = _group_draws(r, latents_sizes, L, M)
+    r.permutation(range(N))
+    plan = {"group_idx": group_idx, "labels": labels}
+    if colored:
+        plan["group_gains"] = _group_gains(r, L, M)
     return plan
 
 
@@ -229,6 +254,62 @@ def factor_vae(eval_codes, group_codes, labels, num_labels):
             "factorVAE_metric_detail": train_data}
 
 
+def logreg_fit(X, y, K, C=1.0, max_iter=50, gtol=1e-10):
+    """The optimum of sklearn's multinomial LogisticRegression(C) on device X [n,d] float64 and class ids y [n] in 0..K-1 (host or device),
+    by eg_score_logreg_fit's float64 Newton iteration, and its training predictions.  ``gtol`` bounds the gradient's inf-norm of the
+    summed objective.  -> (W f64 [K,d+1] (coefficients | intercept), predict int32 [n], correct int64 [1]) on the device, info (host
+    float64: iterations, final |g|inf, objective, status).  Raises RuntimeError when the solver did not reach gtol."""
+    _require_cuda(X)
+    X = X.to(torch.float64).contiguous()
+    n, d = X.shape
+    dev = X.device
+    y_d = (y if torch.is_tensor(y) else torch.from_numpy(np.asarray(y).reshape(-1))).to(device=dev, dtype=torch.int32).contiguous()
+    if y_d.numel() != n:
+        raise ValueError(f"{y_d.numel()} labels for {n} rows")
+    ws = torch.empty(max(ops.score_logreg_ws_bytes(n, K), 8), device=dev, dtype=torch.uint8)
+    W = torch.empty(K, d + 1, device=dev, dtype=torch.float64)
+    info = torch.empty(4, device=dev, dtype=torch.float64)
+    ops.score_logreg_fit(X, y_d, n, d, K, 1.0 / C, max_iter, gtol, ws, W, info)
+    predict = torch.empty(n, device=dev, dtype=torch.int32)
+    correct = torch.empty(1, device=dev, dtype=torch.int64)
+    ops.score_logreg_accuracy(X, y_d, n, d, K, W, predict, correct)
+    info_h = info.cpu().numpy()                                                    # the one sync: offline evaluation
+    if info_h[3] != 0:
+        raise RuntimeError(f"logistic fit did not reach |g|inf <= {gtol:g}: {int(info_h[0])} iterations, |g|inf = {info_h[1]:.3e} "
+                           f"(status {int(info_h[3])}: {ops.LOGREG_STATUS.get(int(info_h[3]), '?')})")
+    return W, predict, correct, info_h
+
+
+def beta_vae_fit(group_codes, labels, C=1.0, max_iter=50, gtol=1e-10):
+    """Device part of BetaVAEMetric.evaluate (BetVAE.py:256-268): features[g] = np.mean(np.abs(x_g[0::2] - x_g[1::2]), axis=0) bit for
+    bit, then ``logreg_fit`` on (features, labels) and its training predictions.  group_codes [M*L,5] or [M,L,5]; labels become class
+    ids with np.unique(return_inverse=True).
+    -> {"features" f64 [M,5], "W" f64 [K,6], "predict" int32 [M] class ids, "correct" int64 [1]} on the device, "classes", "info" (host)"""
+    labels = np.asarray(labels).reshape(-1)
+    M = labels.size
+    classes, y = np.unique(labels, return_inverse=True)
+    K = classes.size
+    if K < 3:
+        raise ValueError(f"the BetaVAE score fits a multinomial model: {K} distinct labels, at least 3 needed")
+    if group_codes.numel() % (M * NUM_CODES):
+        raise ValueError(f"{group_codes.numel()} code values do not make {M} groups of rows of {NUM_CODES}")
+    L = group_codes.numel() // (M * NUM_CODES)
+    if L % 2:
+        raise ValueError(f"the BetaVAE score pairs each group's rows: L = {L} is odd")
+    _require_cuda(group_codes)
+    gc = group_codes.to(torch.float64).contiguous().reshape(M, L, NUM_CODES)
+    feat = torch.empty(M, NUM_CODES, device=gc.device, dtype=torch.float64)
+    ops.score_pair_absdiff_mean(gc, L, M, NUM_CODES, feat)
+    W, predict, correct, info = logreg_fit(feat, y.reshape(-1), K, C, max_iter, gtol)
+    return {"features": feat, "W": W, "predict": predict, "correct": correct, "classes": classes, "info": info}
+
+
+def beta_vae(group_codes, labels, C=1.0):
+    """-> the reference's dict {"betaVAE_metric": acc}: classifier.score(features, labels) of BetVAE.py:265-272."""
+    fit = beta_vae_fit(group_codes, labels, C)
+    return {"betaVAE_metric": int(fit["correct"].item()) / fit["predict"].numel()}
+
+
 # ================================================================================================
 # drop-in for the scripts' module-level code
 # ================================================================================================
@@ -242,13 +323,13 @@ def load_encoders(kind, encoder_pxy_path, encoder_path, device="cuda", dtype="f3
 
 
 def run_score(kind, metric, npz_path, encoder_pxy_path, encoder_path, seed=None, batch=4096, groups=None, device="cuda"):
-    """What dSprites|colored_dSprites/score/{MIG,FactorVAE}.py do at module level, on the MI355X.  ``seed``: np.random.seed first (else the
-    global numpy stream as it stands).  ``groups``: score only the first groups of the 500-group FactorVAE plan (the plan is drawn in full).
-    Prints the score; returns it (MIG) or the reference's three-key dict (FactorVAE)."""
+    """What dSprites|colored_dSprites/score/{MIG,FactorVAE,BetVAE}.py do at module level, on the MI355X.  ``seed``: np.random.seed first (else
+    the global numpy stream as it stands).  ``groups``: score only the first groups of the 500-group FactorVAE / BetaVAE plan (the plan is
+    drawn in full).  Prints the score; returns it (MIG), the reference's three-key dict (FactorVAE) or its one-key dict (BetaVAE)."""
     if kind not in KINDS:
         raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
-    if metric not in ("mig", "factor_vae"):
-        raise ValueError(f"metric must be 'mig' or 'factor_vae', got {metric!r}")
+    if metric not in ("mig", "factor_vae", "beta_vae"):
+        raise ValueError(f"metric must be 'mig', 'factor_vae' or 'beta_vae', got {metric!r}")
     colored = kind == "colored"
     dataset_zip = np.load(npz_path, encoding="latin1", allow_pickle=True)
     imgs = dataset_zip["imgs"]
@@ -266,6 +347,14 @@ def run_score(kind, metric, npz_path, encoder_pxy_path, encoder_path, seed=None,
         print("MIG score", score)
         return score
     metadata = dataset_zip["metadata"][()]
+    if metric == "beta_vae":
+        plan = beta_vae_plan(metadata["latents_sizes"], N, colored)
+        M = plan["labels"].size if groups is None else int(groups)
+        data = torch.from_numpy(np.ascontiguousarray(imgs)).to(device)
+        gc = rep.codes(data, plan["group_idx"][:M].reshape(-1), plan["group_gains"][:M].reshape(-1, 3) if colored else None)
+        res = beta_vae(gc, plan["labels"][:M])
+        print("acc", res["betaVAE_metric"])
+        return res
     plan = factor_vae_plan(metadata["latents_sizes"], N, colored)
     M = plan["labels"].size if groups is None else int(groups)
     data = torch.from_numpy(np.ascontiguousarray(imgs)).to(device)

@@ -546,7 +546,7 @@ int eg_onehot(const long long* labels, float* out, int B, int n, eg_stream_t s);
 int eg_resample_u8(const unsigned char* src, unsigned char* dst, int planes, int in_h, int in_w, int axis, const int* bounds,
                    const int* kk, int ksize, int o0, int on, int c0, int cn, eg_stream_t s);
 
-/* Disentanglement scores of a trained encoder pair (dSprites/score/MIG.py, FactorVAE.py; colored_dSprites/score/MIG.py, FactorVAE.py).
+/* Disentanglement scores of a trained encoder pair (dSprites/score/MIG.py, FactorVAE.py, BetVAE.py; colored_dSprites/score/ likewise).
  * Staging: out[b][c] = data[idx[b]] * gain[b][c] (uint8 [N][HW] sprites, gain [B][C] fp32 or NULL = 1) -> fp32 NCHW; the reference's
  * imgs[select_index] + add_color_2_img (colored MIG.py:169-184,204; FactorVAE.py:236-254,270,315). */
 int eg_score_stage_u8(const unsigned char* data, const int* idx, const float* gain, float* out, int B, int C, int HW, eg_stream_t s);
@@ -567,6 +567,23 @@ int eg_score_col_std(const double* x, int n, int ncol, double* out, eg_stream_t 
  * np.std(x_g / eval_std, axis=0) (numpy's rule: first NaN, else first minimum); votes [ncol][nlab] int64 (zeroed here) [predict][labels[g]] += 1 */
 int eg_score_fvae_votes(const double* x, int L, int M, int ncol, const double* eval_std, const int* labels, int nlab, int* predict,
                         long long* votes, eg_stream_t s);
+/* BetaVAEMetric.evaluate's features (BetVAE.py:256-257): for group g (rows g*L.. of x [M*L][ncol] float64)
+ * feat[g] = np.mean(np.abs(x_g[0::2] - x_g[1::2]), axis=0), bit for bit (numpy's row-sequential axis-0 reduction).  L must be even. */
+int eg_score_pair_absdiff_mean(const double* x, int L, int M, int ncol, double* feat, eg_stream_t s);
+/* classifier.fit of BetVAE.py:265-266: the optimum of sklearn's multinomial LogisticRegression(C = 1 / inv_C) on X [n][d] float64 with
+ * class ids y [n] int32 in 0..K-1, the minimiser of  sum_i CE(softmax(W [x_i, 1]), y_i) + inv_C / 2 * |coefficients|^2  (intercepts
+ * unpenalised, zero-sum), by a float64 damped Newton iteration from W = 0 in one workgroup (Hessian + v v^T on the intercept block,
+ * Cholesky in LDS, Armijo backtracking); every row sum has a fixed order, two runs give the same bits.  3 <= K <= 8, K (d + 1) <= 64,
+ * inv_C > 0.  Stops when the gradient's inf-norm is <= gtol or after max_iter steps.  W [K][d+1] (coefficients | intercept);
+ * info [4] float64 = (iterations, final |g|inf, objective, status: 0 converged, 1 max_iter reached, 2 line search failed, 3 Hessian not
+ * positive definite, 4 a label outside 0..K-1 (W = 0, nothing computed), 5 non-finite gradient).  ws: eg_score_logreg_ws_bytes bytes. */
+size_t eg_score_logreg_ws_bytes(int n, int K);
+int eg_score_logreg_fit(const double* X, const int* y, int n, int d, int K, double inv_C, int max_iter, double gtol, void* ws, double* W,
+                        double* info, eg_stream_t s);
+/* classifier.score's two parts (BetVAE.py:268): predict[i] = np.argmax of the logits W [x_i, 1] (first index on ties),
+ * correct[0] = #{i: predict[i] == y[i]} (int64, zeroed here) */
+int eg_score_logreg_accuracy(const double* X, const int* y, int n, int d, int K, const double* W, int* predict, long long* correct,
+                             eg_stream_t s);
 
 /* --- device loss log of a training run: replaces the `.item()` calls of the reference's progress lines --
  * celebA/EAD-GAN_celebA.py:404-408, MNIST/EAD-GAN_rpqmnxy.py:453-457, dSprites/rp.py:491-496, colored_dSprites/rp_color.py:523-528,
