@@ -596,3 +596,214 @@ extern "C" int eg_score_logreg_accuracy(const double* X, const int* y, int n, in
     EG_LAUNCH_CHECK();
     return 0;
 }
+
+// ---- SAP ----------------------------------------------------------------------------------------------------------------------------
+// All float64.  Every row sum below has one order: thread t adds rows t, t + SVC_THREADS, ... ascending, a 64-lane butterfly combines
+// the lanes of a wave, and the four wave sums are added as (w0 + w1) + (w2 + w3).  No float atomics and no hand-off between workgroups:
+// two runs give the same bits.
+#define SVC_THREADS 256
+#define SVC_KMAX 64
+
+// sums of NV per-thread values over the workgroup; every thread receives the same totals.  red: [4 * NV] doubles of LDS.
+template <int NV>
+__device__ __forceinline__ void score_block_sum(double (&a)[NV], double* red) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j)
+        for (int o = 32; o > 0; o >>= 1) a[j] += __shfl_xor(a[j], o);
+    __syncthreads();                           // the previous call's readers are done with red
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) red[w * NV + j] = a[j];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NV; ++j) a[j] = (red[j] + red[NV + j]) + (red[2 * NV + j] + red[3 * NV + j]);
+}
+
+// R[i][j] = cov(i, j)^2 / var(i) / var(j) of code column i and factor column j as np.cov(x, y, ddof=1) gives them (SAP.py:295-300): the
+// means first, then the centred sums times 1 / (n - 1).  One workgroup per (i, j).  A zero variance divides 0 by 0: NaN, as in numpy.
+__global__ void __launch_bounds__(SVC_THREADS) score_sq_corr_kernel(const double* __restrict__ codes, int k, const double* __restrict__ fv,
+                                                                    int nf, int n, double* __restrict__ R) {
+    __shared__ double red[4 * 3];
+    const int i = blockIdx.x / nf, j = blockIdx.x - i * nf;
+    const double* x = codes + i;
+    const double* y = fv + j;
+    double s[2] = {0.0, 0.0};
+    for (int r = threadIdx.x; r < n; r += SVC_THREADS) s[0] += x[(size_t)r * k], s[1] += y[(size_t)r * nf];
+    score_block_sum<2>(s, red);
+    const double mx = s[0] / (double)n, my = s[1] / (double)n;
+    double c[3] = {0.0, 0.0, 0.0};
+    for (int r = threadIdx.x; r < n; r += SVC_THREADS) {
+        const double dx = x[(size_t)r * k] - mx, dy = y[(size_t)r * nf] - my;
+        c[0] += dx * dx, c[1] += dy * dy, c[2] += dx * dy;
+    }
+    score_block_sum<3>(c, red);
+    if (threadIdx.x == 0) {
+        const double f = 1.0 / (double)(n - 1);
+        const double vx = c[0] * f, vy = c[1] * f, cxy = c[2] * f;
+        R[blockIdx.x] = cxy * cxy / vx / vy;
+    }
+}
+
+extern "C" int eg_score_sq_corr(const double* codes, int n, int k, const double* fv, int nf, double* R, eg_stream_t s) {
+    EG_REQUIRE(codes && fv && R && k > 0 && nf > 0, "eg_score_sq_corr: bad argument");
+    EG_REQUIRE(n >= 2, "eg_score_sq_corr: n = %d rows, the covariance with ddof = 1 needs at least 2", n);
+    hipLaunchKernelGGL(score_sq_corr_kernel, dim3(k * nf), dim3(SVC_THREADS), 0, (hipStream_t)s, codes, k, fv, nf, n, R);
+    EG_LAUNCH_CHECK();
+    return 0;
+}
+
+// One-feature LinearSVC(C, class_weight="balanced") with sklearn's defaults (SAP.py:303-304): L2 penalty, squared hinge, one-vs-rest,
+// the intercept a regularised weight on a constant feature 1.  For class k, s_i = +1 where y_i = k and -1 elsewhere,
+//   f(w, b) = (w^2 + b^2) / 2 + sum_i c_i max(0, 1 - s_i (w x_i + b))^2,   c_i = C n / (K count_k) where y_i = k, C elsewhere
+// (liblinear weights only the positive side of a one-vs-rest problem).  f is strictly convex: one optimum, whatever liblinear's
+// randomised dual coordinate descent stops at.  Generalised Newton from (0, 0): one pass over the rows gives f, the gradient and the
+// 2 x 2 generalised Hessian I + 2 sum_{active} c_i [x_i, 1][x_i, 1]^T, which is solved in closed form; Armijo backtracking with
+// eg_score_logreg_fit's constants.  The sums at an accepted trial point are the next iteration's.
+struct SvcPoint {
+    double f, gw, gb, hww, hwb, hbb;
+};
+
+__device__ SvcPoint svc1_eval(const double* __restrict__ x, int P, const int* __restrict__ y, int n, int k, double cpos, double C, double w,
+                              double b, double* red) {
+    double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < n; i += SVC_THREADS) {
+        const double xi = x[(size_t)i * P];
+        const bool pos = y[i] == k;
+        const double sg = pos ? 1.0 : -1.0, c = pos ? cpos : C;
+        const double m = 1.0 - sg * (w * xi + b);
+        if (!(m <= 0.0)) {                     // active; a NaN margin enters the sums and surfaces as status 5
+            const double cm = c * m, t = sg * cm, cx = c * xi;
+            a[0] += cm * m;
+            a[1] += t * xi;
+            a[2] += t;
+            a[3] += cx * xi;
+            a[4] += cx;
+            a[5] += c;
+        }
+    }
+    score_block_sum<6>(a, red);
+    SvcPoint p;
+    p.f = 0.5 * (w * w + b * b) + a[0];
+    p.gw = w - 2.0 * a[1];
+    p.gb = b - 2.0 * a[2];
+    p.hww = 1.0 + 2.0 * a[3];
+    p.hwb = 2.0 * a[4];
+    p.hbb = 1.0 + 2.0 * a[5];
+    return p;
+}
+
+// workgroup blockIdx.x = column p * K + class k
+__global__ void __launch_bounds__(SVC_THREADS) score_svc1_fit_kernel(const double* __restrict__ X, const int* __restrict__ y, int n, int P,
+                                                                     int K, double C, int max_iter, double gtol, double* __restrict__ Wout,
+                                                                     double* __restrict__ info) {
+    __shared__ double red[4 * 6];
+    __shared__ int cnt[SVC_KMAX];
+    const int tid = threadIdx.x;
+    const int p = blockIdx.x / K, k = blockIdx.x - p * K;
+    double* wo = Wout + (size_t)blockIdx.x * 2;
+    double* io = info + (size_t)blockIdx.x * 4;
+    if (tid < SVC_KMAX) cnt[tid] = 0;
+    __syncthreads();
+    int bad = 0;
+    for (int i = tid; i < n; i += SVC_THREADS) {
+        const int yi = y[i];
+        if (yi < 0 || yi >= K) bad = 1;
+        else atomicAdd(&cnt[yi], 1);           // integer counts: order free
+    }
+    bad = __syncthreads_or(bad);
+    for (int j = 0; j < K; ++j) bad |= cnt[j] == 0 ? 1 : 0;
+    if (bad) {                                 // a label outside 0..K-1 or a class without a sample: nothing is fitted
+        if (tid == 0) wo[0] = 0.0, wo[1] = 0.0, io[0] = 0.0, io[1] = INFINITY, io[2] = INFINITY, io[3] = 4.0;
+        return;
+    }
+    const double cpos = C * ((double)n / (double)((long long)K * cnt[k]));     // sklearn's balanced weight n / (K count_k), times C
+    const double* x = X + p;
+    double w = 0.0, b = 0.0;
+    SvcPoint cur = svc1_eval(x, P, y, n, k, cpos, C, w, b, red);
+    double gmax = INFINITY;
+    int it = 0, status = 1;
+    for (;;) {
+        gmax = fmax(fabs(cur.gw), fabs(cur.gb));
+        if (!(gmax > gtol)) {
+            status = gmax <= gtol ? 0 : 5;     // 5: the gradient is NaN
+            break;
+        }
+        if (it >= max_iter) break;             // status 1
+        const double det = cur.hww * cur.hbb - cur.hwb * cur.hwb;
+        const double sw = -(cur.hbb * cur.gw - cur.hwb * cur.gb) / det;
+        const double sb = -(cur.hww * cur.gb - cur.hwb * cur.gw) / det;
+        const double gs = cur.gw * sw + cur.gb * sb;
+        if (!(det > 0.0) || !(gs < 0.0)) {     // H >= I in exact arithmetic: only an overflow or a NaN comes here
+            status = 5;
+            break;
+        }
+        const double slack = (double)n * 2.220446049250313e-16 * fabs(cur.f);
+        double t = 1.0, wt = w, bt = b;
+        SvcPoint trial = cur;
+        bool ok = false;
+        for (int h = 0; h < 40; ++h) {
+            wt = w + t * sw, bt = b + t * sb;
+            trial = svc1_eval(x, P, y, n, k, cpos, C, wt, bt, red);
+            if (trial.f <= cur.f + 1e-4 * t * gs + slack) {
+                ok = true;
+                break;
+            }
+            t *= 0.5;
+        }
+        if (!ok) {
+            status = 2;
+            break;
+        }
+        w = wt, b = bt, cur = trial;
+        ++it;
+    }
+    if (tid == 0) wo[0] = w, wo[1] = b, io[0] = (double)it, io[1] = gmax, io[2] = cur.f, io[3] = (double)status;
+}
+
+extern "C" int eg_score_svc1_fit(const double* X, const int* y, int n, int P, int K, double C, int max_iter, double gtol, double* W,
+                                 double* info, eg_stream_t s) {
+    EG_REQUIRE(X && y && W && info && n > 0 && P > 0 && max_iter >= 0 && gtol >= 0.0, "eg_score_svc1_fit: bad argument");
+    EG_REQUIRE(K >= 3 && K <= SVC_KMAX, "eg_score_svc1_fit: K = %d classes, 3..%d supported (liblinear fits K = 2 as one problem)", K, SVC_KMAX);
+    EG_REQUIRE(C > 0.0, "eg_score_svc1_fit: C must be positive");
+    EG_REQUIRE((long long)P * K <= 65535, "eg_score_svc1_fit: P K = %lld problems exceed one launch", (long long)P * K);
+    hipLaunchKernelGGL(score_svc1_fit_kernel, dim3(P * K), dim3(SVC_THREADS), 0, (hipStream_t)s, X, y, n, P, K, C, max_iter, gtol, W, info);
+    EG_LAUNCH_CHECK();
+    return 0;
+}
+
+// predict[p][i] = np.argmax_k (w_pk x_ip + b_pk), the first index on ties (LinearSVC.predict over decision_function, SAP.py:305);
+// correct[p] = #{i: predict[p][i] == y[i]} (zeroed here; one integer atomic per workgroup).  blockIdx.y = column p.
+__global__ void __launch_bounds__(SVC_THREADS) score_svc1_accuracy_kernel(const double* __restrict__ X, const int* __restrict__ y, int n,
+                                                                          int P, int K, const double* __restrict__ W,
+                                                                          int* __restrict__ predict, unsigned long long* __restrict__ correct) {
+    const int p = blockIdx.y;
+    const int i = blockIdx.x * SVC_THREADS + threadIdx.x;
+    const double* wp = W + (size_t)p * K * 2;
+    int hit = 0;
+    if (i < n) {
+        const double xi = X[(size_t)i * P + p];
+        int arg = 0;
+        double best = 0.0;
+        for (int k = 0; k < K; ++k) {
+            const double a = wp[2 * k] * xi + wp[2 * k + 1];
+            if (k == 0 || a > best) best = a, arg = k;
+        }
+        predict[(size_t)p * n + i] = arg;
+        hit = arg == y[i] ? 1 : 0;
+    }
+    const int hits = __syncthreads_count(hit);
+    if (threadIdx.x == 0 && hits) atomicAdd(correct + p, (unsigned long long)hits);
+}
+
+extern "C" int eg_score_svc1_accuracy(const double* X, const int* y, int n, int P, int K, const double* W, int* predict, long long* correct,
+                                      eg_stream_t s) {
+    EG_REQUIRE(X && y && W && predict && correct && n > 0 && P > 0 && K > 0 && P <= 65535, "eg_score_svc1_accuracy: bad argument");
+    hipError_t e = hipMemsetAsync(correct, 0, (size_t)P * sizeof(long long), (hipStream_t)s);
+    if (e != hipSuccess) EG_FAIL((int)e, "eg_score_svc1_accuracy: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(score_svc1_accuracy_kernel, dim3(cdiv(n, SVC_THREADS), P), dim3(SVC_THREADS), 0, (hipStream_t)s, X, y, n, P, K, W,
+                       predict, reinterpret_cast<unsigned long long*>(correct));
+    EG_LAUNCH_CHECK();
+    return 0;
+}

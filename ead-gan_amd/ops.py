@@ -809,6 +809,23 @@ def score_logreg_accuracy(X, y, n, d, K, W, predict, correct):
     lib().call("eg_score_logreg_accuracy", _p(X), _p(y), n, d, K, _p(W), _p(predict), _p(correct), _stream())
 
 
+# info[..., 3] of eg_score_svc1_fit
+SVC_STATUS = {0: "converged", 1: "max_iter reached", 2: "line search failed", 4: "a label outside 0..K-1 or a class without a sample",
+              5: "non-finite objective or gradient"}
+
+
+def score_sq_corr(codes, n, k, fv, nf, R):
+    lib().call("eg_score_sq_corr", _p(codes), n, k, _p(fv), nf, _p(R), _stream())
+
+
+def score_svc1_fit(X, y, n, P, K, C, max_iter, gtol, W, info):
+    lib().call("eg_score_svc1_fit", _p(X), _p(y), n, P, K, C, max_iter, gtol, _p(W), _p(info), _stream())
+
+
+def score_svc1_accuracy(X, y, n, P, K, W, predict, correct):
+    lib().call("eg_score_svc1_accuracy", _p(X), _p(y), n, P, K, _p(W), _p(predict), _p(correct), _stream())
+
+
 # ---- device loss log of a training run (engine.LossLog) ----------------------------------------------
 def runlog_append(losses, n, ring, capacity, head, first_nonfinite):
     """row head % capacity of ring[capacity][n] <- losses[:n]; head += 1; the first non-finite iteration (1-based) latched"""

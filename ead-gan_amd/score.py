@@ -1,5 +1,5 @@
-"""Disentanglement scores of a trained dSprites / colored-dSprites encoder pair on the MI355X: MIG, FactorVAE and BetaVAE
-(dSprites/score/MIG.py, FactorVAE.py, BetVAE.py; colored_dSprites/score/MIG.py, FactorVAE.py, BetVAE.py).
+"""Disentanglement scores of a trained dSprites / colored-dSprites encoder pair on the MI355X: MIG, FactorVAE, BetaVAE and SAP
+(dSprites/score/MIG.py, FactorVAE.py, BetVAE.py, SAP.py; colored_dSprites/score/ likewise).
 
 The reference pushes every sampled image through Encoder_pxy -> inverse translation -> grid_sample(padding_mode='zeros') [-> divide by
 the colour gains] -> Encoder (eval) on the CPU and scores the rows [argmax(cat), cont0, cont1, pxy1, pxy2] with numpy / sklearn.  Here the
@@ -98,6 +98,38 @@ def beta_vae_plan(latents_sizes, N, colored=False, rng=None, L=100, M=500):
     if colored:
         plan["group_gains"] = _group_gains(r, L, M)
     return plan
+
+
+def sap_plan(latents_sizes, N, colored=False, rng=None, L=100, M=500):
+    """load_data's plan (SAP.py:61-85): FactorVAE's group draws and the ``permutation(N)``, both drawn and never used by the score (consumed
+    here so that the stream stands where the script's does), then ``sample_latent(size=N // 10)``: one randint per latent; colored,
+    evaluate() then draws the samples' gains once.  -> {"latent_ids" int [n,6], "idx" int64 [n], "gains" float64 [n,3] or None}"""
+    r = _rs(rng)
+    sizes = np.asarray(latents_sizes)
+    _group_draws(r, sizes, L, M)
+    r.permutation(range(N))
+    n = int(N / 10)
+    samples = np.zeros((n, sizes.size))
+    for lat_i, lat_size in enumerate(sizes):
+        samples[:, lat_i] = r.randint(lat_size, size=n)
+    latent_ids = samples.astype(np.int32)
+    idx = np.dot(latent_ids, latents_bases(sizes)).astype(int)
+    gains = r.uniform(0.5, 1, [n, 3, 1, 1]).reshape(n, 3) if colored else None
+    return {"latent_ids": latent_ids, "idx": idx, "gains": gains}
+
+
+def sap_latents(latent_ids, latents_names, latents_possible_values):
+    """The factor table of load_data (SAP.py:87-97): the archive's value of every sampled latent id, the color column dropped and the
+    shape column minus 1 -> float64 [n,5] (shape 0..2, scale, orientation, posX, posY)"""
+    ids = np.asarray(latent_ids)
+    out = np.zeros((ids.shape[0], 6))
+    for i in range(6):
+        out[:, i] = np.asarray(latents_possible_values[latents_names[i]])[ids[:, i]]
+    if not (np.all(out[:, 0] == 1) and np.min(out[:, 1]) == 1 and np.max(out[:, 1]) == 3):
+        raise ValueError("the sampled latents do not span color 1 and shapes 1..3 (SAP.py:92-94 asserts it)")
+    out = out[:, 1:]
+    out[:, 0] -= 1.0
+    return out
 
 
 # ================================================================================================
@@ -310,6 +342,76 @@ def beta_vae(group_codes, labels, C=1.0):
     return {"betaVAE_metric": int(fit["correct"].item()) / fit["predict"].numel()}
 
 
+def svc1_fit(X, y, K, C=0.01, max_iter=50, gtol=1e-10):
+    """The optimum of sklearn's LinearSVC(C, class_weight="balanced") (its defaults: L2 penalty, squared hinge, one-vs-rest, regularised
+    intercept) for each one-feature column of device X [n,P] float64 (or [n]) against class ids y [n] in 0..K-1 (host or device), by
+    eg_score_svc1_fit's float64 generalised Newton iteration, and the training predictions.  ``gtol`` bounds the gradient's inf-norm of
+    every one-vs-rest problem.  -> (W f64 [P,K,2] (w, b), predict int32 [P,n], correct int64 [P]) on the device, info (host float64
+    [P,K,4]: iterations, final |g|inf, objective, status).  Raises RuntimeError when a problem did not reach gtol."""
+    if K < 3:
+        raise ValueError(f"svc1_fit fits one-vs-rest problems of K >= 3 classes (liblinear fits K = 2 as a single problem), got K = {K}")
+    _require_cuda(X)
+    X = X.to(torch.float64)
+    X = (X.reshape(-1, 1) if X.dim() == 1 else X).contiguous()
+    n, P = X.shape
+    dev = X.device
+    y_d = (y if torch.is_tensor(y) else torch.from_numpy(np.asarray(y).reshape(-1))).to(device=dev, dtype=torch.int32).contiguous()
+    if y_d.numel() != n:
+        raise ValueError(f"{y_d.numel()} labels for {n} rows")
+    W = torch.empty(P, K, 2, device=dev, dtype=torch.float64)
+    info = torch.empty(P, K, 4, device=dev, dtype=torch.float64)
+    ops.score_svc1_fit(X, y_d, n, P, K, float(C), max_iter, gtol, W, info)
+    predict = torch.empty(P, n, device=dev, dtype=torch.int32)
+    correct = torch.empty(P, device=dev, dtype=torch.int64)
+    ops.score_svc1_accuracy(X, y_d, n, P, K, W, predict, correct)
+    info_h = info.cpu().numpy()                                                    # the one sync: offline evaluation
+    if (info_h[:, :, 3] != 0).any():
+        p, k = (int(v[0]) for v in np.nonzero(info_h[:, :, 3]))
+        st = int(info_h[p, k, 3])
+        raise RuntimeError(f"linear SVC fit of column {p}, class {k} did not reach |g|inf <= {gtol:g}: {int(info_h[p, k, 0])} iterations, "
+                           f"|g|inf = {info_h[p, k, 1]:.3e} (status {st}: {ops.SVC_STATUS.get(st, '?')})")
+    return W, predict, correct, info_h
+
+
+def sap_matrix(codes, latents, is_continuous, C=0.01):
+    """SAPMetric.evaluate's score matrix (SAP.py:286-306) of device codes [n,k] against factor values [n,nf] (host or device): a continuous
+    factor's column holds the squared correlations of eg_score_sq_corr, a discrete one's the training accuracy of ``svc1_fit`` on each
+    code column alone (the factor's values cast to int32 as the script casts them, class ids by np.unique).
+    -> (device float64 [k,nf], {factor j: {"W", "predict", "correct" (device), "classes", "info" (host)}})"""
+    _require_cuda(codes)
+    codes = codes.to(torch.float64).contiguous()
+    n, k = codes.shape
+    dev = codes.device
+    fv_h = np.asarray(latents.cpu() if torch.is_tensor(latents) else latents, dtype=np.float64)
+    if fv_h.ndim != 2 or fv_h.shape[0] != n or fv_h.shape[1] != len(is_continuous):
+        raise ValueError(f"factor values {fv_h.shape} do not match {n} codes and {len(is_continuous)} factors")
+    nf = fv_h.shape[1]
+    fv = torch.from_numpy(np.ascontiguousarray(fv_h)).to(dev)
+    R = torch.empty(k, nf, device=dev, dtype=torch.float64)
+    ops.score_sq_corr(codes, n, k, fv, nf, R)                                     # the discrete factors' columns are overwritten below
+    fits = {}
+    for j, cont in enumerate(is_continuous):
+        if cont:
+            continue
+        classes, y = np.unique(fv_h[:, j].astype(np.int32), return_inverse=True)
+        W, predict, correct, info = svc1_fit(codes, y.reshape(-1), classes.size, C)
+        R[:, j] = correct.to(torch.float64) / n                                   # np.mean(pred == gt_values)
+        fits[j] = {"W": W, "predict": predict, "correct": correct, "classes": classes, "info": info}
+    return R, fits
+
+
+def sap(codes, latents, is_continuous):
+    """-> the reference's dict {"SAP_metric", "SAP_metric_detail"} (SAP.py:307-314): per factor the gap between the two best codes"""
+    R, _ = sap_matrix(codes, latents, is_continuous)
+    score_matrix = R.cpu().numpy()
+    sorted_score_matrix = np.sort(score_matrix, axis=0)
+    score = np.mean(sorted_score_matrix[-1, :] - sorted_score_matrix[-2, :])
+    return {"SAP_metric": score, "SAP_metric_detail": score_matrix}
+
+
+SAP_IS_CONTINUOUS = (False, True, True, True, True)          # shape, scale, orientation, posX, posY (SAP.py:103)
+
+
 # ================================================================================================
 # drop-in for the scripts' module-level code
 # ================================================================================================
@@ -325,7 +427,8 @@ def load_encoders(kind, encoder_pxy_path, encoder_path, device="cuda", dtype="f3
 def run_score(kind, metric, npz_path, encoder_pxy_path, encoder_path, seed=None, batch=4096, groups=None, device="cuda"):
     """What dSprites|colored_dSprites/score/{MIG,FactorVAE,BetVAE}.py do at module level, on the MI355X.  ``seed``: np.random.seed first (else
     the global numpy stream as it stands).  ``groups``: score only the first groups of the 500-group FactorVAE / BetaVAE plan (the plan is
-    drawn in full).  Prints the score; returns it (MIG), the reference's three-key dict (FactorVAE) or its one-key dict (BetaVAE)."""
+    drawn in full).  Prints the score; returns it (MIG), the reference's three-key dict (FactorVAE) or its one-key dict (BetaVAE).
+    score/SAP.py is ``run_sap``: this function's refusal of every other metric name is part of its contract."""
     if kind not in KINDS:
         raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
     if metric not in ("mig", "factor_vae", "beta_vae"):
@@ -365,4 +468,26 @@ def run_score(kind, metric, npz_path, encoder_pxy_path, encoder_path, seed=None,
     labels = plan["labels"][:M]
     res = factor_vae(ev, gc, labels, len(set(labels.tolist())))
     print("score", res["factorVAE_metric"])
+    return res
+
+
+def run_sap(kind, npz_path, encoder_pxy_path, encoder_path, seed=None, batch=4096, device="cuda"):
+    """What dSprites|colored_dSprites/score/SAP.py do at module level, on the MI355X (``run_score``'s arguments without the metric name).
+    Prints ``score`` as the script does; returns the reference's dict {"SAP_metric", "SAP_metric_detail"}."""
+    if kind not in KINDS:
+        raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
+    colored = kind == "colored"
+    dataset_zip = np.load(npz_path, encoding="latin1", allow_pickle=True)
+    imgs = dataset_zip["imgs"]
+    metadata = dataset_zip["metadata"][()]
+    P, E = load_encoders(kind, encoder_pxy_path, encoder_path, device)
+    if seed is not None:
+        np.random.seed(seed)
+    rep = Representation(P, E, kind, batch)
+    plan = sap_plan(metadata["latents_sizes"], imgs.shape[0], colored)
+    latents = sap_latents(plan["latent_ids"], metadata["latents_names"], metadata["latents_possible_values"])
+    data = torch.from_numpy(np.ascontiguousarray(imgs)).to(device)
+    codes = rep.codes(data, plan["idx"], plan["gains"])                            # SAP.py:277 builds the same five columns
+    res = sap(codes, latents, SAP_IS_CONTINUOUS)
+    print("score", res["SAP_metric"])
     return res

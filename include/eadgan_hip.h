@@ -546,7 +546,7 @@ int eg_onehot(const long long* labels, float* out, int B, int n, eg_stream_t s);
 int eg_resample_u8(const unsigned char* src, unsigned char* dst, int planes, int in_h, int in_w, int axis, const int* bounds,
                    const int* kk, int ksize, int o0, int on, int c0, int cn, eg_stream_t s);
 
-/* Disentanglement scores of a trained encoder pair (dSprites/score/MIG.py, FactorVAE.py, BetVAE.py; colored_dSprites/score/ likewise).
+/* Disentanglement scores of a trained encoder pair (dSprites/score/MIG.py, FactorVAE.py, BetVAE.py, SAP.py; colored_dSprites/score/ likewise).
  * Staging: out[b][c] = data[idx[b]] * gain[b][c] (uint8 [N][HW] sprites, gain [B][C] fp32 or NULL = 1) -> fp32 NCHW; the reference's
  * imgs[select_index] + add_color_2_img (colored MIG.py:169-184,204; FactorVAE.py:236-254,270,315). */
 int eg_score_stage_u8(const unsigned char* data, const int* idx, const float* gain, float* out, int B, int C, int HW, eg_stream_t s);
@@ -584,6 +584,25 @@ int eg_score_logreg_fit(const double* X, const int* y, int n, int d, int K, doub
  * correct[0] = #{i: predict[i] == y[i]} (int64, zeroed here) */
 int eg_score_logreg_accuracy(const double* X, const int* y, int n, int d, int K, const double* W, int* predict, long long* correct,
                              eg_stream_t s);
+/* SAP (dSprites/score/SAP.py:283-309, colored :304-330).  R [k][nf] float64: R[i][j] = cov(i, j)^2 / var(i) / var(j) of code column i of
+ * codes [n][k] and factor column j of fv [n][nf] (float64) as np.cov(x, y, ddof=1) gives them: the means first, then the centred sums.
+ * One workgroup per (i, j), fixed summation order; a zero variance gives IEEE's NaN as the reference's division does.  n >= 2. */
+int eg_score_sq_corr(const double* codes, int n, int k, const double* fv, int nf, double* R, eg_stream_t s);
+/* classifier.fit of SAP.py:303-304 for P one-feature columns X [n][P] float64 that share the class ids y [n] int32 in 0..K-1: the optimum
+ * of LinearSVC(C, class_weight="balanced") with sklearn's defaults (L2 penalty, squared hinge, one-vs-rest, the intercept a regularised
+ * weight).  Problem (p, k) minimises  (w^2 + b^2) / 2 + sum_i c_i max(0, 1 - s_i (w x_ip + b))^2,  s_i = +1 where y_i = k and -1
+ * elsewhere, c_i = C n / (K count_k) where y_i = k and C elsewhere -- strictly convex, one optimum.  One workgroup per (p, k): float64
+ * generalised Newton from (0, 0) with the 2 x 2 Hessian solved in closed form and eg_score_logreg_fit's Armijo backtracking; counts and
+ * weights come from y on the device; fixed summation order, two runs give the same bits.  3 <= K <= 64, C > 0.  Stops when the
+ * gradient's inf-norm is <= gtol or after max_iter steps.  W [P][K][2] = (w, b); info [P][K][4] float64 = (iterations, final |g|inf,
+ * objective, status: 0 converged, 1 max_iter reached, 2 line search failed, 4 a label outside 0..K-1 or a class without a sample (W = 0,
+ * nothing computed), 5 non-finite).  No workspace. */
+int eg_score_svc1_fit(const double* X, const int* y, int n, int P, int K, double C, int max_iter, double gtol, double* W, double* info,
+                      eg_stream_t s);
+/* classifier.predict of SAP.py:305-306 per column: predict [P][n] int32 = np.argmax_k (w_pk x_ip + b_pk) (first index on ties),
+ * correct [P] int64 (zeroed here) = #{i: predict[p][i] == y[i]} */
+int eg_score_svc1_accuracy(const double* X, const int* y, int n, int P, int K, const double* W, int* predict, long long* correct,
+                           eg_stream_t s);
 
 /* --- device loss log of a training run: replaces the `.item()` calls of the reference's progress lines --
  * celebA/EAD-GAN_celebA.py:404-408, MNIST/EAD-GAN_rpqmnxy.py:453-457, dSprites/rp.py:491-496, colored_dSprites/rp_color.py:523-528,
