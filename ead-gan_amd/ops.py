@@ -826,6 +826,27 @@ def score_svc1_accuracy(X, y, n, P, K, W, predict, correct):
     lib().call("eg_score_svc1_accuracy", _p(X), _p(y), n, P, K, _p(W), _p(predict), _p(correct), _stream())
 
 
+# info[3] of eg_score_softmax_fit: eg_score_logreg_fit's codes and the one the larger solver adds
+SOFTMAX_STATUS = {**LOGREG_STATUS, 6: "a class without a sample"}
+
+
+def score_softmax_ws_bytes(n, d, K):
+    return lib().query("eg_score_softmax_ws_bytes", n, d, K)
+
+
+def score_softmax_fit(X, y, n, d, K, inv_C, max_iter, gtol, ws, W, info):
+    """blocks: the host reads the solver's decision record after every trial (the one entry point that synchronises)"""
+    lib().call("eg_score_softmax_fit", _p(X), _p(y), n, d, K, inv_C, max_iter, gtol, _p(ws), _p(W), _p(info), _stream())
+
+
+def score_softmax_proba(X, n, d, K, W, proba):
+    lib().call("eg_score_softmax_proba", _p(X), n, d, K, _p(W), _p(proba), _stream())
+
+
+def score_auc_ovr(scores, order, offsets, n, K, max_class_rows, less, equal):
+    lib().call("eg_score_auc_ovr", _p(scores), _p(order), _p(offsets), n, K, int(max_class_rows), _p(less), _p(equal), _stream())
+
+
 # ---- device loss log of a training run (engine.LossLog) ----------------------------------------------
 def runlog_append(losses, n, ring, capacity, head, first_nonfinite):
     """row head % capacity of ring[capacity][n] <- losses[:n]; head += 1; the first non-finite iteration (1-based) latched"""

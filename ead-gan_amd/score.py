@@ -1,5 +1,5 @@
-"""Disentanglement scores of a trained dSprites / colored-dSprites encoder pair on the MI355X: MIG, FactorVAE, BetaVAE and SAP
-(dSprites/score/MIG.py, FactorVAE.py, BetVAE.py, SAP.py; colored_dSprites/score/ likewise).
+"""Disentanglement scores of a trained dSprites / colored-dSprites encoder pair on the MI355X: MIG, FactorVAE, BetaVAE, SAP and F-stat
+(dSprites/score/MIG.py, FactorVAE.py, BetVAE.py, SAP.py, F_score.py; colored_dSprites/score/ likewise).
 
 The reference pushes every sampled image through Encoder_pxy -> inverse translation -> grid_sample(padding_mode='zeros') [-> divide by
 the colour gains] -> Encoder (eval) on the CPU and scores the rows [argmax(cat), cont0, cont1, pxy1, pxy2] with numpy / sklearn.  Here the
@@ -118,6 +118,15 @@ def sap_plan(latents_sizes, N, colored=False, rng=None, L=100, M=500):
     return {"latent_ids": latent_ids, "idx": idx, "gains": gains}
 
 
+def fstat_plan(latents_sizes, N, colored=False, rng=None, L=100, M=500):
+    """load_data's plan (F_score.py:37-112): the function is SAP.py's line for line, and evaluate() draws the samples' gains once
+    (colored F_score.py:296), so the draws are ``sap_plan``'s.  The score's ground truth is the sampled latent ids without the color
+    column (F_score.py:104,308).  -> sap_plan's dict + {"latent_id": int32 [n,5]}"""
+    plan = sap_plan(latents_sizes, N, colored, rng, L, M)
+    plan["latent_id"] = plan["latent_ids"][:, 1:]
+    return plan
+
+
 def sap_latents(latent_ids, latents_names, latents_possible_values):
     """The factor table of load_data (SAP.py:87-97): the archive's value of every sampled latent id, the color column dropped and the
     shape column minus 1 -> float64 [n,5] (shape 0..2, scale, orientation, posX, posY)"""
@@ -225,14 +234,14 @@ def discretize(codes, num_bins=20):
     return bins
 
 
-def mig(codes, factor_values, num_bins=20):
-    """MIG of device codes [n,5] against host factor values [n,nf] (MIG.py:304-311).  Factor values become class ids with
-    ``np.unique(return_inverse=True)``, the partition mutual_info_score builds.  -> (score, m [5,nf], H [nf])"""
+def _discrete_mi(codes, factor_values, num_bins=20):
+    """discrete_mutual_info / discrete_entropy of device codes [n,k] (discretised here) against host factor values [n,nf], which become
+    class ids with ``np.unique(return_inverse=True)``, the partition mutual_info_score builds.  -> (m [k,nf], H [nf]) host float64"""
     bins = discretize(codes, num_bins)
     k, n = bins.shape
     fv = np.asarray(factor_values)
-    if fv.shape[0] != n:
-        raise ValueError(f"{fv.shape[0]} factor rows for {n} codes")
+    if fv.ndim != 2 or fv.shape[0] != n:
+        raise ValueError(f"factor values {fv.shape} do not give {n} codes a row of factors each")
     ys, kmax = [], 1
     for j in range(fv.shape[1]):
         u, inv = np.unique(fv[:, j], return_inverse=True)
@@ -245,7 +254,12 @@ def mig(codes, factor_values, num_bins=20):
     mi = torch.empty(k * nf + nf, device=dev, dtype=torch.float64)
     ops.score_mig(bins, k, ys_d, nf, n, kmax, num_bins, ws, mi)
     mi = mi.cpu().numpy()
-    m, H = mi[:k * nf].reshape(k, nf), mi[k * nf:]
+    return mi[:k * nf].reshape(k, nf), mi[k * nf:]
+
+
+def mig(codes, factor_values, num_bins=20):
+    """MIG of device codes [n,5] against host factor values [n,nf] (MIG.py:304-311).  -> (score, m [5,nf], H [nf])"""
+    m, H = _discrete_mi(codes, factor_values, num_bins)
     sorted_m = np.sort(m, axis=0)[::-1]
     with np.errstate(divide="ignore", invalid="ignore"):
         score = np.mean(np.divide(sorted_m[0, :] - sorted_m[1, :], H[:]))
@@ -412,6 +426,123 @@ def sap(codes, latents, is_continuous):
 SAP_IS_CONTINUOUS = (False, True, True, True, True)          # shape, scale, orientation, posX, posY (SAP.py:103)
 
 
+# default |g|inf of softmax_fit: 100 x the largest floor the float64 numpy solver reaches on the production-sized set (6.43e-13) and the
+# fixtures (<= 6.7e-16)
+SOFTMAX_GTOL = 6.5e-11
+
+
+def softmax_fit(X, y, K, C=1.0, max_iter=50, gtol=SOFTMAX_GTOL):
+    """The optimum of sklearn's LogisticRegression(C) on device X [n,d] float64 and class ids y [n] in 0..K-1 (host or device) by
+    eg_score_softmax_fit's float64 Newton iteration: the multinomial objective for K >= 3, the binomial form sklearn fits for K = 2
+    (one weight row).  2 <= K <= 64, K (d + 1) <= 256.  ``gtol`` bounds the gradient's inf-norm of the summed objective.  Blocks: the
+    host reads the solver's decision record after every trial.
+    -> (W f64 [K,d+1] ([1,d+1] for K = 2; coefficients | intercept) on the device, info (host float64: iterations, final |g|inf,
+    objective, status)).  Raises RuntimeError when the solver did not reach gtol."""
+    _require_cuda(X)
+    X = X.to(torch.float64).contiguous()
+    n, d = X.shape
+    dev = X.device
+    y_d = (y if torch.is_tensor(y) else torch.from_numpy(np.asarray(y).reshape(-1))).to(device=dev, dtype=torch.int32).contiguous()
+    if y_d.numel() != n:
+        raise ValueError(f"{y_d.numel()} labels for {n} rows")
+    ws = torch.empty(max(ops.score_softmax_ws_bytes(n, d, K), 8), device=dev, dtype=torch.uint8)
+    W = torch.empty(1 if K == 2 else K, d + 1, device=dev, dtype=torch.float64)
+    info = torch.empty(4, device=dev, dtype=torch.float64)
+    ops.score_softmax_fit(X, y_d, n, d, K, 1.0 / C, max_iter, gtol, ws, W, info)
+    info_h = info.cpu().numpy()
+    if info_h[3] != 0:
+        raise RuntimeError(f"logistic fit did not reach |g|inf <= {gtol:g}: {int(info_h[0])} iterations, |g|inf = {info_h[1]:.3e} "
+                           f"(status {int(info_h[3])}: {ops.SOFTMAX_STATUS.get(int(info_h[3]), '?')})")
+    return W, info_h
+
+
+def softmax_proba(X, W, K):
+    """predict_proba at W: device float64 [n,K] (softmax of the logits; [1 - p, p] for K = 2)"""
+    _require_cuda(X)
+    X = X.to(torch.float64).contiguous()
+    n, d = X.shape
+    if tuple(W.shape) != (1 if K == 2 else K, d + 1):
+        raise ValueError(f"W {tuple(W.shape)} does not fit K = {K} classes of {d} columns")
+    proba = torch.empty(n, K, device=X.device, dtype=torch.float64)
+    ops.score_softmax_proba(X, n, d, K, W.to(torch.float64).contiguous(), proba)
+    return proba
+
+
+def roc_auc_ovr(proba, y, K):
+    """roc_auc_score of every column of device proba [n,K] float64 against the indicator of class ids y [n] (host), from
+    eg_score_auc_ovr's exact pair counts: AUC_k = (2 less + equal) / (2 n_pos n_neg), ties counting one half.  Raises ValueError where
+    sklearn raises: a class without a row, or one that holds every row.
+    -> (auc float64 [K], less uint64 [K], equal uint64 [K]) on the host"""
+    y_h = np.asarray(y.cpu() if torch.is_tensor(y) else y).reshape(-1).astype(np.int64)
+    n = y_h.size
+    if proba.dim() != 2 or tuple(proba.shape) != (n, K):
+        raise ValueError(f"scores {tuple(proba.shape)} do not match {n} labels of {K} classes")
+    if n == 0 or y_h.min() < 0 or y_h.max() >= K:
+        raise ValueError(f"class ids must lie in 0..{K - 1}")
+    counts = np.bincount(y_h, minlength=K)
+    if (counts == 0).any() or (counts == n).any():
+        raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+    _require_cuda(proba)
+    dev = proba.device
+    order = torch.from_numpy(np.argsort(y_h, kind="stable").astype(np.int32)).to(dev)
+    offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)).to(dev)
+    counts_d = torch.empty(2, K, device=dev, dtype=torch.int64)               # uint64 counts: below 2^63 for any n a launch takes
+    ops.score_auc_ovr(proba.to(torch.float64).contiguous(), order, offsets, n, K, int(counts.max()), counts_d[0], counts_d[1])
+    less, equal = (c.astype(np.uint64) for c in counts_d.cpu().numpy())
+    pairs = counts.astype(np.float64) * (n - counts).astype(np.float64)
+    auc = (2.0 * less.astype(np.float64) + equal.astype(np.float64)) / (2.0 * pairs)
+    return auc, less, equal
+
+
+def fstat_modularity(codes, latent_ids, num_bins=20):
+    """The modularity half of FStatMetric.evaluate (F_score.py:313-324): its discretize and mutual_info are MIG.py's make_discretizer
+    and discrete_mutual_info (the same np.histogram / np.digitize / mutual_info_score calls), so the 5 x nf matrix comes from the MIG
+    kernels; the script's arithmetic on it runs on the host.  -> (score, detail [5], mi [5,nf])"""
+    modu_mi, _ = _discrete_mi(codes, latent_ids, num_bins)
+    squared_modu_mi = np.square(modu_mi)
+    max_squared_modu_mi = np.max(squared_modu_mi, axis=1)
+    numerator = np.sum(squared_modu_mi, axis=1) - max_squared_modu_mi
+    denominator = max_squared_modu_mi * (modu_mi.shape[1] - 1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        modu_score_detail = 1.0 - numerator / denominator
+    return np.mean(modu_score_detail), modu_score_detail, modu_mi
+
+
+def fstat_explicitness(codes, latent_ids, C=1.0):
+    """The explicitness half (F_score.py:327-338): per factor the class ids by np.unique, ``softmax_fit`` on all code columns,
+    ``softmax_proba``, and the mean of the per-class one-vs-rest AUCs (roc_auc_score's macro average over the indicator columns).
+    -> (score, detail [nf,1], {factor j: {"W", "proba" (device), "auc", "less", "equal", "classes", "info" (host)}})"""
+    _require_cuda(codes)
+    codes = codes.to(torch.float64).contiguous()
+    ids = np.asarray(latent_ids.cpu() if torch.is_tensor(latent_ids) else latent_ids)
+    if ids.ndim != 2 or ids.shape[0] != codes.shape[0]:
+        raise ValueError(f"latent ids {ids.shape} do not match {codes.shape[0]} codes")
+    detail = np.zeros([ids.shape[1], 1])
+    fits = {}
+    for j in range(ids.shape[1]):
+        classes, y = np.unique(ids[:, j], return_inverse=True)
+        y = y.reshape(-1)
+        if classes.size < 2:
+            raise ValueError(f"factor {j} takes one value: LogisticRegression needs at least 2 classes")
+        W, info = softmax_fit(codes, y, classes.size, C)
+        proba = softmax_proba(codes, W, classes.size)
+        auc, less, equal = roc_auc_ovr(proba, y, classes.size)
+        detail[j] = np.mean(auc)
+        fits[j] = {"W": W, "proba": proba, "auc": auc, "less": less, "equal": equal, "classes": classes, "info": info}
+    return np.mean(detail), detail, fits
+
+
+def fstat(codes, latent_ids):
+    """-> the reference's dict (F_score.py:346-350): FStat_modu_metric, _detail [5], FStat_modu_mi [5,nf], FStat_expl_metric, _detail [nf,1]"""
+    modu_score, modu_score_detail, modu_mi = fstat_modularity(codes, latent_ids)
+    expl_score, expl_score_detail, _ = fstat_explicitness(codes, latent_ids)
+    return {"FStat_modu_metric": modu_score,
+            "FStat_modu_metric_detail": modu_score_detail,
+            "FStat_modu_mi": modu_mi,
+            "FStat_expl_metric": expl_score,
+            "FStat_expl_metric_detail": expl_score_detail}
+
+
 # ================================================================================================
 # drop-in for the scripts' module-level code
 # ================================================================================================
@@ -428,7 +559,8 @@ def run_score(kind, metric, npz_path, encoder_pxy_path, encoder_path, seed=None,
     """What dSprites|colored_dSprites/score/{MIG,FactorVAE,BetVAE}.py do at module level, on the MI355X.  ``seed``: np.random.seed first (else
     the global numpy stream as it stands).  ``groups``: score only the first groups of the 500-group FactorVAE / BetaVAE plan (the plan is
     drawn in full).  Prints the score; returns it (MIG), the reference's three-key dict (FactorVAE) or its one-key dict (BetaVAE).
-    score/SAP.py is ``run_sap``: this function's refusal of every other metric name is part of its contract."""
+    score/SAP.py is ``run_sap`` and score/F_score.py ``run_fstat``: this function's refusal of every other metric name is part of its
+    contract."""
     if kind not in KINDS:
         raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
     if metric not in ("mig", "factor_vae", "beta_vae"):
@@ -490,4 +622,26 @@ def run_sap(kind, npz_path, encoder_pxy_path, encoder_path, seed=None, batch=409
     codes = rep.codes(data, plan["idx"], plan["gains"])                            # SAP.py:277 builds the same five columns
     res = sap(codes, latents, SAP_IS_CONTINUOUS)
     print("score", res["SAP_metric"])
+    return res
+
+
+def run_fstat(kind, npz_path, encoder_pxy_path, encoder_path, seed=None, batch=4096, device="cuda"):
+    """What dSprites|colored_dSprites/score/F_score.py do at module level, on the MI355X (``run_sap``'s arguments).  Prints ``modu_score``
+    and ``expl_score`` as the script does; returns the reference's five-key dict."""
+    if kind not in KINDS:
+        raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
+    colored = kind == "colored"
+    dataset_zip = np.load(npz_path, encoding="latin1", allow_pickle=True)
+    imgs = dataset_zip["imgs"]
+    metadata = dataset_zip["metadata"][()]
+    P, E = load_encoders(kind, encoder_pxy_path, encoder_path, device)
+    if seed is not None:
+        np.random.seed(seed)
+    rep = Representation(P, E, kind, batch)
+    plan = fstat_plan(metadata["latents_sizes"], imgs.shape[0], colored)
+    data = torch.from_numpy(np.ascontiguousarray(imgs)).to(device)
+    codes = rep.codes(data, plan["idx"], plan["gains"])                            # F_score.py:304 builds the same five columns
+    res = fstat(codes, plan["latent_id"])
+    print("modu_score", res["FStat_modu_metric"])
+    print("expl_score", res["FStat_expl_metric"])
     return res

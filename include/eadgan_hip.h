@@ -546,7 +546,7 @@ int eg_onehot(const long long* labels, float* out, int B, int n, eg_stream_t s);
 int eg_resample_u8(const unsigned char* src, unsigned char* dst, int planes, int in_h, int in_w, int axis, const int* bounds,
                    const int* kk, int ksize, int o0, int on, int c0, int cn, eg_stream_t s);
 
-/* Disentanglement scores of a trained encoder pair (dSprites/score/MIG.py, FactorVAE.py, BetVAE.py, SAP.py; colored_dSprites/score/ likewise).
+/* Disentanglement scores of a trained encoder pair (dSprites/score/MIG.py, FactorVAE.py, BetVAE.py, SAP.py, F_score.py; colored_dSprites/score/ likewise).
  * Staging: out[b][c] = data[idx[b]] * gain[b][c] (uint8 [N][HW] sprites, gain [B][C] fp32 or NULL = 1) -> fp32 NCHW; the reference's
  * imgs[select_index] + add_color_2_img (colored MIG.py:169-184,204; FactorVAE.py:236-254,270,315). */
 int eg_score_stage_u8(const unsigned char* data, const int* idx, const float* gain, float* out, int B, int C, int HW, eg_stream_t s);
@@ -603,6 +603,35 @@ int eg_score_svc1_fit(const double* X, const int* y, int n, int P, int K, double
  * correct [P] int64 (zeroed here) = #{i: predict[p][i] == y[i]} */
 int eg_score_svc1_accuracy(const double* X, const int* y, int n, int P, int K, const double* W, int* predict, long long* correct,
                            eg_stream_t s);
+/* F-stat, the explicitness half (dSprites/score/F_score.py:327-338, colored :345-356).  classifier.fit: the optimum of sklearn's
+ * LogisticRegression(C = 1 / inv_C) on X [n][d] float64 with class ids y [n] int32 in 0..K-1.  K >= 3: the multinomial objective of
+ * eg_score_logreg_fit, W [K][d+1] with zero-sum intercepts.  K = 2: the binomial form sklearn fits for two classes,
+ * sum_i [log(1 + exp(z_i)) - y_i z_i] + inv_C / 2 |w|^2 with z_i = w . x_i + b, W [1][d+1] (not the two-class softmax: its penalty
+ * differs).  2 <= K <= 64, K (d + 1) <= 256, inv_C > 0; everything else is refused.  Float64 damped Newton from W = 0 with
+ * eg_score_logreg_fit's Armijo constants and rounding slack.  The row sums run over many workgroups, each a launch of its own in stream
+ * order: probabilities and objective partials, Armijo's test, gradient partials per row slice of an accepted trial, the P x P Hessian as per-slice partial slabs in ws and
+ * their reduction in ascending order; Cholesky and the triangular solves run on the Hessian in global memory in one workgroup.  No
+ * workgroup waits on another, no float atomics: two calls give the same bits.
+ * THE ONE BLOCKING ENTRY POINT OF THIS HEADER: the loop over Newton iterations and backtracking trials runs on the host inside the call.
+ * Every decision (accept, backtrack, converged, failed) is taken on the device in float64 and written to a small record in ws; after
+ * each trial the host copies that record back (a stream synchronisation) only to choose the next launch.  A stream that is capturing
+ * is refused.  info [4] float64 = (iterations, final |g|inf, objective, status: eg_score_logreg_fit's 0..5 -- 0 converged, 1 max_iter
+ * reached, 2 line search failed, 3 Hessian not positive definite, 4 a label outside 0..K-1, 5 non-finite gradient (a non-finite input
+ * ends here) -- and 6 a class without a sample; 4 and 6 leave W = 0).  ws: eg_score_softmax_ws_bytes bytes. */
+size_t eg_score_softmax_ws_bytes(int n, int d, int K);
+int eg_score_softmax_fit(const double* X, const int* y, int n, int d, int K, double inv_C, int max_iter, double gtol, void* ws, double* W,
+                         double* info, eg_stream_t s);
+/* classifier.predict_proba at W (F_score.py:332): proba [n][K] float64 = softmax of the logits, or [1 - p, p] with p = sigmoid(z) for
+ * K = 2 (W [1][d+1]).  The limits of eg_score_softmax_fit. */
+int eg_score_softmax_proba(const double* X, int n, int d, int K, const double* W, double* proba, eg_stream_t s);
+/* roc_auc_score's one-vs-rest pair counts (F_score.py:334-336), exact: for class k over all pairs (positive i: y_i = k, negative j:
+ * y_j != k) of scores [n][K] float64, less[k] = #{s_jk < s_ik} and equal[k] = #{s_jk == s_ik} (uint64, zeroed here; integer atomics).
+ * order [n] int32: the rows grouped by class; offsets [K+1] int32: class k's rows are order[offsets[k] .. offsets[k+1]); max_class_rows:
+ * the largest offsets[k+1] - offsets[k], which sizes the grid (a smaller value would leave positives out).  The host forms
+ * AUC_k = (2 less + equal) / (2 n_pos n_neg), the Mann-Whitney form of the trapezoid roc_auc_score integrates (ties count one half).
+ * Positives sit in registers, negatives stream through LDS in tiles; no sort.  An order entry outside 0..n-1 is skipped, not read. */
+int eg_score_auc_ovr(const double* scores, const int* order, const int* offsets, int n, int K, int max_class_rows,
+                     unsigned long long* less, unsigned long long* equal, eg_stream_t s);
 
 /* --- device loss log of a training run: replaces the `.item()` calls of the reference's progress lines --
  * celebA/EAD-GAN_celebA.py:404-408, MNIST/EAD-GAN_rpqmnxy.py:453-457, dSprites/rp.py:491-496, colored_dSprites/rp_color.py:523-528,
