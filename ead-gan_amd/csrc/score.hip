@@ -333,242 +333,7 @@ extern "C" int eg_score_pair_absdiff_mean(const double* x, int L, int M, int nco
     return 0;
 }
 
-// Multinomial logistic regression, the optimum of sklearn's LogisticRegression(C = 1 / inv_C) for K >= 3 classes:
-//   f(W) = sum_i [ logsumexp_k z_ik - z_i,y_i ] + inv_C / 2 * sum_{k, a < d} W_ka^2,   z_ik = sum_{a<d} W_ka x_ia + W_kd
-// (sklearn minimises f / n, the same point).  Damped Newton from W = 0 in float64 by ONE workgroup: latency-bound, the whole state
-// (P = K (d+1) <= 64 parameters, the P x P Hessian) lives in LDS.  Per iteration
-//   1. gradient and Hessian: rows in tiles of LR_TILE through LDS, every entry summed by one thread over the rows in ascending order;
-//      H += inv_C on the coefficient diagonal and 1/K on the intercept block (v v^T, v = 1/sqrt(K) on each intercept: the one null
-//      direction, a constant added to every intercept, which the gradient is orthogonal to -- the step is the minimum-norm one and
-//      the intercepts stay zero-sum; the mean of the step's intercepts, rounding only, is subtracted);
-//   2. Cholesky H = L L^T in LDS, s = -H^-1 g;
-//   3. Armijo backtracking t = 1, 1/2, ...: f(W + t s) <= f(W) + 1e-4 t g.s + n eps |f(W)| (the last term is the rounding bound of
-//      the row sum: once the decrease falls below what f resolves, the full Newton step is taken as it is).
-// Every row sum has a fixed order: the objective's partial sums are over rows i = slot (mod LR_THREADS) ascending, combined by a
-// halving tree over the LR_THREADS slots; the kernel is always launched as one workgroup of LR_THREADS.  No atomics.
-// ws [n][K] holds the softmax probabilities of the last point the objective was evaluated at (the accepted one when step 1 reads them).
-#define LR_THREADS 256
-#define LR_TILE 64
-#define LR_PMAX 64
-#define LR_KMAX 8
-#define LR_XMAX 22             // d + 1 <= 64 / 3 = 21
-
-struct LogregShared {
-    double H[LR_PMAX * LR_PMAX];
-    double pt[LR_TILE * LR_KMAX];
-    double xt[LR_TILE * LR_XMAX];
-    double red[LR_THREADS];
-    double W[LR_PMAX], Wt[LR_PMAX], g[LR_PMAX], st[LR_PMAX];
-    int yt[LR_TILE];
-};
-
-// f(Wp) and, into ws, every row's probabilities.  All threads return the same value.
-__device__ double logreg_objective(LogregShared& sh, const double* Wp, const double* X, const int* y, int n, int d, int K, double inv_C,
-                                   double* ws) {
-    const int D = d + 1;
-    double part = 0.0;
-    for (int i = threadIdx.x; i < n; i += LR_THREADS) {
-        double z[LR_KMAX];
-        double m = -INFINITY;
-        for (int k = 0; k < K; ++k) {
-            double a = 0.0;
-            for (int c = 0; c < d; ++c) a += Wp[k * D + c] * X[(size_t)i * d + c];
-            a += Wp[k * D + d];
-            z[k] = a;
-            m = fmax(m, a);
-        }
-        const double zym = z[y[i]] - m;        // labels were checked before the first evaluation
-        double se = 0.0;
-        for (int k = 0; k < K; ++k) {
-            z[k] = exp(z[k] - m);
-            se += z[k];
-        }
-        for (int k = 0; k < K; ++k) ws[(size_t)i * K + k] = z[k] / se;
-        part += log(se) - zym;                 // logsumexp_k z_k - z_y
-    }
-    __syncthreads();
-    sh.red[threadIdx.x] = part;
-    __syncthreads();
-    for (int o = LR_THREADS / 2; o > 0; o >>= 1) {
-        if (threadIdx.x < o) sh.red[threadIdx.x] += sh.red[threadIdx.x + o];
-        __syncthreads();
-    }
-    double pen = 0.0;
-    for (int k = 0; k < K; ++k)
-        for (int c = 0; c < d; ++c) pen += Wp[k * D + c] * Wp[k * D + c];
-    const double f = sh.red[0] + 0.5 * inv_C * pen;
-    __syncthreads();
-    return f;
-}
-
-__global__ void __launch_bounds__(LR_THREADS) score_logreg_fit_kernel(const double* X, const int* y, int n, int d, int K, double inv_C,
-                                                                      int max_iter, double gtol, double* ws, double* Wout, double* info) {
-    __shared__ LogregShared sh;
-    const int tid = threadIdx.x;
-    const int D = d + 1, P = K * D;
-    int bad = 0;
-    for (int i = tid; i < n; i += LR_THREADS) bad |= (y[i] < 0 || y[i] >= K) ? 1 : 0;
-    bad = __syncthreads_or(bad);
-    if (tid < P) sh.W[tid] = 0.0;
-    __syncthreads();
-    if (bad) {                                 // a label outside 0..K-1: nothing is indexed with it
-        if (tid < P) Wout[tid] = 0.0;
-        if (tid == 0) info[0] = 0.0, info[1] = INFINITY, info[2] = INFINITY, info[3] = 4.0;
-        return;
-    }
-    double f = logreg_objective(sh, sh.W, X, y, n, d, K, inv_C, ws);
-    double gmax = INFINITY;
-    int it = 0, status = 1;
-    for (;;) {
-        // ---- 1. gradient and Hessian at W (probabilities in ws) ----
-        double hacc[LR_PMAX * LR_PMAX / LR_THREADS];
-#pragma unroll
-        for (int j = 0; j < LR_PMAX * LR_PMAX / LR_THREADS; ++j) hacc[j] = 0.0;
-        double gacc = 0.0;
-        for (int r0 = 0; r0 < n; r0 += LR_TILE) {
-            const int nr = n - r0 < LR_TILE ? n - r0 : LR_TILE;
-            __syncthreads();
-            for (int e = tid; e < nr * K; e += LR_THREADS) sh.pt[e] = ws[(size_t)r0 * K + e];
-            for (int e = tid; e < nr * D; e += LR_THREADS) {
-                const int r = e / D, c = e - r * D;
-                sh.xt[e] = c < d ? X[(size_t)(r0 + r) * d + c] : 1.0;
-            }
-            if (tid < nr) sh.yt[tid] = y[r0 + tid];
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < LR_PMAX * LR_PMAX / LR_THREADS; ++j) {
-                const int e = tid + j * LR_THREADS;
-                if (e < P * P) {
-                    const int row = e / P, col = e - row * P;
-                    const int k = row / D, a = row - k * D, l = col / D, b = col - l * D;
-                    double acc = hacc[j];
-                    for (int r = 0; r < nr; ++r) {
-                        const double pk = sh.pt[r * K + k], pl = sh.pt[r * K + l];
-                        const double w = k == l ? pk * (1.0 - pk) : -(pk * pl);
-                        acc += w * (sh.xt[r * D + a] * sh.xt[r * D + b]);
-                    }
-                    hacc[j] = acc;
-                }
-            }
-            if (tid < P) {
-                const int k = tid / D, a = tid - k * D;
-                for (int r = 0; r < nr; ++r) gacc += (sh.pt[r * K + k] - (sh.yt[r] == k ? 1.0 : 0.0)) * sh.xt[r * D + a];
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < LR_PMAX * LR_PMAX / LR_THREADS; ++j) {
-            const int e = tid + j * LR_THREADS;
-            if (e < P * P) {
-                const int row = e / P, col = e - row * P;
-                const int a = row % D, b = col % D;
-                double h = hacc[j];
-                if (row == col && a < d) h += inv_C;
-                if (a == d && b == d) h += 1.0 / (double)K;
-                sh.H[row * LR_PMAX + col] = h;
-            }
-        }
-        if (tid < P) sh.g[tid] = gacc + ((tid % D) < d ? inv_C * sh.W[tid] : 0.0);
-        __syncthreads();
-        gmax = 0.0;
-        for (int j = 0; j < P; ++j) gmax = fmax(gmax, fabs(sh.g[j]));
-        if (!(gmax > gtol)) {
-            status = gmax <= gtol ? 0 : 5;                         // 5: the gradient is NaN
-            break;
-        }
-        if (it >= max_iter) break;                                 // status 1
-        // ---- 2. Cholesky (lower triangle, in place) and s = -H^-1 g ----
-        bool spd = true;
-        for (int j = 0; j < P; ++j) {
-            const double djj = sh.H[j * LR_PMAX + j];
-            if (!(djj > 0.0)) {
-                spd = false;
-                break;                                             // read by every thread before anyone writes: uniform
-            }
-            const double ljj = sqrt(djj);
-            __syncthreads();
-            for (int i = j + tid; i < P; i += LR_THREADS) sh.H[i * LR_PMAX + j] = i == j ? ljj : sh.H[i * LR_PMAX + j] / ljj;
-            __syncthreads();
-            const int m = P - j - 1;
-            for (int e = tid; e < m * m; e += LR_THREADS) {
-                const int i = j + 1 + e / m, c = j + 1 + e % m;
-                if (c <= i) sh.H[i * LR_PMAX + c] -= sh.H[i * LR_PMAX + j] * sh.H[c * LR_PMAX + j];
-            }
-            __syncthreads();
-        }
-        if (!spd) {
-            status = 3;
-            break;
-        }
-        if (tid < P) sh.st[tid] = -sh.g[tid];
-        __syncthreads();
-        for (int j = 0; j < P; ++j) {                              // L u = -g
-            const double uj = sh.st[j] / sh.H[j * LR_PMAX + j];
-            __syncthreads();
-            if (tid == j) sh.st[j] = uj;
-            if (tid > j && tid < P) sh.st[tid] -= sh.H[tid * LR_PMAX + j] * uj;
-            __syncthreads();
-        }
-        for (int j = P - 1; j >= 0; --j) {                         // L^T s = u
-            const double sj = sh.st[j] / sh.H[j * LR_PMAX + j];
-            __syncthreads();
-            if (tid == j) sh.st[j] = sj;
-            if (tid < j) sh.st[tid] -= sh.H[j * LR_PMAX + tid] * sj;
-            __syncthreads();
-        }
-        double sb = 0.0;                                           // the step has no component along v; what rounding puts there
-        for (int k = 0; k < K; ++k) sb += sh.st[k * D + d];        // (about n eps per step) is taken out, so the intercepts stay zero-sum
-        sb /= (double)K;
-        __syncthreads();
-        if (tid < K) sh.st[tid * D + d] -= sb;
-        __syncthreads();
-        double gs = 0.0;
-        for (int j = 0; j < P; ++j) gs += sh.g[j] * sh.st[j];
-        // ---- 3. Armijo backtracking ----
-        const double slack = (double)n * 2.220446049250313e-16 * fabs(f);
-        double t = 1.0, fn = f;
-        bool ok = false;
-        for (int h = 0; h < 40; ++h) {
-            __syncthreads();
-            if (tid < P) sh.Wt[tid] = sh.W[tid] + t * sh.st[tid];
-            __syncthreads();
-            fn = logreg_objective(sh, sh.Wt, X, y, n, d, K, inv_C, ws);
-            if (fn <= f + 1e-4 * t * gs + slack) {
-                ok = true;
-                break;
-            }
-            t *= 0.5;
-        }
-        if (!ok) {
-            status = 2;
-            break;
-        }
-        if (tid < P) sh.W[tid] = sh.Wt[tid];
-        __syncthreads();
-        f = fn;
-        ++it;
-    }
-    __syncthreads();
-    if (tid < P) Wout[tid] = sh.W[tid];
-    if (tid == 0) info[0] = (double)it, info[1] = gmax, info[2] = f, info[3] = (double)status;
-}
-
-extern "C" size_t eg_score_logreg_ws_bytes(int n, int K) {
-    return n > 0 && K > 0 ? (size_t)n * K * sizeof(double) : 0;
-}
-
-extern "C" int eg_score_logreg_fit(const double* X, const int* y, int n, int d, int K, double inv_C, int max_iter, double gtol, void* ws,
-                                   double* W, double* info, eg_stream_t s) {
-    EG_REQUIRE(X && y && ws && W && info && n > 0 && d > 0 && max_iter >= 0 && gtol >= 0.0, "eg_score_logreg_fit: bad argument");
-    EG_REQUIRE(K >= 3 && K <= LR_KMAX, "eg_score_logreg_fit: K = %d classes, 3..%d supported (sklearn fits K = 2 in the binomial form)", K, LR_KMAX);
-    EG_REQUIRE((long long)K * (d + 1) <= LR_PMAX, "eg_score_logreg_fit: K (d + 1) = %lld parameters exceed the %d the LDS Hessian holds",
-               (long long)K * (d + 1), LR_PMAX);
-    EG_REQUIRE(inv_C > 0.0, "eg_score_logreg_fit: inv_C must be positive (the penalty makes the Hessian definite)");
-    hipLaunchKernelGGL(score_logreg_fit_kernel, dim3(1), dim3(LR_THREADS), 0, (hipStream_t)s, X, y, n, d, K, inv_C, max_iter, gtol,
-                       (double*)ws, W, info);
-    EG_LAUNCH_CHECK();
-    return 0;
-}
-
+// The fit itself (classifier.fit of BetVAE.py:265-266) is eg_score_softmax_fit (score_fstat.hip); its training predictions:
 // predict[i] = np.argmax of the logits of row i (first index on ties); correct[0] = #{predict == y} (zeroed here; integer atomics)
 __global__ void score_logreg_accuracy_kernel(const double* __restrict__ X, const int* __restrict__ y, int n, int d, int K,
                                              const double* __restrict__ W, int* __restrict__ predict, unsigned long long* __restrict__ correct) {
@@ -660,7 +425,8 @@ extern "C" int eg_score_sq_corr(const double* codes, int n, int k, const double*
 // (liblinear weights only the positive side of a one-vs-rest problem).  f is strictly convex: one optimum, whatever liblinear's
 // randomised dual coordinate descent stops at.  Generalised Newton from (0, 0): one pass over the rows gives f, the gradient and the
 // 2 x 2 generalised Hessian I + 2 sum_{active} c_i [x_i, 1][x_i, 1]^T, which is solved in closed form; Armijo backtracking with
-// eg_score_logreg_fit's constants.  The sums at an accepted trial point are the next iteration's.
+// eg_score_softmax_fit's constants (1e-4, halving, 40 trials, the n eps |f| slack).  The sums at an accepted trial point are the next
+// iteration's.
 struct SvcPoint {
     double f, gw, gb, hww, hwb, hbb;
 };

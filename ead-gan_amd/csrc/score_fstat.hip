@@ -1,7 +1,17 @@
-// F-stat disentanglement score (dSprites/score/F_score.py, colored_dSprites/score/ likewise): the explicitness half on the device.
-//   eg_score_softmax_fit    the optimum of sklearn's LogisticRegression(C) on all code columns, K = 2 .. 64 classes, K (d + 1) <= 256
+// The logistic solver of the fitted scores and the explicitness half of F-stat (dSprites/score/F_score.py, BetVAE.py;
+// colored_dSprites/score/ likewise) on the device.
+//   eg_score_softmax_fit    the optimum of sklearn's LogisticRegression(C), K = 2 .. 64 classes, K (d + 1) <= 256: F-stat's fit on all
+//                           code columns and the BetaVAE score's classifier
 //   eg_score_softmax_proba  predict_proba at that optimum
 //   eg_score_auc_ovr        exact one-vs-rest pair counts of roc_auc_score (Mann-Whitney form)
+// The objective, K >= 3 (sklearn minimises f / n, the same point):
+//   f(W) = sum_i [ logsumexp_k z_ik - z_i,y_i ] + inv_C / 2 * sum_{k, a < d} W_ka^2,   z_ik = sum_{a<d} W_ka x_ia + W_kd
+// and for K = 2 the binomial form with one weight row, sum_i [ log(1 + exp(z_i)) - y_i z_i ] + inv_C / 2 * |w|^2.  Damped Newton from
+// W = 0: s = -H^-1 g by Cholesky, then Armijo backtracking t = 1, 1/2, ... (SM_TRIALS trials at most) until
+//   f(W + t s) <= f(W) + 1e-4 t g.s + n eps |f(W)|
+// where the last term is the rounding bound of the row sum: once the decrease falls below what f resolves, the full Newton step is taken
+// as it is.  The iteration stops when |g|inf <= gtol or after max_iter steps.  info[3]: 0 converged, 1 max_iter reached, 2 line search
+// failed, 3 Hessian not positive definite, 4 a label outside 0..K-1, 5 non-finite gradient, 6 a class without a sample.
 // All float64.  No float atomics, no hand-off between workgroups inside a launch: every row sum has one order (rows ascending inside a
 // slice, slices ascending), so two calls give the same bits.
 #include <math.h>
@@ -13,7 +23,7 @@
 #define SM_KMAX 64
 #define SM_SLICES 64           // row slices of the gradient / Hessian sums at most
 #define SM_SLICE_ROWS 1024     // rows per slice at least (below SM_SLICES slices)
-#define SM_TRIALS 40           // Armijo halvings of one Newton step (eg_score_logreg_fit's)
+#define SM_TRIALS 40           // Armijo halvings of one Newton step at most
 #define SM_EPS 2.220446049250313e-16
 
 // The decision record of the Newton iteration: written by the kernels below in float64, read by the host after each trial only to choose
@@ -204,8 +214,8 @@ __global__ void __launch_bounds__(SM_THREADS) sm_grad_kernel(SmWs w, const doubl
     if (tid < m.P) w.gpart[(size_t)blockIdx.x * m.P + tid] = acc;
 }
 
-// The decision after a trial, one workgroup: f(W + t s) from the partials in a fixed order and Armijo's test with eg_score_logreg_fit's
-// constants and rounding slack.  A rejected trial halves t (or ends the fit with status 2); an accepted one becomes the new W and asks for
+// The decision after a trial, one workgroup: f(W + t s) from the partials in a fixed order and Armijo's test with the constants and
+// rounding slack of the file header.  A rejected trial halves t (or ends the fit with status 2); an accepted one becomes the new W and asks for
 // its gradient (SM_GRAD), which sm_grad_kernel and sm_converge_kernel supply behind this launch.
 __global__ void __launch_bounds__(SM_THREADS) sm_decide_kernel(SmWs w, SmDims m, double inv_C) {
     __shared__ double red[SM_THREADS];

@@ -792,19 +792,6 @@ def score_pair_absdiff_mean(x, L, M, ncol, feat):
     lib().call("eg_score_pair_absdiff_mean", _p(x), L, M, ncol, _p(feat), _stream())
 
 
-# info[3] of eg_score_logreg_fit
-LOGREG_STATUS = {0: "converged", 1: "max_iter reached", 2: "line search failed", 3: "Hessian not positive definite",
-                 4: "a label outside 0..K-1", 5: "non-finite gradient"}
-
-
-def score_logreg_ws_bytes(n, K):
-    return lib().query("eg_score_logreg_ws_bytes", n, K)
-
-
-def score_logreg_fit(X, y, n, d, K, inv_C, max_iter, gtol, ws, W, info):
-    lib().call("eg_score_logreg_fit", _p(X), _p(y), n, d, K, inv_C, max_iter, gtol, _p(ws), _p(W), _p(info), _stream())
-
-
 def score_logreg_accuracy(X, y, n, d, K, W, predict, correct):
     lib().call("eg_score_logreg_accuracy", _p(X), _p(y), n, d, K, _p(W), _p(predict), _p(correct), _stream())
 
@@ -826,8 +813,9 @@ def score_svc1_accuracy(X, y, n, P, K, W, predict, correct):
     lib().call("eg_score_svc1_accuracy", _p(X), _p(y), n, P, K, _p(W), _p(predict), _p(correct), _stream())
 
 
-# info[3] of eg_score_softmax_fit: eg_score_logreg_fit's codes and the one the larger solver adds
-SOFTMAX_STATUS = {**LOGREG_STATUS, 6: "a class without a sample"}
+# info[3] of eg_score_softmax_fit
+SOFTMAX_STATUS = {0: "converged", 1: "max_iter reached", 2: "line search failed", 3: "Hessian not positive definite",
+                  4: "a label outside 0..K-1", 5: "non-finite gradient", 6: "a class without a sample"}
 
 
 def score_softmax_ws_bytes(n, d, K):

@@ -300,29 +300,32 @@ def factor_vae(eval_codes, group_codes, labels, num_labels):
             "factorVAE_metric_detail": train_data}
 
 
+def _class_ids(y, n, dev):
+    """class ids y [n] (host or device) -> contiguous int32 [n] on ``dev``"""
+    y_d = (y if torch.is_tensor(y) else torch.from_numpy(np.asarray(y).reshape(-1))).to(device=dev, dtype=torch.int32).contiguous()
+    if y_d.numel() != n:
+        raise ValueError(f"{y_d.numel()} labels for {n} rows")
+    return y_d
+
+
 def logreg_fit(X, y, K, C=1.0, max_iter=50, gtol=1e-10):
-    """The optimum of sklearn's multinomial LogisticRegression(C) on device X [n,d] float64 and class ids y [n] in 0..K-1 (host or device),
-    by eg_score_logreg_fit's float64 Newton iteration, and its training predictions.  ``gtol`` bounds the gradient's inf-norm of the
-    summed objective.  -> (W f64 [K,d+1] (coefficients | intercept), predict int32 [n], correct int64 [1]) on the device, info (host
-    float64: iterations, final |g|inf, objective, status).  Raises RuntimeError when the solver did not reach gtol."""
+    """The optimum of sklearn's multinomial LogisticRegression(C) on device X [n,d] float64 and class ids y [n] in 0..K-1 (host or device):
+    ``softmax_fit`` and its training predictions.  ``gtol`` bounds the gradient's inf-norm of the summed objective.  3 <= K <= 64,
+    K (d + 1) <= 256; K = 2 is refused, because the prediction kernel reads K weight rows and the binomial fit has one.
+    -> (W f64 [K,d+1] (coefficients | intercept), predict int32 [n], correct int64 [1]) on the device, info (host float64: iterations,
+    final |g|inf, objective, status).  Raises RuntimeError when the solver did not reach gtol."""
+    if K == 2:
+        raise RuntimeError("logreg_fit: K = 2 classes: sklearn fits two classes in the binomial form, whose one weight row has no "
+                           "argmax (softmax_fit fits it)")
     _require_cuda(X)
     X = X.to(torch.float64).contiguous()
     n, d = X.shape
     dev = X.device
-    y_d = (y if torch.is_tensor(y) else torch.from_numpy(np.asarray(y).reshape(-1))).to(device=dev, dtype=torch.int32).contiguous()
-    if y_d.numel() != n:
-        raise ValueError(f"{y_d.numel()} labels for {n} rows")
-    ws = torch.empty(max(ops.score_logreg_ws_bytes(n, K), 8), device=dev, dtype=torch.uint8)
-    W = torch.empty(K, d + 1, device=dev, dtype=torch.float64)
-    info = torch.empty(4, device=dev, dtype=torch.float64)
-    ops.score_logreg_fit(X, y_d, n, d, K, 1.0 / C, max_iter, gtol, ws, W, info)
+    y_d = _class_ids(y, n, dev)
+    W, info_h = softmax_fit(X, y_d, K, C, max_iter, gtol)
     predict = torch.empty(n, device=dev, dtype=torch.int32)
     correct = torch.empty(1, device=dev, dtype=torch.int64)
     ops.score_logreg_accuracy(X, y_d, n, d, K, W, predict, correct)
-    info_h = info.cpu().numpy()                                                    # the one sync: offline evaluation
-    if info_h[3] != 0:
-        raise RuntimeError(f"logistic fit did not reach |g|inf <= {gtol:g}: {int(info_h[0])} iterations, |g|inf = {info_h[1]:.3e} "
-                           f"(status {int(info_h[3])}: {ops.LOGREG_STATUS.get(int(info_h[3]), '?')})")
     return W, predict, correct, info_h
 
 
@@ -369,9 +372,7 @@ def svc1_fit(X, y, K, C=0.01, max_iter=50, gtol=1e-10):
     X = (X.reshape(-1, 1) if X.dim() == 1 else X).contiguous()
     n, P = X.shape
     dev = X.device
-    y_d = (y if torch.is_tensor(y) else torch.from_numpy(np.asarray(y).reshape(-1))).to(device=dev, dtype=torch.int32).contiguous()
-    if y_d.numel() != n:
-        raise ValueError(f"{y_d.numel()} labels for {n} rows")
+    y_d = _class_ids(y, n, dev)
     W = torch.empty(P, K, 2, device=dev, dtype=torch.float64)
     info = torch.empty(P, K, 4, device=dev, dtype=torch.float64)
     ops.score_svc1_fit(X, y_d, n, P, K, float(C), max_iter, gtol, W, info)
@@ -442,9 +443,7 @@ def softmax_fit(X, y, K, C=1.0, max_iter=50, gtol=SOFTMAX_GTOL):
     X = X.to(torch.float64).contiguous()
     n, d = X.shape
     dev = X.device
-    y_d = (y if torch.is_tensor(y) else torch.from_numpy(np.asarray(y).reshape(-1))).to(device=dev, dtype=torch.int32).contiguous()
-    if y_d.numel() != n:
-        raise ValueError(f"{y_d.numel()} labels for {n} rows")
+    y_d = _class_ids(y, n, dev)
     ws = torch.empty(max(ops.score_softmax_ws_bytes(n, d, K), 8), device=dev, dtype=torch.uint8)
     W = torch.empty(1 if K == 2 else K, d + 1, device=dev, dtype=torch.float64)
     info = torch.empty(4, device=dev, dtype=torch.float64)
@@ -555,30 +554,34 @@ def load_encoders(kind, encoder_pxy_path, encoder_path, device="cuda", dtype="f3
     return P.to(device).eval(), E.to(device).eval()
 
 
+def _open_run(kind, npz_path, encoder_pxy_path, encoder_path, seed, batch, device):
+    """What every score script does before its plan: the archive, the encoders, then ``np.random.seed(seed)`` (else the global numpy
+    stream as it stands).  -> (the open archive, its imgs, the Representation, kind == "colored")"""
+    if kind not in KINDS:
+        raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
+    dataset_zip = np.load(npz_path, encoding="latin1", allow_pickle=True)
+    imgs = dataset_zip["imgs"]
+    P, E = load_encoders(kind, encoder_pxy_path, encoder_path, device)
+    if seed is not None:
+        np.random.seed(seed)
+    return dataset_zip, imgs, Representation(P, E, kind, batch), kind == "colored"
+
+
 def run_score(kind, metric, npz_path, encoder_pxy_path, encoder_path, seed=None, batch=4096, groups=None, device="cuda"):
     """What dSprites|colored_dSprites/score/{MIG,FactorVAE,BetVAE}.py do at module level, on the MI355X.  ``seed``: np.random.seed first (else
     the global numpy stream as it stands).  ``groups``: score only the first groups of the 500-group FactorVAE / BetaVAE plan (the plan is
     drawn in full).  Prints the score; returns it (MIG), the reference's three-key dict (FactorVAE) or its one-key dict (BetaVAE).
     score/SAP.py is ``run_sap`` and score/F_score.py ``run_fstat``: this function's refusal of every other metric name is part of its
     contract."""
-    if kind not in KINDS:
-        raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
     if metric not in ("mig", "factor_vae", "beta_vae"):
         raise ValueError(f"metric must be 'mig', 'factor_vae' or 'beta_vae', got {metric!r}")
-    colored = kind == "colored"
-    dataset_zip = np.load(npz_path, encoding="latin1", allow_pickle=True)
-    imgs = dataset_zip["imgs"]
-    latents_values = dataset_zip["latents_values"]
-    P, E = load_encoders(kind, encoder_pxy_path, encoder_path, device)
-    if seed is not None:
-        np.random.seed(seed)
-    rep = Representation(P, E, kind, batch)
+    dataset_zip, imgs, rep, colored = _open_run(kind, npz_path, encoder_pxy_path, encoder_path, seed, batch, device)
     N = imgs.shape[0]
     if metric == "mig":
         plan = mig_plan(N, colored)
         data = torch.from_numpy(np.ascontiguousarray(imgs)).to(device)
         codes = rep.codes(data, plan["idx"], plan["gains"])
-        score, _, _ = mig(codes, latents_values[:, 1:6][plan["idx"]])
+        score, _, _ = mig(codes, dataset_zip["latents_values"][:, 1:6][plan["idx"]])
         print("MIG score", score)
         return score
     metadata = dataset_zip["metadata"][()]
@@ -606,16 +609,8 @@ def run_score(kind, metric, npz_path, encoder_pxy_path, encoder_path, seed=None,
 def run_sap(kind, npz_path, encoder_pxy_path, encoder_path, seed=None, batch=4096, device="cuda"):
     """What dSprites|colored_dSprites/score/SAP.py do at module level, on the MI355X (``run_score``'s arguments without the metric name).
     Prints ``score`` as the script does; returns the reference's dict {"SAP_metric", "SAP_metric_detail"}."""
-    if kind not in KINDS:
-        raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
-    colored = kind == "colored"
-    dataset_zip = np.load(npz_path, encoding="latin1", allow_pickle=True)
-    imgs = dataset_zip["imgs"]
+    dataset_zip, imgs, rep, colored = _open_run(kind, npz_path, encoder_pxy_path, encoder_path, seed, batch, device)
     metadata = dataset_zip["metadata"][()]
-    P, E = load_encoders(kind, encoder_pxy_path, encoder_path, device)
-    if seed is not None:
-        np.random.seed(seed)
-    rep = Representation(P, E, kind, batch)
     plan = sap_plan(metadata["latents_sizes"], imgs.shape[0], colored)
     latents = sap_latents(plan["latent_ids"], metadata["latents_names"], metadata["latents_possible_values"])
     data = torch.from_numpy(np.ascontiguousarray(imgs)).to(device)
@@ -628,16 +623,8 @@ def run_sap(kind, npz_path, encoder_pxy_path, encoder_path, seed=None, batch=409
 def run_fstat(kind, npz_path, encoder_pxy_path, encoder_path, seed=None, batch=4096, device="cuda"):
     """What dSprites|colored_dSprites/score/F_score.py do at module level, on the MI355X (``run_sap``'s arguments).  Prints ``modu_score``
     and ``expl_score`` as the script does; returns the reference's five-key dict."""
-    if kind not in KINDS:
-        raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
-    colored = kind == "colored"
-    dataset_zip = np.load(npz_path, encoding="latin1", allow_pickle=True)
-    imgs = dataset_zip["imgs"]
+    dataset_zip, imgs, rep, colored = _open_run(kind, npz_path, encoder_pxy_path, encoder_path, seed, batch, device)
     metadata = dataset_zip["metadata"][()]
-    P, E = load_encoders(kind, encoder_pxy_path, encoder_path, device)
-    if seed is not None:
-        np.random.seed(seed)
-    rep = Representation(P, E, kind, batch)
     plan = fstat_plan(metadata["latents_sizes"], imgs.shape[0], colored)
     data = torch.from_numpy(np.ascontiguousarray(imgs)).to(device)
     codes = rep.codes(data, plan["idx"], plan["gains"])                            # F_score.py:304 builds the same five columns

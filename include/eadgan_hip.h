@@ -570,18 +570,8 @@ int eg_score_fvae_votes(const double* x, int L, int M, int ncol, const double* e
 /* BetaVAEMetric.evaluate's features (BetVAE.py:256-257): for group g (rows g*L.. of x [M*L][ncol] float64)
  * feat[g] = np.mean(np.abs(x_g[0::2] - x_g[1::2]), axis=0), bit for bit (numpy's row-sequential axis-0 reduction).  L must be even. */
 int eg_score_pair_absdiff_mean(const double* x, int L, int M, int ncol, double* feat, eg_stream_t s);
-/* classifier.fit of BetVAE.py:265-266: the optimum of sklearn's multinomial LogisticRegression(C = 1 / inv_C) on X [n][d] float64 with
- * class ids y [n] int32 in 0..K-1, the minimiser of  sum_i CE(softmax(W [x_i, 1]), y_i) + inv_C / 2 * |coefficients|^2  (intercepts
- * unpenalised, zero-sum), by a float64 damped Newton iteration from W = 0 in one workgroup (Hessian + v v^T on the intercept block,
- * Cholesky in LDS, Armijo backtracking); every row sum has a fixed order, two runs give the same bits.  3 <= K <= 8, K (d + 1) <= 64,
- * inv_C > 0.  Stops when the gradient's inf-norm is <= gtol or after max_iter steps.  W [K][d+1] (coefficients | intercept);
- * info [4] float64 = (iterations, final |g|inf, objective, status: 0 converged, 1 max_iter reached, 2 line search failed, 3 Hessian not
- * positive definite, 4 a label outside 0..K-1 (W = 0, nothing computed), 5 non-finite gradient).  ws: eg_score_logreg_ws_bytes bytes. */
-size_t eg_score_logreg_ws_bytes(int n, int K);
-int eg_score_logreg_fit(const double* X, const int* y, int n, int d, int K, double inv_C, int max_iter, double gtol, void* ws, double* W,
-                        double* info, eg_stream_t s);
-/* classifier.score's two parts (BetVAE.py:268): predict[i] = np.argmax of the logits W [x_i, 1] (first index on ties),
- * correct[0] = #{i: predict[i] == y[i]} (int64, zeroed here) */
+/* classifier.score's two parts (BetVAE.py:268) at the W [K][d+1] of eg_score_softmax_fit (K >= 3: one weight row per class):
+ * predict[i] = np.argmax of the logits W [x_i, 1] (first index on ties), correct[0] = #{i: predict[i] == y[i]} (int64, zeroed here) */
 int eg_score_logreg_accuracy(const double* X, const int* y, int n, int d, int K, const double* W, int* predict, long long* correct,
                              eg_stream_t s);
 /* SAP (dSprites/score/SAP.py:283-309, colored :304-330).  R [k][nf] float64: R[i][j] = cov(i, j)^2 / var(i) / var(j) of code column i of
@@ -592,9 +582,9 @@ int eg_score_sq_corr(const double* codes, int n, int k, const double* fv, int nf
  * of LinearSVC(C, class_weight="balanced") with sklearn's defaults (L2 penalty, squared hinge, one-vs-rest, the intercept a regularised
  * weight).  Problem (p, k) minimises  (w^2 + b^2) / 2 + sum_i c_i max(0, 1 - s_i (w x_ip + b))^2,  s_i = +1 where y_i = k and -1
  * elsewhere, c_i = C n / (K count_k) where y_i = k and C elsewhere -- strictly convex, one optimum.  One workgroup per (p, k): float64
- * generalised Newton from (0, 0) with the 2 x 2 Hessian solved in closed form and eg_score_logreg_fit's Armijo backtracking; counts and
- * weights come from y on the device; fixed summation order, two runs give the same bits.  3 <= K <= 64, C > 0.  Stops when the
- * gradient's inf-norm is <= gtol or after max_iter steps.  W [P][K][2] = (w, b); info [P][K][4] float64 = (iterations, final |g|inf,
+ * generalised Newton from (0, 0) with the 2 x 2 Hessian solved in closed form and eg_score_softmax_fit's Armijo backtracking (1e-4,
+ * halving, 40 trials, the n eps |f| slack); counts and weights come from y on the device; fixed summation order, two runs give the
+ * same bits.  3 <= K <= 64, C > 0.  Stops when the gradient's inf-norm is <= gtol or after max_iter steps.  W [P][K][2] = (w, b); info [P][K][4] float64 = (iterations, final |g|inf,
  * objective, status: 0 converged, 1 max_iter reached, 2 line search failed, 4 a label outside 0..K-1 or a class without a sample (W = 0,
  * nothing computed), 5 non-finite).  No workspace. */
 int eg_score_svc1_fit(const double* X, const int* y, int n, int P, int K, double C, int max_iter, double gtol, double* W, double* info,
@@ -603,21 +593,26 @@ int eg_score_svc1_fit(const double* X, const int* y, int n, int P, int K, double
  * correct [P] int64 (zeroed here) = #{i: predict[p][i] == y[i]} */
 int eg_score_svc1_accuracy(const double* X, const int* y, int n, int P, int K, const double* W, int* predict, long long* correct,
                            eg_stream_t s);
-/* F-stat, the explicitness half (dSprites/score/F_score.py:327-338, colored :345-356).  classifier.fit: the optimum of sklearn's
- * LogisticRegression(C = 1 / inv_C) on X [n][d] float64 with class ids y [n] int32 in 0..K-1.  K >= 3: the multinomial objective of
- * eg_score_logreg_fit, W [K][d+1] with zero-sum intercepts.  K = 2: the binomial form sklearn fits for two classes,
+/* The logistic fit of the fitted scores: classifier.fit of F-stat's explicitness half (dSprites/score/F_score.py:327-338, colored
+ * :345-356) and of the BetaVAE score (BetVAE.py:265-266).  The optimum of sklearn's LogisticRegression(C = 1 / inv_C) on X [n][d] float64
+ * with class ids y [n] int32 in 0..K-1.  K >= 3: the multinomial objective
+ * sum_i CE(softmax(W [x_i, 1]), y_i) + inv_C / 2 * |coefficients|^2  (sklearn's objective times n; intercepts unpenalised), W [K][d+1]
+ * (coefficients | intercept) with zero-sum intercepts.  K = 2: the binomial form sklearn fits for two classes,
  * sum_i [log(1 + exp(z_i)) - y_i z_i] + inv_C / 2 |w|^2 with z_i = w . x_i + b, W [1][d+1] (not the two-class softmax: its penalty
- * differs).  2 <= K <= 64, K (d + 1) <= 256, inv_C > 0; everything else is refused.  Float64 damped Newton from W = 0 with
- * eg_score_logreg_fit's Armijo constants and rounding slack.  The row sums run over many workgroups, each a launch of its own in stream
- * order: probabilities and objective partials, Armijo's test, gradient partials per row slice of an accepted trial, the P x P Hessian as per-slice partial slabs in ws and
- * their reduction in ascending order; Cholesky and the triangular solves run on the Hessian in global memory in one workgroup.  No
- * workgroup waits on another, no float atomics: two calls give the same bits.
+ * differs).  2 <= K <= 64, K (d + 1) <= 256, inv_C > 0; everything else is refused.  Float64 damped Newton from W = 0: the Hessian (for
+ * K >= 3 plus v v^T on the intercept block, v = 1 / sqrt(K), the one null direction; the mean of the step's intercepts, rounding only, is
+ * taken out), Cholesky, and Armijo backtracking t = 1, 1/2, ... for 40 trials at most until
+ * f(W + t s) <= f(W) + 1e-4 t g.s + n eps |f(W)|  (the last term is the rounding bound of the row sum).  Stops when the gradient's
+ * inf-norm is <= gtol or after max_iter steps.  The row sums run over many workgroups, each a launch of its own in stream
+ * order: probabilities and objective partials, Armijo's test, gradient partials per row slice of an accepted trial, the P x P Hessian
+ * as per-slice partial slabs in ws and their reduction in ascending order; Cholesky and the triangular solves run on the Hessian in
+ * global memory in one workgroup.  No workgroup waits on another, no float atomics: two calls give the same bits.
  * THE ONE BLOCKING ENTRY POINT OF THIS HEADER: the loop over Newton iterations and backtracking trials runs on the host inside the call.
  * Every decision (accept, backtrack, converged, failed) is taken on the device in float64 and written to a small record in ws; after
  * each trial the host copies that record back (a stream synchronisation) only to choose the next launch.  A stream that is capturing
- * is refused.  info [4] float64 = (iterations, final |g|inf, objective, status: eg_score_logreg_fit's 0..5 -- 0 converged, 1 max_iter
- * reached, 2 line search failed, 3 Hessian not positive definite, 4 a label outside 0..K-1, 5 non-finite gradient (a non-finite input
- * ends here) -- and 6 a class without a sample; 4 and 6 leave W = 0).  ws: eg_score_softmax_ws_bytes bytes. */
+ * is refused.  info [4] float64 = (iterations, final |g|inf, objective, status: 0 converged, 1 max_iter reached, 2 line search failed,
+ * 3 Hessian not positive definite, 4 a label outside 0..K-1, 5 non-finite gradient (a non-finite input ends here), 6 a class without a
+ * sample; 4 and 6 leave W = 0).  ws: eg_score_softmax_ws_bytes bytes. */
 size_t eg_score_softmax_ws_bytes(int n, int d, int K);
 int eg_score_softmax_fit(const double* X, const int* y, int n, int d, int K, double inv_C, int max_iter, double gtol, void* ws, double* W,
                          double* info, eg_stream_t s);

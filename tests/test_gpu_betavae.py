@@ -1,4 +1,4 @@
-"""The BetaVAE score of dSprites / colored-dSprites encoders on the MI355X (ead-gan_amd/score.py, csrc/score.hip) against the reference's
+"""The BetaVAE score of dSprites / colored-dSprites encoders on the MI355X (ead-gan_amd/score.py, csrc/score.hip, score_fstat.hip) against the reference's
 own score/BetVAE.py, recorded in tests/golden/score_betavae_{dsprites,colored}.npz by tests/make_betavae_golden.py.
 
 The solver is judged three ways: by an optimality certificate (numpy's float64 gradient of the objective at the returned W), against the
@@ -140,7 +140,8 @@ PROBLEMS = {
     "separable_3x1": lambda: (np.array([[-1.0], [0.3], [2.0]]), np.array([0, 1, 2]), 3),     # one row per class: line search, rank-one term
     "n61_K3_d5": lambda: problem(61, 3, 5, 1),
     "n500_K5_d5": lambda: problem(500, 5, 5, 2),                                             # the reference's size
-    "n5003_K8_d7": lambda: problem(5003, 8, 7, 3),                                           # K (d+1) = 64, ragged last tile
+    "n5003_K8_d7": lambda: problem(5003, 8, 7, 3),                                           # K (d+1) = 64, five row slices, ragged last
+    "n61_K8_d8": lambda: problem(61, 8, 8, 5),                                               # K (d+1) = 72: four and a half Hessian tiles
     "n61_constant_column": lambda: problem(61, 3, 5, 4, const_col=2),
 }
 
@@ -170,9 +171,9 @@ def test_solver_refuses_what_it_cannot_fit():
     Xd = torch.from_numpy(X).to(DEV)
     with pytest.raises(RuntimeError, match="binomial"):
         eg.score.logreg_fit(Xd, y % 2, 2)
-    X9 = torch.zeros(61, 8, device=DEV, dtype=torch.float64)
+    X33 = torch.zeros(61, 32, device=DEV, dtype=torch.float64)
     with pytest.raises(RuntimeError, match="exceed"):
-        eg.score.logreg_fit(X9, y, 8)                                                     # 8 * 9 = 72 parameters
+        eg.score.logreg_fit(X33, y, 8)                                                    # 8 * 33 = 264 parameters
     for bad in (3, -1):
         yb = y.copy()
         yb[17] = bad
@@ -180,6 +181,19 @@ def test_solver_refuses_what_it_cannot_fit():
             eg.score.logreg_fit(Xd, yb, 3)
     W, _, _, info = eg.score.logreg_fit(Xd, y, 3)
     assert info[3] == 0 and torch.isfinite(W).all()
+
+
+def test_logreg_fit_is_softmax_fit():
+    """one solver behind both Python paths: the same bits, and the predictions are numpy's argmax at that W"""
+    X, y, K = PROBLEMS["n61_K3_d5"]()
+    Xd = torch.from_numpy(X).to(DEV)
+    W, predict, correct, info = eg.score.logreg_fit(Xd, y, K, gtol=1e-10)
+    Ws, infos = eg.score.softmax_fit(Xd, y, K, gtol=1e-10)
+    assert torch.equal(W, Ws) and np.array_equal(info, infos)
+    Xt = np.concatenate([X, np.ones((X.shape[0], 1))], 1)
+    want = np.argmax(Xt @ W.cpu().numpy().T, axis=1)
+    assert np.array_equal(predict.cpu().numpy(), want)
+    assert int(correct.item()) == int((want == y).sum())
 
 
 # ---- 4. end to end through run_score ----------------------------------------------------------------------------------------------------
