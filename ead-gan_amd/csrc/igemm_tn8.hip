@@ -16,6 +16,30 @@
 //     barrier; both operands are K-major in memory, fragments come from `ds_read_b64_tr_b16` (transposed LDS reads);
 //   * both operands staged by LDS-DMA (buffer descriptors, 256-byte rows, 32-byte blocks XOR-swizzled on the source side) into a ring
 //     of three stages, two K steps in flight behind a counted vmcnt, one barrier per K step.
+//
+// K loop (software-pipelined, the shape of igemm_nt8s.hip).  A K step is two 32-row halves; the fragments of a half are 16 registers
+// of P (af0 / af1, double buffered) and 32 of the patch (bfr[j], column tile j).  Every half walks its MFMAs column tile by column tile:
+// the NI MFMAs of column tile j, then the reads of the NEXT half's bfr[j] and of one row tile of its P fragments, then -- in the second
+// half -- one DMA piece of the step three ahead with its address arithmetic, then __builtin_amdgcn_sched_barrier(0).  No MFMA waits for
+// a read issued in its own group, and nothing but four fragment reads stands in front of an iteration's first MFMA.  The order in which
+// an accumulator tile receives its MFMAs (K steps in order, half 0 before half 1, the same operands) is that of the loop this replaced:
+// the slabs are bit-identical.
+//
+//     iteration t, stage st = t % 3:
+//       half A   MFMA(step t, half 0)  |  reads (step t, half 1) from stage st
+//       s_waitcnt vmcnt(pieces of step t+2) lgkmcnt(0) ; s_barrier
+//       half B   MFMA(step t, half 1)  |  reads (step t+1, half 0) from stage (t+1) % 3  |  DMA of step t+3 into stage st
+//
+// Hazards.  Before the loop steps 0, 1, 2 are issued, step 0 is waited for and published by a barrier, and its half 0 is read.
+// RAW: the pieces of step t+1 were issued in iteration t-2 (or the prologue); the only pieces issued after them are those of step t+2,
+// so the counted vmcnt in the middle of iteration t has them landed for this wave and the barrier behind it for every wave; the first
+// read of step t+1 is in half B of iteration t, behind that barrier (its half 1 is read in half A of iteration t+1).
+// WAR: stage st is read for the last time in half A of iteration t (step t, half 1); the lgkmcnt(0) in front of the barrier retires those
+// reads in every wave before any wave issues a piece of step t+3 into the stage, in half B behind the barrier.  Stage (t+1) % 3 is
+// written next in half B of iteration t+1, behind that iteration's barrier, when its last reads (half A of t+1) are retired the same way.
+// Past the last step the reads of half B fetch stale bytes of a valid stage that no MFMA uses (no DMA is in flight then).
+// The builtins do not touch memory as far as the optimiser knows: the empty asm statements in publish() keep the reads on their side
+// of wait and barrier at IR level, sched_barrier(0) in the machine scheduler; the emitted loop was read against this list.
 #include <string.h>
 #include <algorithm>
 
@@ -36,6 +60,18 @@ __device__ __forceinline__ void tn8_wait(int n) {        // vmcnt(n) lgkmcnt(0) 
         default: __builtin_amdgcn_s_waitcnt(7 | (7 << 4)); break;
     }
 }
+__device__ __forceinline__ void tn8_wait2(int n) {       // the prologue's: two K steps may stay in flight, n = 2 * (0..7)
+    switch (n) {
+        case 2: __builtin_amdgcn_s_waitcnt(2 | (7 << 4)); break;
+        case 4: __builtin_amdgcn_s_waitcnt(4 | (7 << 4)); break;
+        case 6: __builtin_amdgcn_s_waitcnt(6 | (7 << 4)); break;
+        case 8: __builtin_amdgcn_s_waitcnt(8 | (7 << 4)); break;
+        case 10: __builtin_amdgcn_s_waitcnt(10 | (7 << 4)); break;
+        case 12: __builtin_amdgcn_s_waitcnt(12 | (7 << 4)); break;
+        case 14: __builtin_amdgcn_s_waitcnt(14 | (7 << 4)); break;
+        default: __builtin_amdgcn_s_waitcnt(0 | (7 << 4)); break;
+    }
+}
 
 // CH: channels per tile on both sides (128: the CelebA layers; 64: the dSprites generators; 32: the first trunk layers of the dSprites networks,
 // whose 64 x 32 tile of P is four DMA pieces: waves 0..3 issue one each) = 16-bit elements per LDS row
@@ -48,8 +84,12 @@ __global__ __launch_bounds__(512) void igemm_tn8_kernel(const Tn8Params p) {
     constexpr int NI = CH / 32, NJ = CH / 16;            // MFMA tiles per wave: output channels (half of CH) x input channels
     constexpr int NPP_P = (64 / RPP + 7) / 8;            // P pieces per wave and K step
     constexpr int PW_P = 64 / RPP < 8 ? 64 / RPP : 8;    // waves that issue P pieces
+    constexpr int NPP_X = (EG_TN8_XSLOTS / RPP + 7) / 8; // patch pieces per wave and K step, at most (5, 3, 2)
+    constexpr int PPG = (NPP_P + NPP_X + NJ - 1) / NJ;   // DMA pieces per MFMA group of the issuing half (1, 1, 2)
     constexpr int STAGE_P = 64 * ROWB, STAGE_X = EG_TN8_XSLOTS * ROWB, STAGE = STAGE_P + STAGE_X;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+    static_assert(STAGE % ROWB == 0 && STAGE_P % ROWB == 0, "stage offsets keep the block bits of a row address clear");
+    static_assert(NPP_X <= 5 && NPP_P <= 2 && 2 * (NPP_P + NPP_X) <= 14, "piece tables, vmcnt range of tn8_wait");
+    extern __shared__ __attribute__((aligned(256))) char smem[];     // (a row address keeps its block bits clear: see xk[])
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tp = wave >> 1, nh = wave & 1;             // this wave's tap of the class and half of the 128 output channels
@@ -64,19 +104,26 @@ __global__ __launch_bounds__(512) void igemm_tn8_kernel(const Tn8Params p) {
     const unsigned row_bytes = (unsigned)p.C * 2u;
     const int g = lane >> 4, li = lane & 15, q = li >> 2, pc = li & 3;
 
-    // ---- fragment addresses (loop invariant): K rows 8g + q (+4) of both 32-row MFMA steps, as P rows and as patch pixels ----
-    int prow[4], xrow[4];                                // byte offset of the row + its swizzle key in the low bits (rows are 256-byte aligned)
+    // ---- fragment addresses (loop invariant) ----
+    // A lane reads K rows r = 32 kb + 8 g + 4 h + q (kb: 32-row half of the step, h: low / high transposed read).  The 16-channel block
+    // `blk` of row r lives at r * ROWB + ((blk ^ key(r)) << 5), key(r) = tn8_fsw(r) mod NBLK.  As rows of P the four r of a lane share
+    // one key (bits 0, 1 and 3 of r are q and g & 1): one register per output-channel tile, the four rows are `offset:` immediates.  As
+    // patch pixels their keys differ: one register per row with the key folded in, the block of column tile j is one XOR away.
+    int pk[NI], xk[4];
+    {
+        const int r = 8 * g + q, key = tn8_fsw(r) & (NBLK - 1);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) pk[i] = r * ROWB + ((((nh * NI + i) ^ key) << 5) | (pc << 3));
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int r = (i >> 1) * 32 + 8 * g + (i & 1) * 4 + q;
-        prow[i] = r * ROWB + (tn8_fsw(r) & (NBLK - 1));
         int img, oy;
         if (p.nimg == 1) { img = 0; oy = r >> p.lOW; }
         else { img = r >> (p.lOH + p.lOW); oy = (r >> p.lOW) & OHm; }
         const int px = (img * p.PH + oy + ay) * p.PW + (r & OWm) + ax;
-        xrow[i] = px * ROWB + (tn8_fsw(px) & (NBLK - 1));
+        xk[i] = STAGE_P + px * ROWB + (((tn8_fsw(px) & (NBLK - 1)) << 5) | (pc << 3));
     }
-    auto frag_addr = [&](int rowkey, int blk) { return (rowkey & ~7) + (((blk ^ (rowkey & 7)) << 5) | (pc << 3)); };
 
     // ---- DMA source offsets ----
     const int c16 = lane % CPR, rsub = lane / CPR;       // a piece = RPP rows x ROWB bytes; lane -> (row, 16-byte chunk)
@@ -89,10 +136,11 @@ __global__ __launch_bounds__(512) void igemm_tn8_kernel(const Tn8Params p) {
         const int src16 = (((c16 >> 1) ^ (tn8_fsw(r) & (NBLK - 1))) << 1) | (c16 & 1);
         vP[j] = (unsigned)r * (unsigned)p.N * 2u + (unsigned)n0 * 2u + (unsigned)src16 * 16u;
     }
-    // patch pieces w, w + 8, ...: lane part of the source offset, source row relative to the step's first source row, x validity
-    int xa[5], xdy[5];
+    // patch pieces w, w + 8, ...: the lane's source offset relative to (image of the step, source row 2 * first lattice row, column 0)
+    // and its source row relative to that row; a pixel slot outside the patch or the image in x gets a row no step can make valid
+    int xa[NPP_X], xdy[NPP_X];
 #pragma unroll
-    for (int j = 0; j < 5; ++j) {
+    for (int j = 0; j < NPP_X; ++j) {
         const unsigned ps = (unsigned)(RPP * (wave + 8 * j) + rsub);
         const unsigned img = (ps * p.inv_plane) >> 20;
         const unsigned rem = ps - img * (unsigned)(p.PH * p.PW);
@@ -100,32 +148,45 @@ __global__ __launch_bounds__(512) void igemm_tn8_kernel(const Tn8Params p) {
         const int ix = (int)qx * 2 + rx - 1;
         const int src16 = (((c16 >> 1) ^ (tn8_fsw((int)ps) & (NBLK - 1))) << 1) | (c16 & 1);
         const bool ok = (int)ps < p.npix && ix >= 0 && ix < p.W;
-        xdy[j] = (int)qy * 2 + ry - 1;                  // source row = 2 * (first lattice row of the step) + xdy
-        xa[j] = ok ? (int)(((img * (unsigned)(p.H * p.W) + (unsigned)ix) * row_bytes) + (unsigned)c0 * 2u + (unsigned)src16 * 16u) : -1;
+        const int dy = (int)qy * 2 + ry - 1;            // source row = 2 * (first lattice row of the step) + dy
+        xdy[j] = ok ? dy : 0x40000000;
+        xa[j] = (int)(((img * (unsigned)(p.H * p.W) + (unsigned)ix) * row_bytes) + (unsigned)c0 * 2u + (unsigned)src16 * 16u) + dy * p.W * (int)row_bytes;
     }
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem + (unsigned)wave * 1024u;
+    const unsigned sm0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
+    const unsigned lds0 = sm0 + (unsigned)wave * 1024u;
+    const bool p_wave = PW_P == 8 || wave < PW_P;        // this wave issues P pieces
+    int nxp = 0;                                         // patch pieces this wave issues per K step (pieces past the patch would land in the next stage)
+    for (int j = 0; j < p.npp; ++j) nxp += (wave + 8 * j) * RPP < p.npix;
+    const int per = (p_wave ? NPP_P : 0) + nxp;          // pieces this wave issues per K step
 
-    auto issue = [&](int s, int stage) {                // K step s of this block into ring stage `stage`
+    // the DMA of one K step, piece by piece: the step's scalar terms, then piece k = 0 .. NPP_P + NPP_X - 1 (P first)
+    struct Step { unsigned base, soffP; int ybase, pixoff; };
+    auto step_of = [&](int s, int stage) {
+        Step d;
         const int m0s = mbeg + (s << 6);
-        const unsigned base = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)stage * STAGE);
-        const unsigned soffP = (unsigned)m0s * (unsigned)p.N * 2u;
-        if (PW_P == 8 || wave < PW_P) eg_bufdma1f<0>(srdP, vP[0], soffP, base);
-        if constexpr (NPP_P > 1) eg_bufdma1f<0x2000>(srdP, vP[NPP_P - 1], soffP, base);
+        d.base = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)stage * STAGE);
+        d.soffP = (unsigned)m0s * (unsigned)p.N * 2u;
         const int b_s = m0s >> (p.lOH + p.lOW);
-        const int oy_s = p.nimg == 1 ? ((m0s >> p.lOW) & OHm) : 0;
-        const int ybase = oy_s * 2;
-        const int pixbase = (b_s * p.H + ybase) * p.W;   // source pixel of (image b_s, row 2 * oy_s, column 0)
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            if (j < p.npp && (wave + 8 * j) * RPP < p.npix) {       // (pieces past the patch would land in the next stage)
-                const int iy = ybase + xdy[j];
-                const bool ok = xa[j] >= 0 && iy >= 0 && iy < p.H;
-                const unsigned v = ok ? (unsigned)(xa[j] + (pixbase + xdy[j] * p.W) * (int)row_bytes) : EG_OOB;
-                if (j == 0) eg_bufdma1f<STAGE_P>(srdX, v, 0u, base);
-                if (j == 1) eg_bufdma1f<STAGE_P + 0x2000>(srdX, v, 0u, base);
-                if (j == 2) eg_bufdma1f<STAGE_P + 0x4000>(srdX, v, 0u, base);
-                if (j == 3) eg_bufdma1f<STAGE_P + 0x6000>(srdX, v, 0u, base);
-                if (j == 4) eg_bufdma1f<STAGE_P + 0x8000>(srdX, v, 0u, base);
+        d.ybase = p.nimg == 1 ? ((m0s >> p.lOW) & OHm) * 2 : 0;
+        d.pixoff = (b_s * p.H + d.ybase) * p.W * (int)row_bytes;      // source pixel of (image b_s, row 2 * oy_s, column 0)
+        return d;
+    };
+    auto issue_piece = [&](const Step& d, int k) {       // k is a constant after unrolling
+        if (k < NPP_P) {
+            if (p_wave) {
+                if (k == 0) eg_bufdma1f<0>(srdP, vP[0], d.soffP, d.base);
+                if (k == 1) eg_bufdma1f<0x2000>(srdP, vP[NPP_P - 1], d.soffP, d.base);
+            }
+        } else if (k - NPP_P < NPP_X) {
+            const int j = k - NPP_P;
+            if (j < nxp) {
+                const int jj = j < NPP_X ? j : 0;        // (j itself; keeps the index in range where the compiler cannot see the guard above)
+                const unsigned v = (unsigned)(d.ybase + xdy[jj]) < (unsigned)p.H ? (unsigned)(xa[jj] + d.pixoff) : EG_OOB;
+                if (j == 0) eg_bufdma1f<STAGE_P>(srdX, v, 0u, d.base);
+                if (j == 1) eg_bufdma1f<STAGE_P + 0x2000>(srdX, v, 0u, d.base);
+                if (j == 2) eg_bufdma1f<STAGE_P + 0x4000>(srdX, v, 0u, d.base);
+                if (j == 3) eg_bufdma1f<STAGE_P + 0x6000>(srdX, v, 0u, d.base);
+                if (j == 4) eg_bufdma1f<STAGE_P + 0x8000>(srdX, v, 0u, d.base);
             }
         }
     };
@@ -137,55 +198,84 @@ __global__ __launch_bounds__(512) void igemm_tn8_kernel(const Tn8Params p) {
         for (int j = 0; j < NJ; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
-    auto tr2 = [&](const char* base, int a_lo, int a_hi) {          // 8 K-consecutive 16-bit elements of one column: two transposed reads
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(base + a_lo));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(base + a_hi));
+    auto tr2 = [&](unsigned a_lo, unsigned a_hi) {       // 8 K-consecutive 16-bit elements of one column: two transposed reads (LDS addresses)
+        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(size_t)a_lo);
+        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(size_t)a_hi);
         return make_uint4(((uint32_t)(uint16_t)lo[0]) | ((uint32_t)(uint16_t)lo[1] << 16), ((uint32_t)(uint16_t)lo[2]) | ((uint32_t)(uint16_t)lo[3] << 16),
                           ((uint32_t)(uint16_t)hi[0]) | ((uint32_t)(uint16_t)hi[1] << 16), ((uint32_t)(uint16_t)hi[2]) | ((uint32_t)(uint16_t)hi[3] << 16));
     };
-    auto compute = [&](int stage) {
-        const char* sp = smem + stage * STAGE;
-        const char* sx = sp + STAGE_P;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            uint4 af[NI], bfr[NJ];
-#pragma unroll
-            for (int i = 0; i < NI; ++i) af[i] = tr2(sp, frag_addr(prow[2 * kb], nh * NI + i), frag_addr(prow[2 * kb + 1], nh * NI + i));
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) bfr[j] = tr2(sx, frag_addr(xrow[2 * kb], j), frag_addr(xrow[2 * kb + 1], j));
-#pragma unroll
-            for (int i = 0; i < NI; ++i)
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    if constexpr (std::is_same<T, f16_t>::value)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, af[i]), __builtin_bit_cast(f16x8_t, bfr[j]), acc[i][j], 0, 0, 0);
-                    else
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af[i]), __builtin_bit_cast(bf16x8_t, bfr[j]), acc[i][j], 0, 0, 0);
-                }
-        }
-    };
-    auto barrier = [&]() {
+    uint4 af0[NI], af1[NI], bfr[NJ];                     // P fragments of the two 32-row halves (double buffered), patch fragments (reloaded column tile by column tile)
+    // the counted wait + barrier that publishes a K step.  The empty asm statements pin the fragment reads at IR level: to the optimiser
+    // neither builtin touches memory, and a read whose only users sit behind the barrier may otherwise sink past both (the prologue's
+    // reads did); sched_barrier(0) pins the machine scheduler.
+    auto publish = [&](int n, auto widec) {
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        if (decltype(widec)::value) tn8_wait2(n);
+        else tn8_wait(n);
         __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
     };
+    // one half of a K step, column tile by column tile: the NI MFMAs of column tile j on the fragments in registers, then the reads of
+    // the NEXT half (half `kb` of the stage at byte offset `soff`) -- bfr[j] into the registers those MFMAs have just released, one row
+    // tile of `na` per group -- then, in the issuing half, PPG DMA pieces of the step `d` describes.
+    auto half = [&](const uint4 (&ca)[NI], uint4 (&na)[NI], int soff, auto kbc, auto dmc, const Step& d, bool dm) {
+        constexpr int kb = decltype(kbc)::value;
+        constexpr bool DM = decltype(dmc)::value;
+        const unsigned sb = sm0 + (unsigned)soff, sp = sb + kb * 32 * ROWB;      // (xk[] holds the rows of both halves, pk[] those of half 0)
+        const unsigned x_lo = sb + (unsigned)xk[2 * kb], x_hi = sb + (unsigned)xk[2 * kb + 1];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                if constexpr (std::is_same<T, f16_t>::value)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, ca[i]), __builtin_bit_cast(f16x8_t, bfr[j]), acc[i][j], 0, 0, 0);
+                else
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, ca[i]), __builtin_bit_cast(bf16x8_t, bfr[j]), acc[i][j], 0, 0, 0);
+            }
+            bfr[j] = tr2(x_lo ^ (unsigned)(j << 5), x_hi ^ (unsigned)(j << 5));
+            if (j < NI) na[j] = tr2(sp + (unsigned)pk[j], sp + (unsigned)pk[j] + 4 * ROWB);
+            if constexpr (DM) {
+                if (dm) {
+#pragma unroll
+                    for (int k = j * PPG; k < (j + 1) * PPG; ++k) issue_piece(d, k);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
 
-    // ring: K step s lives in stage s % 3; steps s + 1 and s + 2 are in flight while step s is multiplied
-    int per = (PW_P == 8 || wave < PW_P) ? NPP_P : 0;    // pieces this wave issues per K step
-    for (int j = 0; j < p.npp; ++j) per += (wave + 8 * j) * RPP < p.npix;
-    if (nk > 0) issue(0, 0);
-    if (nk > 1) issue(1, 1);
-    tn8_wait(nk > 1 ? per : 0);
-    barrier();
+    // ring: K step s lives in stage s % 3.  Prologue: steps 0, 1, 2 in flight, step 0 landed and published, its first half in registers.
+    const int npro = min(nk, 3);
+    for (int s = 0; s < npro; ++s) {
+        const Step d = step_of(s, s);
+#pragma unroll
+        for (int k = 0; k < NPP_P + NPP_X; ++k) issue_piece(d, k);
+    }
+    publish(per * max(npro - 1, 0), std::true_type{});
+    {
+        const unsigned x_lo = sm0 + (unsigned)xk[0], x_hi = sm0 + (unsigned)xk[1];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) bfr[j] = tr2(x_lo ^ (unsigned)(j << 5), x_hi ^ (unsigned)(j << 5));
+#pragma unroll
+        for (int i = 0; i < NI; ++i) af0[i] = tr2(sm0 + (unsigned)pk[i], sm0 + (unsigned)pk[i] + 4 * ROWB);
+    }
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0xc07f);                  // lgkmcnt(0) alone: the loop's own waits then count the loop's reads only
+    __builtin_amdgcn_sched_barrier(0);
     int st = 0;
     for (int t = 0; t < nk; ++t) {
-        const int st2 = st == 0 ? 2 : st - 1;            // (t + 2) % 3: last read in iteration t - 1, retired before its barrier
-        const bool more = t + 2 < nk;
-        if (more) issue(t + 2, st2);
-        compute(st);
-        // everything but this iteration's own pieces has landed (K step t + 1); this wave's fragment reads of stage st are retired
-        tn8_wait(more ? per : 0);
-        barrier();
-        st = st == 2 ? 0 : st + 1;
+        const int st1 = st == 2 ? 0 : st + 1;            // stage of K step t + 1
+        const bool dm = t + 3 < nk;
+        const Step d = step_of(t + 3, st);               // K step t + 3 goes where K step t is
+        // half 0 of step t | reads of its half 1
+        half(af0, af1, st * STAGE, std::integral_constant<int, 1>{}, std::false_type{}, d, false);
+        // K step t + 1 has landed (everything but the pieces of step t + 2); this wave's reads of stage st are retired
+        publish(t + 2 < nk ? per : 0, std::false_type{});
+        // half 1 of step t | reads of half 0 of step t + 1 (past the last step: stale bytes of a valid stage that nobody uses) | DMA
+        half(af1, af0, st1 * STAGE, std::integral_constant<int, 0>{}, std::true_type{}, d, dm);
+        st = st1;
     }
 
     // ---- slab[split][n][tap][c] ----
