@@ -835,6 +835,26 @@ def score_auc_ovr(scores, order, offsets, n, K, max_class_rows, less, equal):
     lib().call("eg_score_auc_ovr", _p(scores), _p(order), _p(offsets), n, K, int(max_class_rows), _p(less), _p(equal), _stream())
 
 
+# status[0] bits of eg_score_norm_gram
+NORM_GRAM_ZERO_VAR, NORM_GRAM_NONFINITE = 1, 2
+
+
+def score_norm_gram_ws_bytes(n, k, nf):
+    return lib().query("eg_score_norm_gram_ws_bytes", n, k, nf)
+
+
+def score_norm_gram(codes, fv, n, k, nf, ws, mean, std, G, status):
+    lib().call("eg_score_norm_gram", _p(codes), _p(fv), n, k, nf, _p(ws), _p(mean), _p(std), _p(G), _p(status), _stream())
+
+
+# info[..., 3] of eg_score_lasso_gram_fit
+LASSO_STATUS = {0: "converged", 1: "max_sweeps reached", 2: "non-finite", 3: "non-positive diagonal"}
+
+
+def score_lasso_gram_fit(G, k, nf, alpha, max_sweeps, tol, W, info):
+    lib().call("eg_score_lasso_gram_fit", _p(G), k, nf, float(alpha), int(max_sweeps), float(tol), _p(W), _p(info), _stream())
+
+
 # ---- device loss log of a training run (engine.LossLog) ----------------------------------------------
 def runlog_append(losses, n, ring, capacity, head, first_nonfinite):
     """row head % capacity of ring[capacity][n] <- losses[:n]; head += 1; the first non-finite iteration (1-based) latched"""

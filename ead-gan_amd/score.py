@@ -1,11 +1,11 @@
-"""Disentanglement scores of a trained dSprites / colored-dSprites encoder pair on the MI355X: MIG, FactorVAE, BetaVAE, SAP and F-stat
-(dSprites/score/MIG.py, FactorVAE.py, BetVAE.py, SAP.py, F_score.py; colored_dSprites/score/ likewise).
+"""Disentanglement scores of a trained dSprites / colored-dSprites encoder pair on the MI355X: MIG, FactorVAE, BetaVAE, SAP, F-stat and
+DCI (dSprites/score/MIG.py, FactorVAE.py, BetVAE.py, SAP.py, F_score.py, DCI.py; colored_dSprites/score/ likewise).
 
 The reference pushes every sampled image through Encoder_pxy -> inverse translation -> grid_sample(padding_mode='zeros') [-> divide by
 the colour gains] -> Encoder (eval) on the CPU and scores the rows [argmax(cat), cont0, cont1, pxy1, pxy2] with numpy / sklearn.  Here the
 sampling plan is host numpy (the reference's draws, in its order), the dataset sits in HBM as uint8, the encoder passes run in fixed-size
-chunks on the existing engines, and the metric arithmetic runs in float64 kernels (csrc/score.hip).  Only the plan goes up and only the
-metric's scalars / small matrices come down.  There is no CPU fallback.
+chunks on the existing engines, and the metric arithmetic runs in float64 kernels (csrc/score.hip, score_fstat.hip, score_dci.hip).
+Only the plan goes up and only the metric's scalars / small matrices come down.  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -125,6 +125,12 @@ def fstat_plan(latents_sizes, N, colored=False, rng=None, L=100, M=500):
     plan = sap_plan(latents_sizes, N, colored, rng, L, M)
     plan["latent_id"] = plan["latent_ids"][:, 1:]
     return plan
+
+
+def dci_plan(latents_sizes, N, colored=False, rng=None, L=100, M=500):
+    """load_data's plan (DCI.py:36-111): the function is SAP.py's line for line, and evaluate() draws the samples' gains once (colored
+    DCI.py:351), so the draws are ``sap_plan``'s; the factor table is ``sap_latents`` of its ids.  -> sap_plan's dict"""
+    return sap_plan(latents_sizes, N, colored, rng, L, M)
 
 
 def sap_latents(latent_ids, latents_names, latents_possible_values):
@@ -542,6 +548,89 @@ def fstat(codes, latent_ids):
             "FStat_expl_metric_detail": expl_score_detail}
 
 
+# default KKT residual of lasso_fit: 100 x the largest floor the float64 numpy coordinate descent of tests/make_dci_golden.py reaches on
+# the production-sized set (1.29e-16) and the fixtures (<= 3.9e-17)
+DCI_KKT_TOL = 1.3e-14
+DCI_ALPHA = 0.02                                             # DCIMetric's Lasso(alpha) (DCI.py:251)
+DCI_TINY = 1e-12                                             # DCIMetric.TINY (DCI.py:302)
+
+
+def lasso_fit(codes, latents, alpha=DCI_ALPHA, max_sweeps=10000, tol=DCI_KKT_TOL):
+    """The optimum of sklearn's Lasso(alpha) for every column of ``latents`` [n,nf] (host or device) on device codes [n,k] float64, both
+    normalised as DCIMetric.normalize does (DCI.py:304-309,355-364): eg_score_norm_gram's moments and correlation matrix G, then
+    eg_score_lasso_gram_fit's cyclic coordinate descent on G until the KKT residual is <= tol.  k + nf <= 32.  One host read: the
+    solver's info with the moments' status word behind it.
+    -> {"R" f64 [k,nf] = |W|^T, "W" f64 [nf,k], "mean" f64 [k+nf], "std" f64 [k+nf], "G" f64 [k+nf,k+nf]} on the device, "info" (host
+    float64 [nf,4]: sweeps, final KKT residual, objective, status).  Raises ValueError for a column without variance (the reference's
+    normalize yields NaN there and sklearn raises), RuntimeError when a target did not reach tol."""
+    _require_cuda(codes)
+    codes = codes.to(torch.float64).contiguous()
+    n, k = codes.shape
+    dev = codes.device
+    fv = latents if torch.is_tensor(latents) else torch.from_numpy(np.ascontiguousarray(np.asarray(latents, dtype=np.float64)))
+    fv = fv.to(device=dev, dtype=torch.float64).contiguous()
+    if fv.dim() != 2 or fv.shape[0] != n:
+        raise ValueError(f"factor values {tuple(fv.shape)} do not give {n} codes a row of factors each")
+    nf = fv.shape[1]
+    m = k + nf
+    ws = torch.empty(max(ops.score_norm_gram_ws_bytes(n, k, nf), 8), device=dev, dtype=torch.uint8)
+    mean = torch.empty(m, device=dev, dtype=torch.float64)
+    std = torch.empty(m, device=dev, dtype=torch.float64)
+    G = torch.empty(m, m, device=dev, dtype=torch.float64)
+    rec = torch.zeros(nf * 4 + 1, device=dev, dtype=torch.float64)                 # info [nf,4] | the int32 status words
+    info, status = rec[:nf * 4].view(nf, 4), rec[nf * 4:].view(torch.int32)
+    W = torch.empty(nf, k, device=dev, dtype=torch.float64)
+    ops.score_norm_gram(codes, fv, n, k, nf, ws, mean, std, G, status)
+    ops.score_lasso_gram_fit(G, k, nf, alpha, max_sweeps, tol, W, info)
+    rec_h = rec.cpu()                                                              # the one sync: offline evaluation
+    info_h = rec_h[:nf * 4].view(nf, 4).numpy().copy()
+    flags, col = (int(v) for v in rec_h[nf * 4:].view(torch.int32))
+    if flags:
+        which = f"code column {col}" if col < k else f"factor column {col - k}"
+        if flags & ops.NORM_GRAM_NONFINITE:
+            raise ValueError(f"{which} has a moment that is not finite")
+        raise ValueError(f"{which} has zero variance: DCIMetric.normalize divides by its standard deviation")
+    if (info_h[:, 3] != 0).any():
+        j = int(np.nonzero(info_h[:, 3])[0][0])
+        st = int(info_h[j, 3])
+        raise RuntimeError(f"Lasso fit of factor {j} did not reach a KKT residual <= {tol:g}: {int(info_h[j, 0])} sweeps, residual "
+                           f"{info_h[j, 1]:.3e} (status {st}: {ops.LASSO_STATUS.get(st, '?')})")
+    return {"R": W.abs().t().contiguous(), "W": W, "mean": mean, "std": std, "G": G, "info": info_h}
+
+
+def dci_scores(R, regressor="Lasso"):
+    """DCIMetric.evaluate's arithmetic on the importance matrix R [k,nf] (DCI.py:311-321,376-399), operation for operation on the host
+    -> the reference's dict; a code no factor uses (a zero row) gives the NaN the script's 0 / 0 gives"""
+    R = np.asarray(R, dtype=np.float64)
+
+    def entropic(r):
+        """per column of r: 1 - the entropy of the column's shares, in units of log(rows)"""
+        share = np.abs(r) / np.sum(np.abs(r), axis=0)
+        return [1 - (-p.dot(np.log(p + DCI_TINY) / np.log(p.shape[0] + DCI_TINY))) for p in share.T]
+
+    with np.errstate(divide="ignore", invalid="ignore"):
+        disent = entropic(R.T)                                                     # per code, over the factors
+        code_weight = np.sum(R, 1) / np.sum(R)
+        complete = entropic(R)                                                     # per factor, over the codes
+        res = {f"DCI_{regressor}_disent_metric_detail": disent,
+               f"DCI_{regressor}_disent_metric": np.sum(np.array(disent) * code_weight),
+               f"DCI_{regressor}_complete_metric_detail": complete,
+               f"DCI_{regressor}_complete_metric": np.mean(complete),
+               f"DCI_{regressor}_metric_detail": R}
+    return res
+
+
+def dci(codes, latents, regressor="Lasso"):
+    """-> the reference's dict (DCI.py:391-399) for DCIMetric's default regressor, Lasso(alpha = 0.02): DCI_Lasso_disent_metric_detail
+    (list [k]), DCI_Lasso_disent_metric, DCI_Lasso_complete_metric_detail (list [nf]), DCI_Lasso_complete_metric, DCI_Lasso_metric_detail
+    (R [k,nf]).  The script's other regressors have no fixed target: LassoCV picks alpha from a grid by cross-validation folds, the
+    random forests are random."""
+    if regressor != "Lasso":
+        raise NotImplementedError(f"dci: regressor {regressor!r} is not built: only 'Lasso', the script's default, is a fixed target "
+                                  "(LassoCV selects a discrete alpha, the random forests are random)")
+    return dci_scores(lasso_fit(codes, latents)["R"].cpu().numpy(), regressor)
+
+
 # ================================================================================================
 # drop-in for the scripts' module-level code
 # ================================================================================================
@@ -571,8 +660,8 @@ def run_score(kind, metric, npz_path, encoder_pxy_path, encoder_path, seed=None,
     """What dSprites|colored_dSprites/score/{MIG,FactorVAE,BetVAE}.py do at module level, on the MI355X.  ``seed``: np.random.seed first (else
     the global numpy stream as it stands).  ``groups``: score only the first groups of the 500-group FactorVAE / BetaVAE plan (the plan is
     drawn in full).  Prints the score; returns it (MIG), the reference's three-key dict (FactorVAE) or its one-key dict (BetaVAE).
-    score/SAP.py is ``run_sap`` and score/F_score.py ``run_fstat``: this function's refusal of every other metric name is part of its
-    contract."""
+    score/SAP.py is ``run_sap``, score/F_score.py ``run_fstat`` and score/DCI.py ``run_dci``: this function's refusal of every other metric
+    name is part of its contract."""
     if metric not in ("mig", "factor_vae", "beta_vae"):
         raise ValueError(f"metric must be 'mig', 'factor_vae' or 'beta_vae', got {metric!r}")
     dataset_zip, imgs, rep, colored = _open_run(kind, npz_path, encoder_pxy_path, encoder_path, seed, batch, device)
@@ -631,4 +720,19 @@ def run_fstat(kind, npz_path, encoder_pxy_path, encoder_path, seed=None, batch=4
     res = fstat(codes, plan["latent_id"])
     print("modu_score", res["FStat_modu_metric"])
     print("expl_score", res["FStat_expl_metric"])
+    return res
+
+
+def run_dci(kind, npz_path, encoder_pxy_path, encoder_path, seed=None, batch=4096, device="cuda"):
+    """What dSprites|colored_dSprites/score/DCI.py do at module level, on the MI355X (``run_sap``'s arguments).  Prints ``disent_scores``
+    and ``complete_avg`` as the script does; returns the reference's five-key dict."""
+    dataset_zip, imgs, rep, colored = _open_run(kind, npz_path, encoder_pxy_path, encoder_path, seed, batch, device)
+    metadata = dataset_zip["metadata"][()]
+    plan = dci_plan(metadata["latents_sizes"], imgs.shape[0], colored)
+    latents = sap_latents(plan["latent_ids"], metadata["latents_names"], metadata["latents_possible_values"])
+    data = torch.from_numpy(np.ascontiguousarray(imgs)).to(device)
+    codes = rep.codes(data, plan["idx"], plan["gains"])                            # DCI.py:350 builds the same five columns
+    res = dci(codes, latents)
+    print("disent_scores", res["DCI_Lasso_disent_metric_detail"])
+    print("complete_avg", res["DCI_Lasso_complete_metric"])
     return res

@@ -546,7 +546,7 @@ int eg_onehot(const long long* labels, float* out, int B, int n, eg_stream_t s);
 int eg_resample_u8(const unsigned char* src, unsigned char* dst, int planes, int in_h, int in_w, int axis, const int* bounds,
                    const int* kk, int ksize, int o0, int on, int c0, int cn, eg_stream_t s);
 
-/* Disentanglement scores of a trained encoder pair (dSprites/score/MIG.py, FactorVAE.py, BetVAE.py, SAP.py, F_score.py; colored_dSprites/score/ likewise).
+/* Disentanglement scores of a trained encoder pair (dSprites/score/MIG.py, FactorVAE.py, BetVAE.py, SAP.py, F_score.py, DCI.py; colored_dSprites/score/ likewise).
  * Staging: out[b][c] = data[idx[b]] * gain[b][c] (uint8 [N][HW] sprites, gain [B][C] fp32 or NULL = 1) -> fp32 NCHW; the reference's
  * imgs[select_index] + add_color_2_img (colored MIG.py:169-184,204; FactorVAE.py:236-254,270,315). */
 int eg_score_stage_u8(const unsigned char* data, const int* idx, const float* gain, float* out, int B, int C, int HW, eg_stream_t s);
@@ -627,6 +627,29 @@ int eg_score_softmax_proba(const double* X, int n, int d, int K, const double* W
  * Positives sit in registers, negatives stream through LDS in tiles; no sort.  An order entry outside 0..n-1 is skipped, not read. */
 int eg_score_auc_ovr(const double* scores, const int* order, const int* offsets, int n, int K, int max_class_rows,
                      unsigned long long* less, unsigned long long* equal, eg_stream_t s);
+
+/* DCI with the script's default regressor, Lasso(alpha = 0.02) (dSprites/score/DCI.py:304-309,354-374; colored :323-328,381-401).
+ * DCIMetric.normalize of codes [n][k] and fv [n][nf] (float64) as moments and one matrix: mean [k+nf], stddev [k+nf] (np.std: ddof = 0, two
+ * passes) and G [(k+nf)][(k+nf)] = Z^T Z / n of the normalised columns Z = (X - mean) / stddev of [codes | fv], symmetric bit for bit; each
+ * fit of the script depends on the data through G alone (G[:k][:k] its Gram matrix, G[:k][k+j] factor j's right-hand side).  The rows
+ * are spread over up to 1024 workgroups (512 rows each at least); slice sums, then centred cross products per slice, then one
+ * workgroup adds the slices in ascending order: no float atomics, two calls give the same bits.  n >= 2, k >= 1, nf >= 1, k + nf <= 32.
+ * status [2] int32: [0] = 0, or bit 0: a column whose minimum equals its maximum (no variance; its mean is that value, its stddev 0),
+ * bit 1: a column whose sum or centred square sum is not finite; [1] = the lowest such column, or -1.  A flagged column's entries of G
+ * hold what IEEE's 0 / 0 gives; the status word is how the caller learns of it.  ws: eg_score_norm_gram_ws_bytes bytes. */
+size_t eg_score_norm_gram_ws_bytes(int n, int k, int nf);
+int eg_score_norm_gram(const double* codes, const double* fv, int n, int k, int nf, void* ws, double* mean, double* stddev, double* G,
+                       int* status, eg_stream_t s);
+/* regressor.fit of DCI.py:361-364 for every factor at once, on G [(k+nf)][(k+nf)] of eg_score_norm_gram: for factor j, with A = G[:k][:k],
+ * c = G[:k][k+j], the optimum of  f(w) = (G[k+j][k+j] - 2 c.w + w.A w) / 2 + alpha |w|_1,  which is sklearn's Lasso objective
+ * (1 / 2n) |y - X w - b|^2 + alpha |w|_1 on the normalised columns (their intercept b is zero); convex, one optimum when A is definite.
+ * One wave per factor, w and g in registers: cyclic coordinate descent with soft thresholding from w = 0; before the first sweep and after each one the KKT
+ * residual  max_i ( w_i != 0 ? |g_i - alpha sign(w_i)| : max(|g_i| - alpha, 0) ),  g = c - A w formed afresh, ends the fit when it is
+ * <= tol, max_sweeps ends it otherwise.  W [nf][k]; info [nf][4] float64 = (sweeps, final KKT residual, objective, status: 0 converged,
+ * 1 max_sweeps reached, 2 a non-finite entry or residual, 3 a diagonal entry of A that is not positive; 2 and 3 found in G leave W = 0).
+ * k >= 1, nf >= 1, k + nf <= 32, alpha >= 0.  No workspace. */
+int eg_score_lasso_gram_fit(const double* G, int k, int nf, double alpha, int max_sweeps, double tol, double* W, double* info,
+                            eg_stream_t s);
 
 /* --- device loss log of a training run: replaces the `.item()` calls of the reference's progress lines --
  * celebA/EAD-GAN_celebA.py:404-408, MNIST/EAD-GAN_rpqmnxy.py:453-457, dSprites/rp.py:491-496, colored_dSprites/rp_color.py:523-528,
