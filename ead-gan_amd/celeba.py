@@ -15,6 +15,7 @@ import numpy as np
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 from torch.nn.utils import spectral_norm
 
 from . import ops
@@ -754,29 +755,78 @@ class _DiscFn(torch.autograd.Function):
 # ================================================================================================
 # affine utilities (celebA/utils_rpqxy.py) and the STN warp
 # ================================================================================================
+class _ThetaFn(torch.autograd.Function):
+    """code [B, ld] -> theta [B, 2, 3] by ``ops.theta_<kind>``; backward: ``ops.theta_bwd`` (no double backward)"""
+
+    @staticmethod
+    def forward(ctx, code, kind):
+        B, ld = code.shape
+        theta = torch.empty(B, 2, 3, device=code.device, dtype=torch.float32)
+        getattr(ops, "theta_" + kind)(code, ld, B, theta)
+        ctx.save_for_backward(code)
+        ctx.kind = kind
+        return theta
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dtheta):
+        code, = ctx.saved_tensors
+        dcode = torch.empty_like(code)
+        ops.theta_bwd(ops.THETA_KINDS[ctx.kind], code, code.shape[1], code.shape[0], dtheta.float().contiguous(), dcode)
+        return dcode, None
+
+
+def _code_to_theta(kind, code_input_raw):
+    """rows 0, 1 of the kind's matrix, differentiable with respect to the codes"""
+    _require_cuda(code_input_raw)
+    return _ThetaFn.apply(code_input_raw.float().contiguous(), kind)
+
+
 def get_matrix(code_input_raw):
     """[B,>=5] latent codes -> [B,3,3] affine matrices R(theta) Z(p,q) T(x,y)  (utils_rpqxy.py:59-80)."""
-    _require_cuda(code_input_raw)
-    c = code_input_raw.float().contiguous()
-    B = c.shape[0]
-    theta = torch.empty(B, 2, 3, device=c.device, dtype=torch.float32)
-    ops.theta_rpqxy(c, c.shape[1], B, theta)
-    A = torch.zeros(B, 3, 3, device=c.device, dtype=torch.float32)
+    theta = _code_to_theta("rpqxy", code_input_raw)
+    A = torch.zeros(theta.shape[0], 3, 3, device=theta.device, dtype=torch.float32)
     A[:, :2] = theta
     A[:, 2, 2] = 1.0
     return A
 
 
+class _WarpFn(torch.autograd.Function):
+    """``ops.warp_affine`` / ``ops.warp_affine_zeros``; backward: ``ops.warp_affine_bwd`` for the inputs that need it (no double backward)"""
+
+    @staticmethod
+    def forward(ctx, img, theta, zeros):
+        out = torch.empty_like(img)
+        B, C, H, W = img.shape
+        (ops.warp_affine_zeros if zeros else ops.warp_affine)(img, theta, out, B, C, H, W)
+        ctx.save_for_backward(img, theta)
+        ctx.zeros = zeros
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        img, theta = ctx.saved_tensors
+        B, C, H, W = img.shape
+        dimg = torch.empty_like(img) if ctx.needs_input_grad[0] else None
+        dtheta = torch.empty_like(theta) if ctx.needs_input_grad[1] else None
+        ops.warp_affine_bwd(img, theta, dout.float().contiguous(), dimg, dtheta, B, C, H, W, ctx.zeros)
+        return dimg, dtheta, None
+
+
 class transformation_2D(nn.Module):
-    """affine_grid + grid_sample(bilinear, border, align_corners=False) as one HIP kernel (:144-158)."""
+    """affine_grid + grid_sample(bilinear, ``padding_mode`` 'border' or 'zeros', align_corners=False) as one HIP kernel (:144-158;
+    'zeros': colored_dSprites/pxy_color.py:90); differentiable with respect to the image and the matrix."""
+
+    def __init__(self, padding_mode="border"):
+        super().__init__()
+        if padding_mode not in ("border", "zeros"):
+            raise ValueError("transformation_2D: padding_mode must be 'border' or 'zeros'")
+        self.padding_mode = padding_mode
 
     def stn(self, x, matrix_2D):
         _require_cuda(x)
-        x = x.float().contiguous()
-        out = torch.empty_like(x)
-        B, C, H, W = x.shape
-        ops.warp_affine(x, matrix_2D.float().contiguous(), out, B, C, H, W)
-        return out
+        return _WarpFn.apply(x.float().contiguous(), matrix_2D.float().contiguous(), self.padding_mode == "zeros")
 
     def forward(self, img, matrix_2D):
         return self.stn(img, matrix_2D)

@@ -10,7 +10,7 @@ import torch
 from . import dsprites as ds
 from . import ops
 from .celeba import GRAD_UP, _require_cuda, transformation_2D          # noqa: F401
-from .dsprites import get_matrix, get_matrix_D, get_matrix_pxy_align, mutual_info_loss, to_categorical      # noqa: F401
+from .dsprites import get_matrix, get_matrix_D, get_matrix_pxy, get_matrix_pxy_align, mutual_info_loss, to_categorical      # noqa: F401
 
 opt = argparse.Namespace(n_epochs=100, batch_size=128, lr=0.0002, b1=0.5, b2=0.999, n_cpu=8, latent_dim=200, code_dim=7, n_classes=3,
                          img_size=64, channels=3, sample_interval=1000)           # argparse defaults rp_color.py:40-51

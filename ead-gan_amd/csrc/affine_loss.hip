@@ -1,6 +1,7 @@
 // Affine warp (F.affine_grid + F.grid_sample bilinear/border, celebA/EAD-GAN_celebA.py:146-152), latent-code ->
 // matrix kernels (celebA/utils_rpqxy.py:59-80) and the fused loss heads with their gradients
-// (celebA/EAD-GAN_celebA.py:161-169,342,355-362,383-395).  All reductions are single-block and deterministic.
+// (celebA/EAD-GAN_celebA.py:161-169,342,355-362,383-395).  All reductions are single-block and deterministic; the one result that is
+// not bitwise reproducible is dimg of eg_warp_affine_bwd (LDS float adds in arrival order).
 #include "affine_math.h"
 
 // theta[b][2][3] from 5 latent codes (row stride ldc)
@@ -21,6 +22,42 @@ extern "C" int eg_theta_rpqxy(const float* code, int ldc, int B, float* theta, e
     return 0;
 }
 
+// The bilinear cell of output pixel (x, y) under theta t[6]: the sample coordinates of F.affine_grid (align_corners=False), the clamp of
+// grid_sample's padding mode, the cell's corner (x0, y0), its weights and which taps lie inside the image.  ONE expression for the forward
+// warps and for eg_warp_affine_bwd, which must land in the cell the forward landed in (the file is compiled without fp contraction).
+// mx / my: d(clamped coordinate) / d(coordinate), grid_sample's rule -- 'border': 0 where the unclamped coordinate is <= 0 or >= size - 1;
+// 'zeros': 1 (the clamp to [-2, size + 1] only keeps the index arithmetic finite: all four taps are outside there anyway).
+struct WarpCell {
+    float xn, yn, wx0, wx1, wy0, wy1, mx, my;
+    int x0, y0;
+    bool vx0, vx1, vy0, vy1;
+};
+template <bool ZEROS>
+__device__ __forceinline__ WarpCell warp_cell(const float* t, int x, int y, int H, int W) {
+    WarpCell k;
+    const float xn = (2.f * x + 1.f) / W - 1.f, yn = (2.f * y + 1.f) / H - 1.f;
+    const float gx = t[0] * xn + t[1] * yn + t[2];
+    const float gy = t[3] * xn + t[4] * yn + t[5];
+    float ix = ((gx + 1.f) * W - 1.f) * 0.5f, iy = ((gy + 1.f) * H - 1.f) * 0.5f;
+    if (!ZEROS) {
+        k.mx = (ix <= 0.f || ix >= (float)(W - 1)) ? 0.f : 1.f;
+        k.my = (iy <= 0.f || iy >= (float)(H - 1)) ? 0.f : 1.f;
+        ix = fminf(fmaxf(ix, 0.f), (float)(W - 1));
+        iy = fminf(fmaxf(iy, 0.f), (float)(H - 1));
+    } else {
+        k.mx = 1.f; k.my = 1.f;
+        ix = fminf(fmaxf(ix, -2.f), (float)(W + 1));
+        iy = fminf(fmaxf(iy, -2.f), (float)(H + 1));
+    }
+    const float fx = floorf(ix), fy = floorf(iy);
+    k.xn = xn; k.yn = yn;
+    k.x0 = (int)fx; k.y0 = (int)fy;
+    k.wx1 = ix - fx; k.wx0 = 1.f - k.wx1; k.wy1 = iy - fy; k.wy0 = 1.f - k.wy1;
+    k.vx0 = k.x0 >= 0 && k.x0 < W; k.vx1 = k.x0 + 1 >= 0 && k.x0 + 1 < W;
+    k.vy0 = k.y0 >= 0 && k.y0 < H; k.vy1 = k.y0 + 1 >= 0 && k.y0 + 1 < H;
+    return k;
+}
+
 // out[b,c,y,x] = bilinear sample of img[b,c] at theta[b] * (xn, yn, 1), align_corners=False, border padding
 template <bool ZEROS>      // ZEROS: grid_sample(padding_mode='zeros') (colored_dSprites/pxy_color.py:90), else 'border'
 __global__ void warp_affine_kernel(const float* __restrict__ img, const float* __restrict__ theta, float* __restrict__ out, int B, int C,
@@ -30,21 +67,10 @@ __global__ void warp_affine_kernel(const float* __restrict__ img, const float* _
     if (idx >= total) return;
     const int x = (int)(idx % W), y = (int)((idx / W) % H), b = (int)(idx / ((size_t)W * H));
     const float* t = theta + (size_t)b * 6;
-    const float xn = (2.f * x + 1.f) / W - 1.f, yn = (2.f * y + 1.f) / H - 1.f;
-    const float gx = t[0] * xn + t[1] * yn + t[2];
-    const float gy = t[3] * xn + t[4] * yn + t[5];
-    float ix = ((gx + 1.f) * W - 1.f) * 0.5f, iy = ((gy + 1.f) * H - 1.f) * 0.5f;
-    if (!ZEROS) {
-        ix = fminf(fmaxf(ix, 0.f), (float)(W - 1));
-        iy = fminf(fmaxf(iy, 0.f), (float)(H - 1));
-    } else {                                        // keep the index arithmetic finite for far-away samples (all four taps are outside anyway)
-        ix = fminf(fmaxf(ix, -2.f), (float)(W + 1));
-        iy = fminf(fmaxf(iy, -2.f), (float)(H + 1));
-    }
-    const float fx = floorf(ix), fy = floorf(iy);
-    const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-    const float wx1 = ix - fx, wx0 = 1.f - wx1, wy1 = iy - fy, wy0 = 1.f - wy1;
-    const bool vx0 = x0 >= 0 && x0 < W, vx1 = x1 >= 0 && x1 < W, vy0 = y0 >= 0 && y0 < H, vy1 = y1 >= 0 && y1 < H;
+    const WarpCell k = warp_cell<ZEROS>(t, x, y, H, W);
+    const int x0 = k.x0, y0 = k.y0, x1 = x0 + 1, y1 = y0 + 1;
+    const float wx0 = k.wx0, wx1 = k.wx1, wy0 = k.wy0, wy1 = k.wy1;
+    const bool vx0 = k.vx0, vx1 = k.vx1, vy0 = k.vy0, vy1 = k.vy1;
     for (int c = 0; c < C; ++c) {
         const float* p = img + ((size_t)b * C + c) * H * W;
         float v = 0.f;
@@ -88,16 +114,10 @@ __global__ __launch_bounds__(256) void warp_affine_rpqxy_kernel(const float* __r
     }
     __syncthreads();
     const int x = (int)(idx % W), y = (int)((idx / W) % H);
-    const float xn = (2.f * x + 1.f) / W - 1.f, yn = (2.f * y + 1.f) / H - 1.f;
-    const float gx = th[0] * xn + th[1] * yn + th[2];
-    const float gy = th[3] * xn + th[4] * yn + th[5];
-    float ix = ((gx + 1.f) * W - 1.f) * 0.5f, iy = ((gy + 1.f) * H - 1.f) * 0.5f;
-    ix = fminf(fmaxf(ix, 0.f), (float)(W - 1));
-    iy = fminf(fmaxf(iy, 0.f), (float)(H - 1));
-    const float fx = floorf(ix), fy = floorf(iy);
-    const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-    const float wx1 = ix - fx, wx0 = 1.f - wx1, wy1 = iy - fy, wy0 = 1.f - wy1;
-    const bool vx0 = x0 >= 0 && x0 < W, vx1 = x1 >= 0 && x1 < W, vy0 = y0 >= 0 && y0 < H, vy1 = y1 >= 0 && y1 < H;
+    const WarpCell k = warp_cell<false>(th, x, y, H, W);
+    const int x0 = k.x0, y0 = k.y0, x1 = x0 + 1, y1 = y0 + 1;
+    const float wx0 = k.wx0, wx1 = k.wx1, wy0 = k.wy0, wy1 = k.wy1;
+    const bool vx0 = k.vx0, vx1 = k.vx1, vy0 = k.vy0, vy1 = k.vy1;
     for (int c = 0; c < C; ++c) {
         const float* p = img + ((size_t)b * C + c) * H * W;
         float v = 0.f;
@@ -122,6 +142,133 @@ extern "C" int eg_warp_affine_zeros(const float* img, const float* theta, float*
     EG_REQUIRE(img && theta && out, "eg_warp_affine_zeros: null pointer");
     const size_t total = (size_t)B * H * W;
     hipLaunchKernelGGL(warp_affine_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)s, img, theta, out, B, C, H, W);
+    EG_LAUNCH_CHECK();
+    return 0;
+}
+
+// Backward of the two warps (grid_sample's own derivative rules).  Grid (B, C + 1): workgroup (b, c < C) writes the plane dimg[b, c],
+// workgroup (b, C) writes dtheta[b]; an output that is not asked for has no workgroups.
+//   dimg: one fp32 plane of H * W floats in LDS -- cleared, every output pixel adds dout * weight to its (inside) taps with LDS float adds,
+//         then the plane goes to HBM with plain stores: every element written once, no global atomics, no zero-fill launch.
+//         The LDS adds arrive in any order: dimg is NOT bitwise reproducible (neither is torch's grid_sample backward).  Their rate sets
+//         the launch's time, which is why the planes of a sample are spread over C workgroups.
+//   dtheta: d out / d ix = sum_c dout * ((v01 - v00) wy0 + (v11 - v10) wy1) (outside taps read 0), times W / 2 (the un-normalisation) and
+//         the clamp's mx; likewise iy.  grid x = t0 xn + t1 yn + t2, so each thread keeps (gx xn, gx yn, gx, gy xn, gy yn, gy) over its
+//         pixels (fixed stride, channels outermost) and the six sums go through block_sum: dtheta IS bitwise reproducible.
+#define WARP_BWD_THREADS 512
+#define WARP_BWD_MAX_HW 16384
+template <bool ZEROS>
+__global__ __launch_bounds__(WARP_BWD_THREADS) void warp_affine_bwd_kernel(const float* __restrict__ img, const float* __restrict__ theta,
+                                                                           const float* __restrict__ dout, float* __restrict__ dimg,
+                                                                           float* __restrict__ dtheta, int C, int H, int W) {
+    extern __shared__ __attribute__((aligned(16))) float plane[];      // [H * W] (the dtheta workgroup: block_sum's 16 floats)
+    const int HW = H * W, b = blockIdx.x, tid = threadIdx.x;
+    const float* t = theta + (size_t)b * 6;
+    if ((int)blockIdx.y < (dimg ? C : 0)) {
+        const size_t base = ((size_t)b * C + blockIdx.y) * HW;
+        for (int i = tid; i < HW; i += WARP_BWD_THREADS) plane[i] = 0.f;
+        __syncthreads();
+        for (int i = tid; i < HW; i += WARP_BWD_THREADS) {
+            const int y = i / W, x = i - y * W;
+            const WarpCell k = warp_cell<ZEROS>(t, x, y, H, W);
+            float* q = plane + (k.y0 * W + k.x0);                       // added to only where the tap is inside
+            const float g = dout[base + i];
+            if (k.vx0 && k.vy0) atomicAdd(q, g * (k.wx0 * k.wy0));
+            if (k.vx1 && k.vy0) atomicAdd(q + 1, g * (k.wx1 * k.wy0));
+            if (k.vx0 && k.vy1) atomicAdd(q + W, g * (k.wx0 * k.wy1));
+            if (k.vx1 && k.vy1) atomicAdd(q + W + 1, g * (k.wx1 * k.wy1));
+        }
+        __syncthreads();
+        if ((HW & 3) == 0 && (reinterpret_cast<uintptr_t>(dimg) & 15) == 0) {
+            float4* d4 = reinterpret_cast<float4*>(dimg + base);
+            for (int i = tid; i < (HW >> 2); i += WARP_BWD_THREADS) d4[i] = reinterpret_cast<const float4*>(plane)[i];
+        } else {
+            for (int i = tid; i < HW; i += WARP_BWD_THREADS) dimg[base + i] = plane[i];
+        }
+        return;
+    }
+    float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < C; ++c) {
+        const size_t base = ((size_t)b * C + c) * HW;
+        const float* p = img + base;
+        for (int i = tid; i < HW; i += WARP_BWD_THREADS) {
+            const int y = i / W, x = i - y * W;
+            const WarpCell k = warp_cell<ZEROS>(t, x, y, H, W);
+            const int i00 = k.y0 * W + k.x0;                            // read only where the tap is inside
+            const float v00 = k.vx0 && k.vy0 ? p[i00] : 0.f, v01 = k.vx1 && k.vy0 ? p[i00 + 1] : 0.f;
+            const float v10 = k.vx0 && k.vy1 ? p[i00 + W] : 0.f, v11 = k.vx1 && k.vy1 ? p[i00 + W + 1] : 0.f;
+            const float g = dout[base + i];
+            const float gx = g * ((v01 - v00) * k.wy0 + (v11 - v10) * k.wy1) * (k.mx * (0.5f * W));
+            const float gy = g * ((v10 - v00) * k.wx0 + (v11 - v01) * k.wx1) * (k.my * (0.5f * H));
+            acc[0] += gx * k.xn; acc[1] += gx * k.yn; acc[2] += gx;
+            acc[3] += gy * k.xn; acc[4] += gy * k.yn; acc[5] += gy;
+        }
+    }
+    for (int j = 0; j < 6; ++j) {
+        const float tot = block_sum(acc[j], plane);
+        if (tid == 0) dtheta[(size_t)b * 6 + j] = tot;
+    }
+}
+
+extern "C" int eg_warp_affine_bwd(const float* img, const float* theta, const float* dout, float* dimg, float* dtheta, int B, int C, int H, int W,
+                                  int zeros, eg_stream_t s) {
+    EG_REQUIRE(img && theta && dout && B > 0 && C > 0 && C < 65535 && H > 0 && W > 0, "eg_warp_affine_bwd: bad argument");
+    EG_REQUIRE((size_t)H * W <= WARP_BWD_MAX_HW, "eg_warp_affine_bwd: H * W above 16384 (one image plane is kept in LDS)");
+    if (!dimg && !dtheta) return 0;
+    const dim3 grid(B, (dimg ? C : 0) + (dtheta ? 1 : 0));
+    const size_t lds = ((size_t)H * W < 16 ? 16 : (size_t)H * W) * sizeof(float);
+    if (zeros)
+        hipLaunchKernelGGL(warp_affine_bwd_kernel<true>, grid, dim3(WARP_BWD_THREADS), lds, (hipStream_t)s, img, theta, dout, dimg, dtheta, C, H, W);
+    else
+        hipLaunchKernelGGL(warp_affine_bwd_kernel<false>, grid, dim3(WARP_BWD_THREADS), lds, (hipStream_t)s, img, theta, dout, dimg, dtheta, C, H, W);
+    EG_LAUNCH_CHECK();
+    return 0;
+}
+
+// dcode = J^T dtheta of the code -> theta kernels of this file (kind 0 .. 4: eg_theta_rpqxy, _rpqmnxy, _rp, _pxy, _pxy_align_inv): one thread
+// per sample evaluates the kind's matrix function on dual numbers (affine_math.h) and contracts the 6 x N Jacobian with dtheta[b]; the two pxy
+// kinds are closed forms.  Every column of the dcode row is written: the gradient in the kind's columns, 0 elsewhere.
+template <int N, typename F>
+__device__ __forceinline__ void theta_bwd_dual(const float* __restrict__ c, const float* __restrict__ g, float* __restrict__ d, F matrix) {
+    Dual<N> v[N];
+    for (int i = 0; i < N; ++i) v[i] = dvar<N>(c[i], i);
+    const Aff<Dual<N>> m = matrix(v);
+    for (int i = 0; i < N; ++i)
+        d[i] = g[0] * m.a.d[i] + g[1] * m.b.d[i] + g[2] * m.c.d[i] + g[3] * m.d.d[i] + g[4] * m.e.d[i] + g[5] * m.f.d[i];
+}
+__global__ void theta_bwd_kernel(int kind, const float* __restrict__ code, int ldc, int B, const float* __restrict__ dtheta, float* __restrict__ dcode) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const float* c = code + (size_t)b * ldc;
+    const float* g = dtheta + (size_t)b * 6;
+    float* d = dcode + (size_t)b * ldc;
+    int n;
+    if (kind == 0) {
+        n = 5; theta_bwd_dual<5>(c, g, d, [](const Dual<5>* v) { return matrix_rpqxy<Dual<5>>(v); });
+    } else if (kind == 1) {
+        n = 7; theta_bwd_dual<7>(c, g, d, [](const Dual<7>* v) { return matrix_rpqmnxy<Dual<7>>(v); });
+    } else if (kind == 2) {
+        n = 4; theta_bwd_dual<4>(c, g, d, [](const Dual<4>* v) { return matrix_rp<Dual<4>>(v); });
+    } else if (kind == 3) {                             // theta = [[p, 0, p x], [0, p, p y]], p = 1 + .1 c0, x = .1 c1, y = .1 c2
+        n = 3;
+        const float p = c[0] * 0.1f + 1.f, x = c[1] * 0.1f, y = c[2] * 0.1f;
+        d[0] = 0.1f * (g[0] + g[4] + x * g[2] + y * g[5]);
+        d[1] = 0.1f * (p * g[2]);
+        d[2] = 0.1f * (p * g[5]);
+    } else {                                            // theta = [[1, 0, -.1 c1], [0, 1, -.1 c2]]
+        n = 3;
+        d[0] = 0.f;
+        d[1] = -(0.1f * g[2]);
+        d[2] = -(0.1f * g[5]);
+    }
+    for (int j = n; j < ldc; ++j) d[j] = 0.f;
+}
+
+extern "C" int eg_theta_bwd(int kind, const float* code, int ldc, int B, const float* dtheta, float* dcode, eg_stream_t s) {
+    static const int ncode[5] = {5, 7, 4, 3, 3};
+    EG_REQUIRE(kind >= 0 && kind <= 4, "eg_theta_bwd: kind must be 0 .. 4");
+    EG_REQUIRE(code && dtheta && dcode && B > 0 && ldc >= ncode[kind], "eg_theta_bwd: bad argument");
+    hipLaunchKernelGGL(theta_bwd_kernel, dim3(cdiv(B, 128)), dim3(128), 0, (hipStream_t)s, kind, code, ldc, B, dtheta, dcode);
     EG_LAUNCH_CHECK();
     return 0;
 }

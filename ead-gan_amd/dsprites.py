@@ -13,7 +13,7 @@ import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
 from . import ops
-from .celeba import GRAD_UP, IMG_GEMM, _HipModule, _require_cuda, transformation_2D      # noqa: F401
+from .celeba import GRAD_UP, IMG_GEMM, _code_to_theta, _HipModule, _require_cuda, transformation_2D      # noqa: F401
 from .engine import FUSE_DRAWS, Arena, ConvRec, DeviceSampler, ResidentStep, SideStream, SyncScratch, Workspace, bn_train_backward, bn_train_forward, capture_step, check_usable, parse_dtype
 from .ops import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, EG_F32, OUT_NCHW_F32
 from .trunk import Head, TrunkEngine
@@ -456,23 +456,21 @@ def _theta_to_A(theta):
 
 def get_matrix(code_input_raw):
     """[B,>=4] codes -> [B,3,3] = R(theta) Z(p,p) T(x,y)  (utils_rp.py:94-115)."""
-    _require_cuda(code_input_raw)
-    c = code_input_raw.float().contiguous()
-    theta = torch.empty(c.shape[0], 2, 3, device=c.device)
-    ops.theta_rp(c, c.shape[1], c.shape[0], theta)
-    return _theta_to_A(theta)
+    return _theta_to_A(_code_to_theta("rp", code_input_raw))
 
 
 get_matrix_D = get_matrix        # identical formulas (utils_rp.py:38-59)
 
 
+def get_matrix_pxy(code_input_raw):
+    """[B,>=3] codes (p, x, y) -> [B,3,3] = Z(p,p) T(x,y), p = 1 + .1 c0, x, y = .1 c1, .1 c2  (utils_pxy.py:49-66)."""
+    return _theta_to_A(_code_to_theta("pxy", code_input_raw))
+
+
 def get_matrix_pxy_align(code_input_raw):
     """translation-only alignment matrix T(.1 c1, .1 c2)  (utils_pxy.py:69-87)."""
-    _require_cuda(code_input_raw)
-    c = code_input_raw.float().contiguous()
-    theta = torch.empty(c.shape[0], 2, 3, device=c.device)
-    ops.theta_pxy_align_inv(c, c.shape[1], c.shape[0], theta)
-    theta[:, :, 2] = -theta[:, :, 2]             # the kernel produces the inverse the loop actually uses (rp.py:376)
+    theta = _code_to_theta("pxy_align_inv", code_input_raw)
+    theta[:, :, 2] = -theta[:, :, 2]             # the kernel produces the inverse the loop actually uses (rp.py:376); autograd follows the flip
     return _theta_to_A(theta)
 
 

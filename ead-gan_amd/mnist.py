@@ -14,7 +14,7 @@ import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
 from . import ops
-from .celeba import GRAD_UP, _HipModule, _require_cuda, transformation_2D      # noqa: F401  (same STN warp in both scripts)
+from .celeba import GRAD_UP, _code_to_theta, _HipModule, _require_cuda, transformation_2D      # noqa: F401  (same STN warp in both scripts)
 from .engine import (FUSE_DRAWS, Arena, ConvRec, DeviceSampler, ResidentStep, SideStream, SyncScratch, Workspace, bn_train_backward, bn_train_forward, capture_step, check_usable,
                      parse_dtype)
 from .ops import ACT_LRELU, ACT_NONE, ACT_TANH, EG_F32, OUT_NCHW_F32
@@ -412,12 +412,8 @@ def _approx(dev):
 
 def get_matrix(code_input_raw):
     """[B,7] codes -> [B,3,3] = R(theta) Z(p,q) S(m,n) T(x,y)  (utils_rpqmnxy.py:87-114)."""
-    _require_cuda(code_input_raw)
-    c = code_input_raw.float().contiguous()
-    B = c.shape[0]
-    theta = torch.empty(B, 2, 3, device=c.device, dtype=torch.float32)
-    ops.theta_rpqmnxy(c, c.shape[1], B, theta)
-    A = torch.zeros(B, 3, 3, device=c.device, dtype=torch.float32)
+    theta = _code_to_theta("rpqmnxy", code_input_raw)
+    A = torch.zeros(theta.shape[0], 3, 3, device=theta.device, dtype=torch.float32)
     A[:, :2] = theta
     A[:, 2, 2] = 1.0
     return A

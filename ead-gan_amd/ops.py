@@ -735,6 +735,21 @@ def warp_affine_zeros(img, theta, out, B, C, H, W):
     lib().call("eg_warp_affine_zeros", _p(img), _p(theta), _p(out), B, C, H, W, _stream())
 
 
+def warp_affine_bwd(img, theta, dout, dimg, dtheta, B, C, H, W, zeros=False):
+    """backward of warp_affine (``zeros``: of warp_affine_zeros): writes every element of ``dimg`` [B,C,H,W] and ``dtheta`` [B,6]; either may
+    be None.  H * W <= 16384."""
+    lib().call("eg_warp_affine_bwd", _p(img), _p(theta), _p(dout), _p(dimg), _p(dtheta), B, C, H, W, int(bool(zeros)), _stream())
+
+
+# kind argument of theta_bwd; theta_<name>(code, ldc, B, theta) is the forward
+THETA_KINDS = {"rpqxy": 0, "rpqmnxy": 1, "rp": 2, "pxy": 3, "pxy_align_inv": 4}
+
+
+def theta_bwd(kind, code, ldc, B, dtheta, dcode):
+    """dcode [B, ldc] = J^T dtheta of theta_<kind> (``kind``: a value of THETA_KINDS); columns past the kind's codes are written 0"""
+    lib().call("eg_theta_bwd", kind, _p(code), ldc, B, _p(dtheta), _p(dcode), _stream())
+
+
 def affine_para_rpqmnxy(code, ldc, B, para):
     lib().call("eg_affine_para_rpqmnxy", _p(code), ldc, B, _p(para), _stream())
 

@@ -493,6 +493,16 @@ int eg_loss_affine_pxy(const float* o_real, const float* o_trans, int ld, int c0
                        float* loss, float* d_real, float* d_trans, float* pred_out, eg_stream_t s);
 /* transformation_2D with grid_sample(padding_mode='zeros') (colored_dSprites/pxy_color.py:86-92) */
 int eg_warp_affine_zeros(const float* img, const float* theta, float* out, int B, int C, int H, int W, eg_stream_t s);
+/* backward of eg_warp_affine (zeros = 0, 'border') / eg_warp_affine_zeros (zeros = 1): dimg [B,C,H,W] and dtheta [B,6]; either may be
+ * null.  Every element of a non-null output is WRITTEN (no pre-zeroed buffer needed, nothing is accumulated into it).  grid_sample's
+ * derivative rules: 'border' has no coordinate gradient where the unclamped coordinate is <= 0 or >= size - 1, 'zeros' counts inside
+ * taps only.  dtheta is bitwise reproducible (fixed-order sums); dimg is summed by LDS float adds in arrival order and is not (nor is
+ * torch's).  One image plane is kept in LDS: H * W <= 16384. */
+int eg_warp_affine_bwd(const float* img, const float* theta, const float* dout, float* dimg, float* dtheta,
+                       int B, int C, int H, int W, int zeros, eg_stream_t s);
+/* dcode = J^T dtheta for the code -> theta maps; kind: 0 rpqxy (5 codes), 1 rpqmnxy (7), 2 rp (4), 3 pxy (3), 4 pxy_align_inv (3).
+ * dcode [B][ldc]: the kind's columns get the gradient, every other column of the row is written 0 (as d_real / d_trans are). */
+int eg_theta_bwd(int kind, const float* code, int ldc, int B, const float* dtheta, float* dcode, eg_stream_t s);
 
 /* --- image grids of the sampling tools: torchvision.utils.make_grid / save_image (0.8.2, not vendored) as the reference
  * calls them -- MNIST/EAD-GAN_rpqmnxy.py:281-330, MNIST/generate_image.py:122-138, celebA/EAD-GAN_celebA.py:238-287,
