@@ -1,5 +1,5 @@
 // torch.optim.Adam's element update (celebA/EAD-GAN_celebA.py:211-217), shared by the flat-arena kernel (sn_adam.hip) and the kernels that
-// update a convolution's master weights and write its packed panels in the same pass (igemm.hip): one definition, so a parameter gets the
+// update a convolution's master weights and write its packed panels in the same pass (pack.hip): one definition, so a parameter gets the
 // same bits whichever kernel updates it.
 #pragma once
 #include "eg_common.h"

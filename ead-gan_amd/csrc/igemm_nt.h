@@ -1,4 +1,4 @@
-// Shared pieces of the NT implicit-GEMM kernels (igemm.hip, igemm_nt8.hip): launch parameters, LDS image of a K row,
+// Shared pieces of the NT implicit-GEMM kernels (igemm.hip, igemm_nt8s.hip, igemm_nt8h.hip): launch parameters, LDS image of a K row,
 // MFMA step, buffer-descriptor LDS-DMA helpers and the fused epilogue through LDS.  gfx950 only.
 #pragma once
 #include <type_traits>
@@ -55,7 +55,7 @@ struct NtParams {
 // counters at zero again.
 #define EG_SPLIT_CNT_BYTES 4096
 
-// patch geometry of igemm_nt8p_kernel (igemm_nt8.hip): filter taps grouped into classes that walk one pixel lattice
+// patch geometry of igemm_nt8p_kernel (igemm_nt8s.hip): filter taps grouped into classes that walk one pixel lattice
 struct NtClass { int oy0, ox0, AH, AW, ty0, tys, tx0, txs; };       // source = stride * lattice + o0; tap(ay, ax) = (ty0 + ay*tys, tx0 + ax*txs)
 struct Nt8pPhase { int ncls; NtClass cls[4]; };
 struct Nt8pGeom {
@@ -65,6 +65,11 @@ struct Nt8pGeom {
     Nt8pPhase ph[4];
 };
 #define EG_P8P_SLOTS 448
+
+// the 8-wave NT kernels' launchers (igemm_nt8s.hip, igemm_nt8h.hip), called by the planner's dispatch in igemm.hip
+bool eg_nt8p_geometry(const NtParams& p, int nphase, Nt8pGeom& g);
+template <typename T> void eg_launch_nt8s(const NtParams& p, const Nt8pGeom& g, bool patch, int nphase, int ns, hipStream_t st);
+template <typename T> void eg_launch_nt8h(const NtParams& p, int nphase, int ns, hipStream_t st);
 
 // launch parameters of igemm_tn8_kernel (igemm_tn8.hip): weight gradients of the 4x4 / stride-2 layers, taps grouped by input parity
 struct Tn8Params {
@@ -81,6 +86,9 @@ struct Tn8Params {
 
 #define EG_TN8_XSLOTS 136                   // patch pixel slots per stage (34 pieces of 4 pixels x 256 B, or 17 of 8 pixels x 128 B)
 
+// its planner and launcher (igemm_tn8.hip), called by eg_conv_wgrad in igemm_tn.hip
+bool eg_tn8_plan(const eg_conv* c, int dtype, Tn8Params& p, int* nsplit, int wgs_target);
+template <typename T> void eg_launch_tn8(const Tn8Params& p, int nsplit, hipStream_t st);
 
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 static inline int bk_of(int dtype) { return dtype == EG_F32 ? 32 : 64; }

@@ -2,7 +2,7 @@
 // registers: while a wave issues the 32 MFMAs of K tile t it reads the fragments of K tile t+1 from LDS and issues the LDS-DMA pieces
 // of K tile t+3, interleaved group by group (4 MFMAs | 4 ds_read_b128 | 1 DMA piece).
 //
-// Why (profiles/r02_b_pmc_nt_variants.txt, r02_a_nt8_ablation.txt): with two barriers per 16 MFMAs (igemm_nt8.hip) the waves spend
+// Why (profiles/r02_b_pmc_nt_variants.txt, r02_a_nt8_ablation.txt): with two barriers per 16 MFMAs (the first 8-wave kernel, since removed) the waves spend
 // 44 % of their cycles parked -- the three streams of a phase (fragment reads, DMA issue, MFMA) overlap only through the partner wave,
 // and only as well as the two halves of a phase happen to balance.  Here every wave overlaps its own streams and meets the others
 // once per K tile (the barrier that publishes the next K tile's DMA pieces).

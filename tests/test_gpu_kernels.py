@@ -1043,7 +1043,7 @@ def test_few_row_deep_k_launch_splits_k_inside_the_register_staged_kernel(case, 
     torch.testing.assert_close(zs["split"].float(), zs["plain"].float(), rtol=rt, atol=at)
 
 
-# (nsplit, n_rows, C, T): every summation path of wgrad_reduce_kernel (csrc/igemm.hip).  nsplit < 16 runs the LEAN instantiation (256 threads),
+# (nsplit, n_rows, C, T): every summation path of wgrad_reduce_kernel (csrc/grad_reduce.hip).  nsplit < 16 runs the LEAN instantiation (256 threads),
 # nsplit >= 16 the full one, with 1024 threads where T * 16 float4 > 128 and at most 2048 blocks.  Paths: float4 blocks (C % 64 == 0 chunks),
 # float4 split groups (nsplit >= 16 and 2 T * 16 <= threads), ragged split groups (a chunk narrower than 64, nsplit >= 16, T <= 2), the one-chain
 # scalar loop (ragged chunks otherwise: C = 32 / T = 16 is the small networks' 32-channel layers); C = 100 has a float4 chunk and a ragged one
