@@ -46,7 +46,8 @@ class EgSnLayer(ctypes.Structure):
 
 class EgRngSeg(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int), ("out", ctypes.c_void_p), ("n", ctypes.c_size_t), ("a", ctypes.c_float), ("b", ctypes.c_float),
-                ("stream_id", ctypes.c_uint), ("onehot", ctypes.c_void_p), ("onehot_n", ctypes.c_int)]
+                ("stream_id", ctypes.c_uint), ("onehot", ctypes.c_void_p), ("onehot_n", ctypes.c_int),
+                ("elem0", ctypes.c_size_t), ("total", ctypes.c_size_t)]
 
 
 class EgHead(ctypes.Structure):

@@ -19,7 +19,7 @@ from torch.autograd.function import once_differentiable
 from torch.nn.utils import spectral_norm
 
 from . import ops
-from .engine import FUSE_DRAWS, Arena, ConvRec, SideStream, TrainerState, Workspace, capture_step, check_usable, parse_dtype
+from .engine import FUSE_DRAWS, Arena, ConvRec, SideStream, TrainerState, Workspace, capture_step, check_usable, parse_dtype, shard_span
 from .ops import (ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH, EG_BF16, EG_F32, OUT_NCHW_F32)
 
 # module-level hyper-parameters, mirroring the reference's global ``opt`` (argparse defaults, :39-51)
@@ -951,14 +951,19 @@ class DeviceInputs:
     of the iteration's hipGraph, so a replay needs no host work at all.  Draws are reproducible per (seed, step) and have the
     reference's distributions; they are NOT numpy's stream (parity tests keep using ``load_inputs`` with host draws)."""
 
-    def __init__(self, dataset_u8: torch.Tensor, seed: int = 0, flip: bool = True, sampling: str = "permutation"):
+    def __init__(self, dataset_u8: torch.Tensor, seed: int = 0, flip: bool = True, sampling: str = "permutation", *, rank: int = 0,
+                 world: int = 1):
         """``sampling``: "permutation" (default) = DataLoader(shuffle=True) of the reference (:204-206): a keyed permutation of the dataset
-        per epoch, every image exactly once, batches of constant size straddle epoch ends; "replacement" = independent uniform draws"""
+        per epoch, every image exactly once, batches of constant size straddle epoch ends; "replacement" = independent uniform draws.
+        ``rank`` / ``world`` (data parallel): every draw is this rank's shard of the global batch's draw (engine.shard_span): the ranks'
+        slots, concatenated, are one rank's at the global batch; ``step`` counts global iterations on every rank"""
         _require_cuda(dataset_u8)
         if dataset_u8.dtype != torch.uint8 or dataset_u8.dim() != 4:
             raise ValueError("dataset must be a uint8 [N, C, H, W] device tensor")
         if sampling not in ("permutation", "replacement"):
             raise ValueError("sampling must be 'permutation' or 'replacement'")
+        shard_span(0, rank, world)
+        self.rank, self.world = int(rank), int(world)
         self.data = dataset_u8.contiguous()
         self.sampling = sampling
         self.seed, self.flip = int(seed), flip
@@ -980,7 +985,7 @@ class DeviceInputs:
             ops.rng_fill_multi([first,                                                      # which images: epoch permutation / uniform draws
                                 (ops.RNG_BERNOULLI, self.flips, 0.5, 0.0, 2),               # RandomHorizontalFlip(p=0.5)
                                 (ops.RNG_NORMAL, tr.z, 0.0, 1.0, 3), (ops.RNG_UNIFORM, tr.code, -1.0, 1.0, 4),
-                                (ops.RNG_RANDINT, tr.labels, 0, tr.G.n_classes, 5, tr.onehot)], self.seed, self.step)
+                                (ops.RNG_RANDINT, tr.labels, 0, tr.G.n_classes, 5, tr.onehot)], self.seed, self.step, self.rank, self.world)
             def gather():                               # ToTensor + Normalize(.5,.5)
                 ops.gather_u8_images(self.data, self.idx, self.flips if self.flip else None, tr.real, B, C, H, W, 2.0 / 255.0, -1.0, tick=self.step)
             if tr.side is not None:
@@ -989,14 +994,14 @@ class DeviceInputs:
                 gather()
             return
         if self.sampling == "permutation":
-            ops.rng_fill(ops.RNG_EPOCH_PERM, self.idx, N, 0, self.seed, self.step, 1)
+            ops.rng_fill(ops.RNG_EPOCH_PERM, self.idx, N, 0, self.seed, self.step, 1, self.rank, self.world)
         else:
-            ops.rng_fill(ops.RNG_RANDINT, self.idx, 0, N, self.seed, self.step, 1)
-        ops.rng_fill(ops.RNG_BERNOULLI, self.flips, 0.5, 0.0, self.seed, self.step, 2)     # RandomHorizontalFlip(p=0.5)
+            ops.rng_fill(ops.RNG_RANDINT, self.idx, 0, N, self.seed, self.step, 1, self.rank, self.world)
+        ops.rng_fill(ops.RNG_BERNOULLI, self.flips, 0.5, 0.0, self.seed, self.step, 2, self.rank, self.world)     # RandomHorizontalFlip(p=0.5)
         ops.gather_u8_images(self.data, self.idx, self.flips if self.flip else None, tr.real, B, C, H, W, 2.0 / 255.0, -1.0)   # ToTensor + Normalize(.5,.5)
-        ops.rng_fill(ops.RNG_NORMAL, tr.z, 0.0, 1.0, self.seed, self.step, 3)
-        ops.rng_fill(ops.RNG_UNIFORM, tr.code, -1.0, 1.0, self.seed, self.step, 4)
-        ops.rng_fill(ops.RNG_RANDINT, tr.labels, 0, tr.G.n_classes, self.seed, self.step, 5)
+        ops.rng_fill(ops.RNG_NORMAL, tr.z, 0.0, 1.0, self.seed, self.step, 3, self.rank, self.world)
+        ops.rng_fill(ops.RNG_UNIFORM, tr.code, -1.0, 1.0, self.seed, self.step, 4, self.rank, self.world)
+        ops.rng_fill(ops.RNG_RANDINT, tr.labels, 0, tr.G.n_classes, self.seed, self.step, 5, self.rank, self.world)
         ops.onehot(tr.labels, tr.onehot, B, tr.G.n_classes)
         ops.counter_add(self.step, 1)
 

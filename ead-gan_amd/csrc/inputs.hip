@@ -56,15 +56,20 @@ __device__ __forceinline__ uint32_t epoch_perm(uint32_t r, uint32_t N, const uin
 }
 
 // kind 0: uniform [a, b) fp32; 1: normal(mean a, std b) fp32 (Box-Muller); 2: integers in [a, b) as int64; 3: Bernoulli(a) as uint8;
-// 4: epoch permutation -- dataset indices in [0, a) as int64 for positions step * n + i (see epoch_perm).
+// 4: epoch permutation -- dataset indices in [0, a) as int64 for positions step * total + elem0 + i (see epoch_perm).
 // Quad q of a draw depends on (q, step, stream id, seed) only -- not on the launch shape -- so one launch over several draws
 // (rng_fill_multi_kernel) writes the very values the single launches write.  onehot (kind 2): out row i also sets onehot[i][0..onehot_n).
+// Sharded draws (data parallel): the launch writes the n local elements [elem0, elem0 + n) of a global draw of `total` elements -- local
+// element i is element g = elem0 + i of that draw, lane g % 4 of quad g / 4 -- so the ranks' outputs, concatenated, are the one-rank draw.
+// A shard may begin or end inside a quad (or a Box-Muller pair): the edge quads are evaluated whole and only the owned lanes are stored.
+// out / onehot are indexed locally.  elem0 = 0, total = n is the unsharded draw.
 __device__ __forceinline__ void rng_fill_quads(int kind, void* __restrict__ out, size_t n, float a, float b, const Philox& ph, uint32_t st,
-                                               uint32_t stream_id, size_t q0, size_t qstride, float* __restrict__ onehot, int onehot_n) {
+                                               uint32_t stream_id, size_t q0, size_t qstride, float* __restrict__ onehot, int onehot_n,
+                                               size_t elem0, size_t total) {
     if (kind == 4) {
         const uint32_t N = (uint32_t)a;
         for (size_t i = q0; i < n; i += qstride) {
-            const uint64_t pos = (uint64_t)st * n + i;
+            const uint64_t pos = (uint64_t)st * total + elem0 + i;
             const uint64_t epoch = pos / N;
             uint32_t k[4] = {(uint32_t)epoch, (uint32_t)(epoch >> 32), 0x5045524Du, stream_id};
             ph(k);
@@ -72,7 +77,8 @@ __device__ __forceinline__ void rng_fill_quads(int kind, void* __restrict__ out,
         }
         return;
     }
-    for (size_t q = q0; q * 4 < n; q += qstride) {
+    const size_t end = elem0 + n;
+    for (size_t q = elem0 / 4 + q0; q * 4 < end; q += qstride) {
         uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), st, stream_id};
         ph(c);
         float v[4];
@@ -89,8 +95,10 @@ __device__ __forceinline__ void rng_fill_quads(int kind, void* __restrict__ out,
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const size_t i = q * 4 + e;
-            if (i >= n) break;
+            const size_t g = q * 4 + e;
+            if (g >= end) break;
+            if (g < elem0) continue;                            // a lane of the first quad that the previous shard owns
+            const size_t i = g - elem0;
             if (kind == 0) {
                 float r = a + (b - a) * v[e];
                 if (r >= b) r = nextafterf(b, a);              // fp32 rounding must not reach the open end of [a, b)
@@ -109,10 +117,11 @@ __device__ __forceinline__ void rng_fill_quads(int kind, void* __restrict__ out,
 }
 
 __global__ void rng_fill_kernel(int kind, void* __restrict__ out, size_t n, float a, float b, uint64_t seed, const int* __restrict__ step,
-                                uint32_t stream_id) {
+                                uint32_t stream_id, size_t elem0, size_t total) {
     const Philox ph{(uint32_t)seed, (uint32_t)(seed >> 32)};
     const uint32_t st = step ? (uint32_t)step[0] : 0u;
-    rng_fill_quads(kind, out, n, a, b, ph, st, stream_id, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x, nullptr, 0);
+    rng_fill_quads(kind, out, n, a, b, ph, st, stream_id, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x, nullptr, 0,
+                   elem0, total);
 }
 
 // several draws of one iteration in ONE launch (blockIdx.y = draw): the five draws + the one-hot labels of the CelebA loop were six
@@ -123,8 +132,11 @@ __global__ void rng_fill_multi_kernel(const RngSegs segs, uint64_t seed, const i
     const uint32_t st = step ? (uint32_t)step[0] : 0u;
     const eg_rng_seg& g = segs.s[blockIdx.y];
     rng_fill_quads(g.kind, g.out, g.n, g.a, g.b, ph, st, g.stream_id, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x,
-                   g.onehot, g.onehot_n);
+                   g.onehot, g.onehot_n, g.elem0, g.total);
 }
+
+// quads of the global draw that hold an element of the shard [elem0, elem0 + n)
+static size_t shard_quads(size_t elem0, size_t n) { return (elem0 + n + 3) / 4 - elem0 / 4; }
 
 extern "C" int eg_rng_fill_multi(const eg_rng_seg* segs, int nseg, unsigned long long seed, const int* step, eg_stream_t s) {
     EG_REQUIRE(segs && nseg >= 1 && nseg <= 8, "eg_rng_fill_multi: 1..8 draws");
@@ -134,8 +146,9 @@ extern "C" int eg_rng_fill_multi(const eg_rng_seg* segs, int nseg, unsigned long
     for (int i = 0; i < nseg; ++i) {
         EG_REQUIRE(segs[i].out && segs[i].kind >= 0 && segs[i].kind <= 4 && (!segs[i].onehot || (segs[i].kind == 2 && segs[i].onehot_n > 0)), "eg_rng_fill_multi: bad draw %d", i);
         EG_REQUIRE(segs[i].kind != 4 || (segs[i].a >= 1.f && segs[i].a <= 16777216.f && segs[i].a == floorf(segs[i].a)), "eg_rng_fill_multi: epoch permutation needs 1 <= N <= 2^24 (a)");
+        EG_REQUIRE(segs[i].elem0 <= segs[i].total && segs[i].n <= segs[i].total - segs[i].elem0, "eg_rng_fill_multi: draw %d: elem0 + n exceeds total", i);
         p.s[i] = segs[i];
-        maxq = std::max(maxq, (segs[i].n + 3) / 4);
+        maxq = std::max(maxq, shard_quads(segs[i].elem0, segs[i].n));
     }
     const int blocks = (int)((maxq + 255) / 256 > 256 ? 256 : (maxq + 255) / 256);
     hipLaunchKernelGGL(rng_fill_multi_kernel, dim3(blocks, nseg), dim3(256), 0, (hipStream_t)s, p, (uint64_t)seed, step);
@@ -144,13 +157,15 @@ extern "C" int eg_rng_fill_multi(const eg_rng_seg* segs, int nseg, unsigned long
 }
 
 extern "C" int eg_rng_fill(int kind, void* out, size_t n, float a, float b, unsigned long long seed, const int* step, unsigned int stream_id,
-                           eg_stream_t s) {
+                           size_t elem0, size_t total, eg_stream_t s) {
     EG_REQUIRE(out && kind >= 0 && kind <= 4, "eg_rng_fill: bad argument");
+    EG_REQUIRE(elem0 <= total && n <= total - elem0, "eg_rng_fill: elem0 + n exceeds total");
     EG_REQUIRE(kind != 4 || (a >= 1.f && a <= 16777216.f && a == floorf(a)), "eg_rng_fill: epoch permutation needs 1 <= N <= 2^24 (a)");
     if (n == 0) return 0;
-    const size_t quads = (n + 3) / 4;
+    const size_t quads = shard_quads(elem0, n);
     const int blocks = (int)((quads + 255) / 256 > 1024 ? 1024 : (quads + 255) / 256);
-    hipLaunchKernelGGL(rng_fill_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)s, kind, out, n, a, b, (uint64_t)seed, step, (uint32_t)stream_id);
+    hipLaunchKernelGGL(rng_fill_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)s, kind, out, n, a, b, (uint64_t)seed, step, (uint32_t)stream_id,
+                       elem0, total);
     EG_LAUNCH_CHECK();
     return 0;
 }

@@ -303,18 +303,33 @@ def bn_train_backward(dt, z, da, dz, M, C, bn, mean, invstd, act, slope, dgamma,
 FUSE_DRAWS = True
 
 
+def shard_span(numel, rank, world):
+    """-> (elem0, total): the span a rank's draw of ``numel`` elements takes in the global draw of ``world`` ranks (eg_rng_fill's
+    ``elem0`` / ``total``): rank r owns the elements [r * numel, (r + 1) * numel) of ``world * numel``, the rows of its slice of the
+    global batch.  THE place that computes it."""
+    numel, rank, world = int(numel), int(rank), int(world)
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError(f"shard_span: need world >= 1 and 0 <= rank < world, got rank {rank}, world {world}")
+    return rank * numel, world * numel
+
+
 class DeviceSampler:
     """Shared part of the trainers' device-side input pipelines: a uint8 dataset resident in HBM, a device step counter and
     counter-based draws (ops.rng_fill: reproducible per (seed, step, stream), the reference's distributions, NOT numpy's stream --
     parity tests keep feeding host draws through ``load_inputs``).  Sampling follows ``DataLoader(shuffle=True)``: a keyed permutation of the
     dataset per epoch, every image exactly once (``sampling="replacement"``: independent uniform draws).  Subclasses implement ``enqueue(trainer)``: fill the trainer's static input slots, then tick
-    the counter; inside ``trainer.capture(inputs=...)`` those launches are part of the iteration's hipGraph."""
+    the counter; inside ``trainer.capture(inputs=...)`` those launches are part of the iteration's hipGraph.
+    ``rank`` / ``world`` (data parallel): every draw is this rank's shard of the global batch's draw (``shard_span``), so the ranks'
+    slots, concatenated in rank order, are the slots of one rank at the global batch, and an epoch visits every image once over all
+    ranks.  ``step`` counts global iterations on every rank."""
 
-    def __init__(self, dataset_u8: torch.Tensor, seed: int = 0, sampling: str = "permutation"):
+    def __init__(self, dataset_u8: torch.Tensor, seed: int = 0, sampling: str = "permutation", *, rank: int = 0, world: int = 1):
         if not dataset_u8.is_cuda or dataset_u8.dtype != torch.uint8:
             raise ValueError("dataset must be a uint8 device tensor")
         if sampling not in ("permutation", "replacement"):
             raise ValueError("sampling must be 'permutation' (DataLoader(shuffle=True): every image once per epoch) or 'replacement'")
+        shard_span(0, rank, world)
+        self.rank, self.world = int(rank), int(world)
         self.data = dataset_u8.contiguous()
         self.sampling = sampling
         self.seed = int(seed)
@@ -338,13 +353,13 @@ class DeviceSampler:
     def end_draws(self):
         draws, self._draws = self._draws, None
         if draws:
-            ops.rng_fill_multi(draws, self.seed, self.step)
+            ops.rng_fill_multi(draws, self.seed, self.step, self.rank, self.world)
 
     def draw(self, kind, out, a, b, stream_id):
         if self._draws is not None:
             self._draws.append((kind, out, a, b, stream_id))
             return
-        ops.rng_fill(kind, out, a, b, self.seed, self.step, stream_id)
+        ops.rng_fill(kind, out, a, b, self.seed, self.step, stream_id, self.rank, self.world)
 
     def sample_indices(self, B, stream_id=1):
         idx = self.buf("idx", (B,), torch.int64)

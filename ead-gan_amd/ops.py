@@ -686,18 +686,27 @@ def loss_info_rpqxy(o_gen, o_trans, o_real, ld, c_cont, n_cont, n_cat, B, code, 
 RNG_UNIFORM, RNG_NORMAL, RNG_RANDINT, RNG_BERNOULLI, RNG_EPOCH_PERM = 0, 1, 2, 3, 4
 
 
-def rng_fill(kind, out, a, b, seed, step, stream_id):
-    """out <- kind(a, b) from Philox4x32-10 keyed by ``seed``, counted by (element, device counter ``step``, ``stream_id``)"""
-    lib().call("eg_rng_fill", kind, _p(out), out.numel(), float(a), float(b), int(seed), _p(step), int(stream_id), _stream())
+def _shard_span(numel, rank, world):
+    from .engine import shard_span              # engine imports this module
+    return shard_span(numel, rank, world)
 
 
-def rng_fill_multi(draws, seed, step):
+def rng_fill(kind, out, a, b, seed, step, stream_id, rank=0, world=1):
+    """out <- kind(a, b) from Philox4x32-10 keyed by ``seed``, counted by (element, device counter ``step``, ``stream_id``).
+    ``rank`` / ``world``: ``out`` is this rank's shard of a draw of ``world * out.numel()`` elements -- the ranks' outputs, concatenated,
+    are the one-rank draw of the global batch (engine.shard_span)"""
+    elem0, total = _shard_span(out.numel(), rank, world)
+    lib().call("eg_rng_fill", kind, _p(out), out.numel(), float(a), float(b), int(seed), _p(step), int(stream_id), elem0, total, _stream())
+
+
+def rng_fill_multi(draws, seed, step, rank=0, world=1):
     """several draws in ONE launch, the values of one rng_fill each: draws = [(kind, out, a, b, stream_id[, onehot tensor])]"""
     arr = (EgRngSeg * len(draws))()
     for i, d in enumerate(draws):
         kind, out, a, b, sid = d[:5]
         oh = d[5] if len(d) > 5 else None
-        arr[i] = EgRngSeg(kind, _p(out), out.numel(), float(a), float(b), int(sid), _p(oh), oh.shape[1] if oh is not None else 0)
+        elem0, total = _shard_span(out.numel(), rank, world)
+        arr[i] = EgRngSeg(kind, _p(out), out.numel(), float(a), float(b), int(sid), _p(oh), oh.shape[1] if oh is not None else 0, elem0, total)
     lib().call("eg_rng_fill_multi", arr, len(draws), int(seed), _p(step), _stream())
 
 

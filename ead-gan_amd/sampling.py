@@ -154,15 +154,21 @@ def sample_inputs(kind, n=10, rng=None):
     return out
 
 
-def sample_image(kind, generator, n=10, batches_done=0, real=None, trans=None, out_dir=".", rng=None, device="cuda"):
+def sample_image(kind, generator, n=10, batches_done=0, real=None, trans=None, out_dir=".", rng=None, device="cuda", write=True):
     """One call of the script's ``sample_image``: runs the generator (in whatever mode the caller left it -- the training scripts sample in
     train mode, the tools after ``.eval()``) on every traversal input and writes ``<out_dir>/<dir>/<batches_done>.png``.
-    ``real`` / ``trans``: the two image batches the training scripts also dump.  Returns the written paths."""
+    ``real`` / ``trans``: the two image batches the training scripts also dump.  Returns the written paths.
+    ``write=False``: only the generator runs (in train mode its BatchNorm running statistics move as in a writing call -- how the ranks
+    > 0 of a data-parallel run stay bit-equal to rank 0 without a broadcast); no file is written, [] is returned."""
     sprite = _PLANS[kind][9]
     given = [real, trans]
     paths = []
     with torch.no_grad():
         for d, inputs, gridded in sample_inputs(kind, n, rng):
+            if not write:
+                if inputs is not None:
+                    generator(*[torch.from_numpy(a).to(device) for a in inputs])
+                continue
             if inputs is None:
                 img = given.pop(0)
                 if img is None:

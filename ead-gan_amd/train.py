@@ -3,7 +3,8 @@
 dSprites/pxy.py:189-205, colored_dSprites/pxy_color.py:218-234) -- around the fused trainers' ``step_resident()``, with a loss log that
 lives on the device (engine.LossLog, written inside the captured iteration) and a full-state checkpoint from which a run continues bit
 for bit (``trainer.state_dict()``).  The loop only enqueues; every blocking wait goes through ``TrainRun._wait`` and is recorded.
-Single process only."""
+Data parallel: one TrainRun per rank around a trainer with ``allreduce`` / ``sync_bn`` and a sampler sharded by (rank, world); eager
+launches only, rank 0 alone prints and writes, and the run adds no collective of its own."""
 from __future__ import annotations
 
 import os
@@ -104,21 +105,37 @@ class TrainRun:
     engine.CaptureFailed propagates (no in-process fallback).  ``log_in_graph=False``: the trainer runs without the log (its
     graph is node for node the one ``capture(inputs=...)`` alone gives) and the loop enqueues the append after every iteration -- the
     trade for the small-network steps, where the log's launches are measurable; the dSprites lines then print 0 for the two
-    separate info terms, which only a trainer with a log computes."""
+    separate info terms, which only a trainer with a log computes.
+
+    Data parallel (``inputs.world`` > 1, the world of the trainer's ``allreduce`` / ``sync_bn``): ``graph=False`` is required; the
+    iteration count, cadence, sample seeds and file names are those of one process at the global batch ``B * world``; rank 0 prints and
+    writes every file, the other ranks write none (``files == []``) and print nothing but execute every ``_wait`` and keep ``history``
+    / ``lines`` of their own shard.  The run adds no collective: rank 0's lines and ``losses.npy`` carry rank 0's shard losses."""
 
     def __init__(self, kind, trainer, inputs, out_dir, n_epochs, sample_interval=None, seed=0, graph=True, log_capacity=1024, log_in_graph=True):
         self.plan = _plan(kind)
         if getattr(trainer, "STATE_KIND", None) != kind:
             raise ValueError(f"a {kind!r} run needs a {kind!r} trainer, got {type(trainer).__name__}")
-        if getattr(trainer, "allreduce", None) is not None or getattr(trainer, "sync_bn", None) is not None:
-            raise NotImplementedError("training runs are single process: a trainer with allreduce / sync_bn is not supported (DESIGN 5)")
+        self.rank, self.world = int(getattr(inputs, "rank", 0)), int(getattr(inputs, "world", 1))
+        trainer_world = 1                                           # a trainer without collectives is one process
+        for coll in (getattr(trainer, "allreduce", None), getattr(trainer, "sync_bn", None)):
+            if coll is not None:
+                trainer_world = int(getattr(coll, "world", 1))
+                break
+        if self.world != trainer_world:
+            raise ValueError(f"the sampler shards the batch over world = {self.world} ranks, the trainer's collectives span {trainer_world}: "
+                             "build the sampler with the rank / world of the trainer's allreduce / sync_bn")
+        if graph and self.world > 1:
+            raise ValueError(f"a data-parallel run (world = {self.world}) launches eagerly: pass graph=False (a captured multi-rank "
+                             "iteration is not supported, DESIGN 6i)")
         self.kind, self.trainer, self.inputs, self.out_dir = kind, trainer, inputs, str(out_dir)
         self.n_epochs = int(n_epochs)
         self.sample_interval = self.plan["interval"] if sample_interval is None else int(sample_interval)
         self.seed, self.graph, self.log_in_graph = int(seed), bool(graph), bool(log_in_graph)
         self.log = LossLog(trainer, log_capacity)
         self.n_images = int(inputs.data.shape[0])
-        self.L = loader_len(self.n_images, trainer.B)
+        self.global_batch = int(trainer.B) * self.world
+        self.L = loader_len(self.n_images, self.global_batch)
         self.batches_done = 0
         self.history = np.zeros((0, self.log.n), np.float32)       # loss rows of the iterations [0, len)
         self.lines = []                                             # every line printed so far
@@ -127,7 +144,8 @@ class TrainRun:
         self._prints = []                                           # (iteration, slot of its min / max values or None) not printed yet
         self._prepared = False
         self._enqueued = 0
-        os.makedirs(self.out_dir, exist_ok=True)
+        if self.rank == 0:
+            os.makedirs(self.out_dir, exist_ok=True)
         trainer.inputs, trainer.log = inputs, (self.log if self.log_in_graph else None)
         if self.plan["minmax"]:
             dev = trainer.losses.device
@@ -158,11 +176,12 @@ class TrainRun:
             self.history = np.concatenate((self.history, self.log.rows(since=have)), 0)
         while self._prints and self._prints[0][0] < len(self.history):
             it, slot = self._prints.pop(0)
-            out = [progress_line(self.kind, it, self.n_epochs, self.n_images, self.trainer.B, self.history[it])]
+            out = [progress_line(self.kind, it, self.n_epochs, self.n_images, self.global_batch, self.history[it])]
             if slot is not None:
                 out += minmax_lines(self.kind, self._mm_host[slot].tolist())
-            for ln in out:
-                print(ln, flush=True)
+            if self.rank == 0:
+                for ln in out:
+                    print(ln, flush=True)
             self.lines += out
         if self.log.mirror_flag:
             raise NonFiniteLoss(self.log.mirror_flag)
@@ -180,14 +199,18 @@ class TrainRun:
         self._prints.append((it, slot))
 
     def _sample(self, it):
+        # Every rank runs the generator on the (seeded, identical) sample inputs: in train mode that moves its BatchNorm running
+        # statistics, and the replicas stay bit-equal without a broadcast.  Rank 0 alone writes the grids.
         tr = self.trainer
         real, trans = {"celeba": lambda: (tr.real, tr.scaled), "mnist": lambda: (tr.real, tr.scaled),
                        "dsprites": lambda: (tr.align, tr.trans2), "colored": lambda: (tr.align, tr.trans2)}[self.kind]()
         rng = np.random.RandomState(sample_seed(self.seed, it))
         self.files += sampling.sample_image(self.plan["grid"], tr.G, n=10, batches_done=it, real=real[:100], trans=trans[:100],
-                                            out_dir=self.out_dir, rng=rng, device=tr.losses.device)
+                                            out_dir=self.out_dir, rng=rng, device=tr.losses.device, write=self.rank == 0)
 
     def _checkpoint(self, it):
+        if self.rank != 0:
+            return
         tr, od = self.trainer, self.out_dir
         names = [os.path.join(od, n) for n in checkpoint_files(self.kind, it)]
         if self.kind == "celeba":
@@ -255,8 +278,11 @@ class TrainRun:
         return self
 
     def _write_state(self):
+        if self.rank != 0:                                          # the replicas are identical: every rank resumes from rank 0's file
+            return None
         sd = self.trainer.state_dict()
         sd["run.kind"] = self.kind
+        sd["run.world"] = int(self.world)
         sd["run.batches_done"] = int(self.batches_done)
         sd["run.losses"] = torch.from_numpy(self.history[:self.batches_done].copy())
         path = os.path.join(self.out_dir, f"run_state_{self.batches_done}.pt")
@@ -267,17 +293,22 @@ class TrainRun:
 
     def save(self):
         """``out_dir/run_state_<batches_done>.pt``: the trainer's full state, ``batches_done`` and the loss rows so far; and
-        ``out_dir/losses.npy``"""
+        ``out_dir/losses.npy``.  Rank 0 only: the other ranks of a data-parallel run write nothing and return None."""
         if len(self.history) < self.batches_done:
             self._wait("end")
         return self._write_state()
 
     @classmethod
     def resume(cls, path, kind, trainer, inputs, out_dir, n_epochs, **kw):
-        """continue the run saved in ``path`` on a (fresh or used) trainer of the same kind with a sampler of the same seed"""
+        """continue the run saved in ``path`` on a (fresh or used) trainer of the same kind with a sampler of the same seed.  Data
+        parallel: every rank loads rank 0's file (the replicas are identical; without SyncBN each rank takes rank 0's BatchNorm running
+        statistics, as DDP broadcasts buffers); the loss rows of the iterations before the file are rank 0's on every rank."""
         sd = torch.load(path, map_location="cpu", weights_only=True)
         if sd.get("run.kind") != kind:
             raise ValueError(f"run.kind: {sd.get('run.kind')!r} in the file, {kind!r} asked for")
+        file_world, have_world = int(sd.get("run.world", 1)), int(getattr(inputs, "world", 1))
+        if file_world != have_world:
+            raise ValueError(f"run.world: {file_world} in the file, {have_world} in the attached sampler")
         run = cls(kind, trainer, inputs, out_dir, n_epochs, **kw)
         trainer.load_state_dict(sd)
         run.batches_done = int(sd["run.batches_done"])

@@ -525,9 +525,16 @@ int eg_quantize_u8(const float* x, int C, int H, int W, const float* range, unsi
  * stream_id), key = seed: reproducible per (seed, step), same distributions as the reference, NOT numpy's stream.
  * kind 0: uniform [a,b) fp32; 1: normal(a, b) fp32; 2: integers in [a,b) as int64; 3: Bernoulli(a) as uint8;
  * 4: epoch permutation (DataLoader(shuffle=True), celebA.py:204-206): int64 dataset indices in [0, N = a) for the stream positions
- *    *step * n + i -- a keyed bijection per epoch (position / N), every index exactly once per epoch, nothing stored; N <= 2^24 */
+ *    *step * total + elem0 + i -- a keyed bijection per epoch (position / N), every index exactly once per epoch, nothing stored;
+ *    N <= 2^24
+ * Sharded draws (data parallel): the call writes the n LOCAL elements [elem0, elem0 + n) of a global draw of `total` elements
+ * (elem0 + n <= total is required).  Kinds 0-3: local element i is element g = elem0 + i of that draw -- lane g % 4 of the Philox block
+ * with counter (g / 4 lo, g / 4 hi, *step, stream_id); for kind 1 the Box-Muller output of that lane, so a shard may begin or end inside a
+ * pair or a quad.  Kind 4: the batch stride of the stream is the GLOBAL batch `total`, *step counts global iterations.  The ranks'
+ * outputs, concatenated in rank order, are bit for bit the one call with elem0 = 0, total = n_global; elem0 = 0, total = n is the
+ * unsharded draw.  out (and the fused one-hot rows) are indexed locally. */
 int eg_rng_fill(int kind, void* out, size_t n, float a, float b, unsigned long long seed, const int* step, unsigned int stream_id,
-                eg_stream_t s);
+                size_t elem0, size_t total, eg_stream_t s);
 /* several draws in ONE launch (the same values as one eg_rng_fill per draw).  onehot != NULL (kind 2 only): row i of onehot[n][onehot_n] is
  * the one-hot code of draw i (to_categorical fused). */
 typedef struct eg_rng_seg {
@@ -538,6 +545,7 @@ typedef struct eg_rng_seg {
     unsigned int stream_id;
     float* onehot;
     int onehot_n;
+    size_t elem0, total;            /* the shard [elem0, elem0 + n) of a global draw of `total` elements, as in eg_rng_fill */
 } eg_rng_seg;
 int eg_rng_fill_multi(const eg_rng_seg* segs, int nseg, unsigned long long seed, const int* step, eg_stream_t s);
 int eg_counter_add(int* counter, int v, eg_stream_t s);
