@@ -15,20 +15,20 @@ import numpy as np
 
 import torch
 import torch.nn as nn
-from torch.autograd.function import once_differentiable
 from torch.nn.utils import spectral_norm
 
-from . import ops
-from .engine import FUSE_DRAWS, Arena, ConvRec, SideStream, TrainerState, Workspace, capture_step, check_usable, parse_dtype, shard_span
-from .ops import (ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH, EG_BF16, EG_F32, OUT_NCHW_F32)
+from . import affine, engine, ops
+from .affine import _code_to_theta, theta_to_matrix, transformation_2D      # noqa: F401  (drop-in names of the reference script)
+from .engine import (ConvRec, DeviceSampler, ResidentStep, SideStream, SyncScratch, Workspace, _HipModule, _require_cuda, bn_bwd_epilogue, bn_train_backward,
+                     bn_train_forward, convt_img, import_adam_moments, parse_dtype, stat_buffer, to_categorical, wgrad_side)      # noqa: F401
+from .ops import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH
 
 # module-level hyper-parameters, mirroring the reference's global ``opt`` (argparse defaults, :39-51)
 opt = argparse.Namespace(n_epochs=50, batch_size=16, lr=0.0002, b1=0.5, b2=0.999, n_cpu=8, latent_dim=200, code_dim=8,
                          n_classes=10, img_size=64, channels=3, sample_interval=4000)
 
-# Reference paths the tests compare the production ones against (they monkeypatch these; nothing else changes them).
-# image-side transposed convolutions (128 -> C) as one GEMM + col2im gather (True) or as the 4-phase implicit GEMM (False)
-IMG_GEMM = True
+# Reference path the tests compare the production one against (they monkeypatch it; nothing else changes it; engine.IMG_GEMM and
+# engine.FUSE_DRAWS are the other two).
 # optimizer.step() of a convolution weight and the refresh of its packed panels as ONE launch per layer (ops.adam_pack_conv / adam_pack_rows);
 # False: one Adam launch over the arena (or bucket) followed by the re-packing launches (same bits either way)
 FUSE_ADAM = True
@@ -57,17 +57,6 @@ G_WIDTHS = (1024, 512, 256, 128)
 D_WIDTHS = (128, 256, 512, 1024)
 LRELU_SLOPE = 0.1
 SN_EPS = 1e-12
-
-
-def to_categorical(y, num_columns, device=None):
-    """one-hot float tensor (celebA/EAD-GAN_celebA.py:56-62)."""
-    y = torch.as_tensor(np.asarray(y), dtype=torch.int64, device=device)
-    return torch.nn.functional.one_hot(y, num_columns).to(torch.float32)
-
-
-def _require_cuda(t):
-    if not t.is_cuda:
-        raise RuntimeError("ead-gan_amd runs on MI355X only: tensors must be on a HIP device (no CPU fallback)")
 
 
 # ================================================================================================
@@ -108,8 +97,7 @@ class _GenEngine:
         self.a = [torch.empty_like(t) for t in self.z]
         self.mean = [e(W[i + 1], dt=torch.float32) for i in range(3)]
         self.invstd = [e(W[i + 1], dt=torch.float32) for i in range(3)]
-        self.bn_stats = [e(3 * W[i + 1], dt=torch.float32) for i in range(3)]      # synchronised BatchNorm: local (n, mean, M2) / local sums
-        self.bn_sums = [e(2 * W[i + 1], dt=torch.float32) for i in range(3)]
+        self.sync_scratch = SyncScratch(W[1:], dev)                     # synchronised BatchNorm: local (n, mean, M2) / local sums
         self.img = e(B, gen.channels, s * 16, s * 16, dt=torch.float32)
         # gradient scratch (ping-pong between layers)
         self.dimg_z = torch.empty_like(self.img)
@@ -127,12 +115,7 @@ class _GenEngine:
         return getattr(self.gen.conv_blocks[idx], kind)
 
     def _stat_buf(self, key, c, bwd, ep, C):
-        """(nrb, buffer) if the launch described by (c, bwd, ep) can take its column statistics in the epilogue, else (0, None).  Asked
-        once per layer with the very epilogue the launch uses (same hints, same split-K scratch)."""
-        if key not in self._stat:
-            nrb = ops.conv_stat_blocks(c, self.dtype, bwd, ep)
-            self._stat[key] = (nrb, torch.empty(2 * C * nrb, device=self.inp.device, dtype=torch.float32) if nrb else None)
-        return self._stat[key]
+        return stat_buffer(self._stat, key, c, self.dtype, bwd, ep, C, self.inp.device)
 
     # gradient buckets in the order the backward pass completes them: (tag of the lane chain that writes it last, parameter names)
     BUCKETS = (("G4", ("conv_blocks.10.weight", "conv_blocks.10.bias")),
@@ -188,35 +171,15 @@ class _GenEngine:
             r = self.mid[i]
             bn = self.gen.conv_blocks[idx + 1]
             M = self.z[i].numel() // W[i + 1]
-            nrb, stat = self._stat_buf(("fwd", i), r.c, True, ops.epilogue(bias=self._p(idx, "bias")), W[i + 1]) if (training and sync is None) else (0, None)
-            if nrb:
-                # BatchNorm batch statistics from the transposed convolution's epilogue: z is read once (apply) instead of twice
-                ops.conv_bwd_data(r.c, dt, x, r.wp_bwd, self.z[i], ops.epilogue(bias=self._p(idx, "bias"), stat_mode=ops.STAT_MOMENTS, stat_out=stat))
-                ops.bn_fwd_train_fused(dt, self.z[i], self.a[i], M, W[i + 1], stat, nrb, M // nrb, bn.weight, bn.bias, bn.eps, bn.momentum, bn.running_mean,
-                                       bn.running_var, bn.num_batches_tracked, self.mean[i], self.invstd[i], small, ACT_RELU)
-                x = self.a[i]
-                continue
-            ops.conv_bwd_data(r.c, dt, x, r.wp_bwd, self.z[i], ops.epilogue(bias=self._p(idx, "bias")))
-            if training and sync is not None:
-                ops.bn_stats_local(dt, self.z[i], M, W[i + 1], small, self.bn_stats[i])
-                allst = sync.gather_stats(self.bn_stats[i])
-                ops.bn_fwd_from_stats(dt, self.z[i], self.a[i], M, W[i + 1], allst, sync.world, M * sync.world, bn.weight, bn.bias, bn.eps, bn.momentum,
-                                      bn.running_mean, bn.running_var, bn.num_batches_tracked, self.mean[i], self.invstd[i], small, ACT_RELU)
-            elif training:
-                ops.bn_fwd_train(dt, self.z[i], self.a[i], M, W[i + 1], bn.weight, bn.bias, bn.eps, bn.momentum, bn.running_mean,
-                                 bn.running_var, bn.num_batches_tracked, self.mean[i], self.invstd[i], small, ACT_RELU)
-            else:
-                ops.bn_fwd_eval(dt, self.z[i], self.a[i], M, W[i + 1], bn.weight, bn.bias, bn.eps, bn.running_mean, bn.running_var, small, ACT_RELU)
+            # BatchNorm batch statistics from the transposed convolution's epilogue where it can take them: z is read once (apply) instead of twice
+            fused = self._stat_buf(("fwd", i), r.c, True, ops.epilogue(bias=self._p(idx, "bias")), W[i + 1]) if (training and sync is None) else (0, None)
+            ops.conv_bwd_data(r.c, dt, x, r.wp_bwd, self.z[i],
+                              ops.epilogue(bias=self._p(idx, "bias"), stat_mode=ops.STAT_MOMENTS if fused[0] else ops.STAT_NONE, stat_out=fused[1]))
+            bn_train_forward(dt, self.z[i], self.a[i], M, W[i + 1], bn, self.mean[i], self.invstd[i], small, ACT_RELU, 0.0, sync, self.sync_scratch.stats[i],
+                             training, fused)
             x = self.a[i]
-        if IMG_GEMM and ops.convt_img_mfma_ok(dt, self.gen.channels, self.l4g.H, self.l4g.W, G_WIDTHS[3], 4, 2, 1):
-            # the last transposed convolution + Tanh in one launch: the GEMM's 48 columns per pixel stay in LDS
-            ops.convt_img_mfma(dt, x, self.l4g.wp_fwd, self._p(10, "bias"), self.img, B, self.gen.channels, self.l4g.H, self.l4g.W, ACT_TANH, 0.0)
-        elif IMG_GEMM:
-            ops.conv_fwd(self.l4g.c, dt, x, self.l4g.wp_fwd, self.cols4, None)
-            ops.col2im_img(dt, self.cols4, B, self.gen.channels, self.l4g.H, self.l4g.W, 4, 2, 1, self._p(10, "bias"), ACT_TANH, 0.0, self.img)
-        else:
-            ops.conv_bwd_data(self.l4.c, dt, x, self.l4.wp_bwd, self.img,
-                              ops.epilogue(bias=self._p(10, "bias"), act=ACT_TANH, out_mode=OUT_NCHW_F32))
+        # the last transposed convolution + Tanh, in one launch where the kernel takes it: the GEMM's 48 columns per pixel stay in LDS
+        convt_img(dt, x, self.l4g, self.cols4, self.l4, self._p(10, "bias"), ACT_TANH, self.img, True)
         return self.img
 
     def backward(self, dimg, grad, side=None, sync=None, store=False):
@@ -231,12 +194,6 @@ class _GenEngine:
         acc = not store
         gof = lambda name: gen.arena.grad_of(name, grad)
         C, S = gen.channels, self.img.shape[-1]
-        def wgrad_side(fn, lane, tag=None):
-            if side is None:
-                fn(ws)
-            else:
-                side.defer(lane, fn, tag)
-
         direct = ops.conv_img_mfma_ok(dt, C, S, S, W[3], 4, 2, 1)
         if not direct:
             # tanh backward fused with the bias gradient of the last ConvTranspose2d
@@ -251,114 +208,43 @@ class _GenEngine:
                 ops.im2col_img(dt, self.dimg_z, self.patches, B, C, S, S, 4, 2, 1, self.kp)
             ns = ops.conv_wgrad(self.l4p.c, dt, self.patches, self.a[2], wsw.slab, wsw.wgs_target)
             ops.wgrad_reduce(wsw.slab, ns, W[3], W[3], self.kp, 1, gof("conv_blocks.10.weight"), accumulate=acc)
-        wgrad_side(l4_wgrad, 0, "G4")
+        wgrad_side(side, ws, 0, l4_wgrad, "G4")
+        bn_of = lambda i: gen.conv_blocks[(1, 4, 7)[i] + 1]
+        bwd_ep = lambda fused, i: bn_bwd_epilogue(fused[1], self.z[i], self.mean[i], self.invstd[i], bn_of(i)) if fused[0] else None
         fused = (0, None)                               # (row blocks, sums) if da[i] came with its BatchNorm backward sums (then it holds dy)
         if direct:
             # d(a) = Conv2d(C -> 128, 4, 2, 1) of d(img) * tanh'(img): straight from the two fp32 images, no patch rows -- and, in the same
             # launch, dy = da * relu'(bn(z)) with the two sums of the last BatchNorm layer's backward
-            ep4 = None
             if sync is None:
-                if "bwd2" not in self._stat:
-                    nrb = ops.conv_img_mfma_stat_blocks(B, S, S)
-                    self._stat["bwd2"] = (nrb, torch.empty(2 * W[3] * nrb, device=self.inp.device, dtype=torch.float32))
-                fused = self._stat["bwd2"]
-                bn3 = gen.conv_blocks[8]
-                ep4 = ops.epilogue(stat_mode=ops.STAT_BN_BWD, stat_out=fused[1], stat_aux=self.z[2], stat_p=(self.mean[2], self.invstd[2], bn3.weight, bn3.bias),
-                                   stat_act=ACT_RELU)
-            ops.conv_img_mfma(dt, [dimg], self.l4p.wp_fwd, self.da[2], B, C, S, S, ep4, gates=[self.img], gate_act=ACT_TANH)
+                fused = stat_buffer(self._stat, "bwd2", None, dt, False, None, W[3], self.inp.device, nrb=lambda: ops.conv_img_mfma_stat_blocks(B, S, S))
+            ops.conv_img_mfma(dt, [dimg], self.l4p.wp_fwd, self.da[2], B, C, S, S, bwd_ep(fused, 2), gates=[self.img], gate_act=ACT_TANH)
         else:
             ops.conv_fwd(self.l4p.c, dt, self.patches, self.l4p.wp_fwd, self.da[2], None)
         # L3..L1
         for i, idx in ((2, 7), (1, 4), (0, 1)):
             r = self.mid[i]
-            bn = gen.conv_blocks[idx + 1]
             M = self.z[i].numel() // W[i + 1]
-            if fused[0]:
-                ops.bn_bwd_fused(dt, self.z[i], self.da[i], self.dz[i], M, W[i + 1], fused[1], fused[0], bn.weight, bn.bias, self.mean[i], self.invstd[i],
-                                 gof(f"conv_blocks.{idx + 1}.weight"), gof(f"conv_blocks.{idx + 1}.bias"), ws.sums, ws.small, accumulate=acc)
-            elif sync is not None:
-                ops.bn_bwd_sums_local(dt, self.z[i], self.da[i], M, W[i + 1], bn.weight, bn.bias, self.mean[i], self.invstd[i], ACT_RELU, 0.0,
-                                      gof(f"conv_blocks.{idx + 1}.weight"), gof(f"conv_blocks.{idx + 1}.bias"), self.bn_sums[i], ws.small,
-                                      accumulate=acc)
-                sync.reduce_sums(self.bn_sums[i])
-                ops.bn_bwd_from_sums(dt, self.z[i], self.da[i], self.dz[i], M, W[i + 1], self.bn_sums[i], M * sync.world, bn.weight, bn.bias,
-                                     self.mean[i], self.invstd[i], ACT_RELU, 0.0, ws.small)
-            else:
-                ops.bn_bwd(dt, self.z[i], self.da[i], self.dz[i], M, W[i + 1], bn.weight, bn.bias, self.mean[i], self.invstd[i], ACT_RELU, 0.0,
-                           gof(f"conv_blocks.{idx + 1}.weight"), gof(f"conv_blocks.{idx + 1}.bias"), ws.sums, ws.small, accumulate=acc)
+            bn_train_backward(dt, self.z[i], self.da[i], self.dz[i], M, W[i + 1], bn_of(i), self.mean[i], self.invstd[i], ACT_RELU, 0.0,
+                              gof(f"conv_blocks.{idx + 1}.weight"), gof(f"conv_blocks.{idx + 1}.bias"), ws, sync, self.sync_scratch.sums[i], fused, acc)
             x_in = self.a[i - 1] if i > 0 else self.h0
 
             def mid_wgrad(wsw, i=i, idx=idx, r=r, M=M, x_in=x_in):
                 ns = ops.conv_wgrad(r.c, dt, self.dz[i], x_in, wsw.slab, wsw.wgs_target)
                 ops.wgrad_reduce(wsw.slab, ns, r.Cout, r.Cout, r.Cin, 16, gof(f"conv_blocks.{idx}.weight"), accumulate=acc)
                 ops.bias_grad(dt, self.dz[i], M, W[i + 1], wsw.small, gof(f"conv_blocks.{idx}.bias"), accumulate=acc)
-            wgrad_side(mid_wgrad, i + 1, f"G{i + 1}")
+            wgrad_side(side, ws, i + 1, mid_wgrad, f"G{i + 1}")
             fused = (0, None)
             if i > 0 and sync is None:
                 # the launch that produces d(a[i-1]) also forms dy = da * relu'(bn(z)) and the two sums of that layer's BatchNorm backward
                 fused = self._stat_buf(("bwd", i - 1), r.c, False, ops.epilogue(), W[i])
-            if fused[0]:
-                bnl = gen.conv_blocks[(1, 4, 7)[i - 1] + 1]
-                ops.conv_fwd(r.c, dt, self.dz[i], r.wp_fwd, self.da[i - 1],
-                             ops.epilogue(stat_mode=ops.STAT_BN_BWD, stat_out=fused[1], stat_aux=self.z[i - 1],
-                                          stat_p=(self.mean[i - 1], self.invstd[i - 1], bnl.weight, bnl.bias), stat_act=ACT_RELU))
-            else:
-                ops.conv_fwd(r.c, dt, self.dz[i], r.wp_fwd, self.da[i - 1] if i > 0 else self.dh0, None)
+            ops.conv_fwd(r.c, dt, self.dz[i], r.wp_fwd, self.da[i - 1] if i > 0 else self.dh0, bwd_ep(fused, i - 1))
 
         # L0
         def l0_wgrad(wsw):
             ns = ops.conv_wgrad(self.l0w.c, dt, self.dh0, self.inp, wsw.slab, wsw.wgs_target)
             ops.wgrad_reduce(wsw.slab, ns, self.cpad, self.cin, W[0], 16, gof("conv_blocks.0.weight"), accumulate=acc)
             ops.bias_grad(dt, self.dh0, B * 16, W[0], wsw.small, gof("conv_blocks.0.bias"), accumulate=acc)
-        wgrad_side(l0_wgrad, 0, "G0")
-
-
-class _HipModule(nn.Module):
-    """Shared plumbing: flat arena, per-batch engines, invalidation when the module is moved."""
-
-    compute_dtype = EG_F32
-
-    def _init_engine_state(self, dtype):
-        self.compute_dtype = parse_dtype(dtype)
-        self._arena = None
-        self._engines = {}
-
-    def _apply(self, fn, *a, **k):
-        out = super()._apply(fn, *a, **k)
-        self._arena, self._engines = None, {}
-        return out
-
-    @property
-    def arena(self) -> Arena:
-        if self._arena is None:
-            p = next(self.parameters())
-            _require_cuda(p)
-            self._arena = Arena(self)
-            self._engines = {}
-        return self._arena
-
-    def set_compute_dtype(self, dtype):
-        self.compute_dtype = parse_dtype(dtype)
-
-    def repack(self):
-        """Refresh the packed (kernel-layout, compute-dtype) weight panels after the fp32 masters changed."""
-        for e in self._engines.values():
-            e.repack()
-
-    def fresh_engine(self, B):
-        """The engine for batch size B with panels re-packed from the masters: the drop-in forward path.  The kernels read packed
-        copies of the convolution weights, and the masters can change behind the module's back in ways nothing reports --
-        ``optimizer.step()`` bumps a version counter, ``module.apply(weights_init_normal)`` writes through ``.data`` and does not -- so
-        every drop-in forward re-packs first (2 small launches per layer, asynchronous).  The fused trainers keep masters and panels in
-        step themselves and never come through here."""
-        eng = self.engine(B)
-        eng.repack()
-        return eng
-
-    def load_state_dict(self, *a, **k):
-        out = super().load_state_dict(*a, **k)
-        self.repack()
-        return out
+        wgrad_side(side, ws, 0, l0_wgrad, "G0")
 
 
 class Generator(_HipModule):
@@ -531,14 +417,11 @@ class _DiscEngine:
 
     def _stat_buf(self, i, T, c, ep):
         """fused sums of layer i's bias gradient / spectral-norm coefficient in the backward-data launch that produces dzs_i (T tapes):
-        (row blocks, buffer), (0, None) where that launch cannot take them (see _GenEngine._stat_buf)"""
-        key = (i, T)
-        if key not in self._stat:
-            ok = self.rows(i + 1) % 256 == 0
-            nrb = ops.conv_stat_blocks(c, self.dtype, True, ep) if ok else 0
-            N = D_WIDTHS[i]
-            self._stat[key] = (nrb, torch.empty(N * nrb + nrb * (N // 128), device=self.out.device, dtype=torch.float32) if nrb else None)
-        return self._stat[key]
+        (row blocks, buffer), (0, None) where that launch cannot take them (engine.stat_buffer; whole 256-row tiles per tape only)"""
+        N = D_WIDTHS[i]
+        return stat_buffer(self._stat, (i, T), c, self.dtype, True, ep, N, self.out.device,
+                           nrb=lambda: ops.conv_stat_blocks(c, self.dtype, True, ep) if self.rows(i + 1) % 256 == 0 else 0,
+                           floats=lambda nrb: N * nrb + nrb * (N // 128))
 
     def _sn_tape(self, t, training=True):
         ops.sn_power_iter_multi(self._sn(t), self.sn_scratch, training, SN_EPS)
@@ -626,19 +509,13 @@ class _DiscEngine:
         g = self.geo[T]
         sl = lambda buf: buf[t0 * (buf.shape[0] // self.NT):]
         K = 16 * W[3]
-        def wgrad_side(fn, lane, tag=None):
-            if side is None:
-                fn(ws)
-            else:
-                side.defer(lane, fn, tag)
-
         if need_wgrad:
             def head_wgrad(wsw):
                 ops.cast_pad(dt, dout, self.dout_t, T * B, self.nout, 32)
                 ns = ops.conv_wgrad(g["headw"], dt, sl(self.a[3]), self.dout_t, wsw.slab, wsw.wgs_target)
                 ops.wgrad_reduce(wsw.slab, ns, 32, self.nout, W[3], 16, gof("main.8.weight"), accumulate=acc)
                 ops.dense_small_bgrad(dout, gof("main.8.bias"), T * B, self.nout, accumulate=acc)
-            wgrad_side(head_wgrad, 0, "D4")
+            wgrad_side(side, ws, 0, head_wgrad, "D4")
         # dzs_3 = (W5^T dout) * lrelu'(a3) / sigma_3[tape]
         if not head_done:
             ops.dense_small_bwd(dt, dout, self.head.wp_fwd, sl(self.a[3]), sl(self.dz[3]), T * B, K, self.head.Kpad_fwd, self.nout, ACT_LRELU, LRELU_SLOPE,
@@ -667,7 +544,7 @@ class _DiscEngine:
                     taps = 16 if i > 0 else 1
                     ops.wgrad_reduce_rank1(wsw.slab, ns, W[i], W[i], self.cin[i], taps, gof(f"main.{2 * i}.weight_orig"), T, self.coef[i],
                                            self.u[i][t0:], self.v[i][t0:], accumulate=acc)
-                wgrad_side(layer_wgrad, i + 1, f"D{i}")
+                wgrad_side(side, ws, i + 1, layer_wgrad, f"D{i}")
             if i > 0:
                 # dzs_{i-1} = conv^T(dzs_i, W_i) * lrelu'(a_{i-1}) / sigma_{i-1}[tape]
                 kw = dict(sigma=self.sigma[i - 1][t0:], sigma_rows=self.rows(i), mask=sl(self.a[i - 1]), mask_act=ACT_LRELU, mask_slope=LRELU_SLOPE)
@@ -677,13 +554,7 @@ class _DiscEngine:
                     kw.update(stat_mode=ops.STAT_SN_BIAS, stat_out=fused[1], stat_p=(self._m(i - 1).bias,), stat_slope=LRELU_SLOPE)
                 ops.conv_bwd_data(geo, dt, sl(self.dz[i]), self.mid[i - 1].wp_bwd, sl(self.dz[i - 1]), ops.epilogue(**kw))
         if need_dimg:
-            if IMG_GEMM and ops.convt_img_mfma_ok(dt, self.C, self.S // 2, self.S // 2, W[0], 4, 2, 1):
-                ops.convt_img_mfma(dt, sl(self.dz[0]), self.l1g.wp_fwd, None, self.dimg, B, self.C, self.S // 2, self.S // 2, ACT_NONE, 0.0)
-            elif IMG_GEMM:
-                ops.conv_fwd(self.l1g.c, dt, sl(self.dz[0]), self.l1g.wp_fwd, self.cols1, None)
-                ops.col2im_img(dt, self.cols1, B, self.C, self.S // 2, self.S // 2, 4, 2, 1, None, ACT_NONE, 0.0, self.dimg)
-            else:
-                ops.conv_bwd_data(self.l1.c, dt, sl(self.dz[0]), self.l1.wp_bwd, self.dimg, ops.epilogue(out_mode=OUT_NCHW_F32))
+            convt_img(dt, sl(self.dz[0]), self.l1g, self.cols1, self.l1, None, ACT_NONE, self.dimg, True)
             return self.dimg
         return None
 
@@ -753,123 +624,20 @@ class _DiscFn(torch.autograd.Function):
 
 
 # ================================================================================================
-# affine utilities (celebA/utils_rpqxy.py) and the STN warp
+# affine utilities (celebA/utils_rpqxy.py); the STN warp and the code -> matrix functions: affine.py
 # ================================================================================================
-class _ThetaFn(torch.autograd.Function):
-    """code [B, ld] -> theta [B, 2, 3] by ``ops.theta_<kind>``; backward: ``ops.theta_bwd`` (no double backward)"""
-
-    @staticmethod
-    def forward(ctx, code, kind):
-        B, ld = code.shape
-        theta = torch.empty(B, 2, 3, device=code.device, dtype=torch.float32)
-        getattr(ops, "theta_" + kind)(code, ld, B, theta)
-        ctx.save_for_backward(code)
-        ctx.kind = kind
-        return theta
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dtheta):
-        code, = ctx.saved_tensors
-        dcode = torch.empty_like(code)
-        ops.theta_bwd(ops.THETA_KINDS[ctx.kind], code, code.shape[1], code.shape[0], dtheta.float().contiguous(), dcode)
-        return dcode, None
-
-
-def _code_to_theta(kind, code_input_raw):
-    """rows 0, 1 of the kind's matrix, differentiable with respect to the codes"""
-    _require_cuda(code_input_raw)
-    return _ThetaFn.apply(code_input_raw.float().contiguous(), kind)
-
-
 def get_matrix(code_input_raw):
     """[B,>=5] latent codes -> [B,3,3] affine matrices R(theta) Z(p,q) T(x,y)  (utils_rpqxy.py:59-80)."""
-    theta = _code_to_theta("rpqxy", code_input_raw)
-    A = torch.zeros(theta.shape[0], 3, 3, device=theta.device, dtype=torch.float32)
-    A[:, :2] = theta
-    A[:, 2, 2] = 1.0
-    return A
+    return theta_to_matrix(_code_to_theta("rpqxy", code_input_raw))
 
 
-class _WarpFn(torch.autograd.Function):
-    """``ops.warp_affine`` / ``ops.warp_affine_zeros``; backward: ``ops.warp_affine_bwd`` for the inputs that need it (no double backward)"""
-
-    @staticmethod
-    def forward(ctx, img, theta, zeros):
-        out = torch.empty_like(img)
-        B, C, H, W = img.shape
-        (ops.warp_affine_zeros if zeros else ops.warp_affine)(img, theta, out, B, C, H, W)
-        ctx.save_for_backward(img, theta)
-        ctx.zeros = zeros
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dout):
-        img, theta = ctx.saved_tensors
-        B, C, H, W = img.shape
-        dimg = torch.empty_like(img) if ctx.needs_input_grad[0] else None
-        dtheta = torch.empty_like(theta) if ctx.needs_input_grad[1] else None
-        ops.warp_affine_bwd(img, theta, dout.float().contiguous(), dimg, dtheta, B, C, H, W, ctx.zeros)
-        return dimg, dtheta, None
-
-
-class transformation_2D(nn.Module):
-    """affine_grid + grid_sample(bilinear, ``padding_mode`` 'border' or 'zeros', align_corners=False) as one HIP kernel (:144-158;
-    'zeros': colored_dSprites/pxy_color.py:90); differentiable with respect to the image and the matrix."""
-
-    def __init__(self, padding_mode="border"):
-        super().__init__()
-        if padding_mode not in ("border", "zeros"):
-            raise ValueError("transformation_2D: padding_mode must be 'border' or 'zeros'")
-        self.padding_mode = padding_mode
-
-    def stn(self, x, matrix_2D):
-        _require_cuda(x)
-        return _WarpFn.apply(x.float().contiguous(), matrix_2D.float().contiguous(), self.padding_mode == "zeros")
-
-    def forward(self, img, matrix_2D):
-        return self.stn(img, matrix_2D)
-
-
-# The regularizer kernels return the gradient of an MSE, gs * (pred - target) * J with gs = 2 * scale / (n B); the drop-in backward gets J^T dpred
-# out of them with target = pred - dpred * (n B / 2).  The kernel then recovers dpred * n B / 2 as a float32 difference of two numbers of size
-# |pred|: relative error 2^-24 * |pred| / (|dpred| n B / 2), 2e-4 for an upstream gradient of 1e-6 at B = 128.  Both the target's offset and
-# 1 / scale therefore carry the factor GRAD_UP, a power of two (exact in both places): the difference is then GRAD_UP times larger than the
-# rounding of pred, and once it exceeds |pred| its error is its own rounding, 2^-24 relative.  Overflow would need |dpred| n B / 2 > 7e28.
-GRAD_UP = 2.0 ** 32
-
-
-class _AffineRegFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, real_code, trans_code):
-        B, ld = real_code.shape
-        pred = torch.empty(B, 5, device=real_code.device, dtype=torch.float32)
-        zero_code = torch.zeros(B, 5, device=real_code.device, dtype=torch.float32)
-        ops.loss_affine_rpqxy(real_code, trans_code, ld, 0, B, zero_code, 5, 1.0, None, None, None, pred)
-        ctx.save_for_backward(real_code, trans_code)
-        return pred
-
-    @staticmethod
-    def backward(ctx, dpred):
-        # d/dcode of sum_j dpred_j * pred_j  ==  gradient of the MSE kernel with target = pred - dpred*(5B/2); target and scale carry the
-        # power of two GRAD_UP (see there)
-        real_code, trans_code = ctx.saved_tensors
-        B, ld = real_code.shape
-        pred = torch.empty(B, 5, device=real_code.device, dtype=torch.float32)
-        zero_code = torch.zeros(B, 5, device=real_code.device, dtype=torch.float32)
-        ops.loss_affine_rpqxy(real_code, trans_code, ld, 0, B, zero_code, 5, 1.0, None, None, None, pred)
-        tgt = pred - dpred.float() * (GRAD_UP * 5.0 * B / 2.0)
-        d_real = torch.empty_like(real_code)
-        d_trans = torch.empty_like(trans_code)
-        ops.loss_affine_rpqxy(real_code, trans_code, ld, 0, B, tgt.contiguous(), 5, 1.0 / GRAD_UP, None, d_real, d_trans, None)
-        return d_real, d_trans
+_regularizer = affine.regularizer(lambda real, trans, ld, B, target, scale, d_real, d_trans, pred: ops.loss_affine_rpqxy(
+    real, trans, ld, 0, B, target, 5, scale, None, d_real, d_trans, pred), 5)
 
 
 def affine_regularzier(real_code, trans_code):
     """closed-form relative-transform recovery (utils_rpqxy.py:82-116); spelling follows the reference."""
-    _require_cuda(real_code)
-    return _AffineRegFn.apply(real_code.float().contiguous(), trans_code.float().contiguous())
+    return _regularizer(real_code, trans_code)
 
 
 # ================================================================================================
@@ -943,7 +711,7 @@ def resize_center_crop_u8(images_u8: torch.Tensor, size: int = 64) -> torch.Tens
     return out
 
 
-class DeviceInputs:
+class DeviceInputs(DeviceSampler):
     """Device-side replacement of the loop's host input work (celebA/EAD-GAN_celebA.py:194-206 DataLoader + RandomHorizontalFlip +
     ToTensor + Normalize(0.5, 0.5); :308-317 numpy draws of z ~ N(0,1), code ~ U(-1,1), labels ~ randint): a uint8 [N,3,64,64] dataset
     resident in HBM (resized / cropped once on the way in: ``resize_center_crop_u8``) and a counter-based generator.  ``enqueue(trainer)`` fills the trainer's
@@ -953,64 +721,44 @@ class DeviceInputs:
 
     def __init__(self, dataset_u8: torch.Tensor, seed: int = 0, flip: bool = True, sampling: str = "permutation", *, rank: int = 0,
                  world: int = 1):
-        """``sampling``: "permutation" (default) = DataLoader(shuffle=True) of the reference (:204-206): a keyed permutation of the dataset
-        per epoch, every image exactly once, batches of constant size straddle epoch ends; "replacement" = independent uniform draws.
-        ``rank`` / ``world`` (data parallel): every draw is this rank's shard of the global batch's draw (engine.shard_span): the ranks'
-        slots, concatenated, are one rank's at the global batch; ``step`` counts global iterations on every rank"""
+        """``sampling``, ``rank`` / ``world``: engine.DeviceSampler ("permutation" = DataLoader(shuffle=True) of the reference, :204-206;
+        batches of constant size straddle epoch ends)"""
         _require_cuda(dataset_u8)
         if dataset_u8.dtype != torch.uint8 or dataset_u8.dim() != 4:
             raise ValueError("dataset must be a uint8 [N, C, H, W] device tensor")
-        if sampling not in ("permutation", "replacement"):
-            raise ValueError("sampling must be 'permutation' or 'replacement'")
-        shard_span(0, rank, world)
-        self.rank, self.world = int(rank), int(world)
-        self.data = dataset_u8.contiguous()
-        self.sampling = sampling
-        self.seed, self.flip = int(seed), flip
-        dev = dataset_u8.device
-        self.step = torch.zeros(1, device=dev, dtype=torch.int32)
-        self.idx = None
-        self.flips = None
+        super().__init__(dataset_u8, seed, sampling, rank=rank, world=world)
+        self.flip = flip
 
     def enqueue(self, tr: "CelebATrainer"):
         B = tr.B
         N, C, H, W = self.data.shape
-        if self.idx is None or self.idx.numel() != B:
-            self.idx = torch.empty(B, device=self.data.device, dtype=torch.int64)
-            self.flips = torch.empty(B, device=self.data.device, dtype=torch.uint8)
-        if FUSE_DRAWS:
-            # the five draws + the one-hot labels as one launch, the counter tick inside the gather: 3 launches instead of 8 at the head of
-            # the iteration's critical chain (the same values: a draw depends on (element, step, stream id, seed) only)
-            first = (ops.RNG_EPOCH_PERM, self.idx, N, 0, 1) if self.sampling == "permutation" else (ops.RNG_RANDINT, self.idx, 0, N, 1)
-            ops.rng_fill_multi([first,                                                      # which images: epoch permutation / uniform draws
-                                (ops.RNG_BERNOULLI, self.flips, 0.5, 0.0, 2),               # RandomHorizontalFlip(p=0.5)
-                                (ops.RNG_NORMAL, tr.z, 0.0, 1.0, 3), (ops.RNG_UNIFORM, tr.code, -1.0, 1.0, 4),
-                                (ops.RNG_RANDINT, tr.labels, 0, tr.G.n_classes, 5, tr.onehot)], self.seed, self.step, self.rank, self.world)
-            def gather():                               # ToTensor + Normalize(.5,.5)
-                ops.gather_u8_images(self.data, self.idx, self.flips if self.flip else None, tr.real, B, C, H, W, 2.0 / 255.0, -1.0, tick=self.step)
-            if tr.side is not None:
-                tr._inputs_tail = gather                # the pipelined body runs it on its preparation lane, in front of the warp
-            else:
-                gather()
+        # the five draws + the one-hot labels as one launch, the counter tick inside the gather: 3 launches instead of 8 at the head of
+        # the iteration's critical chain (the same values: a draw depends on (element, step, stream id, seed) only)
+        self.begin_draws()
+        idx = self.sample_indices(B, 1)                                 # which images: epoch permutation / uniform draws
+        flips = self.buf("flips", (B,), torch.uint8)
+        self.draw(ops.RNG_BERNOULLI, flips, 0.5, 0.0, 2)                # RandomHorizontalFlip(p=0.5)
+        self.draw(ops.RNG_NORMAL, tr.z, 0.0, 1.0, 3)
+        self.draw(ops.RNG_UNIFORM, tr.code, -1.0, 1.0, 4)
+        self.labels_onehot("labels", tr.onehot, tr.G.n_classes, 5, lab=tr.labels)
+        self.end_draws()
+        fused = engine.FUSE_DRAWS
+
+        def gather():                                   # ToTensor + Normalize(.5,.5)
+            ops.gather_u8_images(self.data, idx, flips if self.flip else None, tr.real, B, C, H, W, 2.0 / 255.0, -1.0, tick=self.step if fused else None)
+        if fused and tr.side is not None:
+            tr._inputs_tail = gather                    # the pipelined body runs it on its preparation lane, in front of the warp
             return
-        if self.sampling == "permutation":
-            ops.rng_fill(ops.RNG_EPOCH_PERM, self.idx, N, 0, self.seed, self.step, 1, self.rank, self.world)
-        else:
-            ops.rng_fill(ops.RNG_RANDINT, self.idx, 0, N, self.seed, self.step, 1, self.rank, self.world)
-        ops.rng_fill(ops.RNG_BERNOULLI, self.flips, 0.5, 0.0, self.seed, self.step, 2, self.rank, self.world)     # RandomHorizontalFlip(p=0.5)
-        ops.gather_u8_images(self.data, self.idx, self.flips if self.flip else None, tr.real, B, C, H, W, 2.0 / 255.0, -1.0)   # ToTensor + Normalize(.5,.5)
-        ops.rng_fill(ops.RNG_NORMAL, tr.z, 0.0, 1.0, self.seed, self.step, 3, self.rank, self.world)
-        ops.rng_fill(ops.RNG_UNIFORM, tr.code, -1.0, 1.0, self.seed, self.step, 4, self.rank, self.world)
-        ops.rng_fill(ops.RNG_RANDINT, tr.labels, 0, tr.G.n_classes, self.seed, self.step, 5, self.rank, self.world)
-        ops.onehot(tr.labels, tr.onehot, B, tr.G.n_classes)
-        ops.counter_add(self.step, 1)
+        gather()
+        if not fused:
+            self.tick()
 
 
 # data parallel: gradient buckets that cross the links as one message, in completion order (contiguous in the arenas)
 COMM_GROUPS = {"G": (("G4", "G3", "G2"), ("G1", "G0")), "D": (("D4", "D3"), ("D2", "D1", "D0"))}
 
 
-class CelebATrainer(TrainerState):
+class CelebATrainer(ResidentStep):
     """One call of :meth:`train_step` == one iteration of the reference loop body
     (celebA/EAD-GAN_celebA.py:299-401): G adversarial step, D step, info+affine step, three Adams
     (lr 1e-3 / 2e-4 / 2e-4, betas (.5,.999), :211-217) -- hand-scheduled over the C ABI with dead work removed
@@ -1132,7 +880,7 @@ class CelebATrainer(TrainerState):
     def _inputs_head(self):
         G, B = self.G, self.B
         # A = get_matrix(code[:, :5]); scaled = trans_2D(real, A[:, 0:2])           (:325-327)
-        if FUSE_DRAWS and (G.img_size * G.img_size) % 256 == 0:
+        if engine.FUSE_DRAWS and (G.img_size * G.img_size) % 256 == 0:
             ops.warp_affine_rpqxy(self.real, self.code, G.code_dim, self.theta, self.scaled, B, G.channels, G.img_size, G.img_size, zero=self.losses)
             return
         ops.fill_f32(self.losses)
@@ -1141,13 +889,7 @@ class CelebATrainer(TrainerState):
 
     def _reduce(self, flat):
         """gradient average over the ranks, on the CURRENT stream (the optimizer lane: only that lane waits for the collective)"""
-        ar = self.allreduce
-        if ar is None:
-            return
-        if hasattr(ar, "start"):
-            ar.finish(ar.start(flat))
-        else:
-            ar(flat)
+        engine.allreduce_finish(self.allreduce, flat, engine.allreduce_start(self.allreduce, flat))
 
     def _step_body_serial(self):
         """one stream, program order of the reference loop body (overlap=False; the pipelined body below is bit-identical)"""
@@ -1381,24 +1123,10 @@ class CelebATrainer(TrainerState):
     def import_adam_state(self, opt_G, opt_D, opt_info):
         """Load exp_avg / exp_avg_sq / step of three ``torch.optim.Adam`` objects built like the reference's
         (celebA/EAD-GAN_celebA.py:211-217: G params | D params | G+D params, in ``.parameters()`` order)."""
-        def fill(opt, params, m, v, off0=0):
-            off = off0
-            step = 0
-            for p in params:
-                st = opt.state.get(p, {})
-                n = p.numel()
-                if st:
-                    m[off:off + n].copy_(st["exp_avg"].reshape(-1))
-                    v[off:off + n].copy_(st["exp_avg_sq"].reshape(-1))
-                    step = int(st["step"])
-                off += n
-            return step
-        gp, dp = opt_G.param_groups[0]["params"], opt_D.param_groups[0]["params"]
-        ip = opt_info.param_groups[0]["params"]
-        s0 = fill(opt_G, gp, self.mG, self.vG)
-        s1 = fill(opt_D, dp, self.mD, self.vD)
-        s2 = fill(opt_info, ip[:len(gp)], self.miG, self.viG)
-        fill(opt_info, ip[len(gp):], self.miD, self.viD)
+        nG, nD = len(list(self.G.parameters())), len(list(self.D.parameters()))
+        s0 = import_adam_moments(opt_G, [(nG, self.mG, self.vG)])
+        s1 = import_adam_moments(opt_D, [(nD, self.mD, self.vD)])
+        s2 = import_adam_moments(opt_info, [(nG, self.miG, self.viG), (nD, self.miD, self.viD)])
         self.steps.copy_(torch.tensor([s0, s1, s2], dtype=torch.int32))
 
     def load_inputs(self, real_imgs, z, code, labels):
@@ -1420,24 +1148,11 @@ class CelebATrainer(TrainerState):
         Gradients: an iteration never clears the gradient arenas (every backward pass stores), so ``capture(warmup=False)`` clears them
         once, outside the graph -- the gradients a previous eager iteration left in ``.grad`` are gone after this call; read them before
         capturing.  With ``warmup=True`` nothing is cleared: the arenas hold the warm-up iteration's gradients, as after any iteration."""
-        if warmup:
-            self._step_body()
-        else:
+        if not warmup:
             # a replay clears nothing (WRITER TABLE): the arenas enter the graph's first replay cleared, as they enter the first eager iteration
             ops.fill_f32(self.G.arena.grad)
             ops.fill_f32(self.D.arena.grad)
-        if inputs is not None:
-            self.inputs = inputs
-        if log is not None:
-            self.log = log
-        return capture_step(self, self._step_with_inputs)
-
-    def _step_with_inputs(self):
-        if getattr(self, "inputs", None) is not None:
-            self.inputs.enqueue(self)
-        self._step_body()
-        if self.log is not None:                        # behind the body's join of its lanes, on the main stream
-            self.log.append()
+        return super().capture(warmup, inputs, log)
 
     # -- full state (engine.TrainerState) -------------------------------------------------------------
     STATE_KIND = "celeba"
@@ -1454,15 +1169,8 @@ class CelebATrainer(TrainerState):
         if self.de._head_scratch is not None:
             self.de._head_scratch[1].zero_()
 
-    def step_resident(self):
-        """Run one iteration on whatever is in the static input slots (or on fresh device-side draws if the trainer was captured /
-        configured with a DeviceInputs); returns the device loss tensor [g,d,info,_]."""
-        check_usable(self)
-        if self.graph is not None:
-            self.graph.replay()
-        else:
-            self._step_with_inputs()
-        return self.losses
+    # step_resident() (engine.ResidentStep): one iteration on whatever is in the static input slots (or on fresh device-side draws if the
+    # trainer was captured / configured with a DeviceInputs); returns the device loss tensor [g,d,info,_]
 
     def train_step(self, real_imgs, z, code, labels):
         """train-loop entry: real_imgs [B,3,64,64] in [-1,1], z [B,200], code [B,8], labels int64 [B]."""

@@ -7,9 +7,9 @@ import argparse
 
 import torch
 
+from . import affine, ops
 from . import dsprites as ds
-from . import ops
-from .celeba import GRAD_UP, _require_cuda, transformation_2D          # noqa: F401
+from .affine import transformation_2D          # noqa: F401
 from .dsprites import get_matrix, get_matrix_D, get_matrix_pxy, get_matrix_pxy_align, mutual_info_loss, to_categorical      # noqa: F401
 
 opt = argparse.Namespace(n_epochs=100, batch_size=128, lr=0.0002, b1=0.5, b2=0.999, n_cpu=8, latent_dim=200, code_dim=7, n_classes=3,
@@ -46,29 +46,13 @@ def from_latent_vector_2_color_para_pxy(code_input_raw):
     return code_input_raw * 0.1 + 1
 
 
-class _AffineColorFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, real_code, trans_code):
-        B, ld = real_code.shape
-        pred = torch.empty(B, 7, device=real_code.device)
-        ops.loss_affine_rp_color(real_code, trans_code, ld, 0, B, torch.zeros(B, 7, device=real_code.device), 7, 1.0, None, None, None, pred)
-        ctx.save_for_backward(real_code, trans_code, pred)
-        return pred
-
-    @staticmethod
-    def backward(ctx, dpred):
-        real_code, trans_code, pred = ctx.saved_tensors
-        B, ld = real_code.shape
-        tgt = (pred - dpred.float() * (GRAD_UP * 7.0 * B / 2.0)).contiguous()
-        d_real, d_trans = torch.empty_like(real_code), torch.empty_like(trans_code)
-        ops.loss_affine_rp_color(real_code, trans_code, ld, 0, B, tgt, 7, 1.0 / GRAD_UP, None, d_real, d_trans, None)
-        return d_real, d_trans
+_regularizer = affine.regularizer(lambda real, trans, ld, B, target, scale, d_real, d_trans, pred: ops.loss_affine_rp_color(
+    real, trans, ld, 0, B, target, 7, scale, None, d_real, d_trans, pred), 7)
 
 
 def affine_color_regularzier(real_code, trans_code):
     """utils_rp_color.py:100-139: 4 affine codes as dSprites + relative RGB gains."""
-    _require_cuda(real_code)
-    return _AffineColorFn.apply(real_code.float().contiguous(), trans_code.float().contiguous())
+    return _regularizer(real_code, trans_code)
 
 
 class ColoredTrainer(ds.DspritesTrainer):

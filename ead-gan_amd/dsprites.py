@@ -6,17 +6,18 @@ entry :class:`DspritesTrainer` (loop body rp.py:365-482).  torch modules are par
 from __future__ import annotations
 
 import argparse
+import itertools
 
-import numpy as np
 import torch
 import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
-from . import ops
-from .celeba import GRAD_UP, IMG_GEMM, _code_to_theta, _HipModule, _require_cuda, transformation_2D      # noqa: F401
-from .engine import FUSE_DRAWS, Arena, ConvRec, DeviceSampler, ResidentStep, SideStream, SyncScratch, Workspace, bn_train_backward, bn_train_forward, capture_step, check_usable, parse_dtype
-from .ops import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, EG_F32, OUT_NCHW_F32
-from .trunk import Head, TrunkEngine
+from . import affine, engine, ops
+from .affine import _code_to_theta, theta_to_matrix, transformation_2D      # noqa: F401
+from .engine import (Arena, ConvRec, DeviceSampler, ResidentStep, SideStream, SyncScratch, Workspace, _HipModule, _require_cuda, bn_bwd_epilogue, bn_train_backward,
+                     bn_train_forward, convt_img, import_adam_moments, parse_dtype, stat_buffer, to_categorical, wgrad_side)      # noqa: F401
+from .ops import ACT_LRELU, ACT_RELU, ACT_SIGMOID, EG_F32
+from .trunk import Head, TrunkEngine, _TrunkFn
 
 opt = argparse.Namespace(n_epochs=100, batch_size=128, lr=0.0001, b1=0.5, b2=0.999, n_cpu=8, latent_dim=200, code_dim=4, n_classes=3,
                          img_size=64, channels=1, sample_interval=1000)           # argparse defaults rp.py:40-51
@@ -26,11 +27,6 @@ TRUNK = (32, 32, 64, 64)
 # two GEMMs over them.  Same results within fp32 summation order (tests), one launch fewer, but SLOWER in the step: dSprites 1.305 -> 1.32 ms,
 # colored 2.50 -> 2.53 (profiles/r03_zzo_ab_l4_direct.txt): the statistics instantiation of the image kernel runs two workgroups per CU.
 # So no engine takes it by itself (``_GenEngine.l4_direct`` starts False); the layer-wise tests set the attribute to check this form of the layer too.
-
-
-def to_categorical(y, num_columns, device=None):
-    y = torch.as_tensor(np.asarray(y), dtype=torch.int64, device=device)
-    return torch.nn.functional.one_hot(y, num_columns).to(torch.float32)
 
 
 def _trunk(ch, sn, slope):
@@ -152,7 +148,6 @@ class Discriminator(_TrunkModule):
         return [Head("fc2", self.fc2, sn=False)]
 
     def forward(self, img):
-        from .mnist import _TrunkFn
         _require_cuda(img)
         eng = self.fresh_engine(img.shape[0])
         t = self._next_tape
@@ -184,7 +179,6 @@ class Encoder(_TrunkModule):
         return [Head("cat_layer.0", self.cat_layer[0], sn=True), Head("cont_layer.0", self.cont_layer[0], sn=True)]
 
     def forward(self, img):
-        from .mnist import _TrunkFn
         _require_cuda(img)
         eng = self.fresh_engine(img.shape[0])
         t = self._next_tape
@@ -202,7 +196,7 @@ class _GenEngine:
         dev = gen.arena.flat.device
         tdt = ops.torch_dtype(dtype)
         self.ws = ws = Workspace.get(dev)
-        self._stat = {}                                 # fused-statistics buffers per launch (celeba._GenEngine._stat_buf)
+        self._stat = {}                                 # fused-statistics buffers per launch (engine.stat_buffer)
         self.cin = gen.n_classes + gen.code_dim
         self.cpad = ops.round_up(self.cin, 8)
         self.CH = gen.channels
@@ -214,7 +208,7 @@ class _GenEngine:
         self.kp = ops.round_up(self.k0, 8)
         self.l4p = ConvRec(dtype, B, 32, 32, self.kp, 64, 1, 1, 0, device=dev, want_bwd=False, ws=ws)
         # forward of the last ConvTranspose2d(64 -> C) as ONE GEMM over the 32x32 lattice with N = 16 taps x C columns + the col2im gather
-        # (eg_col2im_img): every activation read once instead of 16 times (see celeba._GenEngine.l4g)
+        # (eg_col2im_img): every activation read once instead of 16 times (engine.convt_img)
         self.l4g = ConvRec(dtype, B, 32, 32, 64, self.k0, 1, 1, 0, device=dev, want_bwd=False, want_wgrad=False, ws=ws)
         self.l4_direct = False                          # the image-direct backward of the last layer: measured slower, set by tests only (module comment)
         self.cols4 = torch.empty(B * 32 * 32, self.k0, device=dev, dtype=tdt)
@@ -244,11 +238,7 @@ class _GenEngine:
         self.repack()
 
     def _stat_buf(self, key, c, bwd, ep, C):
-        """(nrb, buffer) if the launch described by (c, bwd, ep) can take its column statistics in the epilogue, else (0, None)"""
-        if key not in self._stat:
-            nrb = ops.conv_stat_blocks(c, self.dtype, bwd, ep)
-            self._stat[key] = (nrb, torch.empty(2 * C * nrb, device=self.inp.device, dtype=torch.float32) if nrb else None)
-        return self._stat[key]
+        return stat_buffer(self._stat, key, c, self.dtype, bwd, ep, C, self.inp.device)
 
     @ops.batched_packs
     def repack(self):
@@ -280,29 +270,15 @@ class _GenEngine:
             r = self.mid[i]
             bn = cb[idx + 1]
             M = B * (8 << i) ** 2
-            nrb, stat = self._stat_buf(("fwd", i), r.c, True, ops.epilogue(bias=cb[idx].bias), 64) if (training and sync is None) else (0, None)
-            if nrb:
-                # BatchNorm batch statistics from the transposed convolution's epilogue (celeba._GenEngine.forward): two launches instead of three
-                ops.conv_bwd_data(r.c, dt, x, r.wp_bwd, self.z[i], ops.epilogue(bias=cb[idx].bias, stat_mode=ops.STAT_MOMENTS, stat_out=stat))
-                ops.bn_fwd_train_fused(dt, self.z[i], self.a[i], M, 64, stat, nrb, M // nrb, bn.weight, bn.bias, bn.eps, bn.momentum, bn.running_mean,
-                                       bn.running_var, bn.num_batches_tracked, self.mean[i], self.invstd[i], ws.small, ACT_RELU)
-                x = self.a[i]
-                continue
-            ops.conv_bwd_data(r.c, dt, x, r.wp_bwd, self.z[i], ops.epilogue(bias=cb[idx].bias))
-            if training:
-                bn_train_forward(dt, self.z[i], self.a[i], B * (8 << i) ** 2, 64, bn, self.mean[i], self.invstd[i], ws.small, ACT_RELU, 0.0, sync,
-                                 self.sync_scratch.stats[i])
-            else:
-                ops.bn_fwd_eval(dt, self.z[i], self.a[i], B * (8 << i) ** 2, 64, bn.weight, bn.bias, bn.eps, bn.running_mean, bn.running_var, ws.small, ACT_RELU)
+            # BatchNorm batch statistics from the transposed convolution's epilogue where it can take them: two launches instead of three
+            fused = self._stat_buf(("fwd", i), r.c, True, ops.epilogue(bias=cb[idx].bias), 64) if (training and sync is None) else (0, None)
+            ops.conv_bwd_data(r.c, dt, x, r.wp_bwd, self.z[i],
+                              ops.epilogue(bias=cb[idx].bias, stat_mode=ops.STAT_MOMENTS if fused[0] else ops.STAT_NONE, stat_out=fused[1]))
+            bn_train_forward(dt, self.z[i], self.a[i], M, 64, bn, self.mean[i], self.invstd[i], ws.small, ACT_RELU, 0.0, sync, self.sync_scratch.stats[i],
+                             training, fused)
             x = self.a[i]
-        if IMG_GEMM and self.l4g.Kpad_fwd == 64 and ops.convt_img_mfma_ok(dt, self.CH, 32, 32, 64, 4, 2, 1):
-            # GEMM + col2im gather as ONE launch (the columns stay in LDS; celeba._GenEngine.forward): same bits
-            ops.convt_img_mfma(dt, x, self.l4g.wp_fwd, cb[9].bias, self.img, B, self.CH, 32, 32, ACT_SIGMOID, 0.0, K=64)
-        elif IMG_GEMM:
-            ops.conv_fwd(self.l4g.c, dt, x, self.l4g.wp_fwd, self.cols4, None)
-            ops.col2im_img(dt, self.cols4, B, self.CH, 32, 32, 4, 2, 1, cb[9].bias, ACT_SIGMOID, 0.0, self.img)
-        else:
-            ops.conv_bwd_data(self.l4.c, dt, x, self.l4.wp_bwd, self.img, ops.epilogue(bias=cb[9].bias, act=ACT_SIGMOID, out_mode=OUT_NCHW_F32))
+        # GEMM + col2im gather as ONE launch (the columns stay in LDS: same bits) where the panel's K is one 64-wide step
+        convt_img(dt, x, self.l4g, self.cols4, self.l4, cb[9].bias, ACT_SIGMOID, self.img, self.l4g.Kpad_fwd == 64)
         return self.img
 
     def backward(self, dimg, grad, sync=None, side=None):
@@ -310,17 +286,10 @@ class _GenEngine:
         dt, B, g, ws = self.dtype, self.B, self.gen, self.ws
         cb = g.conv_block
         gof = lambda name: g.arena.grad_of(name, grad)
-        nlane = [0]
-
-        def wgrad_side(fn):
-            if side is None:
-                fn(ws)
-            else:
-                side.defer(nlane[0], fn)
-                nlane[0] += 1
+        lanes = itertools.count()
         ops.act_grad_mul_bias_nchw(dimg, self.img, self.dimg_z, B, self.CH, 64 * 64, ACT_SIGMOID, 0.0, ws.small, gof("conv_block.9.bias"))
         # the last layer's backward straight from the image gradient (no patch rows in HBM): weight gradient by eg_wgrad_img, input gradient by
-        # eg_conv_img_mfma with the BatchNorm-backward sums of the layer below in its epilogue (celeba._GenEngine.backward)
+        # eg_conv_img_mfma with the BatchNorm-backward sums of the layer below in its epilogue (as celeba._GenEngine.backward)
         direct = self.l4_direct and sync is None
         if not direct:
             ops.im2col_img(dt, self.dimg_z, self.patches, B, self.CH, 64, 64, 4, 2, 1, self.kp)
@@ -331,48 +300,36 @@ class _GenEngine:
             else:
                 ns = ops.conv_wgrad(self.l4p.c, dt, self.patches, self.a[2], wsw.slab, wsw.wgs_target)
             ops.wgrad_reduce_perm(wsw.slab, ns, 64, 64, self.kp, 1, gof("conv_block.9.weight"), 0, 0, self.k0)
-        wgrad_side(l4_wgrad)
+        wgrad_side(side, ws, next(lanes), l4_wgrad)
 
         def bn_bwd_ep(i, c):
-            """(row blocks, sums, epilogue) if the launch that produces da[i] can also form dy = da * relu'(bn(z)) and the two sums of layer
-            i's BatchNorm backward (celeba._GenEngine.backward), else (0, None, None)"""
-            nrb, stat = self._stat_buf(("bwd", i), c, False, ops.epilogue(), 64) if sync is None else (0, None)
-            if not nrb:
-                return 0, None, None
-            bnl = cb[(0, 3, 6)[i] + 1]
-            return nrb, stat, ops.epilogue(stat_mode=ops.STAT_BN_BWD, stat_out=stat, stat_aux=self.z[i], stat_p=(self.mean[i], self.invstd[i], bnl.weight, bnl.bias),
-                                           stat_act=ACT_RELU)
+            """((row blocks, sums), epilogue) if the launch that produces da[i] can also form dy = da * relu'(bn(z)) and the two sums of layer
+            i's BatchNorm backward (engine.bn_bwd_epilogue), else ((0, None), None)"""
+            fused = self._stat_buf(("bwd", i), c, False, ops.epilogue(), 64) if sync is None else (0, None)
+            return fused, bn_bwd_epilogue(fused[1], self.z[i], self.mean[i], self.invstd[i], cb[(0, 3, 6)[i] + 1]) if fused[0] else None
         if direct:
-            if "bwd_img" not in self._stat:
-                nrb = ops.conv_img_mfma_stat_blocks(B, 64, 64)
-                self._stat["bwd_img"] = (nrb, torch.empty(2 * 64 * nrb, device=self.inp.device, dtype=torch.float32))
-            nrb, stat = self._stat["bwd_img"]
-            fused = (nrb, stat, ops.epilogue(stat_mode=ops.STAT_BN_BWD, stat_out=stat, stat_aux=self.z[2], stat_p=(self.mean[2], self.invstd[2], cb[7].weight, cb[7].bias),
-                                             stat_act=ACT_RELU))
-            ops.conv_img_mfma(dt, [self.dimg_z], self.l4p.wp_fwd, self.da[2], B, self.CH, 64, 64, fused[2], N=64)
+            fused = stat_buffer(self._stat, "bwd_img", None, dt, False, None, 64, self.inp.device, nrb=lambda: ops.conv_img_mfma_stat_blocks(B, 64, 64))
+            ops.conv_img_mfma(dt, [self.dimg_z], self.l4p.wp_fwd, self.da[2], B, self.CH, 64, 64,
+                              bn_bwd_epilogue(fused[1], self.z[2], self.mean[2], self.invstd[2], cb[7]), N=64)
         else:
-            fused = bn_bwd_ep(2, self.l4p.c)
-            ops.conv_fwd(self.l4p.c, dt, self.patches, self.l4p.wp_fwd, self.da[2], fused[2])
+            fused, ep = bn_bwd_ep(2, self.l4p.c)
+            ops.conv_fwd(self.l4p.c, dt, self.patches, self.l4p.wp_fwd, self.da[2], ep)
         for i, idx in ((2, 6), (1, 3), (0, 0)):
             r = self.mid[i]
             bn = cb[idx + 1]
             M = B * (8 << i) ** 2
-            if fused[0]:
-                ops.bn_bwd_fused(dt, self.z[i], self.da[i], self.dz[i], M, 64, fused[1], fused[0], bn.weight, bn.bias, self.mean[i], self.invstd[i],
-                                 gof(f"conv_block.{idx + 1}.weight"), gof(f"conv_block.{idx + 1}.bias"), ws.sums, ws.small)
-            else:
-                bn_train_backward(dt, self.z[i], self.da[i], self.dz[i], M, 64, bn, self.mean[i], self.invstd[i], ACT_RELU, 0.0,
-                                  gof(f"conv_block.{idx + 1}.weight"), gof(f"conv_block.{idx + 1}.bias"), ws, sync, self.sync_scratch.sums[i])
+            bn_train_backward(dt, self.z[i], self.da[i], self.dz[i], M, 64, bn, self.mean[i], self.invstd[i], ACT_RELU, 0.0,
+                              gof(f"conv_block.{idx + 1}.weight"), gof(f"conv_block.{idx + 1}.bias"), ws, sync, self.sync_scratch.sums[i], fused)
             x_in = self.a[i - 1] if i > 0 else self.h
 
             def mid_wgrad(wsw, i=i, idx=idx, r=r, M=M, x_in=x_in):
                 ns = ops.conv_wgrad(r.c, dt, self.dz[i], x_in, wsw.slab, wsw.wgs_target)
                 ops.wgrad_reduce(wsw.slab, ns, 64, 64, 64, 16, gof(f"conv_block.{idx}.weight"))
                 ops.bias_grad(dt, self.dz[i], M, 64, wsw.small, gof(f"conv_block.{idx}.bias"))
-            wgrad_side(mid_wgrad)
+            wgrad_side(side, ws, next(lanes), mid_wgrad)
             if i > 0:
-                fused = bn_bwd_ep(i - 1, r.c)
-                ops.conv_fwd(r.c, dt, self.dz[i], r.wp_fwd, self.da[i - 1], fused[2])
+                fused, ep = bn_bwd_ep(i - 1, r.c)
+                ops.conv_fwd(r.c, dt, self.dz[i], r.wp_fwd, self.da[i - 1], ep)
             else:                                    # into the ReLU output of fc2: mask fused into the epilogue
                 ops.conv_fwd(r.c, dt, self.dz[i], r.wp_fwd, self.dh, ops.epilogue(mask=self.h, mask_act=ACT_RELU))
 
@@ -383,7 +340,7 @@ class _GenEngine:
             ops.fill_f32(self.gb2_perm)
             ops.bias_grad(dt, self.dh, B, 1024, wsw.small, self.gb2_perm)
             ops.gather_add(gof("fc2.0.bias"), self.gb2_perm, 1024, 16, 1, 64)
-        wgrad_side(fc2_wgrad)
+        wgrad_side(side, ws, next(lanes), fc2_wgrad)
         ops.conv_bwd_data(self.f2.c, dt, self.dh, self.f2.wp_bwd, self.dz1, ops.epilogue(mask=self.a1, mask_act=ACT_RELU))
 
         # fc1
@@ -391,7 +348,7 @@ class _GenEngine:
             ns = ops.conv_wgrad(self.f1.c, dt, self.inp, self.dz1, wsw.slab, wsw.wgs_target)
             ops.wgrad_reduce_perm(wsw.slab, ns, 128, 128, self.cpad, 1, gof("fc1.0.weight"), 0, 0, self.cin)
             ops.bias_grad(dt, self.dz1, B, 128, wsw.small, gof("fc1.0.bias"))
-        wgrad_side(fc1_wgrad)
+        wgrad_side(side, ws, next(lanes), fc1_wgrad)
 
 
 class Generator(_HipModule):
@@ -446,17 +403,9 @@ class _GenFn(torch.autograd.Function):
 # ================================================================================================
 # affine utilities / losses
 # ================================================================================================
-def _theta_to_A(theta):
-    B = theta.shape[0]
-    A = torch.zeros(B, 3, 3, device=theta.device, dtype=torch.float32)
-    A[:, :2] = theta
-    A[:, 2, 2] = 1.0
-    return A
-
-
 def get_matrix(code_input_raw):
     """[B,>=4] codes -> [B,3,3] = R(theta) Z(p,p) T(x,y)  (utils_rp.py:94-115)."""
-    return _theta_to_A(_code_to_theta("rp", code_input_raw))
+    return theta_to_matrix(_code_to_theta("rp", code_input_raw))
 
 
 get_matrix_D = get_matrix        # identical formulas (utils_rp.py:38-59)
@@ -464,39 +413,23 @@ get_matrix_D = get_matrix        # identical formulas (utils_rp.py:38-59)
 
 def get_matrix_pxy(code_input_raw):
     """[B,>=3] codes (p, x, y) -> [B,3,3] = Z(p,p) T(x,y), p = 1 + .1 c0, x, y = .1 c1, .1 c2  (utils_pxy.py:49-66)."""
-    return _theta_to_A(_code_to_theta("pxy", code_input_raw))
+    return theta_to_matrix(_code_to_theta("pxy", code_input_raw))
 
 
 def get_matrix_pxy_align(code_input_raw):
     """translation-only alignment matrix T(.1 c1, .1 c2)  (utils_pxy.py:69-87)."""
     theta = _code_to_theta("pxy_align_inv", code_input_raw)
     theta[:, :, 2] = -theta[:, :, 2]             # the kernel produces the inverse the loop actually uses (rp.py:376); autograd follows the flip
-    return _theta_to_A(theta)
+    return theta_to_matrix(theta)
 
 
-class _AffineRegFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, real_code, trans_code):
-        B, ld = real_code.shape
-        pred = torch.empty(B, 4, device=real_code.device)
-        ops.loss_affine_rp(real_code, trans_code, ld, 0, B, torch.zeros(B, 4, device=real_code.device), 4, 1.0, None, None, None, pred)
-        ctx.save_for_backward(real_code, trans_code, pred)
-        return pred
-
-    @staticmethod
-    def backward(ctx, dpred):
-        real_code, trans_code, pred = ctx.saved_tensors
-        B, ld = real_code.shape
-        tgt = (pred - dpred.float() * (GRAD_UP * 4.0 * B / 2.0)).contiguous()
-        d_real, d_trans = torch.empty_like(real_code), torch.empty_like(trans_code)
-        ops.loss_affine_rp(real_code, trans_code, ld, 0, B, tgt, 4, 1.0 / GRAD_UP, None, d_real, d_trans, None)
-        return d_real, d_trans
+_regularizer = affine.regularizer(lambda real, trans, ld, B, target, scale, d_real, d_trans, pred: ops.loss_affine_rp(
+    real, trans, ld, 0, B, target, 4, scale, None, d_real, d_trans, pred), 4)
 
 
 def affine_regularzier(real_code, trans_code):
     """closed-form relative-transform recovery over the first 4 codes (utils_rp.py:118-147)."""
-    _require_cuda(real_code)
-    return _AffineRegFn.apply(real_code.float().contiguous(), trans_code.float().contiguous())
+    return _regularizer(real_code, trans_code)
 
 
 def mutual_info_loss(c_given_x, c):
@@ -711,7 +644,6 @@ class DspritesTrainer(ResidentStep):
     def import_adam_state(self, opt_D, opt_info):
         """moments and step counts of the two ``torch.optim.Adam`` the reference steps (dSprites/rp.py:270-279: D | G + E parameters,
         ``.parameters()`` order) -- teacher-forced comparisons against a CPU run of the reference loop"""
-        from .engine import import_adam_moments
         n = lambda mod: len(list(mod.parameters()))
         s0 = import_adam_moments(opt_D, [(n(self.D), self.mD, self.vD)])
         s1 = import_adam_moments(opt_info, [(n(self.G), self.miG, self.viG), (n(self.E), self.miE, self.viE)])
@@ -823,14 +755,10 @@ class DspritesTrainer(ResidentStep):
         self._log_info_terms(cat, cont)
         dimg_e = ee.backward(0, 3, {"cat_layer.0": self.d_cat, "cont_layer.0": self.d_cont}, ea.grad, need_dimg=True)
         ops.add_f32(self.dimg, dimg_e, dimg_d)
-        pending = self.allreduce.start(ea.grad) if (self.allreduce is not None and hasattr(self.allreduce, "start")) else None
+        pending = engine.allreduce_start(self.allreduce, ea.grad)
         ge.backward(self.dimg, ga.grad, sync=self.sync_bn)
-        if self.allreduce is not None:
-            self.allreduce(ga.grad)
-            if pending is not None:
-                self.allreduce.finish(pending)
-            elif not hasattr(self.allreduce, "start"):
-                self.allreduce(ea.grad)
+        engine.allreduce_finish(self.allreduce, ga.grad, None)
+        engine.allreduce_finish(self.allreduce, ea.grad, pending)
         self._adam(ga, self.miG, self.viG, self.lr[1], 1, True)
         self._adam(ea, self.miE, self.viE, self.lr[1], 1, False)
         ge.repack()
@@ -914,7 +842,7 @@ class DeviceInputs(DeviceSampler):
         idx = self.sample_indices(tr.B, 1)
         self.codes_and_labels(tr, 2)
         self.end_draws()
-        if FUSE_DRAWS and self.data.dim() == 3:
+        if engine.FUSE_DRAWS and self.data.dim() == 3:
             # gather + uint8 -> float + counter tick as one launch (the gather of the MNIST / CelebA samplers; the same {0, 1} values)
             N, H, W = self.data.shape
             ops.gather_u8_images(self.data, idx, None, tr.img, tr.B, 1, H, W, 1.0, 0.0, tick=self.step)

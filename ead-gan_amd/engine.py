@@ -1,14 +1,33 @@
 """Host-side building blocks shared by the per-dataset models: flat parameter arenas, the shared device
-workspace, and conv-layer records (geometry + packed weight panels) over the C ABI in :mod:`ops`."""
+workspace, conv-layer records (geometry + packed weight panels) over the C ABI in :mod:`ops`, the module base class, and the
+dispatch functions every engine goes through (BatchNorm forms, fused-statistics buffers, the image-side transposed convolution).
+Imports :mod:`ops` only; :mod:`affine`, :mod:`trunk` and the workload modules import this one."""
 from __future__ import annotations
 
 import contextlib
 import os
 
+import numpy as np
 import torch
 
 from . import ops
-from .ops import EG_BF16, EG_F16, EG_F32
+from .ops import ACT_RELU, EG_BF16, EG_F16, EG_F32, OUT_NCHW_F32
+
+# Reference paths the tests compare the production ones against (they monkeypatch these; nothing else changes them).  Every reader, in
+# whichever module, reads ``engine.<NAME>`` at call time -- never ``from .engine import <NAME>`` -- so one patch here reaches them all.
+# image-side transposed convolutions (128 / 64 -> C) as one GEMM + col2im gather (True) or as the 4-phase implicit GEMM (False)
+IMG_GEMM = True
+
+
+def to_categorical(y, num_columns, device=None):
+    """one-hot float tensor (celebA/EAD-GAN_celebA.py:56-62; the same function in the MNIST and dSprites scripts)."""
+    y = torch.as_tensor(np.asarray(y), dtype=torch.int64, device=device)
+    return torch.nn.functional.one_hot(y, num_columns).to(torch.float32)
+
+
+def _require_cuda(t):
+    if not t.is_cuda:
+        raise RuntimeError("ead-gan_amd runs on MI355X only: tensors must be on a HIP device (no CPU fallback)")
 
 
 def parse_dtype(dtype) -> int:
@@ -274,32 +293,98 @@ class SyncScratch:
         self.sums = [torch.empty(2 * c, device=device, dtype=torch.float32) for c in channels]
 
 
-def bn_train_forward(dt, x, y, M, C, bn, mean, invstd, ws_small, act, slope=0.0, sync=None, stats=None):
-    """nn.BatchNorm2d in training mode (batch statistics, running statistics updated).  ``sync`` (a dp.SyncBN): statistics over the
-    global batch of all ranks -- local (n, mean, M2) -> one exchange of 3*C floats -> Chan-combined mean / variance."""
-    if sync is None:
+def bn_train_forward(dt, x, y, M, C, bn, mean, invstd, ws_small, act, slope=0.0, sync=None, stats=None, training=True, fused=(0, None)):
+    """nn.BatchNorm2d forward, THE place that chooses its form.  ``training=False``: running statistics, nothing updated (module.eval()).
+    ``fused`` = (row blocks, moments) that the producing convolution's epilogue left (stat_buffer): x is read once (apply) instead of
+    twice.  ``sync`` (a dp.SyncBN): statistics over the global batch of all ranks -- local (n, mean, M2) -> one exchange of 3*C floats ->
+    Chan-combined mean / variance.  Otherwise batch statistics of this rank; every training form updates the running statistics."""
+    if not training:
+        ops.bn_fwd_eval(dt, x, y, M, C, bn.weight, bn.bias, bn.eps, bn.running_mean, bn.running_var, ws_small, act, slope)
+    elif fused[0]:
+        ops.bn_fwd_train_fused(dt, x, y, M, C, fused[1], fused[0], M // fused[0], bn.weight, bn.bias, bn.eps, bn.momentum, bn.running_mean, bn.running_var,
+                               bn.num_batches_tracked, mean, invstd, ws_small, act, slope)
+    elif sync is None:
         ops.bn_fwd_train(dt, x, y, M, C, bn.weight, bn.bias, bn.eps, bn.momentum, bn.running_mean, bn.running_var, bn.num_batches_tracked, mean, invstd,
                          ws_small, act, slope)
-        return
-    ops.bn_stats_local(dt, x, M, C, ws_small, stats)
-    allst = sync.gather_stats(stats)
-    ops.bn_fwd_from_stats(dt, x, y, M, C, allst, sync.world, M * sync.world, bn.weight, bn.bias, bn.eps, bn.momentum, bn.running_mean, bn.running_var,
-                          bn.num_batches_tracked, mean, invstd, ws_small, act, slope)
+    else:
+        ops.bn_stats_local(dt, x, M, C, ws_small, stats)
+        allst = sync.gather_stats(stats)
+        ops.bn_fwd_from_stats(dt, x, y, M, C, allst, sync.world, M * sync.world, bn.weight, bn.bias, bn.eps, bn.momentum, bn.running_mean, bn.running_var,
+                              bn.num_batches_tracked, mean, invstd, ws_small, act, slope)
 
 
-def bn_train_backward(dt, z, da, dz, M, C, bn, mean, invstd, act, slope, dgamma, dbeta, ws, sync=None, sums=None):
-    """Backward of bn_train_forward (``ws``: a Workspace).  ``sync``: the two per-channel sums over the global batch (one exchange of
-    2*C floats); dgamma / dbeta are this rank's share -- the gradient all-reduce averages them like every other gradient."""
-    if sync is None:
-        ops.bn_bwd(dt, z, da, dz, M, C, bn.weight, bn.bias, mean, invstd, act, slope, dgamma, dbeta, ws.sums, ws.small)
-        return
-    ops.bn_bwd_sums_local(dt, z, da, M, C, bn.weight, bn.bias, mean, invstd, act, slope, dgamma, dbeta, sums, ws.small)
-    sync.reduce_sums(sums)
-    ops.bn_bwd_from_sums(dt, z, da, dz, M, C, sums, M * sync.world, bn.weight, bn.bias, mean, invstd, act, slope, ws.small)
+def bn_train_backward(dt, z, da, dz, M, C, bn, mean, invstd, act, slope, dgamma, dbeta, ws, sync=None, sums=None, fused=(0, None), accumulate=True):
+    """Backward of bn_train_forward's training forms (``ws``: a Workspace).  ``fused`` = (row blocks, sums): ``da`` came from a launch
+    with bn_bwd_epilogue, it already holds dy = da * act'(bn(z)) and the two sums are in the buffer.  ``sync``: the two per-channel sums
+    over the global batch (one exchange of 2*C floats); dgamma / dbeta are this rank's share -- the gradient all-reduce averages them
+    like every other gradient.  ``accumulate=False``: dgamma / dbeta are stored, not added to."""
+    if fused[0]:
+        ops.bn_bwd_fused(dt, z, da, dz, M, C, fused[1], fused[0], bn.weight, bn.bias, mean, invstd, dgamma, dbeta, ws.sums, ws.small, accumulate=accumulate)
+    elif sync is None:
+        ops.bn_bwd(dt, z, da, dz, M, C, bn.weight, bn.bias, mean, invstd, act, slope, dgamma, dbeta, ws.sums, ws.small, accumulate=accumulate)
+    else:
+        ops.bn_bwd_sums_local(dt, z, da, M, C, bn.weight, bn.bias, mean, invstd, act, slope, dgamma, dbeta, sums, ws.small, accumulate=accumulate)
+        sync.reduce_sums(sums)
+        ops.bn_bwd_from_sums(dt, z, da, dz, M, C, sums, M * sync.world, bn.weight, bn.bias, mean, invstd, act, slope, ws.small)
+
+
+def stat_buffer(stat, key, c, dtype, bwd, ep, C, device, nrb=None, floats=None):
+    """(row blocks, buffer) if the launch described by (c, bwd, ep) can take its column statistics in the epilogue, else (0, None).  Asked
+    once per ``key`` of the engine's ``stat`` dict, with the very epilogue the launch uses (same hints, same split-K scratch).  The
+    caller's own rules come as arguments: ``nrb()`` -> row blocks where ops.conv_stat_blocks of this launch is not the whole answer,
+    ``floats(row blocks)`` -> buffer size where it is not the two sums per channel and block of the BatchNorm statistics."""
+    if key not in stat:
+        n = ops.conv_stat_blocks(c, dtype, bwd, ep) if nrb is None else nrb()
+        size = 2 * C * n if floats is None else floats(n)
+        stat[key] = (n, torch.empty(size, device=device, dtype=torch.float32) if n else None)
+    return stat[key]
+
+
+def bn_bwd_epilogue(stat, z, mean, invstd, bn):
+    """epilogue of the launch that produces d(a) of a BatchNorm + ReLU layer: it also forms dy = da * relu'(bn(z)) and leaves the two sums
+    of the layer's BatchNorm backward in ``stat`` (bn_train_backward(..., fused=) takes them)"""
+    return ops.epilogue(stat_mode=ops.STAT_BN_BWD, stat_out=stat, stat_aux=z, stat_p=(mean, invstd, bn.weight, bn.bias), stat_act=ACT_RELU)
+
+
+def convt_img(dt, x, gemm, cols, implicit, bias, act, out, fused):
+    """The image-side transposed convolution (K channels -> the few of an fp32 NCHW image ``out``, + bias + activation), THE place that
+    chooses its form: one launch (GEMM + gather, the columns stay in LDS) where ``fused`` -- the caller's own conditions -- and the
+    kernel allow it; one GEMM over the input pixels with N = taps x C columns into ``cols`` + the col2im gather (every activation read
+    once); or, with IMG_GEMM off or without a GEMM record (``gemm`` None), the 4-phase implicit GEMM of the record ``implicit``."""
+    B, C = out.shape[0], out.shape[1]
+    k, stride, pad = implicit.k, implicit.stride, implicit.pad
+    if gemm is None or not IMG_GEMM:
+        ops.conv_bwd_data(implicit.c, dt, x, implicit.wp_bwd, out, ops.epilogue(bias=bias, act=act, out_mode=OUT_NCHW_F32))
+    elif fused and ops.convt_img_mfma_ok(dt, C, gemm.H, gemm.W, gemm.Cin, k, stride, pad):
+        ops.convt_img_mfma(dt, x, gemm.wp_fwd, bias, out, B, C, gemm.H, gemm.W, act, 0.0, K=gemm.Cin)
+    else:
+        ops.conv_fwd(gemm.c, dt, x, gemm.wp_fwd, cols, None)
+        ops.col2im_img(dt, cols, B, C, gemm.H, gemm.W, k, stride, pad, bias, act, 0.0, out)
+
+
+def wgrad_side(side, ws, lane, fn, tag=None):
+    """a layer's weight- / bias-gradient chain ``fn(workspace)``: on lane ``lane`` of ``side`` (a SideStream) when there is one, else here"""
+    if side is None:
+        fn(ws)
+    else:
+        side.defer(lane, fn, tag)
+
+
+def allreduce_start(ar, flat):
+    """start the gradient average of ``flat`` where the all-reduce has an asynchronous form -> handle, else None"""
+    return ar.start(flat) if ar is not None and hasattr(ar, "start") else None
+
+
+def allreduce_finish(ar, flat, handle):
+    """wait for a started average (``handle``) or, without one, run the blocking form now"""
+    if handle is not None:
+        ar.finish(handle)
+    elif ar is not None:
+        ar(flat)
 
 
 # an iteration's device-side draws as one launch and the counter tick inside the gather (same values); False: one launch per draw, the
-# reference the tests compare against
+# reference the tests compare against.  Read as ``engine.FUSE_DRAWS`` everywhere (see IMG_GEMM)
 FUSE_DRAWS = True
 
 
@@ -386,7 +471,6 @@ class DeviceSampler:
 def unwrap_ring(ring, head, capacity, since=0):
     """Rows of the iterations [max(since, head - capacity), head) of a ring filled by eg_runlog_append (row = iteration % capacity), in
     iteration order: -> (first iteration, array [iterations, n])"""
-    import numpy as np
     first = max(int(since), int(head) - int(capacity), 0)
     idx = np.arange(first, int(head)) % int(capacity)
     return first, np.asarray(ring)[idx].copy()
@@ -407,7 +491,6 @@ class LossLog:
         self._pending = None
         self.mirror_head, self.mirror_flag = 0, 0
         if _host_only_n is not None:                    # a mirror without a device side (reading a saved ring; host tests)
-            import numpy as np
             self.n = int(_host_only_n)
             self.mirror = np.zeros((self.capacity, self.n), np.float32)
             return
@@ -672,7 +755,7 @@ class ConvRec:
                  want_wgrad=True, ws: Workspace | None = None):
         self.dtype = dtype
         self.c = ops.make_conv(B, H, W, Cin, Cout, k, stride, pad, up)
-        self.B, self.H, self.W, self.Cin, self.Cout, self.k = B, H, W, Cin, Cout, k
+        self.B, self.H, self.W, self.Cin, self.Cout, self.k, self.stride, self.pad = B, H, W, Cin, Cout, k, stride, pad
         self.OH = ((H << up) + 2 * pad - k) // stride + 1
         self.OW = ((W << up) + 2 * pad - k) // stride + 1
         tdt = ops.torch_dtype(dtype)
@@ -688,6 +771,54 @@ class ConvRec:
     def pack(self, w_master):
         if self.wp_fwd is not None or self.wp_bwd is not None:
             ops.pack_conv(self.c, self.dtype, w_master, self.wp_fwd, self.wp_bwd)
+
+
+class _HipModule(torch.nn.Module):
+    """Shared plumbing of the drop-in modules: flat arena, per-batch engines, invalidation when the module is moved."""
+
+    compute_dtype = EG_F32
+
+    def _init_engine_state(self, dtype):
+        self.compute_dtype = parse_dtype(dtype)
+        self._arena = None
+        self._engines = {}
+
+    def _apply(self, fn, *a, **k):
+        out = super()._apply(fn, *a, **k)
+        self._arena, self._engines = None, {}
+        return out
+
+    @property
+    def arena(self) -> Arena:
+        if self._arena is None:
+            p = next(self.parameters())
+            _require_cuda(p)
+            self._arena = Arena(self)
+            self._engines = {}
+        return self._arena
+
+    def set_compute_dtype(self, dtype):
+        self.compute_dtype = parse_dtype(dtype)
+
+    def repack(self):
+        """Refresh the packed (kernel-layout, compute-dtype) weight panels after the fp32 masters changed."""
+        for e in self._engines.values():
+            e.repack()
+
+    def fresh_engine(self, B):
+        """The engine for batch size B with panels re-packed from the masters: the drop-in forward path.  The kernels read packed
+        copies of the convolution weights, and the masters can change behind the module's back in ways nothing reports --
+        ``optimizer.step()`` bumps a version counter, ``module.apply(weights_init_normal)`` writes through ``.data`` and does not -- so
+        every drop-in forward re-packs first (2 small launches per layer, asynchronous).  The fused trainers keep masters and panels in
+        step themselves and never come through here."""
+        eng = self.engine(B)
+        eng.repack()
+        return eng
+
+    def load_state_dict(self, *a, **k):
+        out = super().load_state_dict(*a, **k)
+        self.repack()
+        return out
 
 
 def import_adam_moments(opt, arenas):

@@ -8,17 +8,16 @@ from __future__ import annotations
 
 import argparse
 
-import numpy as np
 import torch
 import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
-from . import ops
-from .celeba import GRAD_UP, _code_to_theta, _HipModule, _require_cuda, transformation_2D      # noqa: F401  (same STN warp in both scripts)
-from .engine import (FUSE_DRAWS, Arena, ConvRec, DeviceSampler, ResidentStep, SideStream, SyncScratch, Workspace, bn_train_backward, bn_train_forward, capture_step, check_usable,
-                     parse_dtype)
+from . import affine, engine, ops
+from .affine import _code_to_theta, theta_to_matrix, transformation_2D      # noqa: F401  (same STN warp in all scripts)
+from .engine import (Arena, ConvRec, DeviceSampler, ResidentStep, SideStream, SyncScratch, Workspace, _HipModule, _require_cuda, bn_train_backward, bn_train_forward,
+                     capture_step, check_usable, import_adam_moments, parse_dtype, to_categorical, wgrad_side)      # noqa: F401
 from .ops import ACT_LRELU, ACT_NONE, ACT_TANH, EG_F32, OUT_NCHW_F32
-from .trunk import Head, TrunkEngine
+from .trunk import Head, TrunkEngine, _TrunkFn
 
 opt = argparse.Namespace(n_epochs=200, batch_size=128, lr=0.0001, b1=0.5, b2=0.999, n_cpu=8, latent_dim=62, code_dim=7, n_classes=10,
                          img_size=32, channels=1, sample_interval=4000)          # argparse defaults, :35-48
@@ -34,11 +33,6 @@ def weights_init_normal(m):
     elif classname.find("BatchNorm") != -1:
         torch.nn.init.normal_(m.weight.data, 1.0, 0.02)
         torch.nn.init.constant_(m.bias.data, 0.0)
-
-
-def to_categorical(y, num_columns, device=None):
-    y = torch.as_tensor(np.asarray(y), dtype=torch.int64, device=device)
-    return torch.nn.functional.one_hot(y, num_columns).to(torch.float32)
 
 
 # ================================================================================================
@@ -138,10 +132,7 @@ class _GenEngine:
         ops.conv_fwd(self.l1.c, dt, self.inp, self.l1.wp_fwd, self.h, ops.epilogue(bias=self.bias_perm))
 
         def bn(x, y, mod, i, M, C, act, slope=0.0):
-            if not training:
-                ops.bn_fwd_eval(dt, x, y, M, C, mod.weight, mod.bias, mod.eps, mod.running_mean, mod.running_var, ws.small, act, slope)
-                return
-            bn_train_forward(dt, x, y, M, C, mod, self.mean[i], self.invstd[i], ws.small, act, slope, sync, self.sync_scratch.stats[i])
+            bn_train_forward(dt, x, y, M, C, mod, self.mean[i], self.invstd[i], ws.small, act, slope, sync, self.sync_scratch.stats[i], training)
         s = g.init_size
         bn(self.h, self.a0, cb[0], 0, B * s * s, 128, ACT_NONE)
         # (transposed convolution = backward-data of its conv view)
@@ -162,12 +153,6 @@ class _GenEngine:
         s = g.init_size
         S = 4 * s
 
-        def wgrad_side(fn, lane):
-            if side is None:
-                fn(ws)
-            else:
-                side.defer(lane, fn)
-
         ops.act_grad_mul_bias_nchw(dimg, self.img, self.dimg_z, B, self.CH, S * S, ACT_TANH, 0.0, ws.small, gof("conv_blocks.9.bias"))
         ops.cast_pad(dt, self.dimg_z, self.p8, B * S * S, self.CH, 8)          # [M][1] fp32 (== NCHW with C=1) -> [M][8]
 
@@ -178,7 +163,7 @@ class _GenEngine:
                 return
             ns = ops.conv_wgrad(self.c3.c, dt, self.a2, self.p8, wsw.slab, wsw.wgs_target)
             ops.wgrad_reduce(wsw.slab, ns, 8, self.CH, 64, 9, gof("conv_blocks.9.weight"))
-        wgrad_side(c3_wgrad, 0)
+        wgrad_side(side, ws, 0, c3_wgrad)
         ops.conv_bwd_data(self.c3.c, dt, self.p8, self.c3.wp_bwd, self.da2, None)
 
         def bn_bwd(z, da, dz, mod, i, M, C, act, name):
@@ -192,7 +177,7 @@ class _GenEngine:
             ops.wgrad_reduce(wsw.slab, ns, 128, 128, 64, 16, self.dw4[1], accumulate=False)
             ops.up3_contract(self.dw4[1], gof("conv_blocks.6.weight"), 64, 128)
             ops.bias_grad(dt, self.dz2, B * S * S, 64, wsw.small, gof("conv_blocks.6.bias"))
-        wgrad_side(c2_wgrad, 1)
+        wgrad_side(side, ws, 1, c2_wgrad)
         ops.conv_fwd(self.c2.c, dt, self.dz2, self.c2.wp_fwd, self.da1, None)      # the input gradient at the low resolution: no sum-pool
         # conv1 (128 -> 128 on the 2x-upsampled a0)
         bn_bwd(self.z1, self.da1, self.dz1, cb[3], 1, B * 4 * s * s, 128, ACT_LRELU, "conv_blocks.3")
@@ -202,7 +187,7 @@ class _GenEngine:
             ops.wgrad_reduce(wsw.slab, ns, 128, 128, 128, 16, self.dw4[0], accumulate=False)
             ops.up3_contract(self.dw4[0], gof("conv_blocks.2.weight"), 128, 128)
             ops.bias_grad(dt, self.dz1, B * 4 * s * s, 128, wsw.small, gof("conv_blocks.2.bias"))
-        wgrad_side(c1_wgrad, 2)
+        wgrad_side(side, ws, 2, c1_wgrad)
         ops.conv_fwd(self.c1.c, dt, self.dz1, self.c1.wp_fwd, self.da0, None)
         bn_bwd(self.h, self.da0, self.dh, cb[0], 0, B * s * s, 128, ACT_NONE, "conv_blocks.0")
         # l1: dW[f][k] = sum_b dh[b][n'(f)] * x[b][k]
@@ -214,7 +199,7 @@ class _GenEngine:
             ops.fill_f32(self.gb_perm)
             ops.bias_grad(dt, self.dh, B, self.nl1, wsw.small, self.gb_perm)
             ops.gather_add(gof("l1.0.bias"), self.gb_perm, self.nl1, hw, 1, 128)
-        wgrad_side(l1_wgrad, 3)
+        wgrad_side(side, ws, 3, l1_wgrad)
 
 
 class Generator(_HipModule):
@@ -361,27 +346,6 @@ class Encoder(_TrunkModule):
         return torch.softmax(logits, dim=1), latent, None
 
 
-class _TrunkFn(torch.autograd.Function):
-    """autograd bridge for the eager drop-in path (one tape per call)."""
-
-    @staticmethod
-    def forward(ctx, eng, t, training, names, img, *params):
-        ctx.eng, ctx.t, ctx.names = eng, t, names
-        ctx.need_w = any(p.requires_grad for p in params)
-        ctx.need_img = img.requires_grad
-        outs = eng.forward([img], t, training)
-        return tuple(outs[n].clone() for n in names)
-
-    @staticmethod
-    def backward(ctx, *douts):
-        eng = ctx.eng
-        scratch = torch.zeros_like(eng.owner.arena.grad)
-        d = {n: (g.contiguous() if g is not None else torch.zeros_like(eng.outs[n][:eng.B])) for n, g in zip(ctx.names, douts)}
-        dimg = eng.backward(ctx.t, 1, d, scratch, need_wgrad=ctx.need_w, need_dimg=ctx.need_img)
-        grads = [scratch[off:off + k].view(p.shape) for p, (off, k) in zip(eng.owner.parameters(), eng.owner.arena.slices.values())]
-        return (None, None, None, None, dimg.clone() if dimg is not None else None, *grads)
-
-
 # ================================================================================================
 # affine utilities (MNIST/utils_rpqmnxy.py)
 # ================================================================================================
@@ -412,39 +376,16 @@ def _approx(dev):
 
 def get_matrix(code_input_raw):
     """[B,7] codes -> [B,3,3] = R(theta) Z(p,q) S(m,n) T(x,y)  (utils_rpqmnxy.py:87-114)."""
-    theta = _code_to_theta("rpqmnxy", code_input_raw)
-    A = torch.zeros(theta.shape[0], 3, 3, device=theta.device, dtype=torch.float32)
-    A[:, :2] = theta
-    A[:, 2, 2] = 1.0
-    return A
+    return theta_to_matrix(_code_to_theta("rpqmnxy", code_input_raw))
 
 
-class _AffineRegFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, real_code, trans_code):
-        B, ld = real_code.shape
-        dev = real_code.device
-        pred = torch.empty(B, 7, device=dev)
-        ops.loss_affine_rpqmnxy(real_code, trans_code, ld, 0, B, torch.zeros(B, 7, device=dev), 7, _approx(dev), 1.0, None, None, None, pred,
-                                torch.empty(B, device=dev))
-        ctx.save_for_backward(real_code, trans_code, pred)
-        return pred
-
-    @staticmethod
-    def backward(ctx, dpred):
-        real_code, trans_code, pred = ctx.saved_tensors
-        B, ld = real_code.shape
-        dev = real_code.device
-        tgt = (pred - dpred.float() * (GRAD_UP * 7.0 * B / 2.0)).contiguous()       # MSE gradient with this target and scale 1 / GRAD_UP == J^T dpred (celeba.GRAD_UP)
-        d_real, d_trans = torch.empty_like(real_code), torch.empty_like(trans_code)
-        ops.loss_affine_rpqmnxy(real_code, trans_code, ld, 0, B, tgt, 7, _approx(dev), 1.0 / GRAD_UP, None, d_real, d_trans, None, torch.empty(B, device=dev))
-        return d_real, d_trans
+_regularizer = affine.regularizer(lambda real, trans, ld, B, target, scale, d_real, d_trans, pred: ops.loss_affine_rpqmnxy(
+    real, trans, ld, 0, B, target, 7, _approx(real.device), scale, None, d_real, d_trans, pred, torch.empty(B, device=real.device)), 7)
 
 
 def affine_regularizer(real_code, trans_code):
     """relative transform -> frozen MLP -> latent units (utils_rpqmnxy.py:117-134)."""
-    _require_cuda(real_code)
-    return _AffineRegFn.apply(real_code.float().contiguous(), trans_code.float().contiguous())
+    return _regularizer(real_code, trans_code)
 
 
 # ================================================================================================
@@ -501,7 +442,6 @@ class MnistTrainer(ResidentStep):
     def import_adam_state(self, opt_G, opt_D, opt_info):
         """moments and step counts of three ``torch.optim.Adam`` built like the reference's (MNIST/EAD-GAN_rpqmnxy.py:206-217: G | D | G + E
         parameters, ``.parameters()`` order) -- teacher-forced comparisons against a CPU run of the reference loop"""
-        from .engine import import_adam_moments
         n = lambda mod: len(list(mod.parameters()))
         s0 = import_adam_moments(opt_G, [(n(self.G), self.mG, self.vG)])
         s1 = import_adam_moments(opt_D, [(n(self.D), self.mD, self.vD)])
@@ -552,15 +492,11 @@ class MnistTrainer(ResidentStep):
         ops.loss_affine_rpqmnxy(lat[2 * B:], lat[B:2 * B], cd, 0, B, self.code, cd, self.mlp, laff, self.losses[2:3], self.d_code[2 * B:],
                                 self.d_code[B:2 * B], None, self.ws_aff)
         dimg = ee.backward(0, 3, {"aux_layer.0": self.d_cat, "latent_layer.0": self.d_code}, ea.grad, need_dimg=True)
-        pending = self.allreduce.start(ea.grad) if (self.allreduce is not None and hasattr(self.allreduce, "start")) else None
+        pending = engine.allreduce_start(self.allreduce, ea.grad)
         ge.backward(dimg, ga.grad, side, sync=self.sync_bn)    # overlaps with the encoder-gradient all-reduce
         join()
-        if self.allreduce is not None:
-            self.allreduce(ga.grad)
-            if pending is not None:
-                self.allreduce.finish(pending)
-            elif not hasattr(self.allreduce, "start"):
-                self.allreduce(ea.grad)
+        engine.allreduce_finish(self.allreduce, ga.grad, None)
+        engine.allreduce_finish(self.allreduce, ea.grad, pending)
         self._adam(ga, self.miG, self.viG, self.lr[2], 2, True)
         self._adam(ea, self.miE, self.viE, self.lr[2], 2, False)
         ge.repack()
@@ -607,8 +543,8 @@ class DeviceInputs(DeviceSampler):
         self.draw(ops.RNG_UNIFORM, tr.code, -1.0, 1.0, 4)
         self.end_draws()
         # ToTensor + Normalize(.5,.5); the step counter ticks in the same launch (every draw of the iteration has read it)
-        ops.gather_u8_images(self.data, idx, None, tr.real, B, C, H, W, 2.0 / 255.0, -1.0, tick=self.step if FUSE_DRAWS else None)
-        if not FUSE_DRAWS:
+        ops.gather_u8_images(self.data, idx, None, tr.real, B, C, H, W, 2.0 / 255.0, -1.0, tick=self.step if engine.FUSE_DRAWS else None)
+        if not engine.FUSE_DRAWS:
             self.tick()
 
 

@@ -17,7 +17,7 @@ import torch
 from . import colored as cd
 from . import dsprites as ds
 from . import ops
-from .celeba import _require_cuda
+from .engine import _require_cuda
 
 NUM_CODES = 5           # [argmax(cat), cont0, cont1, pxy1, pxy2] for both workloads
 KINDS = ("dsprites", "colored")

@@ -8,14 +8,14 @@ ONE weight-gradient GEMM covers all tapes and the spectral-norm rank-1 terms are
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, field
+import itertools
+from dataclasses import dataclass
 
 import torch
 
 from . import ops
-from .celeba import IMG_GEMM
-from .engine import ConvRec, Workspace
-from .ops import ACT_LRELU, ACT_NONE, EG_F32, OUT_NCHW_F32
+from .engine import ConvRec, Workspace, bn_train_forward, convt_img, stat_buffer, wgrad_side
+from .ops import ACT_LRELU, ACT_NONE, EG_F32
 
 SN_EPS = 1e-12
 
@@ -56,9 +56,9 @@ class TrunkEngine:
         # records (packed panels) for the largest batch; per-tape-count geometries
         self.l0img = ConvRec(dtype, B, size, size, in_ch, self.W[0], k, 2, pad, device=dev, want_fwd=False, want_wgrad=False, ws=ws)
         self.l0p = ConvRec(dtype, NT * B, size // 2, size // 2, self.kp, self.W[0], 1, 1, 0, device=dev, want_bwd=False, ws=ws)
-        # d(img) as ONE GEMM over the layer-0 lattice with N = k*k*C columns + the col2im gather (eg_col2im_img; see celeba._DiscEngine.l1g) where
+        # d(img) as ONE GEMM over the layer-0 lattice with N = k*k*C columns + the col2im gather (eg_col2im_img; engine.convt_img) where
         # the GEMM engine takes that N (a multiple of 8: the 4x4 dSprites trunks; the 3x3 single-channel MNIST trunk keeps the implicit form)
-        self.l0g = None
+        self.l0g = self.cols0 = None
         if self.k0 % 8 == 0 and in_ch in (1, 3) and size // 2 == (size + 2 * pad - k) // 2 + 1:
             self.l0g = ConvRec(dtype, B, size // 2, size // 2, self.W[0], self.k0, 1, 1, 0, device=dev, want_bwd=False, want_wgrad=False, ws=ws)
             self.cols0 = torch.empty(B * (size // 2) ** 2, self.k0, device=dev, dtype=ops.torch_dtype(dtype))
@@ -203,13 +203,9 @@ class TrunkEngine:
             if bn is not None:
                 # BatchNorm is per forward call: one pass per tape, in tape order (every module's running statistics then see the tapes in the
                 # order of the reference's consecutive calls), while the convolutions around it run once over all T tapes
-                for t in range(t0, t0 + T):
-                    if training:
-                        ops.bn_fwd_train(dt, self._sl(self.a[i], t), self._sl(self.y[i], t), self.rows(i), self.W[i], bn.weight, bn.bias, bn.eps, bn.momentum,
-                                         bn.running_mean, bn.running_var, bn.num_batches_tracked, self.mean[i][t], self.invstd[i][t], self.ws.small, ACT_NONE)
-                    else:   # module.eval() (score/*.load_encoder of the reference): running statistics, nothing updated
-                        ops.bn_fwd_eval(dt, self._sl(self.a[i], t), self._sl(self.y[i], t), self.rows(i), self.W[i], bn.weight, bn.bias, bn.eps,
-                                        bn.running_mean, bn.running_var, self.ws.small, ACT_NONE)
+                for t in range(t0, t0 + T):     # (training=False: module.eval(), score/*.load_encoder of the reference)
+                    bn_train_forward(dt, self._sl(self.a[i], t), self._sl(self.y[i], t), self.rows(i), self.W[i], bn, self.mean[i][t], self.invstd[i][t],
+                                     self.ws.small, ACT_NONE, training=training)
         x = self._inp(self.L, t0)
         for i, f in enumerate(self.fcs):
             ops.conv_fwd(g["fc"][i], dt, x, self.frec[i].wp_fwd, self.fa[i][t0 * B:],
@@ -266,27 +262,17 @@ class TrunkEngine:
     def _sn_stat(self, i, T, c, ep):
         """fused sums of layer i's bias gradient / spectral-norm coefficient in the backward-data launch that produces dzs_i (T tapes): (row
         blocks, buffer), (0, None) where that launch cannot take them (4x4 stride-2 layers, whole 128-row tiles per tape and phase)"""
-        key = (i, T)
-        if key not in self._stat:
+        def nrb():
             ok = self.taps == 16 and self.rows(i + 1) % 128 == 0 and self.dtype != EG_F32
-            nrb = ops.conv_stat_blocks(c, self.dtype, True, ep) if ok else 0
-            if nrb % (4 * T):
-                nrb = 0
-            N = self.W[i]
-            self._stat[key] = (nrb, torch.empty(N * nrb + nrb * max(N // 128, 1), device=self.patches.device, dtype=torch.float32) if nrb else None)
-        return self._stat[key]
+            n = ops.conv_stat_blocks(c, self.dtype, True, ep) if ok else 0
+            return 0 if n % (4 * T) else n
+        N = self.W[i]
+        return stat_buffer(self._stat, (i, T), c, self.dtype, True, ep, N, self.patches.device, nrb=nrb, floats=lambda n: N * n + n * max(N // 128, 1))
 
     def _bwd_pass(self, t0, T, douts, grad, need_wgrad, need_dimg, side=None):
         dt, B, ws, L = self.dtype, self.B, self.ws, self.L
         gof = lambda name: self.owner.arena.grad_of(name, grad)
-        nlane = [0]
-
-        def wgrad_side(fn):                              # a layer's weight- / bias-gradient chain: on a side lane when there is one
-            if side is None:
-                fn(ws)
-            else:
-                side.defer(nlane[0], fn)
-                nlane[0] += 1
+        lanes = itertools.count()                       # a layer's weight- / bias-gradient chain: on the next side lane when there are lanes
         g = self.geo[T]
         kpad = self.head_rec.Kpad_fwd
         rows = T * B
@@ -313,7 +299,7 @@ class TrunkEngine:
                                                self.hu[h.name][t0:], self.hv[h.name][t0:])
                     else:
                         ops.wgrad_reduce(slab, ns, 32, h.N, self.head_C, tk, gof(h.name + ".weight"))
-            wgrad_side(head_wgrad)
+            wgrad_side(side, ws, next(lanes), head_wgrad)
         last = L - 1
         if nf:
             ops.dense_small_bwd(dt, dys32, self.head_rec.wp_fwd, self.fa[-1][t0 * B:], self.fdz[-1][t0 * B:], rows, self.K, kpad, self.ncomb,
@@ -329,7 +315,7 @@ class TrunkEngine:
                         C, tk = (self.W[-1], self.hk * self.hk) if i == 0 else (self.fK[i], 1)
                         ops.wgrad_reduce_rank1(wsw.slab, ns, self.fN[i], self.fN[i], C, tk, gof(nm + ".weight_orig"), T, self.fcoef[i], self.fu[i][t0:],
                                                self.fv[i][t0:])
-                    wgrad_side(fc_wgrad)
+                    wgrad_side(side, ws, next(lanes), fc_wgrad)
                 if i > 0:
                     ops.conv_bwd_data(g["fc"][i], dt, self.fdz[i][t0 * B:], self.frec[i].wp_bwd, self.fdz[i - 1][t0 * B:],
                                       ops.epilogue(sigma=self.fsigma[i - 1][t0:], sigma_rows=B, mask=self.fa[i - 1][t0 * B:], mask_act=ACT_LRELU, mask_slope=self.slope))
@@ -368,24 +354,21 @@ class TrunkEngine:
                         ns = ops.conv_wgrad(geo, dt, self._inp(i, t0), self._sl(self.dz[i], t0), wsw.slab, wsw.wgs_target)
                     ops.wgrad_reduce_rank1(wsw.slab, ns, self.W[i], self.W[i], self.cin[i], self.taps if i > 0 else 1, gof(nm + ".weight_orig"), T,
                                            self.coef[i], self.u[i][t0:], self.v[i][t0:], self.k0 if i == 0 else 0)
-                wgrad_side(layer_wgrad)
+                wgrad_side(side, ws, next(lanes), layer_wgrad)
             fused = (0, None)
             if i > 0:
                 if self.bns[i - 1] is not None:
                     ops.conv_bwd_data(geo, dt, self._sl(self.dz[i], t0), self.mid[i - 1].wp_bwd, self._sl(self.dyb[i - 1], t0), None)
                 else:
                     kw = dict(sigma=self.sigma[i - 1][t0:], sigma_rows=self.rows(i), mask=self._sl(self.a[i - 1], t0), mask_act=ACT_LRELU, mask_slope=self.slope)
-                    # ... and, from the same tile, layer i-1's bias-gradient column sums and spectral-norm coefficient (celeba._DiscEngine.backward)
+                    # ... and, from the same tile, layer i-1's bias-gradient column sums and spectral-norm coefficient (as celeba._DiscEngine.backward)
                     fused = self._sn_stat(i - 1, T, geo, ops.epilogue(**kw)) if need_wgrad else (0, None)
                     if fused[0]:
                         kw.update(stat_mode=ops.STAT_SN_BIAS, stat_out=fused[1], stat_p=(self.convs[i - 1].bias,), stat_slope=self.slope)
                     ops.conv_bwd_data(geo, dt, self._sl(self.dz[i], t0), self.mid[i - 1].wp_bwd, self._sl(self.dz[i - 1], t0), ops.epilogue(**kw))
         if need_dimg:
-            if self.l0g is not None and IMG_GEMM:
-                ops.conv_fwd(self.l0g.c, dt, self._sl(self.dz[0], t0), self.l0g.wp_fwd, self.cols0, None)
-                ops.col2im_img(dt, self.cols0, B, self.in_ch, self.l0g.H, self.l0g.W, self.k_img, 2, self.pad_img, None, ACT_NONE, 0.0, self.dimg)
-            else:
-                ops.conv_bwd_data(self.l0img.c, dt, self._sl(self.dz[0], t0), self.l0img.wp_bwd, self.dimg, ops.epilogue(out_mode=OUT_NCHW_F32))
+            # (no single-launch form here: the GEMM + gather pair or, without a GEMM record, the implicit form)
+            convt_img(dt, self._sl(self.dz[0], t0), self.l0g, self.cols0, self.l0img, None, ACT_NONE, self.dimg, False)
             return self.dimg
         return None
 
@@ -394,3 +377,24 @@ class TrunkEngine:
         loss).  Accumulates into flat ``grad``; returns d(loss)/d(img) of tape t0 if ``need_dimg``.  ``side`` (engine.SideStream): each
         layer's weight- / bias-gradient chain runs on a side lane; the caller joins the lanes before it reads ``grad``."""
         return self._bwd_pass(t0, T, douts, grad, need_wgrad, need_dimg, side)
+
+
+class _TrunkFn(torch.autograd.Function):
+    """autograd bridge for the eager drop-in path (one tape per call)."""
+
+    @staticmethod
+    def forward(ctx, eng, t, training, names, img, *params):
+        ctx.eng, ctx.t, ctx.names = eng, t, names
+        ctx.need_w = any(p.requires_grad for p in params)
+        ctx.need_img = img.requires_grad
+        outs = eng.forward([img], t, training)
+        return tuple(outs[n].clone() for n in names)
+
+    @staticmethod
+    def backward(ctx, *douts):
+        eng = ctx.eng
+        scratch = torch.zeros_like(eng.owner.arena.grad)
+        d = {n: (g.contiguous() if g is not None else torch.zeros_like(eng.outs[n][:eng.B])) for n, g in zip(ctx.names, douts)}
+        dimg = eng.backward(ctx.t, 1, d, scratch, need_wgrad=ctx.need_w, need_dimg=ctx.need_img)
+        grads = [scratch[off:off + k].view(p.shape) for p, (off, k) in zip(eng.owner.parameters(), eng.owner.arena.slices.values())]
+        return (None, None, None, None, dimg.clone() if dimg is not None else None, *grads)

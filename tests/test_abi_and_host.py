@@ -88,6 +88,36 @@ def test_no_environment_switches_in_library_or_package():
     assert len(owners["FUSE_DRAWS"]) + len(owners["FUSE_INPUTS"]) <= 1, owners      # one draws switch under one name
 
 
+def _package_sources():
+    pkg = os.path.join(ROOT, "ead-gan_amd")
+    return {fn: open(os.path.join(pkg, fn)).read() for fn in sorted(os.listdir(pkg)) if fn.endswith(".py")}
+
+
+def test_no_module_imports_from_a_workload_module():
+    """ops <- engine <- (affine, trunk) <- workloads: what two workloads share lives below them, so no module imports from celeba, mnist
+    or dsprites -- except colored, which is dSprites with three channels, and score, which scores the dSprites / colored encoders."""
+    import re
+    allowed = {"colored.py": {"dsprites"}, "score.py": {"dsprites", "colored"}}
+    for fn, src in _package_sources().items():
+        for mod in ("celeba", "mnist", "dsprites", "colored"):
+            if mod in allowed.get(fn, ()) or fn == mod + ".py":
+                continue
+            assert not re.search(rf"^\s*from\s+\.{mod}\s+import\b", src, re.M), (fn, mod)
+            if fn not in ("__init__.py", "sampling.py"):        # the package's own listing; the generator factory (build_generator picks a workload by name)
+                assert not re.search(rf"^\s*from\s+\.\s+import\b[^\n]*\b{mod}\b", src, re.M), (fn, mod)
+
+
+def test_no_switch_is_imported_by_value():
+    """A reference-path switch is read where it is defined (``engine.IMG_GEMM`` at call time): a ``from .module import SWITCH`` binding
+    would keep the old value when a test patches the owner."""
+    import re
+    for fn, src in _package_sources().items():
+        for m in re.finditer(r"^\s*from\s+\.\w*\s+import\s+(\([^)]*\)|[^\n]*)", src, re.M):
+            names = re.sub(r"#[^\n]*", "", m.group(1))
+            for name in ("IMG_GEMM", "FUSE_DRAWS", "FUSE_ADAM"):
+                assert not re.search(rf"\b{name}\b", names), (fn, name)
+
+
 def test_one_entry_point_per_operation():
     """An operation that gains an argument keeps its name: no declared entry point is another one's name plus a suffix."""
     names = set(_pkg()._lib.parse_header())

@@ -503,7 +503,7 @@ def test_ragged_batch_sizes_through_the_drop_in_modules(B):
 @pytest.mark.parametrize("dtype,tol", [("f32", 2e-6), ("bf16", 2e-2)])
 def test_image_side_layers_both_formulations_agree(dtype, tol, monkeypatch):
     """The 128 -> 3 transposed convolutions (G's last layer forward, D's first-layer backward-to-image) as one GEMM + col2im gather (the
-    default) and as the 4-phase implicit GEMM (celeba.IMG_GEMM = False, kept as this test's reference) are the same function: fp32 up to summation order,
+    default) and as the 4-phase implicit GEMM (engine.IMG_GEMM = False, kept as this test's reference) are the same function: fp32 up to summation order,
     bf16 up to one extra rounding of the per-tap partial sums."""
     B = 4
     orc, G, D = build_pair(2, dtype)
@@ -515,13 +515,53 @@ def test_image_side_layers_both_formulations_agree(dtype, tol, monkeypatch):
     G.eval()
     D.eval()                                             # frozen spectral-norm vectors: a training-mode forward would move sigma between the two runs
     for flag in (True, False):
-        monkeypatch.setattr(eg.celeba, "IMG_GEMM", flag)
+        monkeypatch.setattr(eg.engine, "IMG_GEMM", flag)
         with torch.no_grad():
             gen = G(z.to(DEV), onehot.to(DEV), code.to(DEV)).float().cpu().clone()
         x = img.to(DEV).requires_grad_(True)
         cat, cont, val = D(x)
         (val.sum() + cont.sum()).backward()
         outs[flag] = (gen, x.grad.float().cpu().clone())
+    assert rel_err(outs[True][0], outs[False][0]) < tol
+    assert rel_err(outs[True][1], outs[False][1]) < tol
+    assert float(outs[False][1].abs().max()) > 0
+
+
+@pytest.mark.parametrize("dtype,tol", [("f32", 2e-6), ("bf16", 2e-2)])
+def test_dsprites_image_side_layers_both_formulations_agree(dtype, tol, monkeypatch):
+    """The same comparison for the dSprites drop-in modules (64 -> 1: G's last layer in dsprites._GenEngine, D's first-layer
+    backward-to-image in trunk.TrunkEngine), which read the same switch: the kernels of the CelebA layers with K = 64 instead of 128, so
+    the bounds carry over.  The launches are recorded to show that the two runs really took the two forms."""
+    B = 4
+    torch.manual_seed(11)
+    G = eg.dsprites.Generator(channels=1, dtype=dtype).to(DEV)
+    D = eg.dsprites.Discriminator(channels=1, dtype=dtype).to(DEV)
+    gen_in = torch.Generator().manual_seed(5)
+    z_c = torch.cat([F.one_hot(torch.randint(0, 3, (B,), generator=gen_in), 3).float(), torch.rand(B, 4, generator=gen_in) * 2 - 1], 1)
+    img = torch.rand(B, 1, 64, 64, generator=gen_in)
+    for _ in range(3):                                   # power iterations: with the random u, v of a fresh module sigma is far too small, and
+        D(img.to(DEV))                                   # the activations it blows up saturate the sigmoid -- d(img) would be exactly 0
+    G.eval()
+    D.eval()                                             # frozen spectral-norm vectors, as above
+    lib = eg._lib.lib()
+    call, log = lib.call, []
+
+    def recording(name, *args):
+        nchw = name == "eg_conv_bwd_data" and args[-2]._obj.out_mode == eg.ops.OUT_NCHW_F32
+        log.append(name + (":nchw" if nchw else ""))
+        return call(name, *args)
+    monkeypatch.setattr(lib, "call", recording)
+    outs, names = {}, {}
+    for flag in (True, False):
+        monkeypatch.setattr(eg.engine, "IMG_GEMM", flag)
+        del log[:]
+        with torch.no_grad():
+            gen = G(z_c.to(DEV)).float().cpu().clone()
+        x = img.to(DEV).requires_grad_(True)
+        D(x).sum().backward()
+        outs[flag], names[flag] = (gen, x.grad.float().cpu().clone()), set(log)
+    assert "eg_conv_bwd_data:nchw" not in names[True] and names[True] & {"eg_col2im_img", "eg_convt_img_mfma"}
+    assert not names[False] & {"eg_col2im_img", "eg_convt_img_mfma"} and "eg_conv_bwd_data:nchw" in names[False]
     assert rel_err(outs[True][0], outs[False][0]) < tol
     assert rel_err(outs[True][1], outs[False][1]) < tol
     assert float(outs[False][1].abs().max()) > 0

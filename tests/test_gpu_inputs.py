@@ -132,7 +132,7 @@ def test_fused_iteration_head_draws_the_same_batches(monkeypatch):
     data = (co.synthetic_real(64, seed=9) * 127.5 + 127.5).clamp(0, 255).to(torch.uint8).to(DEV)
     runs = []
     for fuse in (False, True):
-        monkeypatch.setattr(eg.celeba, "FUSE_DRAWS", fuse)
+        monkeypatch.setattr(eg.engine, "FUSE_DRAWS", fuse)
         orc = co.CelebAOracle(seed=2)
         G = eg.celeba.Generator(dtype="bf16").to(DEV)
         D = eg.celeba.Discriminator(dtype="bf16").to(DEV)
@@ -219,8 +219,6 @@ def test_small_network_draws_in_one_launch_are_the_same_draws(family, monkeypatc
     runs = []
     for fuse in (False, True):
         monkeypatch.setattr(eg.engine, "FUSE_DRAWS", fuse)
-        monkeypatch.setattr(eg.mnist, "FUSE_DRAWS", fuse)
-        monkeypatch.setattr(eg.dsprites, "FUSE_DRAWS", fuse)
         runs.append(_run_small(family, False))
     (l0, d0, i0, _), (l1, d1, i1, _) = runs
     assert int(i0.step.item()) == 4 and int(i1.step.item()) == 4
