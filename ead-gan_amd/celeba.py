@@ -15,12 +15,14 @@ import numpy as np
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 from torch.nn.utils import spectral_norm
 
 from . import affine, engine, ops
 from .affine import _code_to_theta, theta_to_matrix, transformation_2D      # noqa: F401  (drop-in names of the reference script)
-from .engine import (ConvRec, DeviceSampler, ResidentStep, SideStream, SyncScratch, Workspace, _HipModule, _require_cuda, bn_bwd_epilogue, bn_train_backward,
-                     bn_train_forward, convt_img, import_adam_moments, parse_dtype, stat_buffer, to_categorical, wgrad_side)      # noqa: F401
+from .engine import (ConvRec, DeviceSampler, InputGrad, ResidentStep, SideStream, SyncScratch, Workspace, _HipModule, _require_cuda, bn_bwd_epilogue,
+                     bn_train_backward, bn_train_forward, convt_img, drop_in_backward, import_adam_moments, parse_dtype, stat_buffer, to_categorical,
+                     wants_input_grad, wgrad_side)      # noqa: F401
 from .ops import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH
 
 # module-level hyper-parameters, mirroring the reference's global ``opt`` (argparse defaults, :39-51)
@@ -109,6 +111,8 @@ class _GenEngine:
         ws.need_small(ops.bias_grad_ws_floats(B * 16, W[0]))
         ws.need_sums(2 * max(W))
         self._stat = {}                                                # (kind, layer) -> (row blocks, buffer) of the fused column statistics
+        # d(loss)/d(inputs) from dh0 (NHWC: n' = t*1024 + co) and the master [cin][1024][4][4]: i = t, j = co
+        self.input_grad = InputGrad(dtype, B, 16, W[0], self.cin, (1, 16, 16 * W[0]), dev, 2 * max(W))
         self.repack()
 
     def _p(self, idx, kind):
@@ -182,22 +186,31 @@ class _GenEngine:
         convt_img(dt, x, self.l4g, self.cols4, self.l4, self._p(10, "bias"), ACT_TANH, self.img, True)
         return self.img
 
-    def backward(self, dimg, grad, side=None, sync=None, store=False):
-        """Accumulates d(loss)/d(params) into the flat gradient tensor ``grad`` (arena layout).  ``sync``: as in forward.  With ``side`` (an
+    def backward(self, dimg, grad, side=None, sync=None, store=False, *, dinp=None, need_wgrad=True, training=True):
+        """Differentiates the LATEST forward of this engine (the activations are the engine's, one set per batch size and dtype).
+        Accumulates d(loss)/d(params) into the flat gradient tensor ``grad`` (arena layout).  ``sync``: as in forward.  With ``side`` (an
         engine.SideStream) the weight/bias-gradient work of every layer is enqueued there, behind a fork taken right after
         the layer's output gradient exists; the caller joins before it reads ``grad``.
         ``store``: every slot of ``grad`` has exactly ONE writer in this pass (weights: the slab reduction; convolution biases: the column
         sums; BatchNorm affine: the statistics' final launch), so a caller that wants the gradient of this pass alone -- the trainer --
         lets each of them store instead of add: ``grad`` need not be cleared first and is never read.  The default keeps autograd's
-        accumulate contract (the drop-in modules)."""
+        accumulate contract (the drop-in modules).
+        ``dinp`` (fp32 [B, cin]): receives d(loss)/d(cat(noise, labels, code)) after the last launch of the pass.  ``need_wgrad=False``: no
+        weight-gradient chain runs and no bias / BatchNorm parameter gradient is written (``grad`` is not touched, may be None).
+        ``training=False``: the forward ran with the running statistics (``forward(training=False)``) -- BatchNorm is elementwise
+        (eg_bn_bwd_eval), input gradients only: combine with ``need_wgrad=False``.  The defaults launch what they always launched."""
         dt, B, W, ws, gen = self.dtype, self.B, G_WIDTHS, self.ws, self.gen
+        assert training or not need_wgrad, "eval-mode backward yields input gradients only"
         acc = not store
+        batch_stats = training and sync is None         # the BatchNorm-backward epilogues form the training-mode dy and its sums
+        pscr = self.input_grad.scratch                  # where parameter gradients land that nobody asked for
         gof = lambda name: gen.arena.grad_of(name, grad)
         C, S = gen.channels, self.img.shape[-1]
         direct = ops.conv_img_mfma_ok(dt, C, S, S, W[3], 4, 2, 1)
         if not direct:
             # tanh backward fused with the bias gradient of the last ConvTranspose2d
-            ops.act_grad_mul_bias_nchw(dimg, self.img, self.dimg_z, B, C, S * S, ACT_TANH, 0.0, ws.small, gof("conv_blocks.10.bias"), accumulate=acc)
+            ops.act_grad_mul_bias_nchw(dimg, self.img, self.dimg_z, B, C, S * S, ACT_TANH, 0.0, ws.small,
+                                       gof("conv_blocks.10.bias") if need_wgrad else pscr[:C], accumulate=acc and need_wgrad)
             # L4 = ConvTranspose2d(128 -> C): weight / input gradients as 1x1-conv GEMMs over im2col patches of d(img)
             ops.im2col_img(dt, self.dimg_z, self.patches, B, C, S, S, 4, 2, 1, self.kp)
 
@@ -208,14 +221,15 @@ class _GenEngine:
                 ops.im2col_img(dt, self.dimg_z, self.patches, B, C, S, S, 4, 2, 1, self.kp)
             ns = ops.conv_wgrad(self.l4p.c, dt, self.patches, self.a[2], wsw.slab, wsw.wgs_target)
             ops.wgrad_reduce(wsw.slab, ns, W[3], W[3], self.kp, 1, gof("conv_blocks.10.weight"), accumulate=acc)
-        wgrad_side(side, ws, 0, l4_wgrad, "G4")
+        if need_wgrad:                                  # (direct: dimg_z and the patch rows feed nothing else)
+            wgrad_side(side, ws, 0, l4_wgrad, "G4")
         bn_of = lambda i: gen.conv_blocks[(1, 4, 7)[i] + 1]
         bwd_ep = lambda fused, i: bn_bwd_epilogue(fused[1], self.z[i], self.mean[i], self.invstd[i], bn_of(i)) if fused[0] else None
         fused = (0, None)                               # (row blocks, sums) if da[i] came with its BatchNorm backward sums (then it holds dy)
         if direct:
             # d(a) = Conv2d(C -> 128, 4, 2, 1) of d(img) * tanh'(img): straight from the two fp32 images, no patch rows -- and, in the same
             # launch, dy = da * relu'(bn(z)) with the two sums of the last BatchNorm layer's backward
-            if sync is None:
+            if batch_stats:
                 fused = stat_buffer(self._stat, "bwd2", None, dt, False, None, W[3], self.inp.device, nrb=lambda: ops.conv_img_mfma_stat_blocks(B, S, S))
             ops.conv_img_mfma(dt, [dimg], self.l4p.wp_fwd, self.da[2], B, C, S, S, bwd_ep(fused, 2), gates=[self.img], gate_act=ACT_TANH)
         else:
@@ -224,17 +238,22 @@ class _GenEngine:
         for i, idx in ((2, 7), (1, 4), (0, 1)):
             r = self.mid[i]
             M = self.z[i].numel() // W[i + 1]
+            if need_wgrad:
+                dgamma, dbeta = gof(f"conv_blocks.{idx + 1}.weight"), gof(f"conv_blocks.{idx + 1}.bias")
+            else:
+                dgamma, dbeta = pscr[:W[i + 1]], pscr[W[i + 1]:2 * W[i + 1]]
             bn_train_backward(dt, self.z[i], self.da[i], self.dz[i], M, W[i + 1], bn_of(i), self.mean[i], self.invstd[i], ACT_RELU, 0.0,
-                              gof(f"conv_blocks.{idx + 1}.weight"), gof(f"conv_blocks.{idx + 1}.bias"), ws, sync, self.sync_scratch.sums[i], fused, acc)
+                              dgamma, dbeta, ws, sync, self.sync_scratch.sums[i], fused, acc and need_wgrad, training)
             x_in = self.a[i - 1] if i > 0 else self.h0
 
             def mid_wgrad(wsw, i=i, idx=idx, r=r, M=M, x_in=x_in):
                 ns = ops.conv_wgrad(r.c, dt, self.dz[i], x_in, wsw.slab, wsw.wgs_target)
                 ops.wgrad_reduce(wsw.slab, ns, r.Cout, r.Cout, r.Cin, 16, gof(f"conv_blocks.{idx}.weight"), accumulate=acc)
                 ops.bias_grad(dt, self.dz[i], M, W[i + 1], wsw.small, gof(f"conv_blocks.{idx}.bias"), accumulate=acc)
-            wgrad_side(side, ws, i + 1, mid_wgrad, f"G{i + 1}")
+            if need_wgrad:
+                wgrad_side(side, ws, i + 1, mid_wgrad, f"G{i + 1}")
             fused = (0, None)
-            if i > 0 and sync is None:
+            if i > 0 and batch_stats:
                 # the launch that produces d(a[i-1]) also forms dy = da * relu'(bn(z)) and the two sums of that layer's BatchNorm backward
                 fused = self._stat_buf(("bwd", i - 1), r.c, False, ops.epilogue(), W[i])
             ops.conv_fwd(r.c, dt, self.dz[i], r.wp_fwd, self.da[i - 1] if i > 0 else self.dh0, bwd_ep(fused, i - 1))
@@ -244,7 +263,10 @@ class _GenEngine:
             ns = ops.conv_wgrad(self.l0w.c, dt, self.dh0, self.inp, wsw.slab, wsw.wgs_target)
             ops.wgrad_reduce(wsw.slab, ns, self.cpad, self.cin, W[0], 16, gof("conv_blocks.0.weight"), accumulate=acc)
             ops.bias_grad(dt, self.dh0, B * 16, W[0], wsw.small, gof("conv_blocks.0.bias"), accumulate=acc)
-        wgrad_side(side, ws, 0, l0_wgrad, "G0")
+        if need_wgrad:
+            wgrad_side(side, ws, 0, l0_wgrad, "G0")
+        if dinp is not None:
+            self.input_grad.run(self.dh0, self._p(0, "weight"), dinp)
 
 
 class Generator(_HipModule):
@@ -278,29 +300,31 @@ class Generator(_HipModule):
     def forward(self, noise, labels, code):
         _require_cuda(noise)
         eng = self.fresh_engine(noise.shape[0])
-        if not self.training:
+        if not self.training and not wants_input_grad(noise, labels, code):
             # inference (generate_image.py:146-154, gen_imgs.py:106-120): running-stat BatchNorm, no autograd graph
             with torch.no_grad():
                 return eng.forward(noise.float().contiguous(), labels.float().contiguous(), code.float().contiguous(), training=False).clone()
+        # train mode: input and parameter gradients from one pass (batch statistics couple the samples, the gradient reflects it);
+        # eval mode with an input that requires grad: the same eval forward, input gradients only
         params = [p for p in self.parameters()]
-        return _GenFn.apply(eng, noise.float().contiguous(), labels.float().contiguous(), code.float().contiguous(), *params)
+        return _GenFn.apply(eng, self.training, noise.float().contiguous(), labels.float().contiguous(), code.float().contiguous(), *params)
 
 
 class _GenFn(torch.autograd.Function):
-    """autograd bridge so the drop-in modules compose with torch losses/optimizers (eager mode)."""
+    """autograd bridge so the drop-in modules compose with torch losses/optimizers (eager mode).  The activations live in the engine:
+    ``backward`` differentiates the engine's LATEST forward, so call it before the module runs again at this batch size."""
 
     @staticmethod
-    def forward(ctx, eng, noise, labels, code, *params):
-        ctx.eng = eng
-        return eng.forward(noise, labels, code).clone()
+    def forward(ctx, eng, training, noise, labels, code, *params):
+        ctx.eng, ctx.training = eng, training
+        ctx.widths = (noise.shape[1], labels.shape[1], code.shape[1])
+        return eng.forward(noise, labels, code, training=training).clone()
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dimg):
-        eng = ctx.eng
-        scratch = torch.zeros_like(eng.gen.arena.grad)
-        eng.backward(dimg.contiguous(), scratch)
-        grads = [scratch[off:off + k].view(p.shape) for p, (off, k) in zip(eng.gen.parameters(), eng.gen.arena.slices.values())]
-        return (None, None, None, None, *grads)
+        ins, grads = drop_in_backward(ctx.eng, dimg, ctx.needs_input_grad[2:5], ctx.needs_input_grad[5:], ctx.training, ctx.widths)
+        return (None, None, *ins, *grads)
 
 
 # ================================================================================================

@@ -108,6 +108,10 @@ __global__ void bn_stats_final_kernel(const float* __restrict__ partial, int nrb
     }
 }
 
+// the normalised value from the layer's input and the two per-channel coefficients: THE expression of the apply kernel, shared with the
+// eval-mode backward (eg_bn_bwd_eval), which decides act'(y) on the very y the forward passed to the activation
+__device__ __forceinline__ float bn_affine(float x, float a, float b) { return x * a + b; }
+
 // y = act(x * A[c] + B[c]);  each thread keeps its 16-byte channel chunk fixed (grid stride is a multiple of the row length)
 template <typename T>
 __global__ void bn_apply_kernel(const T* __restrict__ x, T* __restrict__ y, size_t nrows, int C, const float* __restrict__ coef, int act, float slope) {
@@ -124,7 +128,7 @@ __global__ void bn_apply_kernel(const T* __restrict__ x, T* __restrict__ y, size
         uint4 v = *reinterpret_cast<const uint4*>(x + o);
         T* e = reinterpret_cast<T*>(&v);
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) Elt<T>::st(e + j, eg_act(Elt<T>::ld(e + j) * A[j] + Bc[j], act, slope));
+        for (int j = 0; j < VEC; ++j) Elt<T>::st(e + j, eg_act(bn_affine(Elt<T>::ld(e + j), A[j], Bc[j]), act, slope));
         *reinterpret_cast<uint4*>(y + o) = v;
     }
 }
@@ -354,6 +358,49 @@ __device__ __forceinline__ float pre_act_grad(float y, int act, float slope) {
         case EG_ACT_RELU: return y > 0.f ? 1.f : 0.f;
         default: return 1.f;
     }
+}
+
+// ---- eval-mode backward: the statistics are constants, so the layer is elementwise -- dz = da * act'(y) * A[c] with y = bn_affine(z, A[c],
+// B[c]) recomputed from the coefficients of bn_eval_coef_kernel, as the forward had it.  No parameter gradients.
+template <typename T>
+__global__ void bn_bwd_eval_kernel(const T* __restrict__ z, const T* __restrict__ da, T* __restrict__ dz, size_t nrows, int C,
+                                   const float* __restrict__ coef, int act, float slope) {
+    constexpr int VEC = Elt<T>::VEC;
+    const int cpr = C / VEC;
+    const int chunk = (blockIdx.x * blockDim.x + threadIdx.x) % cpr;
+    const size_t row0 = (size_t)(blockIdx.x * blockDim.x + threadIdx.x) / cpr;
+    const size_t rstride = (size_t)gridDim.x * blockDim.x / cpr;
+    float A[VEC], Bc[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) { A[j] = coef[chunk * VEC + j]; Bc[j] = coef[C + chunk * VEC + j]; }
+    for (size_t r = row0; r < nrows; r += rstride) {
+        const size_t o = r * C + (size_t)chunk * VEC;
+        const uint4 vz = *reinterpret_cast<const uint4*>(z + o);
+        uint4 vd = *reinterpret_cast<const uint4*>(da + o);
+        const T* ez = reinterpret_cast<const T*>(&vz);
+        T* ed = reinterpret_cast<T*>(&vd);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j)
+            Elt<T>::st(ed + j, Elt<T>::ld(ed + j) * pre_act_grad(bn_affine(Elt<T>::ld(ez + j), A[j], Bc[j]), act, slope) * A[j]);
+        *reinterpret_cast<uint4*>(dz + o) = vd;
+    }
+}
+
+extern "C" int eg_bn_bwd_eval(int dtype, const void* z, const void* da, void* dz, int M, int C, const float* gamma, const float* beta, float eps,
+                              const float* running_mean, const float* running_var, float* ws, int act, float slope, eg_stream_t s) {
+    EG_REQUIRE(z && da && dz && gamma && beta && running_mean && running_var && ws, "eg_bn_bwd_eval: null pointer");
+    EG_REQUIRE(dtype == EG_F32 || dtype == EG_BF16 || dtype == EG_F16, "dtype must be EG_F32, EG_BF16 or EG_F16");
+    EG_REQUIRE(M > 0 && C > 0 && C % (dtype == EG_F32 ? 4 : 8) == 0, "eg_bn_bwd_eval: C must be a multiple of the 16-byte vector width");
+    EG_REQUIRE(act == EG_ACT_NONE || act == EG_ACT_RELU || act == EG_ACT_LRELU, "eg_bn_bwd_eval: act must be EG_ACT_NONE, EG_ACT_RELU or EG_ACT_LRELU");
+    hipStream_t st = (hipStream_t)s;
+    hipLaunchKernelGGL(bn_eval_coef_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, gamma, beta, running_mean, running_var, eps, C, ws);
+    const int cpr = C / (dtype == EG_F32 ? 4 : 8);
+    const int blocks = bn_apply_blocks((size_t)M, cpr);
+    if (dtype == EG_F32) hipLaunchKernelGGL(bn_bwd_eval_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)z, (const float*)da, (float*)dz, (size_t)M, C, ws, act, slope);
+    else if (dtype == EG_F16) hipLaunchKernelGGL(bn_bwd_eval_kernel<f16_t>, dim3(blocks), dim3(256), 0, st, (const f16_t*)z, (const f16_t*)da, (f16_t*)dz, (size_t)M, C, ws, act, slope);
+    else hipLaunchKernelGGL(bn_bwd_eval_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, (const bf16_t*)z, (const bf16_t*)da, (bf16_t*)dz, (size_t)M, C, ws, act, slope);
+    EG_LAUNCH_CHECK();
+    return 0;
 }
 
 template <typename T>

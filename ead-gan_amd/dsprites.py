@@ -10,12 +10,14 @@ import itertools
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 from torch.nn.utils import spectral_norm
 
 from . import affine, engine, ops
 from .affine import _code_to_theta, theta_to_matrix, transformation_2D      # noqa: F401
-from .engine import (Arena, ConvRec, DeviceSampler, ResidentStep, SideStream, SyncScratch, Workspace, _HipModule, _require_cuda, bn_bwd_epilogue, bn_train_backward,
-                     bn_train_forward, convt_img, import_adam_moments, parse_dtype, stat_buffer, to_categorical, wgrad_side)      # noqa: F401
+from .engine import (Arena, ConvRec, DeviceSampler, InputGrad, ResidentStep, SideStream, SyncScratch, Workspace, _HipModule, _require_cuda, bn_bwd_epilogue,
+                     bn_train_backward, bn_train_forward, convt_img, drop_in_backward, import_adam_moments, parse_dtype, stat_buffer, to_categorical,
+                     wants_input_grad, wgrad_side)      # noqa: F401
 from .ops import ACT_LRELU, ACT_RELU, ACT_SIGMOID, EG_F32
 from .trunk import Head, TrunkEngine, _TrunkFn
 
@@ -235,6 +237,8 @@ class _GenEngine:
         ws.need_small(ops.bias_grad_ws_floats(B, 1024))
         ws.need_small(B * self.CH)
         ws.need_sums(128)
+        # d(loss)/d(inputs) from dz1 [B][128] and the master fc1.0.weight [128][cin]: one i, j = the output feature
+        self.input_grad = InputGrad(dtype, B, 1, 128, self.cin, (0, self.cin, 1), dev, 2 * 64)
         self.repack()
 
     def _stat_buf(self, key, c, bwd, ep, C):
@@ -281,16 +285,27 @@ class _GenEngine:
         convt_img(dt, x, self.l4g, self.cols4, self.l4, cb[9].bias, ACT_SIGMOID, self.img, self.l4g.Kpad_fwd == 64)
         return self.img
 
-    def backward(self, dimg, grad, sync=None, side=None):
-        """``side`` (engine.SideStream): the weight- / bias-gradient chains run on side lanes; the caller joins them before reading ``grad``"""
+    def backward(self, dimg, grad, sync=None, side=None, *, dinp=None, need_wgrad=True, training=True):
+        """Differentiates the LATEST forward of this engine (the activations are the engine's, one set per batch size, dtype and slot).
+        ``side`` (engine.SideStream): the weight- / bias-gradient chains run on side lanes; the caller joins them before reading ``grad``.
+        ``dinp`` (fp32 [B, cin]): receives d(loss)/d(z_c) after the last launch of the pass.  ``need_wgrad=False``: no weight-gradient chain
+        runs and no bias / BatchNorm parameter gradient is written (``grad`` is not touched, may be None).  ``training=False``: the forward
+        ran with the running statistics -- BatchNorm is elementwise (eg_bn_bwd_eval), input gradients only: combine with
+        ``need_wgrad=False``.  The defaults launch what they always launched."""
         dt, B, g, ws = self.dtype, self.B, self.gen, self.ws
+        assert training or not need_wgrad, "eval-mode backward yields input gradients only"
         cb = g.conv_block
         gof = lambda name: g.arena.grad_of(name, grad)
         lanes = itertools.count()
-        ops.act_grad_mul_bias_nchw(dimg, self.img, self.dimg_z, B, self.CH, 64 * 64, ACT_SIGMOID, 0.0, ws.small, gof("conv_block.9.bias"))
+        batch_stats = training and sync is None         # the BatchNorm-backward epilogues form the training-mode dy and its sums
+        pscr = self.input_grad.scratch                  # where parameter gradients land that nobody asked for
+        if need_wgrad:
+            ops.act_grad_mul_bias_nchw(dimg, self.img, self.dimg_z, B, self.CH, 64 * 64, ACT_SIGMOID, 0.0, ws.small, gof("conv_block.9.bias"))
+        else:
+            ops.act_grad_mul_bias_nchw(dimg, self.img, self.dimg_z, B, self.CH, 64 * 64, ACT_SIGMOID, 0.0, ws.small, pscr[:self.CH], accumulate=False)
         # the last layer's backward straight from the image gradient (no patch rows in HBM): weight gradient by eg_wgrad_img, input gradient by
         # eg_conv_img_mfma with the BatchNorm-backward sums of the layer below in its epilogue (as celeba._GenEngine.backward)
-        direct = self.l4_direct and sync is None
+        direct = self.l4_direct and batch_stats
         if not direct:
             ops.im2col_img(dt, self.dimg_z, self.patches, B, self.CH, 64, 64, 4, 2, 1, self.kp)
 
@@ -300,12 +315,13 @@ class _GenEngine:
             else:
                 ns = ops.conv_wgrad(self.l4p.c, dt, self.patches, self.a[2], wsw.slab, wsw.wgs_target)
             ops.wgrad_reduce_perm(wsw.slab, ns, 64, 64, self.kp, 1, gof("conv_block.9.weight"), 0, 0, self.k0)
-        wgrad_side(side, ws, next(lanes), l4_wgrad)
+        if need_wgrad:
+            wgrad_side(side, ws, next(lanes), l4_wgrad)
 
         def bn_bwd_ep(i, c):
             """((row blocks, sums), epilogue) if the launch that produces da[i] can also form dy = da * relu'(bn(z)) and the two sums of layer
             i's BatchNorm backward (engine.bn_bwd_epilogue), else ((0, None), None)"""
-            fused = self._stat_buf(("bwd", i), c, False, ops.epilogue(), 64) if sync is None else (0, None)
+            fused = self._stat_buf(("bwd", i), c, False, ops.epilogue(), 64) if batch_stats else (0, None)
             return fused, bn_bwd_epilogue(fused[1], self.z[i], self.mean[i], self.invstd[i], cb[(0, 3, 6)[i] + 1]) if fused[0] else None
         if direct:
             fused = stat_buffer(self._stat, "bwd_img", None, dt, False, None, 64, self.inp.device, nrb=lambda: ops.conv_img_mfma_stat_blocks(B, 64, 64))
@@ -318,15 +334,20 @@ class _GenEngine:
             r = self.mid[i]
             bn = cb[idx + 1]
             M = B * (8 << i) ** 2
-            bn_train_backward(dt, self.z[i], self.da[i], self.dz[i], M, 64, bn, self.mean[i], self.invstd[i], ACT_RELU, 0.0,
-                              gof(f"conv_block.{idx + 1}.weight"), gof(f"conv_block.{idx + 1}.bias"), ws, sync, self.sync_scratch.sums[i], fused)
+            if need_wgrad:
+                bn_train_backward(dt, self.z[i], self.da[i], self.dz[i], M, 64, bn, self.mean[i], self.invstd[i], ACT_RELU, 0.0,
+                                  gof(f"conv_block.{idx + 1}.weight"), gof(f"conv_block.{idx + 1}.bias"), ws, sync, self.sync_scratch.sums[i], fused)
+            else:
+                bn_train_backward(dt, self.z[i], self.da[i], self.dz[i], M, 64, bn, self.mean[i], self.invstd[i], ACT_RELU, 0.0,
+                                  pscr[:64], pscr[64:128], ws, sync, self.sync_scratch.sums[i], fused, accumulate=False, training=training)
             x_in = self.a[i - 1] if i > 0 else self.h
 
             def mid_wgrad(wsw, i=i, idx=idx, r=r, M=M, x_in=x_in):
                 ns = ops.conv_wgrad(r.c, dt, self.dz[i], x_in, wsw.slab, wsw.wgs_target)
                 ops.wgrad_reduce(wsw.slab, ns, 64, 64, 64, 16, gof(f"conv_block.{idx}.weight"))
                 ops.bias_grad(dt, self.dz[i], M, 64, wsw.small, gof(f"conv_block.{idx}.bias"))
-            wgrad_side(side, ws, next(lanes), mid_wgrad)
+            if need_wgrad:
+                wgrad_side(side, ws, next(lanes), mid_wgrad)
             if i > 0:
                 fused, ep = bn_bwd_ep(i - 1, r.c)
                 ops.conv_fwd(r.c, dt, self.dz[i], r.wp_fwd, self.da[i - 1], ep)
@@ -340,7 +361,8 @@ class _GenEngine:
             ops.fill_f32(self.gb2_perm)
             ops.bias_grad(dt, self.dh, B, 1024, wsw.small, self.gb2_perm)
             ops.gather_add(gof("fc2.0.bias"), self.gb2_perm, 1024, 16, 1, 64)
-        wgrad_side(side, ws, next(lanes), fc2_wgrad)
+        if need_wgrad:
+            wgrad_side(side, ws, next(lanes), fc2_wgrad)
         ops.conv_bwd_data(self.f2.c, dt, self.dh, self.f2.wp_bwd, self.dz1, ops.epilogue(mask=self.a1, mask_act=ACT_RELU))
 
         # fc1
@@ -348,7 +370,10 @@ class _GenEngine:
             ns = ops.conv_wgrad(self.f1.c, dt, self.inp, self.dz1, wsw.slab, wsw.wgs_target)
             ops.wgrad_reduce_perm(wsw.slab, ns, 128, 128, self.cpad, 1, gof("fc1.0.weight"), 0, 0, self.cin)
             ops.bias_grad(dt, self.dz1, B, 128, wsw.small, gof("fc1.0.bias"))
-        wgrad_side(side, ws, next(lanes), fc1_wgrad)
+        if need_wgrad:
+            wgrad_side(side, ws, next(lanes), fc1_wgrad)
+        if dinp is not None:
+            self.input_grad.run(self.dz1, g.fc1[0].weight, dinp)
 
 
 class Generator(_HipModule):
@@ -379,25 +404,31 @@ class Generator(_HipModule):
         _require_cuda(z_c)
         z_c = z_c.float().contiguous()
         eng = self.fresh_engine(z_c.shape[0])
-        if not self.training:       # inference (dSprites/gen_imgs.py): running-stat BatchNorm, no autograd graph
+        if not self.training and not wants_input_grad(z_c):
+            # inference (dSprites/gen_imgs.py): running-stat BatchNorm, no autograd graph
             with torch.no_grad():
                 return eng.forward(z_c[:, :self.n_classes].contiguous(), z_c[:, self.n_classes:].contiguous(), training=False).clone()
-        return _GenFn.apply(eng, z_c[:, :self.n_classes].contiguous(), z_c[:, self.n_classes:].contiguous(), *list(self.parameters()))
+        # train mode: input and parameter gradients from one pass (batch statistics couple the samples, the gradient reflects it);
+        # eval mode with a z_c that requires grad: the same eval forward, input gradients only.  autograd concatenates the gradients of
+        # the two slices back into d(z_c)
+        return _GenFn.apply(eng, self.training, z_c[:, :self.n_classes].contiguous(), z_c[:, self.n_classes:].contiguous(), *list(self.parameters()))
 
 
 class _GenFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, eng, labels, code, *params):
-        ctx.eng = eng
-        return eng.forward(labels, code).clone()
+    """autograd bridge of the drop-in generator.  The activations live in the engine: ``backward`` differentiates the engine's LATEST
+    forward, so call it before the module runs again at this batch size."""
 
     @staticmethod
+    def forward(ctx, eng, training, labels, code, *params):
+        ctx.eng, ctx.training = eng, training
+        ctx.widths = (labels.shape[1], code.shape[1])
+        return eng.forward(labels, code, training=training).clone()
+
+    @staticmethod
+    @once_differentiable
     def backward(ctx, dimg):
-        eng = ctx.eng
-        scratch = torch.zeros_like(eng.gen.arena.grad)
-        eng.backward(dimg.contiguous(), scratch)
-        grads = [scratch[off:off + k].view(p.shape) for p, (off, k) in zip(eng.gen.parameters(), eng.gen.arena.slices.values())]
-        return (None, None, None, *grads)
+        ins, grads = drop_in_backward(ctx.eng, dimg, ctx.needs_input_grad[2:4], ctx.needs_input_grad[4:], ctx.training, ctx.widths)
+        return (None, None, *ins, *grads)
 
 
 # ================================================================================================

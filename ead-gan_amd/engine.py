@@ -313,12 +313,18 @@ def bn_train_forward(dt, x, y, M, C, bn, mean, invstd, ws_small, act, slope=0.0,
                               bn.num_batches_tracked, mean, invstd, ws_small, act, slope)
 
 
-def bn_train_backward(dt, z, da, dz, M, C, bn, mean, invstd, act, slope, dgamma, dbeta, ws, sync=None, sums=None, fused=(0, None), accumulate=True):
-    """Backward of bn_train_forward's training forms (``ws``: a Workspace).  ``fused`` = (row blocks, sums): ``da`` came from a launch
-    with bn_bwd_epilogue, it already holds dy = da * act'(bn(z)) and the two sums are in the buffer.  ``sync``: the two per-channel sums
-    over the global batch (one exchange of 2*C floats); dgamma / dbeta are this rank's share -- the gradient all-reduce averages them
-    like every other gradient.  ``accumulate=False``: dgamma / dbeta are stored, not added to."""
-    if fused[0]:
+def bn_train_backward(dt, z, da, dz, M, C, bn, mean, invstd, act, slope, dgamma, dbeta, ws, sync=None, sums=None, fused=(0, None), accumulate=True,
+                      training=True):
+    """Backward of bn_train_forward, THE place that chooses its form (``ws``: a Workspace).  ``fused`` = (row blocks, sums): ``da`` came
+    from a launch with bn_bwd_epilogue, it already holds dy = da * act'(bn(z)) and the two sums are in the buffer.  ``sync``: the two
+    per-channel sums over the global batch (one exchange of 2*C floats); dgamma / dbeta are this rank's share -- the gradient all-reduce
+    averages them like every other gradient.  ``accumulate=False``: dgamma / dbeta are stored, not added to.
+    ``training=False``: backward of the running-statistics forward -- elementwise, the input gradient only; dgamma / dbeta are not
+    touched (may be None) and ``da`` must be the plain activation gradient (no bn_bwd_epilogue on the launch that produced it)."""
+    if not training:
+        assert not fused[0], "the BatchNorm-backward epilogue forms the training-mode dy"
+        ops.bn_bwd_eval(dt, z, da, dz, M, C, bn.weight, bn.bias, bn.eps, bn.running_mean, bn.running_var, ws.small, act, slope)
+    elif fused[0]:
         ops.bn_bwd_fused(dt, z, da, dz, M, C, fused[1], fused[0], bn.weight, bn.bias, mean, invstd, dgamma, dbeta, ws.sums, ws.small, accumulate=accumulate)
     elif sync is None:
         ops.bn_bwd(dt, z, da, dz, M, C, bn.weight, bn.bias, mean, invstd, act, slope, dgamma, dbeta, ws.sums, ws.small, accumulate=accumulate)
@@ -326,6 +332,54 @@ def bn_train_backward(dt, z, da, dz, M, C, bn, mean, invstd, act, slope, dgamma,
         ops.bn_bwd_sums_local(dt, z, da, M, C, bn.weight, bn.bias, mean, invstd, act, slope, dgamma, dbeta, sums, ws.small, accumulate=accumulate)
         sync.reduce_sums(sums)
         ops.bn_bwd_from_sums(dt, z, da, dz, M, C, sums, M * sync.world, bn.weight, bn.bias, mean, invstd, act, slope, ws.small)
+
+
+class InputGrad:
+    """What a generator engine needs for the gradient with respect to its inputs (ops.linear_dinput on the first layer's output gradient
+    and the layer's fp32 master): the split scratch, allocated HERE -- with the engine, never at backward time: a buffer that grows later
+    would move addresses under hipGraphs captured by others -- and ``scratch``, where the bias / BatchNorm parameter gradients of a pass
+    with ``need_wgrad=False`` land (the kernels that form them next to an input gradient always write them)."""
+
+    def __init__(self, dtype, B, NI, NJ, K, strides, device, scratch_floats):
+        self.dtype, self.B, self.NI, self.NJ, self.K, self.strides = dtype, B, NI, NJ, K, tuple(int(s) for s in strides)
+        self.ws = torch.empty(max(1, ops.linear_dinput_ws_floats(B, NI, NJ, K)), device=device, dtype=torch.float32)
+        self.scratch = torch.empty(int(scratch_floats), device=device, dtype=torch.float32)
+
+    def run(self, dH, w, dinp):
+        """dinp [B, K] fp32 <- dH x w (every element stored)"""
+        if dinp.dtype != torch.float32 or tuple(dinp.shape) != (self.B, self.K) or not dinp.is_contiguous():
+            raise ValueError(f"dinp must be a contiguous fp32 [{self.B}, {self.K}] tensor")
+        _require_cuda(dinp)
+        ops.linear_dinput(self.dtype, dH, self.NI * self.NJ, w, dinp, self.B, self.NI, self.NJ, self.K, *self.strides, self.ws)
+
+
+def drop_in_backward(eng, dimg, need_inputs, need_params, training, widths):
+    """Backward of the generators' autograd bridges (``_GenFn`` of celeba, mnist, dsprites) -> ([input gradient or None per input],
+    [parameter gradients]).  ``need_inputs`` / ``need_params``: ``ctx.needs_input_grad`` of the inputs (widths ``widths``, in the order
+    the engine concatenates them) and of the parameters.  One engine pass yields both; without a parameter that needs a gradient the
+    weight-gradient chains are skipped.  ``training=False`` (the forward ran with the running statistics) yields input gradients only."""
+    gen = eng.gen
+    wgrad = any(need_params)
+    if wgrad and not training:
+        raise NotImplementedError("eval-mode generators give input gradients only: a parameter requires grad -- call requires_grad_(False) on "
+                                  "the module (projection, saliency), or use train mode for parameter gradients")
+    scratch = torch.zeros_like(gen.arena.grad) if wgrad else None
+    dinp = torch.empty(eng.B, eng.cin, device=dimg.device, dtype=torch.float32) if any(need_inputs) else None
+    eng.backward(dimg.contiguous(), scratch, dinp=dinp, need_wgrad=wgrad, training=training)
+    ins, col = [], 0
+    for need, w in zip(need_inputs, widths):
+        ins.append(dinp[:, col:col + w].clone() if need else None)
+        col += w
+    if wgrad:
+        grads = [scratch[off:off + k].view(p.shape) for p, (off, k) in zip(gen.parameters(), gen.arena.slices.values())]
+    else:
+        grads = [None] * len(gen.arena.slices)
+    return ins, grads
+
+
+def wants_input_grad(*inputs):
+    """an eval-mode drop-in forward builds a graph only for this: autograd is recording and an input requires grad"""
+    return torch.is_grad_enabled() and any(t.requires_grad for t in inputs)
 
 
 def stat_buffer(stat, key, c, dtype, bwd, ep, C, device, nrb=None, floats=None):

@@ -10,12 +10,14 @@ import argparse
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 from torch.nn.utils import spectral_norm
 
 from . import affine, engine, ops
 from .affine import _code_to_theta, theta_to_matrix, transformation_2D      # noqa: F401  (same STN warp in all scripts)
-from .engine import (Arena, ConvRec, DeviceSampler, ResidentStep, SideStream, SyncScratch, Workspace, _HipModule, _require_cuda, bn_train_backward, bn_train_forward,
-                     capture_step, check_usable, import_adam_moments, parse_dtype, to_categorical, wgrad_side)      # noqa: F401
+from .engine import (Arena, ConvRec, DeviceSampler, InputGrad, ResidentStep, SideStream, SyncScratch, Workspace, _HipModule, _require_cuda, bn_train_backward,
+                     bn_train_forward, capture_step, check_usable, drop_in_backward, import_adam_moments, parse_dtype, to_categorical, wants_input_grad,
+                     wgrad_side)      # noqa: F401
 from .ops import ACT_LRELU, ACT_NONE, ACT_TANH, EG_F32, OUT_NCHW_F32
 from .trunk import Head, TrunkEngine, _TrunkFn
 
@@ -90,6 +92,8 @@ class _GenEngine:
         ws.need_small(ops.bias_grad_ws_floats(B, self.nl1))
         ws.need_small(B * self.CH)
         ws.need_sums(2 * 128)
+        # d(loss)/d(inputs) from dh (NHWC: n' = hw*128 + c) and the master [8192][cin] (row f = c*64 + hw): i = hw, j = c
+        self.input_grad = InputGrad(dtype, B, s * s, 128, self.cin, (self.cin, s * s * self.cin, 1), dev, 2 * 128)
         self.repack()
 
     def _p(self, path):
@@ -143,17 +147,27 @@ class _GenEngine:
         ops.conv_fwd(self.c3f.c, dt, self.a2, self.c3f.wp_fwd, self.img, ops.epilogue(bias=cb[9].bias, act=ACT_TANH, out_mode=OUT_NCHW_F32))
         return self.img
 
-    def backward(self, dimg, grad, side=None, sync=None):
-        """Accumulates d(loss)/d(params) into ``grad``.  With ``side`` (engine.SideStream) every layer's weight-gradient chain (TN GEMM, slab
+    def backward(self, dimg, grad, side=None, sync=None, *, dinp=None, need_wgrad=True, training=True):
+        """Differentiates the LATEST forward of this engine (the activations are the engine's, one set per batch size and dtype).
+        Accumulates d(loss)/d(params) into ``grad``.  With ``side`` (engine.SideStream) every layer's weight-gradient chain (TN GEMM, slab
         reduce, bias sums) is forked onto a lane as soon as the layer's output gradient exists, beside the backward-data chain of the
-        layers below; the caller joins before it reads ``grad``.  Same kernels, same order inside every chain: bit-identical."""
+        layers below; the caller joins before it reads ``grad``.  Same kernels, same order inside every chain: bit-identical.
+        ``dinp`` (fp32 [B, cin]): receives d(loss)/d(cat(noise, labels, code)) after the last launch of the pass.  ``need_wgrad=False``: no
+        weight-gradient chain runs and no bias / BatchNorm parameter gradient is written (``grad`` is not touched, may be None).
+        ``training=False``: the forward ran with the running statistics -- BatchNorm is elementwise (eg_bn_bwd_eval), input gradients
+        only: combine with ``need_wgrad=False``.  The defaults launch what they always launched."""
         dt, B, g, ws = self.dtype, self.B, self.gen, self.ws
+        assert training or not need_wgrad, "eval-mode backward yields input gradients only"
         cb = g.conv_blocks
         gof = lambda name: g.arena.grad_of(name, grad)
         s = g.init_size
         S = 4 * s
+        pscr = self.input_grad.scratch                  # where parameter gradients land that nobody asked for
 
-        ops.act_grad_mul_bias_nchw(dimg, self.img, self.dimg_z, B, self.CH, S * S, ACT_TANH, 0.0, ws.small, gof("conv_blocks.9.bias"))
+        if need_wgrad:
+            ops.act_grad_mul_bias_nchw(dimg, self.img, self.dimg_z, B, self.CH, S * S, ACT_TANH, 0.0, ws.small, gof("conv_blocks.9.bias"))
+        else:
+            ops.act_grad_mul_bias_nchw(dimg, self.img, self.dimg_z, B, self.CH, S * S, ACT_TANH, 0.0, ws.small, pscr[:self.CH], accumulate=False)
         ops.cast_pad(dt, self.dimg_z, self.p8, B * S * S, self.CH, 8)          # [M][1] fp32 (== NCHW with C=1) -> [M][8]
 
         def c3_wgrad(wsw):
@@ -163,12 +177,17 @@ class _GenEngine:
                 return
             ns = ops.conv_wgrad(self.c3.c, dt, self.a2, self.p8, wsw.slab, wsw.wgs_target)
             ops.wgrad_reduce(wsw.slab, ns, 8, self.CH, 64, 9, gof("conv_blocks.9.weight"))
-        wgrad_side(side, ws, 0, c3_wgrad)
+        if need_wgrad:
+            wgrad_side(side, ws, 0, c3_wgrad)
         ops.conv_bwd_data(self.c3.c, dt, self.p8, self.c3.wp_bwd, self.da2, None)
 
         def bn_bwd(z, da, dz, mod, i, M, C, act, name):
-            bn_train_backward(dt, z, da, dz, M, C, mod, self.mean[i], self.invstd[i], act, SLOPE, gof(name + ".weight"), gof(name + ".bias"), ws,
-                              sync, self.sync_scratch.sums[i])
+            if need_wgrad:
+                bn_train_backward(dt, z, da, dz, M, C, mod, self.mean[i], self.invstd[i], act, SLOPE, gof(name + ".weight"), gof(name + ".bias"), ws,
+                                  sync, self.sync_scratch.sums[i])
+            else:
+                bn_train_backward(dt, z, da, dz, M, C, mod, self.mean[i], self.invstd[i], act, SLOPE, pscr[:C], pscr[C:2 * C], ws,
+                                  sync, self.sync_scratch.sums[i], accumulate=False, training=training)
         # conv2 (128 -> 64 on the 2x-upsampled a1)
         bn_bwd(self.z2, self.da2, self.dz2, cb[7], 2, B * S * S, 64, ACT_LRELU, "conv_blocks.7")
 
@@ -177,7 +196,8 @@ class _GenEngine:
             ops.wgrad_reduce(wsw.slab, ns, 128, 128, 64, 16, self.dw4[1], accumulate=False)
             ops.up3_contract(self.dw4[1], gof("conv_blocks.6.weight"), 64, 128)
             ops.bias_grad(dt, self.dz2, B * S * S, 64, wsw.small, gof("conv_blocks.6.bias"))
-        wgrad_side(side, ws, 1, c2_wgrad)
+        if need_wgrad:
+            wgrad_side(side, ws, 1, c2_wgrad)
         ops.conv_fwd(self.c2.c, dt, self.dz2, self.c2.wp_fwd, self.da1, None)      # the input gradient at the low resolution: no sum-pool
         # conv1 (128 -> 128 on the 2x-upsampled a0)
         bn_bwd(self.z1, self.da1, self.dz1, cb[3], 1, B * 4 * s * s, 128, ACT_LRELU, "conv_blocks.3")
@@ -187,7 +207,8 @@ class _GenEngine:
             ops.wgrad_reduce(wsw.slab, ns, 128, 128, 128, 16, self.dw4[0], accumulate=False)
             ops.up3_contract(self.dw4[0], gof("conv_blocks.2.weight"), 128, 128)
             ops.bias_grad(dt, self.dz1, B * 4 * s * s, 128, wsw.small, gof("conv_blocks.2.bias"))
-        wgrad_side(side, ws, 2, c1_wgrad)
+        if need_wgrad:
+            wgrad_side(side, ws, 2, c1_wgrad)
         ops.conv_fwd(self.c1.c, dt, self.dz1, self.c1.wp_fwd, self.da0, None)
         bn_bwd(self.h, self.da0, self.dh, cb[0], 0, B * s * s, 128, ACT_NONE, "conv_blocks.0")
         # l1: dW[f][k] = sum_b dh[b][n'(f)] * x[b][k]
@@ -199,7 +220,10 @@ class _GenEngine:
             ops.fill_f32(self.gb_perm)
             ops.bias_grad(dt, self.dh, B, self.nl1, wsw.small, self.gb_perm)
             ops.gather_add(gof("l1.0.bias"), self.gb_perm, self.nl1, hw, 1, 128)
-        wgrad_side(side, ws, 3, l1_wgrad)
+        if need_wgrad:
+            wgrad_side(side, ws, 3, l1_wgrad)
+        if dinp is not None:
+            self.input_grad.run(self.dh, g.l1[0].weight, dinp)
 
 
 class Generator(_HipModule):
@@ -231,25 +255,31 @@ class Generator(_HipModule):
     def forward(self, noise, labels, code):
         _require_cuda(noise)
         eng = self.fresh_engine(noise.shape[0])
-        if not self.training:       # inference (MNIST/generate_image.py): running-stat BatchNorm, no autograd graph
+        if not self.training and not wants_input_grad(noise, labels, code):
+            # inference (MNIST/generate_image.py): running-stat BatchNorm, no autograd graph
             with torch.no_grad():
                 return eng.forward(noise.float().contiguous(), labels.float().contiguous(), code.float().contiguous(), training=False).clone()
-        return _GenFn.apply(eng, noise.float().contiguous(), labels.float().contiguous(), code.float().contiguous(), *list(self.parameters()))
+        # train mode: input and parameter gradients from one pass (batch statistics couple the samples, the gradient reflects it);
+        # eval mode with an input that requires grad: the same eval forward, input gradients only
+        return _GenFn.apply(eng, self.training, noise.float().contiguous(), labels.float().contiguous(), code.float().contiguous(),
+                            *list(self.parameters()))
 
 
 class _GenFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, eng, noise, labels, code, *params):
-        ctx.eng = eng
-        return eng.forward(noise, labels, code).clone()
+    """autograd bridge of the drop-in generator.  The activations live in the engine: ``backward`` differentiates the engine's LATEST
+    forward, so call it before the module runs again at this batch size."""
 
     @staticmethod
+    def forward(ctx, eng, training, noise, labels, code, *params):
+        ctx.eng, ctx.training = eng, training
+        ctx.widths = (noise.shape[1], labels.shape[1], code.shape[1])
+        return eng.forward(noise, labels, code, training=training).clone()
+
+    @staticmethod
+    @once_differentiable
     def backward(ctx, dimg):
-        eng = ctx.eng
-        scratch = torch.zeros_like(eng.gen.arena.grad)
-        eng.backward(dimg.contiguous(), scratch)
-        grads = [scratch[off:off + k].view(p.shape) for p, (off, k) in zip(eng.gen.parameters(), eng.gen.arena.slices.values())]
-        return (None, None, None, None, *grads)
+        ins, grads = drop_in_backward(ctx.eng, dimg, ctx.needs_input_grad[2:5], ctx.needs_input_grad[5:], ctx.training, ctx.widths)
+        return (None, None, *ins, *grads)
 
 
 # ================================================================================================

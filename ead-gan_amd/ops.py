@@ -121,6 +121,17 @@ def pack_strided2(dtype, w, wp, N, K, Kpad, n_div, s_hi, s_lo, k_div, s_khi, s_k
     lib().call("eg_pack_strided2", dtype, _p(w), _p(wp), N, K, Kpad, n_div, s_hi, s_lo, k_div, s_khi, s_klo, _stream())
 
 
+def linear_dinput_ws_floats(B, NI, NJ, K) -> int:
+    """floats of split scratch ``linear_dinput`` needs for this shape (0: one split, the result is stored directly)"""
+    return lib().query("eg_linear_dinput_ws_floats", B, NI, NJ, K)
+
+
+def linear_dinput(dtype, dH, ldh, w, dX, B, NI, NJ, K, s_i, s_j, s_k, ws=None):
+    """dX[b][k] = sum_ij dH[b][i*NJ + j] * w[i*s_i + j*s_j + k*s_k]: the input gradient of a first layer from its fp32 master ``w``
+    (argument style of ``pack_strided``; ``ws``: fp32 scratch of at least ``linear_dinput_ws_floats`` elements)"""
+    lib().call("eg_linear_dinput", dtype, _p(dH), ldh, _p(w), _p(dX), B, NI, NJ, K, s_i, s_j, s_k, _p(ws), ws.numel() if ws is not None else 0, _stream())
+
+
 # Optional launch recorder (bench.py's roofline pass): when set to a list, every implicit-GEMM launch is bracketed by HIP
 # events on the launch stream and appends (kernel label, algorithmic FLOPs, start event, end event, shape string).
 # Never set on the training path.
@@ -481,6 +492,12 @@ def bn_ws_floats(M, C):
 
 def bn_fwd_eval(dtype, x, y, M, C, gamma, beta, eps, running_mean, running_var, ws, act=ACT_NONE, slope=0.0):
     lib().call("eg_bn_fwd_eval", dtype, _p(x), _p(y), M, C, _p(gamma), _p(beta), float(eps), _p(running_mean), _p(running_var), _p(ws),
+               act, float(slope), _stream())
+
+
+def bn_bwd_eval(dtype, z, da, dz, M, C, gamma, beta, eps, running_mean, running_var, ws, act=ACT_NONE, slope=0.0):
+    """backward of ``bn_fwd_eval`` with respect to its input (elementwise; no parameter gradients)"""
+    lib().call("eg_bn_bwd_eval", dtype, _p(z), _p(da), _p(dz), M, C, _p(gamma), _p(beta), float(eps), _p(running_mean), _p(running_var), _p(ws),
                act, float(slope), _stream())
 
 

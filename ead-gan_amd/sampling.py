@@ -219,6 +219,85 @@ def save_checkpoint(path, generator, discriminator, epoch, batches_done):
                 "epoch": epoch, "batches_done": batches_done}, path)
 
 
+# ------------------------------------------------------------------------------------------------
+# projection: the inputs that reproduce given images
+# ------------------------------------------------------------------------------------------------
+PROJECT_FAMILIES = ("mnist", "celeba", "dsprites", "colored")
+PROJECT_BETAS, PROJECT_EPS = (0.9, 0.999), 1e-8      # torch.optim.Adam's defaults
+
+
+def project_images(kind, generator, target, labels, steps, lr, seed=0, code_range=(-1.0, 1.0), noise=None, code=None):
+    """Find the noise and the affine code with which the eval-mode ``generator`` reproduces ``target`` [B,C,H,W] under the caller's one-hot
+    ``labels`` [B, n_classes] (choosing the class is the encoder's job; the labels are not optimised):
+    ``steps`` Adam steps (learning rate ``lr``, torch's default betas / eps) on  sum_b mean_{C,H,W} (G(noise, labels, code) - target)^2.
+    -> (noise, labels, code, losses [steps + 1, B]): row t of ``losses`` holds the per-sample loss BEFORE step t, the last row the loss
+    of the returned inputs.  ``kind``: a key of ``KINDS`` or its family ('mnist', 'celeba', 'dsprites', 'colored'); the dSprites
+    generators have no noise (None is returned).  Start: noise ~ N(0, 1) from a CPU generator seeded with ``seed``, code = 0; the
+    caller's ``noise`` / ``code`` override them.  After every step the code is clamped to ``code_range`` (None: no clamp).
+    One engine, its panels packed once; every step is the eval forward, the loss and d(img) as torch elementwise ops, the engine's
+    eval backward with ``need_wgrad=False`` (input gradients only) and one ops.adam_step on the flat [noise | code] leaves -- eager
+    launches on the current stream, no host synchronisation inside the loop.  To edit an image: project, move ``code[:, :5]`` (the
+    affine part), generate again."""
+    family = str(kind).split("_")[0]
+    if family not in PROJECT_FAMILIES:
+        raise ValueError(f"project_images: kind {kind!r} (families: {', '.join(PROJECT_FAMILIES)})")
+    if generator.training:
+        raise ValueError("project_images: the generator must be in eval() mode (running-statistics BatchNorm: the samples are independent)")
+    sprite = family in ("dsprites", "colored")
+    target, labels = _dev(target), _dev(labels)
+    dev = target.device
+    B = target.shape[0]
+    nz = 0 if sprite else int(generator.latent_dim)
+    ncode, ncls = int(generator.code_dim), int(generator.n_classes)
+    if tuple(labels.shape) != (B, ncls):
+        raise ValueError(f"project_images: labels must be [{B}, {ncls}] one-hot rows")
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError("project_images: steps must not be negative")
+    # the leaves: one flat fp32 buffer [noise (B*nz) | code (B*ncode)], its two halves viewed as the generator's inputs
+    n = B * (nz + ncode)
+    flat = torch.zeros(n, device=dev, dtype=torch.float32)
+    z, c = flat[:B * nz].view(B, nz), flat[B * nz:].view(B, ncode)
+    if nz:
+        if noise is None:
+            z.copy_(torch.randn(B, nz, generator=torch.Generator().manual_seed(int(seed))))
+        else:
+            z.copy_(noise)
+    if code is not None:
+        c.copy_(code)
+    grad, m, v = torch.empty_like(flat), torch.zeros_like(flat), torch.zeros_like(flat)
+    gz, gc = grad[:B * nz].view(B, nz), grad[B * nz:].view(B, ncode)
+    step = torch.zeros(1, device=dev, dtype=torch.int32)
+    losses = torch.empty(steps + 1, B, device=dev, dtype=torch.float32)
+    eng = generator.fresh_engine(B)
+    if tuple(target.shape) != tuple(eng.img.shape):
+        raise ValueError(f"project_images: target must be {tuple(eng.img.shape)}")
+    dinp = torch.empty(B, eng.cin, device=dev, dtype=torch.float32)
+    diff = torch.empty_like(target)
+    scale = 2.0 / target[0].numel()
+    # column blocks of dinp in the order the engine concatenates its inputs
+    zc, cc = (None, ncls) if sprite else (0, nz + ncls)
+
+    def forward_loss(t):
+        img = eng.forward(labels, c, training=False) if sprite else eng.forward(z, labels, c, training=False)
+        torch.sub(img, target, out=diff)
+        torch.mean((diff * diff).flatten(1), 1, out=losses[t])
+
+    with torch.no_grad():
+        for t in range(steps):
+            forward_loss(t)
+            diff.mul_(scale)                                         # d(sum_b loss_b) / d(img)
+            eng.backward(diff, None, dinp=dinp, need_wgrad=False, training=False)
+            if nz:
+                gz.copy_(dinp[:, zc:zc + nz])
+            gc.copy_(dinp[:, cc:cc + ncode])
+            ops.adam_step(flat, grad, m, v, n, float(lr), PROJECT_BETAS[0], PROJECT_BETAS[1], PROJECT_EPS, step, True)
+            if code_range is not None:
+                c.clamp_(float(code_range[0]), float(code_range[1]))
+        forward_loss(steps)
+    return (z.clone() if nz else None), labels, c.clone(), losses
+
+
 def run_tool(kind, checkpoint, out_dir=".", n=10, batches_done=0, dtype="f32", device="cuda"):
     """generate_image.py / gen_imgs.py as one call: load the checkpoint, eval mode, write the varying_c<i> grids."""
     if kind not in ("mnist_tool", "celeba_tool"):

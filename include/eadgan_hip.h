@@ -204,6 +204,21 @@ int eg_wgrad_reduce_rank1(const float* slab, int nsplit, int n_slab, int n_rows,
 int eg_pack_strided(int dtype, const float* w, void* wp, int N, int K, int Kpad, int n_div, long long s_hi,
                     long long s_lo, long long s_k, eg_stream_t s);
 
+/* Input gradient of a first layer whose output is stored in a permuted order (the layers eg_pack_strided packs: celebA/EAD-GAN_celebA.py:76,
+ * MNIST/EAD-GAN_rpqmnxy.py:77-78, dSprites/rp.py:142):
+ *     dX[b][k] = sum_{i < NI} sum_{j < NJ} dH[b][i*NJ + j] * W[i*s_i + j*s_j + k*s_k]        b < B, k < K
+ * dH: dtype T, row stride ldh elements (16-byte aligned rows); W: the fp32 MASTER, rounded to T in registers (the values the forward's
+ * packed panel holds -- there is no panel of its own to re-pack); dX: fp32 [B][K], exactly K columns; fp32 accumulation (MFMA).  NJ must
+ * be a multiple of 8.  The reduction is split over workgroups in fixed chunks; with more than one split the partial tiles go to ws
+ * (eg_linear_dinput_ws_floats(B, NI, NJ, K) floats, 0 = not needed, ws may be NULL) and are added in split order by a second launch of
+ * the same call: no atomics, every element of dX is stored, nothing needs zeroing, bitwise reproducible.
+ *   CelebA   conv_blocks.0.weight [cin][1024][4][4], dh0 NHWC (n' = t*1024 + co):  NI, NJ = 16, 1024;  s_i, s_j, s_k = 1, 16, 16384
+ *   MNIST    l1.0.weight [8192][cin], dh (n' = hw*128 + c, row f = c*64 + hw):     NI, NJ = 64, 128;   s_i, s_j, s_k = cin, 64*cin, 1
+ *   dSprites fc1.0.weight [128][cin], dz1:                                         NI, NJ = 1, 128;    s_i, s_j, s_k = 0, cin, 1 */
+size_t eg_linear_dinput_ws_floats(int B, int NI, int NJ, int K);
+int eg_linear_dinput(int dtype, const void* dH, long long ldh, const float* W, float* dX, int B, int NI, int NJ, int K, long long s_i,
+                     long long s_j, long long s_k, float* ws, size_t ws_floats, eg_stream_t s);
+
 /* wp[n][k] = w[(n / n_div) * s_hi + (n % n_div) * s_lo + (k / k_div) * s_khi + (k % k_div) * s_klo]  (row AND column permuted) */
 int eg_pack_strided2(int dtype, const float* w, void* wp, int N, int K, int Kpad, int n_div, long long s_hi, long long s_lo,
                      int k_div, long long s_khi, long long s_klo, eg_stream_t s);
@@ -340,6 +355,11 @@ int eg_bn_bwd_from_sums(int dtype, const void* z, const void* da, void* dz, int 
 /* eval mode (module.eval(): generate_image.py:146-154, gen_imgs.py:106-120 of the reference): y = act((x - running_mean) /
  * sqrt(running_var + eps) * gamma + beta); nothing is updated; ws: 2*C floats */
 int eg_bn_fwd_eval(int dtype, const void* x, void* y, int M, int C, const float* gamma, const float* beta, float eps,
+                   const float* running_mean, const float* running_var, float* ws, int act, float slope, eg_stream_t s);
+/* backward of eg_bn_fwd_eval with respect to its input (the statistics are constants, so the layer is elementwise and has no batch
+ * coupling): dz = da * act'(y) * gamma / sqrt(running_var + eps), y recomputed in fp32 from z by the forward's own expression and
+ * coefficients.  act: EG_ACT_NONE, EG_ACT_RELU or EG_ACT_LRELU.  No parameter gradients; ws: 2*C floats */
+int eg_bn_bwd_eval(int dtype, const void* z, const void* da, void* dz, int M, int C, const float* gamma, const float* beta, float eps,
                    const float* running_mean, const float* running_var, float* ws, int act, float slope, eg_stream_t s);
 /* dz from da (gradient w.r.t. the activation output); dgamma / dbeta (+)= their sums; sums: 2*C floats scratch */
 int eg_bn_bwd(int dtype, const void* z, const void* da, void* dz, int M, int C, const float* gamma, const float* beta,
