@@ -128,6 +128,12 @@ struct PackTileParams {
     int t_of[16];          // master tap index of combination q
     int pitch[16];         // row pitch (Kpad) of q's phase
     long long off[16];     // element offset of (c = 0, n = 0) of combination q inside wp_bwd
+    // K padding (only the Adam + pack kernel takes layers that have any): the columns [K, pitch) of every row are written as zeros
+    int pad;               // any panel passed has padding (one test on the kernels' common path, where none has)
+    int kfwd, pitch_fwd;   // columns and row pitch (Kpad) of the forward panel
+    int nph;               // backward (sub-pixel phase) panels
+    int ph_k[4], ph_pitch[4];
+    long long ph_off[4];   // element offset of phase panel i inside wp_bwd
 };
 
 // TTC: taps (k*k) as a compile-time constant (16 for every 4x4 layer; 0 = run time): the index arithmetic below divides by it per element
@@ -177,13 +183,16 @@ __global__ __launch_bounds__(256) void pack_conv_tile_kernel(const PackTileParam
     pack_conv_tile_body<T, TTC, TC>(p, tile, blockIdx.x, blockIdx.y);
 }
 
-// tile-kernel parameters of a layer, or false where only the per-element gather kernels can pack it (ragged channel counts, K padding)
-static bool pack_tile_params(const eg_conv* c, int dtype, void* wp_fwd, void* wp_bwd, PackTileParams& p) {
+// tile-kernel parameters of a layer, or false where only the per-element gather kernels can pack it (ragged channel counts; K padding
+// unless `allow_pad`: the kernel then zero-fills it)
+static bool pack_tile_params(const eg_conv* c, int dtype, void* wp_fwd, void* wp_bwd, PackTileParams& p, bool allow_pad = false) {
     const int T = c->k * c->k, bk = bk_of(dtype);
     bool fast = (c->Cout % 16) == 0 && (c->Cin % 32) == 0 && T <= 16 && (!wp_bwd || c->stride <= 2);
     memset(&p, 0, sizeof(p));
     p.wp_fwd = wp_fwd; p.wp_bwd = wp_bwd; p.Cout = c->Cout; p.Cin = c->Cin; p.T = T;
-    if (fast && wp_fwd && (T * c->Cin) % bk != 0) fast = false;          // K padding: the gather kernel zero-fills
+    p.kfwd = T * c->Cin; p.pitch_fwd = kpad_of(T * c->Cin, dtype);
+    p.pad = wp_fwd && p.kfwd != p.pitch_fwd;
+    if (fast && wp_fwd && (T * c->Cin) % bk != 0 && !allow_pad) fast = false;          // K padding: the gather kernel zero-fills
     if (fast && wp_bwd) {
         long long off = 0;
         for (int ry = 0; ry < c->stride && fast; ++ry)
@@ -191,7 +200,10 @@ static bool pack_tile_params(const eg_conv* c, int dtype, void* wp_fwd, void* wp
                 const BwdAxis ay = bwd_axis(c, ry), ax = bwd_axis(c, rx);
                 const int K = ay.T * ax.T * c->Cout;
                 const int Kpad = kpad_of(K, dtype);
-                if (K != Kpad) { fast = false; break; }
+                if (K != Kpad && !allow_pad) { fast = false; break; }
+                p.ph_k[p.nph] = K; p.ph_pitch[p.nph] = Kpad; p.ph_off[p.nph] = off;
+                if (K != Kpad) p.pad = 1;
+                ++p.nph;
                 for (int ty = 0; ty < ay.T; ++ty)
                     for (int tx = 0; tx < ax.T; ++tx) {
                         const int kh = ay.k0 + ty * c->stride, kw = ax.k0 + tx * c->stride;
@@ -238,7 +250,7 @@ extern "C" int eg_pack_conv(const eg_conv* c, int dtype, const float* w, void* w
 // Adam + re-packing in one pass (torch.optim.Adam.step() on a convolution's weight, celebA/EAD-GAN_celebA.py:344,365,400, followed by
 // the panel refresh every consumer of the weight needs): the pack_conv_tile tiling with the optimizer update applied while the master
 // tile is on its way into LDS -- p, g, m, v are read once, p, m, v written once, both panels written from the tile.
-// Same element update as adam_kernel (adam.h), same panel bytes as eg_pack_conv of the updated master.
+// Same element update as adam_kernel (adam.h), same panel bytes as eg_pack_conv of the updated master, the zeros of the K padding included.
 // ------------------------------------------------------------------------------------------------
 template <typename T, int TTC, bool V4, int TC>
 __global__ __launch_bounds__(256) void adam_pack_conv_tile_kernel(const PackTileParams p, float* __restrict__ w, float* __restrict__ g,
@@ -300,7 +312,7 @@ __global__ __launch_bounds__(256) void adam_pack_conv_tile_kernel(const PackTile
     __syncthreads();
     if (p.wp_fwd) {
         T* dst = reinterpret_cast<T*>(p.wp_fwd);
-        const size_t pitch = (size_t)TT * p.Cin;
+        const size_t pitch = (size_t)p.pitch_fwd;
         for (int it = tid; it < TN * TT * (TC / VEC); it += 256) {
             const int cg = it % (TC / VEC), r = it / (TC / VEC);
             const int t = r % TT, n = r / TT;
@@ -309,6 +321,15 @@ __global__ __launch_bounds__(256) void adam_pack_conv_tile_kernel(const PackTile
 #pragma unroll
             for (int j = 0; j < VEC; ++j) Elt<T>::st(oe + j, tile[(n * TC + cg * VEC + j) * TP + t]);
             *reinterpret_cast<uint4*>(dst + (size_t)(n0 + n) * pitch + (size_t)t * p.Cin + c0 + cg * VEC) = ov;
+        }
+        // K padding of this tile's TN rows (the workgroups of the first Cin tile write it): K = T * Cin and the pitch are multiples of 32
+        // elements, so the 16-byte stores are aligned and cover it exactly
+        if (p.pad && blockIdx.y == 0 && p.kfwd < p.pitch_fwd) {
+            const int nv = (p.pitch_fwd - p.kfwd) / VEC;
+            for (int it = tid; it < TN * nv; it += 256) {
+                const int n = it / nv, j = it - n * nv;
+                *reinterpret_cast<uint4*>(dst + (size_t)(n0 + n) * pitch + p.kfwd + j * VEC) = make_uint4(0u, 0u, 0u, 0u);
+            }
         }
     }
     if (p.wp_bwd) {
@@ -323,13 +344,23 @@ __global__ __launch_bounds__(256) void adam_pack_conv_tile_kernel(const PackTile
             for (int j = 0; j < VEC; ++j) Elt<T>::st(oe + j, tile[((ng * VEC + j) * TC + c) * TP + t]);
             *reinterpret_cast<uint4*>(dst + p.off[q] + (size_t)(c0 + c) * p.pitch[q] + n0 + ng * VEC) = ov;
         }
+        // K padding of this tile's TC rows of every phase panel (the workgroups of the first Cout tile write it): K = taps * Cout is a
+        // multiple of 16 elements and the pitch one of 32
+        if (p.pad && blockIdx.x == 0)
+            for (int ph = 0; ph < p.nph; ++ph) {
+                const int nv = (p.ph_pitch[ph] - p.ph_k[ph]) / VEC;
+                for (int it = tid; it < TC * nv; it += 256) {
+                    const int c = it / nv, j = it - c * nv;
+                    *reinterpret_cast<uint4*>(dst + p.ph_off[ph] + (size_t)(c0 + c) * p.ph_pitch[ph] + p.ph_k[ph] + j * VEC) = make_uint4(0u, 0u, 0u, 0u);
+                }
+            }
     }
 }
 
 extern "C" int eg_adam_pack_conv_ok(const eg_conv* c, int dtype, int has_fwd, int has_bwd) {
     PackTileParams p;
     if (!c || (!has_fwd && !has_bwd) || c->k * c->k > 16) return 0;
-    return pack_tile_params(c, dtype, has_fwd ? (void*)1 : nullptr, has_bwd ? (void*)1 : nullptr, p) ? 1 : 0;
+    return pack_tile_params(c, dtype, has_fwd ? (void*)1 : nullptr, has_bwd ? (void*)1 : nullptr, p, true) ? 1 : 0;
 }
 
 extern "C" int eg_adam_pack_conv(const eg_conv* c, int dtype, float* w, float* g, float* m, float* v, float lr, float b1, float b2, float eps,
@@ -338,7 +369,7 @@ extern "C" int eg_adam_pack_conv(const eg_conv* c, int dtype, float* w, float* g
     EG_REQUIRE(dtype == EG_F32 || dtype == EG_BF16 || dtype == EG_F16, "dtype must be EG_F32, EG_BF16 or EG_F16");
     const int T = c->k * c->k;
     PackTileParams p;
-    EG_REQUIRE(pack_tile_params(c, dtype, wp_fwd, wp_bwd, p), "eg_adam_pack_conv: this layer needs the gather kernels (eg_adam_pack_conv_ok() == 0): run eg_adam_step_zero + eg_pack_conv");
+    EG_REQUIRE(pack_tile_params(c, dtype, wp_fwd, wp_bwd, p, true), "eg_adam_pack_conv: this layer needs the gather kernels (eg_adam_pack_conv_ok() == 0): run eg_adam_step_zero + eg_pack_conv");
     // tile width along Cin: 8 (16-byte panel stores, 8.5 KiB of LDS: fits beside a resident 147-KiB GEMM workgroup, so the update can share
     // CUs with the main chain's convolutions like the LDS-free flat Adam kernel does), not 32 (64-byte stores, 34 KiB)
     constexpr int tc = 8;

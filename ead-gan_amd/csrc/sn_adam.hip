@@ -266,6 +266,7 @@ __global__ void adam_kernel(float* __restrict__ p, float* __restrict__ g, float*
 static void launch_adam(float* p, float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, int* step, int tick,
                         bool zero, hipStream_t st) {
     if (tick) hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, st, step);
+    if (n == 0) return;                                            // an empty slice: the tick alone (a 0-block grid is a launch error)
     size_t head = ((16 - ((uintptr_t)p & 15)) & 15) / 4;
     const bool same = (((uintptr_t)p ^ (uintptr_t)g) & 15) == 0 && (((uintptr_t)p ^ (uintptr_t)m) & 15) == 0 && (((uintptr_t)p ^ (uintptr_t)v) & 15) == 0;
     if (head > n) head = n;
@@ -292,7 +293,6 @@ extern "C" int eg_adam_step(float* p, const float* g, float* m, float* v, size_t
 extern "C" int eg_adam_step_zero(float* p, float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, int* step,
                                  int tick, int zero_grad, eg_stream_t s) {
     EG_REQUIRE(p && g && m && v && step, "eg_adam_step_zero: null pointer");
-    if (n == 0) return 0;
     launch_adam(p, g, m, v, n, lr, b1, b2, eps, step, tick, zero_grad != 0, (hipStream_t)s);
     EG_LAUNCH_CHECK();
     return 0;

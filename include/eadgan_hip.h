@@ -390,6 +390,8 @@ size_t eg_sn_multi_ws_floats(const eg_sn_layer* layers, int nlayers);
 int eg_sn_power_iter_multi(const eg_sn_layer* layers, int nlayers, float* ws, int training, float eps, eg_stream_t s);
 
 /* --- Adam (torch.optim.Adam, celebA/EAD-GAN_celebA.py:211-217) over a flat fp32 arena ----------------------- */
+/* tick: step[0] += 1 before the update (the bias correction reads the counter after the tick).  n == 0 (an empty slice) is valid for
+ * both entry points: with `tick` the counter still advances, no element kernel is launched, the call returns 0. */
 int eg_adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps,
                  int* step, int tick, eg_stream_t s);
 /* the same update on a slice of the arena (one gradient bucket); zero_grad: the gradient slice is cleared in the same pass
@@ -399,7 +401,8 @@ int eg_adam_step_zero(float* p, float* g, float* m, float* v, size_t n, float lr
 /* optimizer.step() on ONE convolution weight (conv view master [Cout][Cin][k][k]) fused with the refresh of its packed panels: the update
  * of eg_adam_step_zero (same bits) applied on the way through the tile transpose of eg_pack_conv (same panel bytes); p / g / m / v are
  * the parameter's slices of the four arenas; `step` is the optimizer's device step counter, already ticked (eg_adam_tick).  Only layers
- * eg_adam_pack_conv_ok() accepts (channel counts in multiples of 16 / 32, no K padding); either panel may be NULL. */
+ * eg_adam_pack_conv_ok() accepts (Cout a multiple of 16, Cin of 32, at most 16 taps, stride <= 2 with a backward panel; where a panel's K
+ * is no multiple of the K block its padding columns are written as zeros, as eg_pack_conv writes them); either panel may be NULL. */
 int eg_adam_pack_conv_ok(const eg_conv* c, int dtype, int has_fwd, int has_bwd);
 int eg_adam_pack_conv(const eg_conv* c, int dtype, float* p, float* g, float* m, float* v, float lr, float b1, float b2, float eps,
                       const int* step, void* wp_fwd, void* wp_bwd, eg_stream_t s);
