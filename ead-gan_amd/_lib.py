@@ -50,6 +50,10 @@ class EgRngSeg(ctypes.Structure):
                 ("elem0", ctypes.c_size_t), ("total", ctypes.c_size_t)]
 
 
+class EgEmaSeg(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("n", ctypes.c_size_t), ("kind", ctypes.c_int)]
+
+
 class EgHead(ctypes.Structure):
     _fields_ = [("x", ctypes.c_void_p), ("wp", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("partials", ctypes.c_void_p), ("nslice", ctypes.c_int),
                 ("y", ctypes.c_void_p), ("dout", ctypes.c_void_p),

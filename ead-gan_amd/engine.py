@@ -612,6 +612,107 @@ class LossLog:
         self.mirror_head, self.mirror_flag = int(head), int(first_nonfinite)
 
 
+def ema_decay(beta, ramp, t):
+    """The decay eg_ema_update applies in its update number ``t`` (0-based), as the float32 the kernel forms: ``beta`` when ``ramp == 0``,
+    else min(beta, (1 + t) / (ramp + t)) -- the same three fp32 operations in the same order (a warm-up: early updates follow the
+    weights closely, from some t on the decay is ``beta`` for good)."""
+    beta, ramp = np.float32(beta), np.float32(ramp)
+    if ramp == 0:
+        return beta
+    tf = np.float32(int(t))
+    return np.minimum(beta, (np.float32(1) + tf) / (ramp + tf))
+
+
+class WeightEMA:
+    """Exponential moving average of the weights of some of a trainer's modules, kept by ONE launch per iteration
+    (``update()``: eg_ema_update over a device-resident segment table built here, once; inside a trainer's captured iteration it is a
+    node of the hipGraph).  Per module the shadow is one flat fp32 tensor the size of ``module.arena.flat`` (one lerp segment, however
+    many parameters; a module without an arena of its own -- Encoder_pxy -- gives one segment per parameter) and one clone per buffer: ``running_mean`` / ``running_var`` are averaged, every other buffer (``num_batches_tracked``,
+    the spectral-norm vectors -- an average of unit vectors is no unit vector) is copied bit for bit.  At construction the shadow equals
+    the modules' current state and no update has been done.  The shadow has no packed panels: it is never an operand of a convolution;
+    ``copy_to`` loads it into a module that is."""
+
+    LERP_BUFFERS = ("running_mean", "running_var")
+
+    def __init__(self, modules, beta=0.999, ramp=0.0):
+        self.beta, self.ramp = float(beta), float(ramp)
+        if not 0.0 <= self.beta < 1.0 or not self.ramp >= 0.0:
+            raise ValueError(f"WeightEMA: need 0 <= beta < 1 and ramp >= 0, got beta = {beta!r}, ramp = {ramp!r}")
+        if not modules:
+            raise ValueError("WeightEMA: no module to track")
+        self.names = tuple(modules)
+        self._flat, self._buffers, self._layout = {}, {}, {}
+        segments = []
+        for name, mod in modules.items():
+            arena = mod.arena                           # None: a module whose parameters were not re-homed by itself (Encoder_pxy)
+            params = dict(mod.named_parameters())
+            if arena is not None:
+                spans = dict(arena.slices)
+                _require_cuda(arena.flat)
+                flat = arena.flat.detach().clone()
+                segments.append((arena.flat, flat, ops.EMA_LERP))
+            else:                                       # one lerp segment per parameter, the shadow flat all the same
+                spans, off = {}, 0
+                for key, p in params.items():
+                    spans[key] = (off, p.numel())
+                    off += p.numel()
+                p0 = next(iter(params.values()))
+                _require_cuda(p0)
+                flat = torch.empty(off, device=p0.device, dtype=torch.float32)
+                for key, p in params.items():
+                    live = p.detach()
+                    if not live.is_contiguous():
+                        raise ValueError(f"WeightEMA: parameter {name}.{key} is not contiguous")
+                    o, k = spans[key]
+                    flat[o:o + k].copy_(live.reshape(-1))
+                    segments.append((live.reshape(-1), flat[o:o + k], ops.EMA_LERP))
+            bufs, layout = {}, []
+            for key, v in mod.state_dict().items():
+                if key in spans:
+                    layout.append((key, spans[key], tuple(v.shape)))
+                    continue
+                live = v.detach()
+                if not live.is_contiguous():
+                    raise ValueError(f"WeightEMA: buffer {name}.{key} is not contiguous")
+                bufs[key] = live.clone()
+                layout.append((key, None, None))
+                segments.append((live, bufs[key], ops.EMA_LERP if key.endswith(self.LERP_BUFFERS) else ops.EMA_COPY))
+            self._flat[name], self._buffers[name], self._layout[name] = flat, bufs, layout
+        self.updates = torch.zeros(2, device=segments[0][0].device, dtype=torch.int32)      # (updates done, arrival counter)
+        self._segments = segments                                                           # the table holds their addresses
+        self.table, self.chunk_first, self.nseg = ops.ema_plan(segments)
+
+    def update(self):
+        ops.ema_update(self.table, self.chunk_first, self.nseg, self.beta, self.ramp, self.updates)
+
+    def state_dict(self, name):
+        """the averaged weights of module ``name`` under the module's own keys in the module's own order (what ``module.state_dict()``
+        gives, so sampling.load_generator / score.load_encoders read a file of it); the values are views of the shadow"""
+        flat, bufs = self._flat[name], self._buffers[name]
+        out = {}
+        for key, span, shape in self._layout[name]:
+            out[key] = bufs[key] if span is None else flat[span[0]:span[0] + span[1]].view(shape)
+        return out
+
+    def copy_to(self, name, module):
+        """load the shadow of ``name`` into ``module`` (same class), in place; its engines' panels are re-packed"""
+        module.load_state_dict(self.state_dict(name))
+        return module
+
+    def state_tensors(self):
+        out = {f"ema.{name}.{k}": v for name in self.names for k, v in self.state_dict(name).items()}
+        out["ema.updates"] = self.updates
+        return out
+
+    def meta(self):
+        return [self.beta, self.ramp, list(self.names)]
+
+    def loaded(self):
+        """after the shadow was written from a saved state: the arrival counter's contract is "left at zero" by every launch; cleared so
+        that a load never depends on that"""
+        self.updates[1:2].zero_()
+
+
 DTYPE_NAMES = {EG_F32: "f32", EG_BF16: "bf16", EG_F16: "f16"}
 STATE_FORMAT = 1
 
@@ -651,6 +752,7 @@ class TrainerState:
     STATE_KIND = None
     inputs = None
     log = None
+    ema = None                                          # a WeightEMA (ResidentStep.attach_ema); None: the state holds no ``ema.*`` key
 
     def _state_extra_tensors(self):
         return {}
@@ -673,6 +775,8 @@ class TrainerState:
             out[f"adam.{name}.m"] = m
             out[f"adam.{name}.v"] = v
         out["adam.steps"] = self.steps
+        if self.ema is not None:
+            out.update(self.ema.state_tensors())
         return out
 
     def _state_spec(self):
@@ -681,6 +785,8 @@ class TrainerState:
             spec.update({"inputs.seed": None, "inputs.step": None, "inputs.sampling": None, "inputs.flip": None})
         if self.log is not None:
             spec.update({"log.head": None, "log.first_nonfinite": None})
+        if self.ema is not None:
+            spec["meta.ema"] = None
         return spec
 
     def _state_dtype(self):
@@ -697,6 +803,8 @@ class TrainerState:
         if self.log is not None:
             sd["log.head"] = int(self.log.head.item())
             sd["log.first_nonfinite"] = int(self.log.first_nonfinite.item())
+        if self.ema is not None:
+            sd["meta.ema"] = self.ema.meta()
         lr = self.lr if isinstance(self.lr, (tuple, list)) else (self.lr,)
         sd.update({"meta.kind": self.STATE_KIND, "meta.dtype": DTYPE_NAMES[self._state_dtype()], "meta.lr": [float(x) for x in lr],
                    "meta.betas": [float(x) for x in self.betas], "meta.format": STATE_FORMAT})
@@ -711,6 +819,20 @@ class TrainerState:
                               ("inputs.flip", int(bool(getattr(self.inputs, "flip", False))))):
                 if sd[key] != have:
                     raise ValueError(f"{key}: {sd[key]!r} in the state, {have!r} in the attached sampler")
+        if self.ema is None:
+            # dropping an average silently would be data loss
+            if "meta.ema" in sd or any(isinstance(k, str) and k.startswith("ema.") for k in sd):
+                raise ValueError("meta.ema: the state carries averaged weights (ema.*), this trainer has none attached: call attach_ema(...) "
+                                 f"with (beta, ramp, modules) = {sd.get('meta.ema')!r} before loading")
+        else:
+            # decay, ramp and the tracked modules are host values baked into a captured iteration, like inputs.seed
+            got, have = sd["meta.ema"], self.ema.meta()
+            try:
+                same = len(got) == 3 and float(got[0]) == have[0] and float(got[1]) == have[1] and list(got[2]) == have[2]
+            except (TypeError, ValueError):             # not [number, number, [names]] at all
+                same = False
+            if not same:
+                raise ValueError(f"meta.ema: {got!r} in the state, {have!r} attached")
         torch.cuda.synchronize()
         with torch.no_grad():
             for k, dst in self._state_tensors().items():
@@ -719,6 +841,8 @@ class TrainerState:
                 self.inputs.step.fill_(int(sd["inputs.step"]))
             if self.log is not None:
                 self.log.load(sd["log.head"], sd["log.first_nonfinite"])
+            if self.ema is not None:
+                self.ema.loaded()
             self._state_zero_scratch()
         if not _skip_repack:
             self._state_repack()
@@ -738,6 +862,24 @@ class ResidentStep(TrainerState):
         self._step_body()
         if self.log is not None:                        # behind the body's joins, on the main stream: the row of THIS iteration
             self.log.append()
+        if self.ema is not None:                        # behind the joins too: every optimizer lane has written this iteration's weights
+            self.ema.update()
+
+    def attach_ema(self, beta=0.999, ramp=0.0, modules=("G",)):
+        """Keep an exponential moving average of the weights of ``modules`` (names of ``_state_modules()``): from now on every iteration
+        ends with one more launch (WeightEMA.update), and the state carries ``ema.*`` / ``meta.ema``.  Before ``capture()`` only: a
+        graph cannot grow a node.  -> the WeightEMA (also ``self.ema``)"""
+        if self.graph is not None:
+            raise RuntimeError("attach_ema: this trainer's iteration is already captured -- attach the average before capture()")
+        have = self._state_modules()
+        names = tuple(modules)
+        for name in names:
+            if name not in have:
+                raise ValueError(f"attach_ema: unknown module {name!r} (this trainer has {', '.join(have)})")
+        if len(set(names)) != len(names):
+            raise ValueError(f"attach_ema: a module is named twice in {names!r}")
+        self.ema = WeightEMA({name: have[name] for name in names}, beta, ramp)
+        return self.ema
 
     def capture(self, warmup=False, inputs=None, log=None):
         """Capture the iteration into one hipGraph; with ``inputs`` (a DeviceSampler of this trainer's module) the graph first draws

@@ -11,7 +11,7 @@ import torch
 
 from ._lib import (ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, EG_BF16, EG_F16, EG_F32, NT_AUTO, NT_BUF128,
                    NT_PERS, NT_REG, NT_S8, NT_S8H, NT_S8P, OUT_NCHW_F32, OUT_NHWC, STAT_BN_BWD, STAT_MOMENTS, STAT_NONE, STAT_SN_BIAS, EgConv, EgEpilogue,
-                   EgHead, EgRngSeg, EgSnLayer, lib)
+                   EgEmaSeg, EgHead, EgRngSeg, EgSnLayer, lib)
 
 __all__ = ["EG_F32", "EG_BF16", "EG_F16", "ACT_NONE", "ACT_LRELU", "ACT_RELU", "ACT_TANH", "ACT_SIGMOID", "OUT_NHWC",
            "OUT_NCHW_F32"]
@@ -729,6 +729,43 @@ def rng_fill_multi(draws, seed, step, rank=0, world=1):
 
 def counter_add(counter, v=1):
     lib().call("eg_counter_add", _p(counter), int(v), _stream())
+
+
+# ---- weight averaging -------------------------------------------------------------------
+EMA_LERP, EMA_COPY = 0, 1
+
+
+def ema_chunk_words() -> int:
+    """32-bit words one workgroup of eg_ema_update moves at a time: the unit eg_ema_plan counts in"""
+    return lib().query("eg_ema_chunk_words")
+
+
+def ema_plan(segments):
+    """segments = [(src, dst, kind)]: contiguous device tensors of equal byte size (a multiple of 4), kind EMA_LERP (fp32) or EMA_COPY.
+    -> (device table, device chunk_first, nseg) for ``ema_update``: validated by eg_ema_plan on the host, then copied to the device
+    once.  The table holds the tensors' addresses: the caller keeps them alive and in place."""
+    n = len(segments)
+    arr = (EgEmaSeg * max(n, 1))()
+    for i, (src, dst, kind) in enumerate(segments):
+        nbytes = src.numel() * src.element_size()
+        if not (src.is_cuda and dst.is_cuda and src.device == dst.device and src.is_contiguous() and dst.is_contiguous()):
+            raise ValueError(f"ema_plan: segment {i}: src and dst must be contiguous tensors on one HIP device")
+        if nbytes != dst.numel() * dst.element_size() or nbytes % 4 or src.dtype != dst.dtype:
+            raise ValueError(f"ema_plan: segment {i}: src and dst must have one dtype and one size, a multiple of 4 bytes")
+        if int(kind) == EMA_LERP and src.dtype != torch.float32:
+            raise ValueError(f"ema_plan: segment {i}: a lerp segment is fp32, got {src.dtype}")
+        arr[i] = EgEmaSeg(_p(src), _p(dst), nbytes // 4, int(kind))
+    first = (ctypes.c_uint * (n + 1))()
+    lib().call("eg_ema_plan", arr, n, first)
+    dev = segments[0][0].device
+    table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+    chunk_first = torch.frombuffer(bytearray(bytes(first)), dtype=torch.int32).to(dev)
+    return table, chunk_first, n
+
+
+def ema_update(table, chunk_first, nseg, beta, ramp, updates):
+    """one launch over the whole table (eg_ema_update in the header); ``updates``: device int32[2] = (updates done, arrival counter)"""
+    lib().call("eg_ema_update", _p(table), _p(chunk_first), int(nseg), float(beta), float(ramp), _p(updates), _stream())
 
 
 def gather_u8_images(data, idx, flip, out, B, C, H, W, scale, shift, tick=None):

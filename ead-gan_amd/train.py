@@ -93,6 +93,39 @@ def checkpoint_files(kind, batches_done):
     return [n % batches_done for n in _FILES[kind]]
 
 
+# the file stem each script gives a module's checkpoint; the averaged copy of a module carries ``_ema`` before the number.  CelebA's script
+# writes one .tar dictionary: its averaged generator is a bare state dict, what sampling.load_generator also reads
+_EMA_STEMS = {"celeba": {"G": "generator", "D": "discriminator"}, "mnist": {"G": "generator", "E": "encoder", "D": "discriminator"},
+              "dsprites": {"E": "encoder", "G": "generator", "D": "discriminator", "P": "encoder_pxy"},
+              "colored": {"E": "encoder", "G": "generator", "D": "discriminator", "P": "encoder_pxy_color"},
+              "pxy": {"P": "encoder_pxy"}, "pxy_color": {"P": "encoder_pxy_color"}}
+
+
+def ema_checkpoint_files(kind, batches_done, names):
+    """names of the files a checkpoint iteration adds for the averaged weights of the tracked modules ``names``, in their
+    order: the script's own name of that module's file with ``_ema`` before the number (``generator_ema_%d.pt``, ``encoder_ema_%d.pt``,
+    ``encoder_pxy_ema_%d.pt``, ...), each a bare state dict"""
+    _plan(kind)
+    stems = _EMA_STEMS[kind]
+    for n in names:
+        if n not in stems:
+            raise ValueError(f"ema_checkpoint_files: a {kind!r} trainer has no module {n!r} (it has {', '.join(stems)})")
+    return [f"{stems[n]}_ema_{int(batches_done)}.pt" for n in names]
+
+
+def _module_like(module):
+    """a fresh module of ``module``'s class and dimensions, on the CPU: the drop-in classes keep every constructor argument as an attribute
+    of the same name (``dtype`` as ``compute_dtype``)"""
+    import inspect
+    kw = {}
+    for name in inspect.signature(type(module).__init__).parameters:
+        if name == "dtype":
+            kw[name] = module.compute_dtype
+        elif name != "self":
+            kw[name] = getattr(module, name)
+    return type(module)(**kw)
+
+
 def sample_seed(seed, batches_done):
     """seed of the sample grids' numpy draws: a function of (run seed, iteration), so a resumed run writes the same PNG bytes"""
     return (int(seed) * 1000003 + int(batches_done) * 7919 + 12345) % (2 ** 32)
@@ -107,12 +140,18 @@ class TrainRun:
     trade for the small-network steps, where the log's launches are measurable; the dSprites lines then print 0 for the two
     separate info terms, which only a trainer with a log computes.
 
+    A trainer with averaged weights (``trainer.attach_ema(...)`` before the run): checkpoint iterations also write one bare
+    state dict per tracked module (``ema_checkpoint_files``), after the script's own files.  ``ema_samples=True``: sample iterations
+    also write the same grids from the averaged generator into ``out_dir/ema/`` -- a scratch generator, built once and filled by
+    ``WeightEMA.copy_to``, in the live generator's mode on the same seeded inputs; nothing of it is state.
+
     Data parallel (``inputs.world`` > 1, the world of the trainer's ``allreduce`` / ``sync_bn``): ``graph=False`` is required; the
     iteration count, cadence, sample seeds and file names are those of one process at the global batch ``B * world``; rank 0 prints and
     writes every file, the other ranks write none (``files == []``) and print nothing but execute every ``_wait`` and keep ``history``
     / ``lines`` of their own shard.  The run adds no collective: rank 0's lines and ``losses.npy`` carry rank 0's shard losses."""
 
-    def __init__(self, kind, trainer, inputs, out_dir, n_epochs, sample_interval=None, seed=0, graph=True, log_capacity=1024, log_in_graph=True):
+    def __init__(self, kind, trainer, inputs, out_dir, n_epochs, sample_interval=None, seed=0, graph=True, log_capacity=1024, log_in_graph=True,
+                 ema_samples=False):
         self.plan = _plan(kind)
         if getattr(trainer, "STATE_KIND", None) != kind:
             raise ValueError(f"a {kind!r} run needs a {kind!r} trainer, got {type(trainer).__name__}")
@@ -147,6 +186,15 @@ class TrainRun:
         if self.rank == 0:
             os.makedirs(self.out_dir, exist_ok=True)
         trainer.inputs, trainer.log = inputs, (self.log if self.log_in_graph else None)
+        self.ema_samples, self._ema_G = bool(ema_samples), None
+        if self.ema_samples:
+            if self.plan["grid"] is None:
+                raise ValueError(f"ema_samples: the {kind!r} script has no sample_image, there is no grid to write")
+            ema = getattr(trainer, "ema", None)
+            if ema is None or "G" not in ema.names:
+                raise ValueError("ema_samples: the trainer keeps no average of its generator -- call trainer.attach_ema(modules=('G', ...)) first")
+            if self.rank == 0:
+                self._ema_G = _module_like(trainer.G).to(trainer.losses.device)
         if self.plan["minmax"]:
             dev = trainer.losses.device
             self._mm_dev = torch.zeros(4, device=dev, dtype=torch.float32)
@@ -207,6 +255,13 @@ class TrainRun:
         rng = np.random.RandomState(sample_seed(self.seed, it))
         self.files += sampling.sample_image(self.plan["grid"], tr.G, n=10, batches_done=it, real=real[:100], trans=trans[:100],
                                             out_dir=self.out_dir, rng=rng, device=tr.losses.device, write=self.rank == 0)
+        if self._ema_G is not None:
+            # the same grids from the averaged weights: the scratch generator's own BatchNorm statistics move in train mode and are
+            # overwritten by the next copy_to -- the trainer's state is not touched
+            G = tr.ema.copy_to("G", self._ema_G).train(tr.G.training)
+            rng = np.random.RandomState(sample_seed(self.seed, it))
+            self.files += sampling.sample_image(self.plan["grid"], G, n=10, batches_done=it, real=real[:100], trans=trans[:100],
+                                                out_dir=os.path.join(self.out_dir, "ema"), rng=rng, device=tr.losses.device)
 
     def _checkpoint(self, it):
         if self.rank != 0:
@@ -224,6 +279,11 @@ class TrainRun:
         else:
             torch.save(tr.P.state_dict(), names[0])
         self.files += names
+        ema = getattr(tr, "ema", None)
+        if ema is not None:
+            for name, fn in zip(ema.names, ema_checkpoint_files(self.kind, it, ema.names)):
+                torch.save({k: v.detach().to("cpu", copy=True) for k, v in ema.state_dict(name).items()}, os.path.join(od, fn))
+                self.files.append(os.path.join(od, fn))
 
     def _prepare(self):
         tr = self.trainer

@@ -699,6 +699,31 @@ int eg_score_lasso_gram_fit(const double* G, int k, int nf, double alpha, int ma
  * NaN or +-Inf and first_nonfinite[0] == 0, first_nonfinite[0] <- the 1-based iteration (sticky).  1 <= n <= 64.  No allocation, no sync. */
 int eg_runlog_append(const float* losses, int n, float* ring, int capacity, int* head, int* first_nonfinite, eg_stream_t s);
 
+/* --- exponential moving average of a trainer's weights (not in the reference, whose scripts sample from the live weights):
+ * ONE launch over a segment table that lives on the device, so the launch can be captured and a replay reads no host memory.
+ * A segment is n 32-bit words.  kind 0 (lerp, fp32): dst = fmaf(1 - b_t, src - dst, dst); kind 1 (copy): dst = src, bit for bit (integer
+ * counters -- an int64 is two words -- and unit vectors, whose average is no unit vector).  b_t = beta when ramp == 0, else
+ * min(beta, (1 + t) / (ramp + t)) in fp32 in this order of operations, t = updates[0] = the number of updates done so far: every
+ * workgroup of a launch uses the same t, and the launch leaves updates[0] = t + 1.  updates[1] counts the arriving workgroups and is zero
+ * between launches (the caller zeroes it once).  src is never written and nothing outside [dst, dst + n) is; the result is elementwise
+ * (no float atomics): two launches from the same state give the same bits.  16-byte accesses where src and dst of a chunk are both
+ * 16-byte aligned, word accesses otherwise.
+ * eg_ema_plan (host only, touches no device): validates a table -- 1 <= nseg <= EG_EMA_MAX_SEGS, src / dst non-null, distinct and 4-byte
+ * aligned, n > 0, kind 0 or 1, at most 2^31 chunks -- and fills chunk_first[nseg + 1], the exclusive prefix of ceil(n / chunk) with
+ * chunk = eg_ema_chunk_words() words.  eg_ema_update takes DEVICE copies of the validated table and of chunk_first; 0 <= beta < 1,
+ * ramp >= 0.  No allocation, no sync. */
+#define EG_EMA_MAX_SEGS 256
+typedef struct eg_ema_seg {
+    const void* src;
+    void* dst;
+    size_t n;                       /* 32-bit words */
+    int kind;
+} eg_ema_seg;
+int eg_ema_chunk_words(void);
+int eg_ema_plan(const eg_ema_seg* segs_host, int nseg, unsigned int* chunk_first_host);
+int eg_ema_update(const eg_ema_seg* segs_dev, const unsigned int* chunk_first_dev, int nseg, float beta, float ramp, int* updates,
+                  eg_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
