@@ -6,6 +6,6 @@ hyphen, so import it with ``importlib.import_module("ead-gan_amd")`` or through 
 ``eadgan`` (``import eadgan``).
 """
 from . import _lib, engine, ops            # noqa: F401
-from . import affine, celeba, colored, dp, dsprites, mnist, sampling, score, train, trunk     # noqa: F401
+from . import affine, celeba, colored, dp, dsprites, mnist, quality, sampling, score, train, trunk     # noqa: F401
 
-__all__ = ["ops", "engine", "affine", "celeba", "mnist", "dsprites", "colored", "trunk", "dp", "score", "sampling", "train"]
+__all__ = ["ops", "engine", "affine", "celeba", "mnist", "dsprites", "colored", "trunk", "dp", "score", "sampling", "quality", "train"]

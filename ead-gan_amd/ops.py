@@ -937,3 +937,65 @@ def score_lasso_gram_fit(G, k, nf, alpha, max_sweeps, tol, W, info):
 def runlog_append(losses, n, ring, capacity, head, first_nonfinite):
     """row head % capacity of ring[capacity][n] <- losses[:n]; head += 1; the first non-finite iteration (1-based) latched"""
     lib().call("eg_runlog_append", _p(losses), int(n), _p(ring), int(capacity), _p(head), _p(first_nonfinite), _stream())
+
+
+# ---- sliced Wasserstein distance (DESIGN 6m) ---------------------------------------------------------
+SWD_FLAG_ZERO_STD, SWD_FLAG_NONFINITE, SWD_FLAG_POSITION = 1, 2, 4
+
+
+def pyr_down(fine, coarse, planes, H):
+    """coarse [planes, H/2, H/2] <- the 5 x 5 binomial filter of fine [planes, H, H] at the even positions (mirror border)"""
+    lib().call("eg_pyr_down", _p(fine), _p(coarse), planes, H, _stream())
+
+
+def pyr_up_sub(fine, coarse, planes, H):
+    """fine [planes, H, H] -= up(coarse [planes, H/2, H/2]), in place"""
+    lib().call("eg_pyr_up_sub", _p(fine), _p(coarse), planes, H, _stream())
+
+
+def swd_patch_stats_ws_doubles(C) -> int:
+    return lib().query("eg_swd_patch_stats_ws_doubles", C)
+
+
+def swd_patch_stats(img, pos, n_desc, P, C, H, ws, stats, flag):
+    """stats [C, 2] float64 <- (mean, population std) of the gathered patch pixels per channel; flag (int32, zeroed by the caller) |= SWD_FLAG_*"""
+    lib().call("eg_swd_patch_stats", _p(img), _p(pos), n_desc, P, C, H, _p(ws), _p(stats), _p(flag), _stream())
+
+
+def swd_unit_columns(dirs, K, D):
+    lib().call("eg_swd_unit_columns", _p(dirs), K, D, _stream())
+
+
+def swd_project_ws_floats(C) -> int:
+    return lib().query("eg_swd_project_ws_floats", C)
+
+
+def swd_project(img, pos, n_desc, P, C, H, dirs, D, stats, ws, out, ld):
+    """out [D, ld] <- projections of the normalised 7 x 7 x C descriptors on the columns of dirs [49 C, D], one direction per row"""
+    lib().call("eg_swd_project", _p(img), _p(pos), n_desc, P, C, H, _p(dirs), D, _p(stats), _p(ws), _p(out), ld, _stream())
+
+
+def sort_tile_elems() -> int:
+    """elements of a column that eg_sort_columns_f32 sorts inside LDS: columns longer than this take global merge passes"""
+    return lib().query("eg_sort_tile_elems")
+
+
+def sort_columns(x, n=None):
+    """x [cols, ld] fp32 (rows contiguous): the first ``n`` (default: all) elements of every row sorted ascending, in place"""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1):
+        raise ValueError("sort_columns: x must be a 2-D fp32 device tensor with contiguous rows")
+    cols, ld = x.shape[0], x.stride(0) if x.shape[0] > 1 else x.shape[1]
+    n = x.shape[1] if n is None else int(n)
+    if not 1 <= n <= x.shape[1]:
+        raise ValueError(f"sort_columns: n must be in 1..{x.shape[1]}")
+    lib().call("eg_sort_columns_f32", _p(x), n, cols, ld, _stream())
+    return x
+
+
+def l1_mean_ws_doubles() -> int:
+    return lib().query("eg_l1_mean_ws_doubles")
+
+
+def l1_mean(a, b, n, cols, ld, ws, out):
+    """out[0] (float64) <- mean |a - b| over the first n elements of the cols rows (row stride ld) of two fp32 arrays"""
+    lib().call("eg_l1_mean_f32", _p(a), _p(b), n, cols, ld, _p(ws), _p(out), _stream())

@@ -1,0 +1,235 @@
+"""Image quality of a generator as a number: the sliced Wasserstein distance of Karras et al., "Progressive Growing of GANs"
+(2018), between real and generated images -- the distribution of local 7 x 7 patches of a Laplacian pyramid, compared at every scale from
+full resolution down to 16 px.  It needs no pretrained network (FID and its relatives need Inception weights) and is deterministic once
+the random draws are fixed.  Not in the reference, whose scripts only write sample grids.
+
+* ``laplacian_pyramid(images)``                  the levels H, H/2 ... 16 (ops.pyr_down / ops.pyr_up_sub)
+* ``swd(real, fake, ...)``                       per-level distances and their mean, times 1e3 as the paper reports them
+* ``draw_plan(seed, shape, ...)``                the patch centres and unit directions ``swd`` draws for that seed
+* ``generate`` / ``real_images``                 the two image sets of an MNIST or CelebA run
+* ``swd_generator(kind, generator, inputs)``     the three together
+* ``SWDPlan``                                    what ``train.TrainRun(..., swd=...)`` scores on checkpoint iterations
+
+Per level and set: patch statistics (ops.swd_patch_stats), then per repeat one fused gather-and-project launch (ops.swd_project: the
+descriptors, 0.6 GB per set and level at full size, never exist), one column sort per set (ops.sort_columns) and one reduction
+(ops.l1_mean).  Everything is enqueued on the current stream; ``swd`` reads the device once, at its end.  There is no CPU path.
+"""
+from __future__ import annotations
+
+from typing import NamedTuple
+
+import torch
+
+from . import ops
+
+PATCH, MIN_SIDE = 7, 16
+# Philox stream ids of this module's draws (ops.rng_fill): a block no sampler uses (the samplers' ids are 1 .. 8).  The device counter of
+# a draw holds the level (centres), level * repeats + repeat (directions) or the batch index (generator inputs).
+SID_POSITIONS, SID_DIRECTIONS, SID_NOISE, SID_LABELS, SID_CODE = 0x5D00, 0x5D01, 0x5D10, 0x5D11, 0x5D12
+# how the trainers see a dataset image: eg_gather_u8_images' scale and shift (celebA/EAD-GAN_celebA.py:194-201, MNIST/EAD-GAN_rpqmnxy.py:235-243)
+_REAL_SCALE = {"mnist": (2.0 / 255.0, -1.0), "celeba": (2.0 / 255.0, -1.0)}
+_SPRITES = ("dsprites", "colored", "pxy")
+
+
+class SWDPlan(NamedTuple):
+    """what a training run scores on its checkpoint iterations: ``n_images`` generated against the first ``n_images`` dataset images"""
+    n_images: int
+    seed: int = 0
+    patches_per_image: int = 128
+    repeats: int = 4
+    dirs: int = 128
+
+
+def level_sides(H):
+    """sides of the pyramid levels of an H x H image, finest first: H, H/2 ... 16"""
+    H = int(H)
+    if H < MIN_SIDE or H & (H - 1):
+        raise ValueError(f"swd: the image side must be a power of two >= {MIN_SIDE}, got {H}")
+    sides = []
+    while H >= MIN_SIDE:
+        sides.append(H)
+        H //= 2
+    return sides
+
+
+def _images(t, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise RuntimeError(f"quality: {name} must be a tensor on the GPU (there is no CPU fallback)")
+    if t.dim() != 4 or t.shape[1] not in (1, 3) or t.shape[2] != t.shape[3]:
+        raise ValueError(f"quality: {name} must be [N, C, H, H] with C = 1 or 3, got {tuple(t.shape)}")
+    level_sides(t.shape[2])
+    return t.detach().float().contiguous()
+
+
+def laplacian_pyramid(images):
+    """[N, C, H, H] on the device -> the Laplacian levels H, H/2 ... 16 as new fp32 tensors, finest first; the coarsest stays Gaussian"""
+    x = _images(images, "images")
+    N, C, H, _ = x.shape
+    pyr = [x.clone()]
+    for side in level_sides(H)[1:]:
+        coarse = torch.empty(N, C, side, side, device=x.device, dtype=torch.float32)
+        ops.pyr_down(pyr[-1], coarse, N * C, 2 * side)
+        ops.pyr_up_sub(pyr[-1], coarse, N * C, 2 * side)
+        pyr.append(coarse)
+    return pyr
+
+
+def draw_plan(seed, shape, patches_per_image=128, repeats=4, dirs=128, device="cuda"):
+    """-> (positions, directions) exactly as ``swd(..., seed=seed)`` draws them for image sets of ``shape`` = (N, C, H, H):
+    positions[l]: int32 [N * P, 2] = (y, x) patch centres of level l, uniform in [3, H_l - 3); directions[l][r]: fp32 [49 C, dirs] with
+    unit columns.  Feed them back through ``swd(positions=..., directions=...)`` or to any other implementation."""
+    N, C, H, W = (int(v) for v in shape)
+    P, R, D = int(patches_per_image), int(repeats), int(dirs)
+    if C not in (1, 3) or H != W or N < 1 or P < 1 or R < 1 or not 1 <= D <= 128:
+        raise ValueError("draw_plan: shape (N, C, H, H) with C = 1 or 3; patches_per_image, repeats >= 1; 1 <= dirs <= 128")
+    dev = torch.device(device)
+    step = torch.zeros(1, device=dev, dtype=torch.int32)
+    positions, directions = [], []
+    for l, side in enumerate(level_sides(H)):
+        draw = torch.empty(N * P, 2, device=dev, dtype=torch.int64)
+        step.fill_(l)
+        ops.rng_fill(ops.RNG_RANDINT, draw, 3, side - 3, seed, step, SID_POSITIONS)
+        positions.append(draw.to(torch.int32))
+        level = []
+        for r in range(R):
+            W_ = torch.empty(PATCH * PATCH * C, D, device=dev, dtype=torch.float32)
+            step.fill_(l * R + r)
+            ops.rng_fill(ops.RNG_NORMAL, W_, 0.0, 1.0, seed, step, SID_DIRECTIONS)
+            ops.swd_unit_columns(W_, W_.shape[0], D)
+            level.append(W_)
+        directions.append(level)
+    return positions, directions
+
+
+def _check_plan(positions, directions, N, C, sides, dev):
+    if len(positions) != len(sides) or len(directions) != len(sides):
+        raise ValueError(f"swd: positions and directions need one entry per level {sides}")
+    n_desc = int(positions[0].shape[0])
+    if n_desc < N or n_desc % N:
+        raise ValueError(f"swd: positions[l] must be [N * P, 2]: {n_desc} rows for N = {N} images")
+    R, D = len(directions[0]), int(directions[0][0].shape[1])
+    for pos, level in zip(positions, directions):
+        if not (pos.is_cuda and pos.dtype == torch.int32 and tuple(pos.shape) == (n_desc, 2) and pos.is_contiguous()):
+            raise ValueError("swd: every positions[l] must be a contiguous int32 device tensor [N * P, 2]")
+        if len(level) != R or R < 1:
+            raise ValueError("swd: every level needs the same number (>= 1) of direction matrices")
+        for W in level:
+            if not (W.is_cuda and W.dtype == torch.float32 and tuple(W.shape) == (PATCH * PATCH * C, D) and W.is_contiguous() and 1 <= D <= 128):
+                raise ValueError(f"swd: every direction matrix must be a contiguous fp32 device tensor [{PATCH * PATCH * C}, D <= 128]")
+    return n_desc, n_desc // N, R, D
+
+
+_FLAG_TEXT = ((ops.SWD_FLAG_ZERO_STD, "a channel without variance"), (ops.SWD_FLAG_NONFINITE, "a NaN or an infinity among the patch pixels"),
+              (ops.SWD_FLAG_POSITION, "a patch centre outside [3, H - 3)"))
+
+
+def swd(real, fake, patches_per_image=128, repeats=4, dirs=128, seed=0, positions=None, directions=None):
+    """Sliced Wasserstein distance between two image sets [N, C, H, H] (C = 1 or 3, H a power of two >= 16) on the device
+    -> {"levels": {H: v, H/2: v, ... 16: v}, "mean": v}, Python floats times 1e3.  ``positions`` / ``directions``: explicit draws in
+    ``draw_plan``'s form (both or neither; the counts then come from their shapes); otherwise drawn from ``seed``.  The same positions
+    serve both sets; each set is normalised per level and channel by its own statistics, so the result does not change under a
+    per-channel rescale a x + b (a > 0) of either set.  A channel with zero variance at some level (or a non-finite pixel) raises
+    ValueError.  One host read, at the end."""
+    A, B = _images(real, "real"), _images(fake, "fake")
+    if A.shape != B.shape or A.device != B.device:
+        raise ValueError(f"swd: the two sets must have one shape on one device, got {tuple(A.shape)} and {tuple(B.shape)}")
+    N, C, H, _ = A.shape
+    sides = level_sides(H)
+    dev = A.device
+    if (positions is None) != (directions is None):
+        raise ValueError("swd: pass positions and directions together (draw_plan returns both)")
+    if positions is None:
+        positions, directions = draw_plan(seed, A.shape, patches_per_image, repeats, dirs, dev)
+    n_desc, P, R, D = _check_plan(positions, directions, N, C, sides, dev)
+    ld = ops.round_up(n_desc, 4)
+    proj = torch.empty(2, D, ld, device=dev, dtype=torch.float32)
+    stats = torch.empty(2, C, 2, device=dev, dtype=torch.float64)
+    stats_ws = torch.empty(ops.swd_patch_stats_ws_doubles(C), device=dev, dtype=torch.float64)
+    proj_ws = torch.empty(ops.swd_project_ws_floats(C), device=dev, dtype=torch.float32)
+    l1_ws = torch.empty(ops.l1_mean_ws_doubles(), device=dev, dtype=torch.float64)
+    flags = torch.zeros(2, len(sides), device=dev, dtype=torch.int32)
+    dist = torch.zeros(len(sides), R, device=dev, dtype=torch.float64)
+    pyrs = (laplacian_pyramid(A), laplacian_pyramid(B))
+    for l, side in enumerate(sides):
+        for s in range(2):
+            ops.swd_patch_stats(pyrs[s][l], positions[l], n_desc, P, C, side, stats_ws, stats[s], flags[s, l:l + 1])
+        for r in range(R):
+            for s in range(2):
+                ops.swd_project(pyrs[s][l], positions[l], n_desc, P, C, side, directions[l][r], D, stats[s], proj_ws, proj[s], ld)
+                ops.sort_columns(proj[s], n_desc)
+            ops.l1_mean(proj[0], proj[1], n_desc, D, ld, l1_ws, dist[l, r:r + 1])
+    host = torch.cat((dist.reshape(-1), flags.reshape(-1).double())).cpu()          # THE host read
+    got, bad = host[:len(sides) * R].reshape(len(sides), R), host[len(sides) * R:].to(torch.int64).reshape(2, len(sides))
+    for s, name in enumerate(("real", "fake")):
+        for l, side in enumerate(sides):
+            why = [text for bit, text in _FLAG_TEXT if int(bad[s, l]) & bit]
+            if why:
+                raise ValueError(f"swd: the {name} set at level {side}: {'; '.join(why)}")
+    levels = {side: 1e3 * float(got[l].mean()) for l, side in enumerate(sides)}
+    return {"levels": levels, "mean": sum(levels.values()) / len(levels)}
+
+
+def _family(kind, what):
+    family = str(kind).split("_")[0]
+    if family in _SPRITES:
+        raise ValueError(f"quality.{what}: the sprite workloads ({kind!r}) are not scored this way -- their `real' distribution is the aligned "
+                         "and warped image and they have disentanglement scores (score.py); quality.swd itself accepts their 64 px images")
+    if family not in _REAL_SCALE:
+        raise ValueError(f"quality.{what}: kind must be of the 'mnist' or 'celeba' family, got {kind!r}")
+    return family
+
+
+def generate(kind, generator, n_images, batch, seed=0):
+    """``n_images`` outputs [n_images, C, H, H] of a generator of the 'mnist' or 'celeba' family in its current mode, in batches of ``batch``:
+    z ~ N(0, 1), uniform class labels and code ~ U(-1, 1) as the training scripts draw them, on the device, keyed by ``seed``.
+    ``n_images % batch != 0`` raises: in train mode BatchNorm makes the composition of a batch part of the result.  The generator's
+    state is left as it was (train-mode BatchNorm moves the running statistics; they are put back)."""
+    _family(kind, "generate")
+    n_images, batch = int(n_images), int(batch)
+    if batch < 1 or n_images < 1 or n_images % batch:
+        raise ValueError(f"quality.generate: n_images = {n_images} is no positive multiple of batch = {batch}")
+    dev = next(generator.parameters()).device
+    if dev.type != "cuda":
+        raise RuntimeError("quality.generate: the generator must be on the GPU (there is no CPU fallback)")
+    ncls = int(generator.n_classes)
+    z = torch.empty(batch, int(generator.latent_dim), device=dev, dtype=torch.float32)
+    code = torch.empty(batch, int(generator.code_dim), device=dev, dtype=torch.float32)
+    lab = torch.empty(batch, device=dev, dtype=torch.int64)
+    onehot = torch.empty(batch, ncls, device=dev, dtype=torch.float32)
+    out = torch.empty(n_images, int(generator.channels), int(generator.img_size), int(generator.img_size), device=dev, dtype=torch.float32)
+    step = torch.zeros(1, device=dev, dtype=torch.int32)
+    keep = {name: b.detach().clone() for name, b in generator.named_buffers()}
+    with torch.no_grad():
+        for i in range(n_images // batch):
+            step.fill_(i)
+            ops.rng_fill_multi([(ops.RNG_NORMAL, z, 0.0, 1.0, SID_NOISE), (ops.RNG_RANDINT, lab, 0, ncls, SID_LABELS, onehot),
+                                (ops.RNG_UNIFORM, code, -1.0, 1.0, SID_CODE)], seed, step)
+            out[i * batch:(i + 1) * batch].copy_(generator(z, onehot, code))
+        for name, b in generator.named_buffers():
+            b.copy_(keep[name])
+    return out
+
+
+def real_images(kind, inputs, n_images):
+    """the first ``n_images`` dataset images as the trainer sees them (scaled to [-1, 1], no flip): ``inputs`` is the run's sampler or its
+    uint8 device dataset [N, C, H, H]"""
+    scale, shift = _REAL_SCALE[_family(kind, "real_images")]
+    data = getattr(inputs, "data", inputs)
+    if not (isinstance(data, torch.Tensor) and data.is_cuda and data.dtype == torch.uint8 and data.dim() == 4):
+        raise ValueError("quality.real_images: inputs must be a sampler or a uint8 device dataset [N, C, H, W]")
+    n = int(n_images)
+    if not 1 <= n <= data.shape[0]:
+        raise ValueError(f"quality.real_images: n_images = {n}, the dataset has {data.shape[0]} images")
+    _, C, H, W = data.shape
+    idx = torch.arange(n, device=data.device, dtype=torch.int64)
+    out = torch.empty(n, C, H, W, device=data.device, dtype=torch.float32)
+    ops.gather_u8_images(data.contiguous(), idx, None, out, n, C, H, W, scale, shift)
+    return out
+
+
+def swd_generator(kind, generator, inputs, n_images=8192, batch=None, seed=0, **swd_kw):
+    """SWD of ``generate(kind, generator, n_images, batch, seed)`` against ``real_images(kind, inputs, n_images)``; ``batch`` defaults to
+    64 (the scripts' batch size) or ``n_images`` if that is smaller; ``swd_kw``: patches_per_image, repeats, dirs"""
+    batch = min(64, int(n_images)) if batch is None else int(batch)
+    fake = generate(kind, generator, n_images, batch, seed)
+    return swd(real_images(kind, inputs, n_images), fake, seed=seed, **swd_kw)

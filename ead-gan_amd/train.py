@@ -7,12 +7,13 @@ Data parallel: one TrainRun per rank around a trainer with ``allreduce`` / ``syn
 launches only, rank 0 alone prints and writes, and the run adds no collective of its own."""
 from __future__ import annotations
 
+import json
 import os
 
 import numpy as np
 import torch
 
-from . import ops, sampling
+from . import ops, quality, sampling
 from .engine import LossLog
 
 # One row per script.  print: the progress line's cadence; fmt: its format string, character for character; cols: which entries of the
@@ -131,6 +132,12 @@ def sample_seed(seed, batches_done):
     return (int(seed) * 1000003 + int(batches_done) * 7919 + 12345) % (2 ** 32)
 
 
+def swd_seed(seed, batches_done, plan_seed=0):
+    """seed of a checkpoint iteration's SWD draws: a function of (run seed, iteration, the plan's own seed) like ``sample_seed``, so a
+    resumed run writes the same line"""
+    return (int(seed) * 1000003 + int(batches_done) * 6151 + int(plan_seed) * 104729 + 54321) % (2 ** 32)
+
+
 class TrainRun:
     """``run(max_iters=None)`` continues from ``batches_done`` until ``n_epochs`` epochs of ``ceil(N / B)`` iterations are done or
     ``max_iters`` more iterations ran; ``save()`` writes ``run_state_<batches_done>.pt``; ``TrainRun.resume(path, ...)`` continues such a
@@ -145,13 +152,20 @@ class TrainRun:
     also write the same grids from the averaged generator into ``out_dir/ema/`` -- a scratch generator, built once and filled by
     ``WeightEMA.copy_to``, in the live generator's mode on the same seeded inputs; nothing of it is state.
 
+    ``swd=quality.SWDPlan(n_images, ...)`` ('mnist' and 'celeba' runs): on checkpoint iterations, after the checkpoint files,
+    rank 0 scores a scratch copy of the live generator -- and, if the trainer averages ``G``, one filled by ``WeightEMA.copy_to`` --
+    in the live generator's mode against the first ``n_images`` dataset images, and appends one JSON line ``{"batches_done", "G"[,
+    "G_ema"]}`` to ``out_dir/swd.jsonl``.  The draws are seeded by ``swd_seed``; trainer, sampler and their counters are not touched, the
+    other ranks do nothing and no collective is added.  The score's one host read follows the checkpoint's ``_wait``: the device is
+    already drained, it waits for the score's own launches only.
+
     Data parallel (``inputs.world`` > 1, the world of the trainer's ``allreduce`` / ``sync_bn``): ``graph=False`` is required; the
     iteration count, cadence, sample seeds and file names are those of one process at the global batch ``B * world``; rank 0 prints and
     writes every file, the other ranks write none (``files == []``) and print nothing but execute every ``_wait`` and keep ``history``
     / ``lines`` of their own shard.  The run adds no collective: rank 0's lines and ``losses.npy`` carry rank 0's shard losses."""
 
     def __init__(self, kind, trainer, inputs, out_dir, n_epochs, sample_interval=None, seed=0, graph=True, log_capacity=1024, log_in_graph=True,
-                 ema_samples=False):
+                 ema_samples=False, swd=None):
         self.plan = _plan(kind)
         if getattr(trainer, "STATE_KIND", None) != kind:
             raise ValueError(f"a {kind!r} run needs a {kind!r} trainer, got {type(trainer).__name__}")
@@ -195,6 +209,17 @@ class TrainRun:
                 raise ValueError("ema_samples: the trainer keeps no average of its generator -- call trainer.attach_ema(modules=('G', ...)) first")
             if self.rank == 0:
                 self._ema_G = _module_like(trainer.G).to(trainer.losses.device)
+        self.swd, self._swd_G = swd, None
+        if swd is not None:
+            if kind not in ("mnist", "celeba"):
+                raise ValueError(f"swd: only 'mnist' and 'celeba' runs are scored (quality.generate), not {kind!r}")
+            swd = self.swd = quality.SWDPlan(*swd)
+            if not 1 <= int(swd.n_images) <= self.n_images:
+                raise ValueError(f"swd: n_images = {swd.n_images}, the dataset has {self.n_images} images")
+            if int(swd.n_images) % min(int(trainer.B), int(swd.n_images)):          # the generator runs at the trainer's batch size
+                raise ValueError(f"swd: n_images = {swd.n_images} is no multiple of the trainer's batch size {trainer.B}")
+            if self.rank == 0:
+                self._swd_G = _module_like(trainer.G).to(trainer.losses.device)
         if self.plan["minmax"]:
             dev = trainer.losses.device
             self._mm_dev = torch.zeros(4, device=dev, dtype=torch.float32)
@@ -285,6 +310,26 @@ class TrainRun:
                 torch.save({k: v.detach().to("cpu", copy=True) for k, v in ema.state_dict(name).items()}, os.path.join(od, fn))
                 self.files.append(os.path.join(od, fn))
 
+    def _score(self, it):
+        """one line of ``swd.jsonl``: the live generator and, where the trainer averages it, the averaged one, as scratch copies"""
+        if self._swd_G is None:
+            return
+        tr, plan = self.trainer, self.swd
+        seed = swd_seed(self.seed, it, plan.seed)
+        kw = dict(n_images=plan.n_images, batch=min(int(tr.B), int(plan.n_images)), seed=seed, patches_per_image=plan.patches_per_image,
+                  repeats=plan.repeats, dirs=plan.dirs)
+        G = self._swd_G
+        G.load_state_dict(tr.G.state_dict())
+        line = {"batches_done": int(it), "G": quality.swd_generator(self.kind, G.train(tr.G.training), self.inputs, **kw)}
+        ema = getattr(tr, "ema", None)
+        if ema is not None and "G" in ema.names:
+            line["G_ema"] = quality.swd_generator(self.kind, ema.copy_to("G", G).train(tr.G.training), self.inputs, **kw)
+        path = os.path.join(self.out_dir, "swd.jsonl")
+        with open(path, "a") as f:
+            f.write(json.dumps(line, sort_keys=True) + "\n")
+        if path not in self.files:
+            self.files.append(path)
+
     def _prepare(self):
         tr = self.trainer
         tr.inputs, tr.log = self.inputs, (self.log if self.log_in_graph else None)
@@ -329,6 +374,7 @@ class TrainRun:
             if do_ckpt:
                 self._wait("checkpoint")
                 self._checkpoint(it)
+                self._score(it)
             self.batches_done = it + 1
             done += 1
             if do_ckpt:

@@ -724,6 +724,45 @@ int eg_ema_plan(const eg_ema_seg* segs_host, int nseg, unsigned int* chunk_first
 int eg_ema_update(const eg_ema_seg* segs_dev, const unsigned int* chunk_first_dev, int nseg, float beta, float ramp, int* updates,
                   eg_stream_t s);
 
+/* --- sliced Wasserstein distance between two image sets (Karras et al., "Progressive Growing of GANs", 2018; not in the
+ * reference, whose scripts have no image-quality number).  Images are planar fp32 [N][C][H][H]; every entry point enqueues eager launches
+ * and never synchronises; no float atomics, fixed summation orders: two calls give the same bits.
+ * Laplacian pyramid, g = outer([1,4,6,4,1], [1,4,6,4,1]) / 256, border i < 0 -> -i, i >= n -> 2(n-1) - i (scipy 'mirror'):
+ * eg_pyr_down   : coarse [planes][H/2][H/2] = the 5 x 5 correlation of fine [planes][H][H] with g at the even rows and columns
+ * eg_pyr_up_sub : fine -= (coarse written into the even positions of a zero image of side H) filtered with 4 g, in place
+ * H is the FINE side in both: a power of two >= 32. */
+int eg_pyr_down(const float* fine, float* coarse, int planes, int H, eg_stream_t s);
+int eg_pyr_up_sub(float* fine, const float* coarse, int planes, int H, eg_stream_t s);
+/* Descriptor i < n_desc is the 7 x 7 x C patch of image i / P around the centre (pos[i][0], pos[i][1]) = (y, x), int32 [n_desc][2], legal
+ * in [3, H - 3); its entry k = c * 49 + dy * 7 + dx is the pixel (c, y - 3 + dy, x - 3 + dx).
+ * eg_swd_patch_stats: stats [C][2] float64 = (mean, population standard deviation) of all n_desc * 49 gathered pixels of the channel,
+ * summed in double about the channel's first gathered pixel.  flag[0] |= 1: a standard deviation is 0; 2: a mean or standard deviation is
+ * not finite (any NaN or infinity among the gathered pixels); 4: a centre outside [3, H - 3) -- such a centre is read clamped into the
+ * range by this call and by eg_swd_project, never outside the image.  The caller zeroes the flag.  ws: eg_swd_patch_stats_ws_doubles(C). */
+size_t eg_swd_patch_stats_ws_doubles(int C);
+int eg_swd_patch_stats(const float* img, const int* pos, int n_desc, int P, int C, int H, double* ws, double* stats, int* flag, eg_stream_t s);
+/* dirs [K][D] fp32: every column divided by its Euclidean norm (the norm formed in double) */
+int eg_swd_unit_columns(float* dirs, int K, int D, eg_stream_t s);
+/* out[d][i] = sum_k w'[k][d] * descriptor_i[k] - sum_k w'[k][d] * mean[c(k)],  w'[k][d] = dirs[k][d] / std[c(k)],  c(k) = k / 49: the
+ * projections of the per-channel normalised descriptors on the D <= 128 columns of dirs [49 C][D], written transposed (row d of out, row
+ * stride ld >= n_desc) so that a direction's column is contiguous; the descriptors are gathered from img in the kernel and never stored.
+ * fp32 operands and fp32 fma accumulation in k order; w' and the constant are formed in double and rounded once.
+ * stats: eg_swd_patch_stats's [C][2]; ws: eg_swd_project_ws_floats(C) floats (w' and the constants). */
+size_t eg_swd_project_ws_floats(int C);
+int eg_swd_project(const float* img, const int* pos, int n_desc, int P, int C, int H, const float* dirs, int D, const double* stats, float* ws,
+                   float* out, size_t ld, eg_stream_t s);
+/* x [cols][ld] fp32: each row's first n elements sorted ascending in place (n >= 1, ld >= n, cols <= 65535, n <= 2^30); +-inf are
+ * ordered as values, -0.0 and +0.0 compare equal, the result for NaN inputs is unspecified.  A bitonic network whose compare-exchanges
+ * all leave the smaller value at the lower index, padded to a power of two with +inf that is never stored: tiles of
+ * eg_sort_tile_elems() elements are sorted in LDS, every merge round above the tile takes one global pass per two strides >= the tile and
+ * one LDS pass for all smaller strides.  No workspace. */
+int eg_sort_tile_elems(void);
+int eg_sort_columns_f32(float* x, int n, int cols, size_t ld, eg_stream_t s);
+/* out[0] (float64) = sum |a - b| / (cols * n) over the first n elements of the rows of a, b [cols][ld]; per-element fp32 difference,
+ * summed in double in a fixed order.  ws: eg_l1_mean_ws_doubles() doubles. */
+size_t eg_l1_mean_ws_doubles(void);
+int eg_l1_mean_f32(const float* a, const float* b, int n, int cols, size_t ld, double* ws, double* out, eg_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
