@@ -1,0 +1,290 @@
+// Exact k nearest neighbours between rows of uint8 (not in the reference, whose scripts never compare a sample with the training
+// set): the device side of quality.nearest_neighbours and quality.nn_two_sample.
+//   d(i, j) = sum_t (q[i][t] - x[j][t])^2 is an integer <= 255^2 * 32768 < 2^31.  With q' = q ^ 0x80 and x' = x ^ 0x80 read as int8 (v - 128; one
+//   XOR per four bytes) d = |q'|^2 + |x'|^2 - 2 q'.x': the dot products on the int8 MFMA (v_mfma_i32_32x32x32_i8, int32 accumulation, exact:
+//   |q'.x'| <= 2^29), the norms with v_dot4 while the operands are staged, the epilogue in uint32 (|q'|^2 + |x'|^2 <= 2^30, d <= 2^31).
+//   knn_tile_kernel    a workgroup owns KNN_TQ queries (two such tiles from KNN_WIDE_NQ queries on) and walks its slice of the database in
+//                      tiles of KNN_TR rows; per tile the dot products go to LDS and thread (query, part of the rows) offers them to a
+//                      sorted list of k packed keys (d << 32 | j) it keeps in LDS, after ONE compare with the list's last key; the lists of
+//                      a query's parts are merged before they leave
+//   knn_merge_kernel   [splits][nq][k] partial lists -> the k smallest keys of a query, unpacked
+// The keys of one query are distinct and totally ordered, so the result is the same set in the same order whatever the tiling, the number
+// of slices and the order in which lists are merged: two calls give the same bits.
+#include "eg_common.h"
+
+#define KNN_TQ 64                 // queries per workgroup tile; from KNN_WIDE_NQ queries on a workgroup owns two such tiles
+#define KNN_WIDE_NQ 256
+#define KNN_TR 128                // database rows per tile (32 per wave)
+#define KNN_KC 128                // bytes of a row staged per step (four MFMA k steps)
+#define KNN_LD (KNN_KC + 16)      // LDS row stride: 16 consecutive rows start in 16 different 16-byte bank groups
+#define KNN_THREADS 256
+#define KNN_KMAX 16
+#define KNN_TARGET_WGS 512        // two workgroups per CU: the database is split until the launch has about this many
+#define KNN_EMPTY 0xffffffffffffffffull
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v16i __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ int sq4(int v) {          // sum of the squares of four int8
+#if __has_builtin(__builtin_amdgcn_sdot4)
+    return __builtin_amdgcn_sdot4(v, v, 0, false);
+#else
+    int s = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const int e = (int)(signed char)(v >> (8 * b));
+        s += e * e;
+    }
+    return s;
+#endif
+}
+
+// 16 bytes of row `row` (< rows, else zeros) at byte k (< K, else zeros), as int8 about 128; *norm += their squares
+__device__ __forceinline__ v4i knn_load(const unsigned char* __restrict__ base, long long row, long long rows, int k, int K, int& norm) {
+    v4i v = {0, 0, 0, 0};
+    if (row < rows && k < K) {
+        v = *(const v4i*)(base + (size_t)row * K + k);
+        v ^= (int)0x80808080;
+        norm += sq4(v.x) + sq4(v.y) + sq4(v.z) + sq4(v.w);
+    }
+    return v;
+}
+
+// sorted ascending list of k keys, slot j of thread t at list[j * KNN_THREADS + t]; key < list[k - 1] on entry
+__device__ __forceinline__ void knn_insert(unsigned long long* list, int k, unsigned long long key) {
+    int j = k - 1;
+    while (j > 0) {
+        const unsigned long long prev = list[(j - 1) * KNN_THREADS];
+        if (prev < key) break;
+        list[j * KNN_THREADS] = prev;
+        --j;
+    }
+    list[j * KNN_THREADS] = key;
+}
+
+// TQ = 64: wave w takes rows 32 w .. of the tile against all 64 queries (2 accumulators).  TQ = 128: the waves form 2 x 2, each 64 rows x 64
+// queries (4 accumulators): 4 LDS fragments per 4 MFMAs instead of 3 per 2, and a third fewer operand bytes staged per multiply-add.
+// KCAP = list capacity, k <= KCAP (1, 8 or 16).
+template <int TQ, int KCAP>
+__global__ __launch_bounds__(KNN_THREADS) void knn_tile_kernel(const unsigned char* __restrict__ q, int nq, const unsigned char* __restrict__ x, int n,
+                                                               int K, int k, long long self0, int tiles_per_split,
+                                                               unsigned long long* __restrict__ part) {
+    // stage[buf]: KNN_TR rows of x, then TQ rows of q, KNN_LD bytes each; after a tile's last step the same bytes hold dots[row][query]
+    __shared__ __attribute__((aligned(16))) unsigned char stage[2][(KNN_TR + TQ) * KNN_LD];
+    __shared__ int xn[KNN_TR], qn[TQ];
+    __shared__ unsigned long long lists[KCAP * KNN_THREADS];       // [k][KNN_THREADS]
+    static_assert(sizeof(stage) >= KNN_TR * TQ * sizeof(int), "the dot products alias the staging buffers");
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    constexpr int RB = TQ / 64, QP = TQ / 32, PARTS = KNN_THREADS / TQ, RP = KNN_TR / PARTS;
+    const int q0 = blockIdx.x * TQ;
+    const int wrow0 = TQ == 64 ? w * 32 : (w >> 1) * 64, wq0 = TQ == 64 ? 0 : (w & 1) * 64;
+    const int ntiles = (int)(((long long)n + KNN_TR - 1) / KNN_TR);
+    const int t_first = blockIdx.y * tiles_per_split, t_end = min(t_first + tiles_per_split, ntiles);
+    const int srow = tid >> 3, sk = (tid & 7) * 16;                // staging: 8 threads per row, 32 rows per pass
+    const int fr = lane & 31, fk = (lane >> 5) * 16;               // fragments: row of the 32 x 32 block, half of the k step
+    const int nsteps = (K + KNN_KC - 1) / KNN_KC;
+
+    unsigned long long* mine = lists + tid;
+    for (int j = 0; j < k; ++j) mine[j * KNN_THREADS] = KNN_EMPTY;
+    unsigned long long kth = KNN_EMPTY;
+    const int sq = tid % TQ, sp = tid / TQ;                        // selection: query of the tile, part of the tile's rows
+    const long long qi = (long long)q0 + sq;
+    const long long excl = self0 >= 0 ? self0 + qi : -1;
+    int qnorm[QP] = {};
+
+    for (int t = t_first; t < t_end; ++t) {
+        const long long r0 = (long long)t * KNN_TR;
+        v16i acc[RB][2];
+#pragma unroll
+        for (int a = 0; a < RB; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) acc[a][b][e] = 0;
+        int xnorm[4] = {0, 0, 0, 0}, qdummy[QP] = {};
+        const bool first = t == t_first;
+        v4i rx[4], rq[QP];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) rx[p] = knn_load(x, r0 + p * 32 + srow, n, sk, K, xnorm[p]);
+#pragma unroll
+        for (int p = 0; p < QP; ++p) rq[p] = knn_load(q, (long long)q0 + p * 32 + srow, nq, sk, K, first ? qnorm[p] : qdummy[p]);
+        __syncthreads();                                           // the previous tile's selection has read its dot products
+#pragma unroll
+        for (int p = 0; p < 4; ++p) *(v4i*)&stage[0][(p * 32 + srow) * KNN_LD + sk] = rx[p];
+#pragma unroll
+        for (int p = 0; p < QP; ++p) *(v4i*)&stage[0][(KNN_TR + p * 32 + srow) * KNN_LD + sk] = rq[p];
+        __syncthreads();
+        for (int c = 0; c < nsteps; ++c) {
+            const bool more = c + 1 < nsteps;
+            if (more) {
+                const int kk = (c + 1) * KNN_KC + sk;
+#pragma unroll
+                for (int p = 0; p < 4; ++p) rx[p] = knn_load(x, r0 + p * 32 + srow, n, kk, K, xnorm[p]);
+#pragma unroll
+                for (int p = 0; p < QP; ++p) rq[p] = knn_load(q, (long long)q0 + p * 32 + srow, nq, kk, K, first ? qnorm[p] : qdummy[p]);
+            }
+            const unsigned char* sb = stage[c & 1];
+#pragma unroll
+            for (int s = 0; s < KNN_KC / 32; ++s) {
+                // both operands take their element j from the same byte t = 32 s + fk + j of their row: the sum over t is the dot product
+                v4i fa[RB], fb[2];
+#pragma unroll
+                for (int a = 0; a < RB; ++a) fa[a] = *(const v4i*)&sb[(wrow0 + a * 32 + fr) * KNN_LD + s * 32 + fk];
+#pragma unroll
+                for (int b = 0; b < 2; ++b) fb[b] = *(const v4i*)&sb[(KNN_TR + wq0 + b * 32 + fr) * KNN_LD + s * 32 + fk];
+#pragma unroll
+                for (int a = 0; a < RB; ++a)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[a], fb[b], acc[a][b], 0, 0, 0);
+            }
+            if (more) {
+                unsigned char* nb = stage[(c + 1) & 1];
+#pragma unroll
+                for (int p = 0; p < 4; ++p) *(v4i*)&nb[(p * 32 + srow) * KNN_LD + sk] = rx[p];
+#pragma unroll
+                for (int p = 0; p < QP; ++p) *(v4i*)&nb[(KNN_TR + p * 32 + srow) * KNN_LD + sk] = rq[p];
+            }
+            __syncthreads();
+        }
+        // row norms: the 8 staging threads of a row are 8 consecutive lanes
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            int v = xnorm[p];
+            v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4);
+            if ((tid & 7) == 0) xn[p * 32 + srow] = v;
+        }
+        if (first) {
+#pragma unroll
+            for (int p = 0; p < QP; ++p) {
+                int v = qnorm[p];
+                v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4);
+                if ((tid & 7) == 0) qn[p * 32 + srow] = v;
+            }
+        }
+        // C layout of the 32 x 32 block (A = x rows, B = queries): column = lane & 31 = query, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
+        int* dots = (int*)&stage[0][0];                            // [KNN_TR][TQ]: the last step's barrier has passed, nobody reads operands
+#pragma unroll
+        for (int a = 0; a < RB; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int row = wrow0 + a * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
+                    dots[row * TQ + wq0 + b * 32 + fr] = acc[a][b][e];
+                }
+        __syncthreads();
+        if (qi < nq) {
+            const unsigned int qnorm_u = (unsigned int)qn[sq];
+            for (int r = 0; r < RP; ++r) {
+                const int row = sp * RP + r;
+                const long long j = r0 + row;
+                if (j >= n) break;
+                const unsigned int d = qnorm_u + (unsigned int)xn[row] - 2u * (unsigned int)dots[row * TQ + sq];
+                const unsigned long long key = ((unsigned long long)d << 32) | (unsigned int)j;
+                if (key < kth && j != excl) {
+                    knn_insert(mine, k, key);
+                    kth = mine[(k - 1) * KNN_THREADS];
+                }
+            }
+        }
+    }
+    // the lists of a query's parts -> part 0's list -> part[split][query][k]
+    __syncthreads();
+    if (sp == 0 && qi < nq) {
+        for (int o = 1; o < PARTS; ++o)
+            for (int j = 0; j < k; ++j) {
+                const unsigned long long key = lists[j * KNN_THREADS + o * TQ + sq];
+                if (key >= kth) break;                             // sorted: the rest of this list is no better
+                knn_insert(mine, k, key);
+                kth = mine[(k - 1) * KNN_THREADS];
+            }
+        unsigned long long* o = part + ((size_t)blockIdx.y * nq + qi) * k;
+        for (int j = 0; j < k; ++j) o[j] = mine[j * KNN_THREADS];
+    }
+}
+
+// one workgroup per query: round r picks the smallest key above round r - 1's (the keys of a query are distinct)
+__global__ __launch_bounds__(256) void knn_merge_kernel(const unsigned long long* __restrict__ part, int splits, int nq, int k, int* __restrict__ dist,
+                                                        int* __restrict__ idx) {
+    __shared__ unsigned long long sm[4];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const int total = splits * k;
+    unsigned long long prev = 0;
+    for (int r = 0; r < k; ++r) {
+        unsigned long long best = KNN_EMPTY;
+        for (int e = tid; e < total; e += 256) {
+            const unsigned long long key = part[((size_t)(e / k) * nq + i) * k + (e % k)];
+            if ((r == 0 || key > prev) && key < best) best = key;
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long other = __shfl_xor(best, o);
+            best = other < best ? other : best;
+        }
+        __syncthreads();
+        if ((tid & 63) == 0) sm[tid >> 6] = best;
+        __syncthreads();
+        best = sm[0];
+#pragma unroll
+        for (int o = 1; o < 4; ++o) best = sm[o] < best ? sm[o] : best;
+        prev = best;
+        if (tid == 0) {
+            dist[(size_t)i * k + r] = (int)(unsigned int)(best >> 32);
+            idx[(size_t)i * k + r] = (int)(unsigned int)best;
+        }
+    }
+}
+
+// tiles of KNN_TR rows a workgroup walks for (nq, n): as few as keep about KNN_TARGET_WGS workgroups in the launch
+static int knn_wg_queries(int nq) { return nq >= KNN_WIDE_NQ ? 2 * KNN_TQ : KNN_TQ; }
+static int knn_tiles_per_split(int nq, int n) {
+    const int tq = knn_wg_queries(nq);
+    const long long qt = ((long long)nq + tq - 1) / tq, rt = ((long long)n + KNN_TR - 1) / KNN_TR;
+    long long want = (KNN_TARGET_WGS + qt - 1) / qt;               // slices wanted
+    if (want < 1) want = 1;
+    if (want > rt) want = rt;
+    return (int)((rt + want - 1) / want);
+}
+
+extern "C" int eg_knn_tile_queries(void) { return KNN_TQ; }
+extern "C" int eg_knn_tile_rows(void) { return KNN_TR; }
+
+extern "C" int eg_knn_splits(int nq, int n) {
+    if (nq < 1 || n < 1) return 0;
+    const int tps = knn_tiles_per_split(nq, n);
+    return (int)((((long long)n + KNN_TR - 1) / KNN_TR + tps - 1) / tps);
+}
+
+extern "C" size_t eg_knn_ws_bytes(int nq, int n, int k) {
+    if (nq < 1 || n < 1 || k < 1) return 0;
+    return (size_t)eg_knn_splits(nq, n) * (size_t)nq * (size_t)k * sizeof(unsigned long long);
+}
+
+extern "C" int eg_knn_u8(const unsigned char* q, int nq, const unsigned char* x, int n, int K, int k, long long self0, void* ws, int* dist, int* idx,
+                         eg_stream_t s) {
+    EG_REQUIRE(q && x && ws && dist && idx, "eg_knn_u8: null pointer");
+    EG_REQUIRE(nq >= 1 && n >= 1, "eg_knn_u8: need nq >= 1 and n >= 1");
+    EG_REQUIRE(K >= 64 && K <= 32768 && K % 64 == 0, "eg_knn_u8: the row length K must be a multiple of 64 in 64 .. 32768 (K = %d)", K);
+    EG_REQUIRE(k >= 1 && k <= KNN_KMAX, "eg_knn_u8: need 1 <= k <= %d (k = %d)", KNN_KMAX, k);
+    const long long candidates = (long long)n - (self0 >= 0 && self0 < n ? 1 : 0);         // of query 0, which has the fewest
+    EG_REQUIRE(k <= candidates, "eg_knn_u8: k = %d, but a query has only %lld candidates", k, candidates);
+    EG_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)ws & 7) == 0, "eg_knn_u8: q and x must be 16-byte aligned, ws 8-byte");
+    const int tps = knn_tiles_per_split(nq, n), splits = eg_knn_splits(nq, n);
+    const int tq = knn_wg_queries(nq), qt = cdiv(nq, tq);
+    EG_REQUIRE(splits <= 65535, "eg_knn_u8: too many slices");
+#define KNN_LAUNCH(TQ, KCAP) \
+    hipLaunchKernelGGL((knn_tile_kernel<TQ, KCAP>), dim3(qt, splits), dim3(KNN_THREADS), 0, (hipStream_t)s, q, nq, x, n, K, k, self0, tps, (unsigned long long*)ws)
+    if (tq == KNN_TQ) {
+        if (k == 1) KNN_LAUNCH(KNN_TQ, 1);
+        else if (k <= 8) KNN_LAUNCH(KNN_TQ, 8);
+        else KNN_LAUNCH(KNN_TQ, KNN_KMAX);
+    } else {
+        if (k == 1) KNN_LAUNCH(2 * KNN_TQ, 1);
+        else if (k <= 8) KNN_LAUNCH(2 * KNN_TQ, 8);
+        else KNN_LAUNCH(2 * KNN_TQ, KNN_KMAX);
+    }
+#undef KNN_LAUNCH
+    hipLaunchKernelGGL(knn_merge_kernel, dim3(nq), dim3(256), 0, (hipStream_t)s, (const unsigned long long*)ws, splits, nq, k, dist, idx);
+    EG_LAUNCH_CHECK();
+    return 0;
+}

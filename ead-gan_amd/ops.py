@@ -999,3 +999,49 @@ def l1_mean_ws_doubles() -> int:
 def l1_mean(a, b, n, cols, ld, ws, out):
     """out[0] (float64) <- mean |a - b| over the first n elements of the cols rows (row stride ld) of two fp32 arrays"""
     lib().call("eg_l1_mean_f32", _p(a), _p(b), n, cols, ld, _p(ws), _p(out), _stream())
+
+
+# ---- exact nearest neighbours over uint8 rows (DESIGN 6n) ---------------------------------------------
+def knn_tile_queries() -> int:
+    """queries per workgroup tile of eg_knn_u8 (from four such tiles of queries on a workgroup owns two)"""
+    return lib().query("eg_knn_tile_queries")
+
+
+def knn_tile_rows() -> int:
+    """database rows per tile of eg_knn_u8"""
+    return lib().query("eg_knn_tile_rows")
+
+
+def knn_splits(nq, n) -> int:
+    """database slices eg_knn_u8 launches for (nq, n)"""
+    return lib().query("eg_knn_splits", int(nq), int(n))
+
+
+def knn_u8(queries, database, k, self0=-1, out=None):
+    """-> (dist, idx), int32 [nq, k] on the device: per row of ``queries`` the ``k`` nearest rows of ``database`` by exact squared L2
+    distance, ascending in (distance, index) -- equal distances go to the lower index.  Both are contiguous uint8 device tensors whose
+    trailing dimensions flatten to the same K (a multiple of 64 in 64 .. 32768).  ``self0 >= 0``: query i is database row self0 + i and
+    does not find itself.  ``out``: an int32 (dist, idx) pair of [nq, k] views with contiguous rows to write instead of new tensors."""
+    for name, t in (("queries", queries), ("database", database)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() >= 2 and t.is_contiguous()):
+            raise ValueError(f"knn_u8: {name} must be a contiguous uint8 device tensor [rows, ...]")
+    nq, n = int(queries.shape[0]), int(database.shape[0])
+    K = queries[0].numel() if nq else 0
+    if nq < 1 or n < 1 or database[0].numel() != K or queries.device != database.device:
+        raise ValueError(f"knn_u8: queries {tuple(queries.shape)} and database {tuple(database.shape)} must have rows of one length on one device")
+    k, self0 = int(k), int(self0)
+    if K % 64 or not 64 <= K <= 32768:
+        raise ValueError(f"knn_u8: the row length must be a multiple of 64 in 64 .. 32768, got {K}")
+    if not 1 <= k <= 16 or k > n - (1 if 0 <= self0 < n else 0):
+        raise ValueError(f"knn_u8: k = {k} must be in 1 .. 16 and no more than the candidates of a query ({n} rows, self0 = {self0})")
+    if out is None:
+        dist = torch.empty(nq, k, device=queries.device, dtype=torch.int32)
+        idx = torch.empty(nq, k, device=queries.device, dtype=torch.int32)
+    else:
+        dist, idx = out
+        for t in (dist, idx):
+            if not (t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == (nq, k) and t.is_contiguous()):
+                raise ValueError(f"knn_u8: out must be two contiguous int32 device tensors [{nq}, {k}]")
+    ws = torch.empty(lib().query("eg_knn_ws_bytes", nq, n, k) // 8, device=queries.device, dtype=torch.int64)
+    lib().call("eg_knn_u8", _p(queries), nq, _p(database), n, K, k, self0, _p(ws), _p(dist), _p(idx), _stream())
+    return dist, idx

@@ -10,6 +10,15 @@ the random draws are fixed.  Not in the reference, whose scripts only write samp
 * ``swd_generator(kind, generator, inputs)``     the three together
 * ``SWDPlan``                                    what ``train.TrainRun(..., swd=...)`` scores on checkpoint iterations
 
+Memorisation: SWD cannot see a generator that copies training images -- it scores perfectly.  The exact nearest-neighbour search
+over the uint8 datasets (ops.knn_u8: integer squared L2 distances on the int8 MFMA, ties to the lower index) answers that twice:
+
+* ``to_u8(images)``                              [-1, 1] fp32 -> the dataset's bytes (the inverse of the trainers' 2/255 u - 1)
+* ``nearest_neighbours(images, database, k)``    distances and indices of the k nearest dataset images
+* ``nn_two_sample(real, fake)``                  the leave-one-out 1-NN two-sample test (Lopez-Paz & Oquab 2017; Xu et al. 2018)
+* ``neighbour_grid`` / ``save_neighbours``       the figure: every query beside its nearest dataset images
+* ``nearest_training_images`` / ``nn_generator`` the two for a generator of an MNIST or CelebA run
+
 Per level and set: patch statistics (ops.swd_patch_stats), then per repeat one fused gather-and-project launch (ops.swd_project: the
 descriptors, 0.6 GB per set and level at full size, never exist), one column sort per set (ops.sort_columns) and one reduction
 (ops.l1_mean).  Everything is enqueued on the current stream; ``swd`` reads the device once, at its end.  There is no CPU path.
@@ -18,9 +27,10 @@ from __future__ import annotations
 
 from typing import NamedTuple
 
+import numpy as np
 import torch
 
-from . import ops
+from . import ops, sampling
 
 PATCH, MIN_SIDE = 7, 16
 # Philox stream ids of this module's draws (ops.rng_fill): a block no sampler uses (the samplers' ids are 1 .. 8).  The device counter of
@@ -233,3 +243,105 @@ def swd_generator(kind, generator, inputs, n_images=8192, batch=None, seed=0, **
     batch = min(64, int(n_images)) if batch is None else int(batch)
     fake = generate(kind, generator, n_images, batch, seed)
     return swd(real_images(kind, inputs, n_images), fake, seed=seed, **swd_kw)
+
+
+# ---- nearest neighbours over the uint8 datasets -----------------------------------------------------------------------------
+def to_u8(images):
+    """fp32 [N, C, H, W] in [-1, 1] on the device -> uint8 [N, C, H, W]: the inverse of the trainers' 2/255 u - 1.  The byte is
+    eg_quantize_u8 of v' = 0.5 v + 0.5 (clamp(v' * 255 + 0.5, 0, 255) truncated), every step a separately rounded fp32 operation, so
+    ``to_u8(real_images(...))`` gives back the dataset's bytes for all 256 values; values outside [-1, 1] clamp."""
+    if not (isinstance(images, torch.Tensor) and images.is_cuda and images.is_floating_point() and images.dim() == 4):
+        raise ValueError("quality.to_u8: images must be a floating-point device tensor [N, C, H, W]")
+    v = images.detach().float().mul(0.5).add_(0.5).contiguous()              # two roundings, as stated
+    out = torch.empty(v.shape, device=v.device, dtype=torch.uint8)
+    per = v[0].numel()
+    step = max(1, (2 ** 31 - 1) // per)                                      # the kernel's extents are ints
+    for i in range(0, v.shape[0], step):
+        part = v[i:i + step]
+        ops.quantize_u8(part, 1, 1, part.numel(), None, out[i:i + step])     # C = H = 1: the flat order
+    return out
+
+
+def _u8_rows(t, name):
+    if isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 4 and t.is_floating_point():
+        return to_u8(t)
+    if isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 4 and t.dtype == torch.uint8:
+        return t.contiguous()
+    raise ValueError(f"quality: {name} must be a float or uint8 device tensor [N, C, H, W]")
+
+
+def _dataset(inputs, what):
+    data = getattr(inputs, "data", inputs)
+    if not (isinstance(data, torch.Tensor) and data.is_cuda and data.dtype == torch.uint8 and data.dim() == 4):
+        raise ValueError(f"quality.{what}: the database must be a sampler or a uint8 device dataset [N, C, H, W]")
+    return data.contiguous()
+
+
+def nearest_neighbours(images, database, k=8):
+    """-> (dist, idx), int32 [N, k] on the device: the ``k`` nearest images of ``database`` (a sampler or its uint8 device dataset) to
+    every image of ``images`` (float in [-1, 1], turned into bytes by ``to_u8``, or uint8), by exact squared L2 distance between the
+    bytes, nearest first; equal distances go to the lower index."""
+    data = _dataset(database, "nearest_neighbours")
+    q = _u8_rows(images, "images")
+    if q.shape[1:] != data.shape[1:]:
+        raise ValueError(f"quality.nearest_neighbours: images {tuple(q.shape[1:])} against a dataset of {tuple(data.shape[1:])}")
+    return ops.knn_u8(q, data, k)
+
+
+def nn_two_sample(real, fake):
+    """Leave-one-out 1-NN two-sample test between two image sets [N, C, H, W] (float in [-1, 1] or uint8):
+    -> {"accuracy", "real", "fake"}, Python floats.  The sets are pooled, real rows first, and every row takes its nearest OTHER row
+    (one ops.knn_u8 call with self0 = 0).  ``real`` = the share of real rows whose neighbour is real, ``fake`` = the share of fake rows
+    whose neighbour is fake, each exactly count / N; ``accuracy`` = their mean.  0.5 says the sets cannot be told apart, 1 that they are
+    trivially separable; ``fake`` well under 0.5 says the generated images sit on top of real ones (memorisation).  Tie rule: of equally
+    distant rows the lower index in the pool wins, so a real row wins a tie against a fake one.  One host read, at the end."""
+    A, B = _u8_rows(real, "real"), _u8_rows(fake, "fake")
+    if A.shape != B.shape or A.device != B.device:
+        raise ValueError(f"nn_two_sample: the two sets must have one shape on one device, got {tuple(A.shape)} and {tuple(B.shape)}")
+    N = int(A.shape[0])
+    pool = torch.cat((A, B))
+    _, idx = ops.knn_u8(pool, pool, 1, self0=0)
+    is_real = idx[:, 0] < N
+    counts = torch.stack((is_real[:N].sum(), (~is_real[N:]).sum())).cpu()     # THE host read
+    r, f = int(counts[0]) / N, int(counts[1]) / N
+    return {"accuracy": 0.5 * (r + f), "real": r, "fake": f}
+
+
+def neighbour_grid(queries, database, idx):
+    """-> fp32 [nq (1 + k), C, H, W] in [0, 1] on the device: row r of the figure is query r followed by the ``k`` dataset images
+    ``idx[r]`` (``nearest_neighbours``' second result)"""
+    data = _dataset(database, "neighbour_grid")
+    q = _u8_rows(queries, "queries")
+    if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dim() == 2 and idx.shape[0] == q.shape[0] and q.shape[1:] == data.shape[1:]):
+        raise ValueError("quality.neighbour_grid: idx must be a device tensor [nq, k] for queries [nq, C, H, W] shaped like the dataset")
+    nq, k = idx.shape
+    rows = torch.cat((q.unsqueeze(1), data[idx.long().reshape(-1)].reshape(nq, k, *data.shape[1:])), 1)
+    # u / 255 correctly rounded, from a table: a device division by a scalar multiplies by the rounded reciprocal and differs in the last bit
+    table = torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255.0)).to(data.device)
+    return table[rows.reshape(nq * (1 + k), *data.shape[1:]).long()]
+
+
+def save_neighbours(fp, queries, database, idx):
+    """writes ``neighbour_grid`` as a PNG with one query and its neighbours per row"""
+    sampling.save_image(neighbour_grid(queries, database, idx), fp, nrow=1 + int(idx.shape[1]))
+
+
+def nearest_training_images(kind, generator, inputs, n_images=64, k=8, batch=None, seed=0, out=None):
+    """``n_images`` outputs of a generator of the 'mnist' or 'celeba' family (``generate``) against the WHOLE dataset of ``inputs``
+    -> (dist, idx) as ``nearest_neighbours`` returns them; ``out``: a path for the figure (``save_neighbours``)"""
+    _family(kind, "nearest_training_images")
+    batch = min(64, int(n_images)) if batch is None else int(batch)
+    fake = to_u8(generate(kind, generator, n_images, batch, seed))
+    dist, idx = nearest_neighbours(fake, inputs, k)
+    if out is not None:
+        save_neighbours(out, fake, inputs, idx)
+    return dist, idx
+
+
+def nn_generator(kind, generator, inputs, n_images=8192, batch=None, seed=0):
+    """``nn_two_sample`` of ``real_images(kind, inputs, n_images)`` against ``generate(kind, generator, n_images, batch, seed)``;
+    ``batch`` as in ``swd_generator``"""
+    _family(kind, "nn_generator")
+    batch = min(64, int(n_images)) if batch is None else int(batch)
+    fake = generate(kind, generator, n_images, batch, seed)
+    return nn_two_sample(real_images(kind, inputs, n_images), fake)

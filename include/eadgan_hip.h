@@ -763,6 +763,24 @@ int eg_sort_columns_f32(float* x, int n, int cols, size_t ld, eg_stream_t s);
 size_t eg_l1_mean_ws_doubles(void);
 int eg_l1_mean_f32(const float* a, const float* b, int n, int cols, size_t ld, double* ws, double* out, eg_stream_t s);
 
+/* --- exact k nearest neighbours between rows of uint8 (not in the reference, whose scripts never compare a sample with the
+ * training set).  q [nq][K] and x [n][K] contiguous uint8, 16-byte aligned; d(i, j) = sum_t (q[i][t] - x[j][t])^2 as an exact integer
+ * (<= 255^2 * 32768 < 2^31).  dist [nq][k] and idx [nq][k] (int32) receive, per query, the k smallest pairs in ascending lexicographic
+ * order of (d, j): equal distances go to the lower index.  The order is total, so the result does not depend on the tiling, on the number
+ * of database slices or on the order of any reduction, and two calls give the same bits.  self0 >= 0 excludes the pair j == self0 + i
+ * (leave-one-out: the queries are the rows self0 ... of the database; queries with self0 + i >= n exclude nothing); self0 < 0 excludes
+ * nothing.  64 <= K <= 32768 with K % 64 == 0; 1 <= k <= 16 and k <= the candidates of every query (n, or n - 1 where a row is excluded).
+ * The dot products run on the int8 MFMA over q ^ 0x80 and x ^ 0x80 (v - 128; distances do not change under the common shift) with int32
+ * accumulation, d = |q'|^2 + |x'|^2 - 2 q'.x' in unsigned 32-bit arithmetic.  A workgroup owns eg_knn_tile_queries() queries (two such tiles from
+ * 4 * eg_knn_tile_queries() queries on: another wave layout) and walks a slice of the database in tiles of eg_knn_tile_rows() rows; the database is cut into eg_knn_splits(nq, n) slices whose partial lists
+ * ([splits][nq][k] packed keys d << 32 | j in ws, eg_knn_ws_bytes(nq, n, k) bytes) a second kernel merges.  No allocation, no sync. */
+int eg_knn_tile_queries(void);
+int eg_knn_tile_rows(void);
+int eg_knn_splits(int nq, int n);
+size_t eg_knn_ws_bytes(int nq, int n, int k);
+int eg_knn_u8(const unsigned char* q, int nq, const unsigned char* x, int n, int K, int k, long long self0, void* ws, int* dist, int* idx,
+              eg_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
