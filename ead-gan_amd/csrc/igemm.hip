@@ -205,51 +205,41 @@ __global__ __launch_bounds__(256) void igemm_nt_kernel(const NtParams p) {
 
     // ---- epilogue ----
     // acc[i][j][r] = C[m = m0 + (wm*TM+i)*16 + frow][n = n0 + (wn*TN+j)*16 + fq*4 + r]
-    if constexpr (STAT) {
+    if (STAT || (p.out_mode == EG_OUT_NHWC && (p.N % VEC) == 0)) {
+        // the shared epilogue through LDS
         NtEpiPre<T, TM, TN, 0> epi;
-        nt_epi_prefetch<T, BM, BN, TM, TN, 256, 0>(epi, p, ph, m0, n0, wm * TM * 16, wn * TN * 16, tid, frow, fq);
-        nt_epilogue_lds_stat<T, BM, BN, TM, TN, 256, 0>(epi, p, ph, acc, smem, m0, n0, wm * TM * 16, wn * TN * 16, tid, frow, fq,
-                                                        phase * gridDim.x + blockIdx.x, 0, 1);
-        return;
-    }
-    if (p.out_mode == EG_OUT_NHWC && (p.N % VEC) == 0) {
-        // the shared epilogue: fp32 tile through LDS (16-byte chunks XOR-swizzled by row), then whole 16-byte vector stores
-        nt_epilogue_lds<T, BM, BN, TM, TN, 256>(p, ph, acc, smem, m0, n0, wm * TM * 16, wn * TN * 16, tid, frow, fq);
+        nt_epi_fetch_reg(epi, p, m0 + wm * TM * 16 + frow, n0 + wn * TN * 16 + fq * 4);
+        if constexpr (STAT)
+            nt_epilogue_lds_stat<T, BM, BN, TM, TN, 256, 0>(epi, p, ph, acc, smem, m0, n0, wm * TM * 16, wn * TN * 16, tid, frow, fq,
+                                                            phase * gridDim.x + blockIdx.x, 0, 1);
+        else nt_epilogue_lds_reg<T, BM, BN, TM, TN, 256>(epi, p, ph, acc, smem, m0, n0, wm * TM * 16, wn * TN * 16, tid, frow, fq);
         return;
     }
     // scalar path: NCHW fp32 image outputs (N = 1..4) and channel counts that are not a multiple of the vector width
-    const T* __restrict__ mask = reinterpret_cast<const T*>(p.mask);
     const EgActFast af = eg_act_fast(p.act, p.slope);
     const EgGradFast gf = eg_grad_fast(p.mask_act, p.mask_slope);
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
         const int m = m0 + (wm * TM + i) * 16 + frow;
         if (m >= p.M) continue;
-        const float inv_sigma = p.sigma ? 1.f / p.sigma[p.sigma_rows ? m / p.sigma_rows : 0] : 1.f;
-        const int b = m >> (p.lOW + p.lOH);
-        const int y = ((m >> p.lOW) & OHm) * p.osy + ph.ooy;
-        const int x = (m & OWm) * p.osx + ph.oox;
-        const size_t pix = ((size_t)b * p.DH + y) * p.DW + x;
+        const float inv_sigma = nt_inv_sigma(p, nt_sigma_at(p, m));
+        const NtPix px = nt_out_byx(p, m, ph.ooy, ph.oox);
+        const size_t pix = nt_pix_index(p, px);
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int n = n0 + (wn * TN + j) * 16 + fq * 4 + r;
                 if (n >= p.N) continue;
-                float v = __fmul_rn(acc[i][j][r], inv_sigma);
-                if (p.bias) v = __fadd_rn(v, p.bias[p.bias_mod ? n % p.bias_mod : n]);
-                v = af.special ? eg_act(v, p.act, p.slope) : eg_act_apply(v, af);
+                float v = nt_epi_finish(acc[i][j][r], inv_sigma, p.bias != nullptr, nt_bias_at(p, n), p, af);
                 if (p.out_mode == EG_OUT_NHWC) {
                     const size_t o = pix * p.N + n;
-                    if (mask) v *= gf.special ? eg_act_grad_from_out(Elt<T>::ld(mask + o), p.mask_act, p.mask_slope) : eg_grad_apply(Elt<T>::ld(mask + o), gf);
-                    Elt<T>::st(reinterpret_cast<T*>(p.dst) + o, v);
+                    if (p.mask) nt_epi_mask<T, 1>(&v, reinterpret_cast<const T*>(p.mask) + o, p, gf);
+                    nt_epi_store<T, 1>(reinterpret_cast<T*>(p.dst) + o, &v);
                 } else {
-                    const size_t o = (((size_t)b * p.N + n) * p.DH + y) * p.DW + x;
-                    if (p.mask) {
-                        const float a = reinterpret_cast<const float*>(p.mask)[o];
-                        v *= gf.special ? eg_act_grad_from_out(a, p.mask_act, p.mask_slope) : eg_grad_apply(a, gf);
-                    }
-                    reinterpret_cast<float*>(p.dst)[o] = v;
+                    const size_t o = (((size_t)px.b * p.N + n) * p.DH + px.y) * p.DW + px.x;
+                    if (p.mask) nt_epi_mask<float, 1>(&v, reinterpret_cast<const float*>(p.mask) + o, p, gf);
+                    nt_epi_store<float, 1>(reinterpret_cast<float*>(p.dst) + o, &v);
                 }
             }
         }
@@ -265,39 +255,6 @@ __global__ __launch_bounds__(256) void igemm_nt_kernel(const NtParams p) {
 // address math and no EXEC juggling in the K loop.  Needs C % BK == 0 (every lane of a K step sits in the same tap) and
 // tensors below 2 GiB; the dispatcher falls back to igemm_nt_dma otherwise.
 // ------------------------------------------------------------------------------------------------
-
-// four 1-KiB LDS-DMA pieces (tile rows (j*4+wave)*8 .. +7, j = 0..3) from one descriptor: LDS bases lds, lds+4K, lds+8K, lds+12K
-__device__ __forceinline__ void eg_bufdma4(const u32x4_t srd, unsigned v0, unsigned v1, unsigned v2, unsigned v3, unsigned soff, unsigned lds) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %7\n\ts_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %5, %6 offen lds\n\t"
-        "s_add_u32 m0, m0, 0x1000\n\ts_nop 0\n\t"
-        "buffer_load_dwordx4 %2, %5, %6 offen lds\n\t"
-        "s_add_u32 m0, m0, 0x1000\n\ts_nop 0\n\t"
-        "buffer_load_dwordx4 %3, %5, %6 offen lds\n\t"
-        "s_add_u32 m0, m0, 0x1000\n\ts_nop 0\n\t"
-        "buffer_load_dwordx4 %4, %5, %6 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(srd), "s"(soff), "s"(lds)
-        : "memory", "scc");
-}
-
-__device__ __forceinline__ void eg_bufdma1(const u32x4_t srd, unsigned v0, unsigned soff, unsigned lds) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %4\n\ts_nop 0\n\t"
-        "buffer_load_dwordx4 %1, %2, %3 offen lds\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(v0), "s"(srd), "s"(soff), "s"(lds)
-        : "memory");
-}
-
-
 template <typename T, bool PROF = false, bool SPLITK = false>   // SPLITK: its own instantiation so that profilers list the split launches apart
 __global__ __launch_bounds__(256) void igemm_nt_buf_kernel(const NtParams p, unsigned long long* prof = nullptr) {
     unsigned long long t_begin = 0, t_wait = 0, t_issue = 0, t_comp = 0, t0 = 0, t1 = 0;
@@ -371,8 +328,9 @@ __global__ __launch_bounds__(256) void igemm_nt_buf_kernel(const NtParams p, uns
     }
     auto issue = [&](int kt, int stage) {
         const unsigned sa = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)stage * STAGE);
-        eg_bufdma4(srdA, va[0], va[1], va[2], va[3], kc_bytes, sa);
-        eg_bufdma4(srdB, vb[0], vb[1], vb[2], vb[3], (unsigned)(kt0 + kt) * 128u, sa + BM * 128);
+        // four 1-KiB pieces each (tile rows (j*4+wave)*8 .. +7, j = 0..3): LDS bases sa, sa+4K, sa+8K, sa+12K
+        eg_bufdma4s<0x1000>(srdA, va[0], va[1], va[2], va[3], kc_bytes, sa);
+        eg_bufdma4s<0x1000>(srdB, vb[0], vb[1], vb[2], vb[3], (unsigned)(kt0 + kt) * 128u, sa + BM * 128);
         kc_bytes += 128u;
         if (kc_bytes >= row_bytes) {               // next tap (uniform branch)
             kc_bytes = 0;
@@ -525,8 +483,8 @@ __global__ __launch_bounds__(256, 2) void igemm_nt_pers_kernel(const NtParams p,
     auto issue_piece = [&](int q, int stage) {
         const unsigned sa = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)stage * STAGE);
         // (single-tap launches whose row is not a whole number of K tiles: chunks past the end of the row read as zeros)
-        if (q < 4) eg_bufdma1(srdA, kc_bytes + (unsigned)srcchunk * 16u < row_bytes ? va[q] : EG_OOB, kc_bytes, sa + q * 0x1000);
-        else eg_bufdma1(srdB, vb[q - 4], (unsigned)lkt * 128u, sa + BM * 128 + (q - 4) * 0x1000);
+        if (q < 4) eg_bufdma1s(srdA, kc_bytes + (unsigned)srcchunk * 16u < row_bytes ? va[q] : EG_OOB, kc_bytes, sa + q * 0x1000);
+        else eg_bufdma1s(srdB, vb[q - 4], (unsigned)lkt * 128u, sa + BM * 128 + (q - 4) * 0x1000);
     };
     auto issue_advance = [&]() {
         ++lkt;
@@ -565,7 +523,7 @@ __global__ __launch_bounds__(256, 2) void igemm_nt_pers_kernel(const NtParams p,
     unsigned g = 0;                                   // global K step: LDS stage = g & 1
     bool stores_pending = false;
     const T* __restrict__ maskp = reinterpret_cast<const T*>(p.mask);
-    typedef typename std::conditional<std::is_same<T, float>::value, uint4, uint2>::type OutVec;   // 4 outputs of one accumulator
+    typedef NtVec<T, 4> OutVec;                       // 4 outputs of one accumulator
 
     while (ct < ntiles) {
         if (stores_pending) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
@@ -594,19 +552,13 @@ __global__ __launch_bounds__(256, 2) void igemm_nt_pers_kernel(const NtParams p,
                 const int m = c_m0 + (wm * TM + i) * 16 + frow;
                 e_ok[i] = m < p.M;
                 const int mc = min(m, p.M - 1);
-                e_sigma[i] = p.sigma ? p.sigma[p.sigma_rows ? mc / p.sigma_rows : 0] : 1.f;
-                const int b = mc >> (p.lOW + p.lOH);
-                const int y = ((mc >> p.lOW) & OHm) * p.osy + c_ooy;
-                const int x = (mc & OWm) * p.osx + c_oox;
-                e_off[i] = (((size_t)b * p.DH + y) * p.DW + x) * p.N + c_n0 + wn * 64 + fq * 4;
+                e_sigma[i] = nt_sigma_at(p, mc);
+                e_off[i] = nt_out_off(p, mc, c_ooy, c_oox, c_n0) + wn * 64 + fq * 4;
             }
 #pragma unroll
             for (int j = 0; j < TN; ++j)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int n = c_n0 + (wn * TN + j) * 16 + fq * 4 + r;
-                    e_bias[j][r] = p.bias ? p.bias[p.bias_mod ? n % p.bias_mod : n] : 0.f;
-                }
+                for (int r = 0; r < 4; ++r) e_bias[j][r] = nt_bias_at(p, c_n0 + (wn * TN + j) * 16 + fq * 4 + r);
             if (maskp) {
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
@@ -637,27 +589,14 @@ __global__ __launch_bounds__(256, 2) void igemm_nt_pers_kernel(const NtParams p,
         const EgGradFast egf = eg_grad_fast(p.mask_act, p.mask_slope);
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
-            const float inv_sigma = p.sigma ? 1.f / e_sigma[i] : 1.f;
+            const float inv_sigma = nt_inv_sigma(p, e_sigma[i]);
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 float f[4];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float x = __fmul_rn(acc[i][j][r], inv_sigma);
-                    if (p.bias) x = __fadd_rn(x, e_bias[j][r]);
-                    f[r] = eaf.special ? eg_act(x, p.act, p.slope) : eg_act_apply(x, eaf);
-                }
-                if (maskp) {
-                    const T* me = reinterpret_cast<const T*>(&e_mask[i][j]);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        f[r] *= egf.special ? eg_act_grad_from_out(Elt<T>::ld(me + r), p.mask_act, p.mask_slope) : eg_grad_apply(Elt<T>::ld(me + r), egf);
-                }
-                OutVec ov;
-                T* oe = reinterpret_cast<T*>(&ov);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) Elt<T>::st(oe + r, f[r]);
-                if (e_ok[i]) *reinterpret_cast<OutVec*>(reinterpret_cast<T*>(p.dst) + e_off[i] + j * 16) = ov;
+                for (int r = 0; r < 4; ++r) f[r] = nt_epi_finish(acc[i][j][r], inv_sigma, p.bias != nullptr, e_bias[j][r], p, eaf);
+                if (maskp) nt_epi_mask<T, 4>(f, reinterpret_cast<const T*>(&e_mask[i][j]), p, egf);
+                if (e_ok[i]) nt_epi_store<T, 4>(reinterpret_cast<T*>(p.dst) + e_off[i] + j * 16, f);
                 acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
             }
         }
@@ -678,7 +617,6 @@ __global__ __launch_bounds__(256) void nt_splitk_epilogue_kernel(const NtParams 
     const unsigned vpr = p.N / VEC;
     const unsigned total = (unsigned)p.M * vpr;
     const int phase = blockIdx.y;
-    const int OWm = (1 << p.lOW) - 1, OHm = (1 << p.lOH) - 1;
     const T* __restrict__ mask = reinterpret_cast<const T*>(p.mask);
     for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
         const unsigned vc = lvpr >= 0 ? (i & (vpr - 1)) : (i % vpr);
@@ -695,32 +633,19 @@ __global__ __launch_bounds__(256) void nt_splitk_epilogue_kernel(const NtParams 
                 f[4 * q] += v.x; f[4 * q + 1] += v.y; f[4 * q + 2] += v.z; f[4 * q + 3] += v.w;
             }
         }
-        const float inv_sigma = p.sigma ? 1.f / p.sigma[p.sigma_rows ? m / p.sigma_rows : 0] : 1.f;
-        const int b = m >> (p.lOW + p.lOH);
-        const int y = ((m >> p.lOW) & OHm) * p.osy + p.ph[phase].ooy;
-        const int x = (m & OWm) * p.osx + p.ph[phase].oox;
-        const size_t o = (((size_t)b * p.DH + y) * p.DW + x) * p.N + n;
+        const float inv_sigma = nt_inv_sigma(p, nt_sigma_at(p, m));
+        const size_t o = nt_out_off(p, m, p.ph[phase].ooy, p.ph[phase].oox, n);
         // bias index of element q: (n + q) % bias_mod; n is a multiple of VEC, so when VEC divides bias_mod it is (n % bias_mod) + q
         const bool bias_vec = p.bias_mod == 0 || (p.bias_mod % VEC) == 0;
         const int nb = p.bias_mod ? n % p.bias_mod : n;
 #pragma unroll
-        for (int q = 0; q < VEC; ++q) {
-            float v = __fmul_rn(f[q], inv_sigma);
-            if (p.bias) v = __fadd_rn(v, p.bias[bias_vec ? nb + q : (n + q) % p.bias_mod]);
-            f[q] = saf.special ? eg_act(v, p.act, p.slope) : eg_act_apply(v, saf);
-        }
+        for (int q = 0; q < VEC; ++q)
+            f[q] = nt_epi_finish(f[q], inv_sigma, p.bias != nullptr, p.bias ? p.bias[bias_vec ? nb + q : (n + q) % p.bias_mod] : 0.f, p, saf);
         if (mask) {
             const uint4 mv = *reinterpret_cast<const uint4*>(mask + o);
-            const T* me = reinterpret_cast<const T*>(&mv);
-#pragma unroll
-            for (int q = 0; q < VEC; ++q)
-                f[q] *= sgf.special ? eg_act_grad_from_out(Elt<T>::ld(me + q), p.mask_act, p.mask_slope) : eg_grad_apply(Elt<T>::ld(me + q), sgf);
+            nt_epi_mask<T, VEC>(f, reinterpret_cast<const T*>(&mv), p, sgf);
         }
-        uint4 ov;
-        T* oe = reinterpret_cast<T*>(&ov);
-#pragma unroll
-        for (int q = 0; q < VEC; ++q) Elt<T>::st(oe + q, f[q]);
-        *reinterpret_cast<uint4*>(reinterpret_cast<T*>(p.dst) + o) = ov;
+        nt_epi_store<T, VEC>(reinterpret_cast<T*>(p.dst) + o, f);
     }
 }
 

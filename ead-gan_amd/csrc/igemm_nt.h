@@ -115,103 +115,88 @@ __device__ __forceinline__ void mfma_step(const uint4& a, const uint4& b, f32x4&
     }
 }
 
-// shared epilogue of the LDS-DMA kernels: a BM x BNW window of the fp32 tile goes through LDS (XOR-swizzled 16-byte chunks), then 16-byte
-// vector stores with the fused 1/sigma, bias, activation and activation-gradient mask.  Callers __syncthreads() before (the K loop's LDS
-// is reused).  row0 / col0: first row / first window column of the calling wave's accumulators (col0 < 0: wave outside the window);
-// nw0: global column of the window's first column; NT threads per workgroup.
-template <typename T, int BM, int BNW, int TM, int TN, int NT>
-__device__ __forceinline__ void nt_epilogue_lds(const NtParams& p, const NtPhase& ph, f32x4 (&acc)[TM][TN], char* smem, int m0, int nw0, int row0,
-                                                int col0, int tid, int frow, int fq) {
-    constexpr int VEC = Elt<T>::VEC;
+// ------------------------------------------------------------------------------------------------
+// The fused epilogue.  Every NT kernel finishes a value alike -- acc * (1 / sigma), + bias, activation, optionally times the
+// activation-gradient mask, rounded to T, stored at the NHWC address of row m of its phase -- and the variants are tested bit for bit
+// against each other, so each step is written once:
+//   nt_out_byx / nt_out_off    destination pixel / NHWC element offset of row m
+//   nt_sigma_at / nt_bias_at   sigma of a row, bias of a column
+//   nt_epi_finish              1/sigma, bias and activation of one accumulator value
+//   nt_epi_mask                N values times the activation-gradient mask
+//   nt_epi_store               N values rounded to T and stored as one vector
+// The register epilogue of igemm_nt_pers, the scalar tail of igemm_nt and nt_splitk_epilogue_kernel (igemm.hip) are these pieces in
+// accumulator / partial-tile layout.  Every other kernel goes through LDS: nt_epi_prefetch, then nt_epi_stage puts the finished fp32
+// BM x BNW window into LDS (16-byte chunks XOR-swizzled by row: nt_tile_at) and nt_epi_rows walks its rows with 16-byte mask loads and
+// stores -- nt_epilogue_lds_reg (register-staged kernel) and nt_epilogue_lds_stat (column statistics, every kernel).  The plain epilogue
+// of the LDS-DMA kernels, nt_epilogue_lds_pre, is the one copy left: same steps, its own text (reason at nt_epi_prefetch).
+// ------------------------------------------------------------------------------------------------
+struct NtPix { int b, y, x; };
+// ooy / oox: the phase's NtPhase.ooy / oox
+__device__ __forceinline__ NtPix nt_out_byx(const NtParams& p, int m, int ooy, int oox) {
     const int OWm = (1 << p.lOW) - 1, OHm = (1 << p.lOH) - 1;
-    constexpr int SW = BNW / 4 < 32 ? BNW / 4 - 1 : 31;     // 16-byte fp32 chunks per tile row - 1
-    float* ct = reinterpret_cast<float*>(smem);
-    const EgActFast af = eg_act_fast(p.act, p.slope);
-    const EgGradFast gf = eg_grad_fast(p.mask_act, p.mask_slope);
-    if (col0 >= 0) {
-        float bias[TN][4];
+    return {m >> (p.lOW + p.lOH), ((m >> p.lOW) & OHm) * p.osy + ooy, (m & OWm) * p.osx + oox};
+}
+__device__ __forceinline__ size_t nt_pix_index(const NtParams& p, const NtPix& q) { return ((size_t)q.b * p.DH + q.y) * p.DW + q.x; }
+__device__ __forceinline__ size_t nt_out_off(const NtParams& p, int m, int ooy, int oox, int n) {
+    return nt_pix_index(p, nt_out_byx(p, m, ooy, oox)) * p.N + n;
+}
+
+// sigma of output row m (sigma_rows rows per tape; 0: one sigma for all) and bias of column n
+__device__ __forceinline__ float nt_sigma_at(const NtParams& p, int m) { return p.sigma ? p.sigma[p.sigma_rows ? m / p.sigma_rows : 0] : 1.f; }
+__device__ __forceinline__ float nt_bias_at(const NtParams& p, int n) { return p.bias ? p.bias[p.bias_mod ? n % p.bias_mod : n] : 0.f; }
+__device__ __forceinline__ float nt_inv_sigma(const NtParams& p, float sigma) { return p.sigma ? 1.f / sigma : 1.f; }
+
+// inv_sigma: nt_inv_sigma(nt_sigma_at(row)); bias: nt_bias_at(column), added when has_bias
+__device__ __forceinline__ float nt_epi_finish(float acc, float inv_sigma, bool has_bias, float bias, const NtParams& p, const EgActFast& af) {
+    float x = __fmul_rn(acc, inv_sigma);
+    if (has_bias) x = __fadd_rn(x, bias);
+    return af.special ? eg_act(x, p.act, p.slope) : eg_act_apply(x, af);
+}
+
+// me: the N stored activations (or pre-activations' signs) the gradient is taken from
+template <typename T, int N>
+__device__ __forceinline__ void nt_epi_mask(float* f, const T* me, const NtParams& p, const EgGradFast& gf) {
+    if (!gf.special) {
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
+        for (int q = 0; q < N; ++q) f[q] *= eg_grad_apply(Elt<T>::ld(me + q), gf);
+    } else {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int n = nw0 + col0 + j * 16 + fq * 4 + r;
-                bias[j][r] = (p.bias && n < p.N) ? p.bias[p.bias_mod ? n % p.bias_mod : n] : 0.f;
-            }
-        eg_if_fast(af.special, [&](auto fast) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                const int row = row0 + i * 16 + frow;
-                const int mrow = min(m0 + row, p.M - 1);
-                const float inv_sigma = p.sigma ? 1.f / p.sigma[p.sigma_rows ? mrow / p.sigma_rows : 0] : 1.f;
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    const int nl = col0 + j * 16 + fq * 4;
-                    float4 v;
-                    float* ve = reinterpret_cast<float*>(&v);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        float x = __fmul_rn(acc[i][j][r], inv_sigma);
-                        if (p.bias && nw0 + nl + r < p.N) x = __fadd_rn(x, bias[j][r]);
-                        if constexpr (decltype(fast)::value) ve[r] = eg_act_apply(x, af);
-                        else ve[r] = eg_act(x, p.act, p.slope);
-                    }
-                    *reinterpret_cast<float4*>(ct + row * BNW + (((nl >> 2) ^ (row & SW)) << 2)) = v;
-                }
-            }
-        });
-    }
-    __syncthreads();
-    constexpr int VPR = BNW / VEC;
-    constexpr int RPP = NT / VPR;
-    const int vc = tid % VPR, vr = tid / VPR;
-    const T* __restrict__ mask = reinterpret_cast<const T*>(p.mask);
-    const int n = nw0 + vc * VEC;
-    if (n < p.N) {
-#pragma unroll 4
-        for (int row = vr; row < BM; row += RPP) {
-            const int m = m0 + row;
-            if (m >= p.M) break;
-            const int b = m >> (p.lOW + p.lOH);
-            const int y = ((m >> p.lOW) & OHm) * p.osy + ph.ooy;
-            const int x = (m & OWm) * p.osx + ph.oox;
-            const size_t o = (((size_t)b * p.DH + y) * p.DW + x) * p.N + n;
-            float f[VEC];
-#pragma unroll
-            for (int q = 0; q < VEC / 4; ++q) {
-                const int chunk = (vc * (VEC / 4) + q) ^ (row & SW);
-                const float4 v = *reinterpret_cast<const float4*>(ct + row * BNW + (chunk << 2));
-                f[q * 4 + 0] = v.x; f[q * 4 + 1] = v.y; f[q * 4 + 2] = v.z; f[q * 4 + 3] = v.w;
-            }
-            if (mask) {
-                const uint4 mv = *reinterpret_cast<const uint4*>(mask + o);
-                const T* me = reinterpret_cast<const T*>(&mv);
-                if (!gf.special) {
-#pragma unroll
-                    for (int q = 0; q < VEC; ++q) f[q] *= eg_grad_apply(Elt<T>::ld(me + q), gf);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < VEC; ++q) f[q] *= eg_act_grad_from_out(Elt<T>::ld(me + q), p.mask_act, p.mask_slope);
-                }
-            }
-            uint4 ov;
-            T* oe = reinterpret_cast<T*>(&ov);
-#pragma unroll
-            for (int q = 0; q < VEC; ++q) Elt<T>::st(oe + q, f[q]);
-            *reinterpret_cast<uint4*>(reinterpret_cast<T*>(p.dst) + o) = ov;
-        }
+        for (int q = 0; q < N; ++q) f[q] *= eg_act_grad_from_out(Elt<T>::ld(me + q), p.mask_act, p.mask_slope);
     }
 }
 
-// Epilogue operands fetched ahead of the last K step (igemm_nt_buf): 1/sigma per accumulator row block, the bias of the lane's 4 x TN
-// columns and the activation-gradient mask vectors of the first PF store iterations -- their global-load latency (the epilogue's
-// critical path: ~40 % of a 16-step launch) overlaps the last MFMA block and the LDS staging.
+template <int BYTES> struct NtBits;
+template <> struct NtBits<16> { typedef uint4 type; };
+template <> struct NtBits<8> { typedef uint2 type; };
+template <> struct NtBits<4> { typedef unsigned type; };
+template <> struct NtBits<2> { typedef unsigned short type; };
+template <typename T, int N> using NtVec = typename NtBits<N * sizeof(T)>::type;      // N elements of T as one load / store
+
+template <typename T, int N>
+__device__ __forceinline__ void nt_epi_store(T* dst, const float* f) {
+    NtVec<T, N> ov;
+    T* oe = reinterpret_cast<T*>(&ov);
+#pragma unroll
+    for (int q = 0; q < N; ++q) Elt<T>::st(oe + q, f[q]);
+    *reinterpret_cast<NtVec<T, N>*>(dst) = ov;
+}
+
+// Epilogue operands fetched ahead of the last K step: sigma per accumulator row block, the bias of the lane's 4 x TN columns and the
+// activation-gradient mask vectors of the first PF store iterations -- their global-load latency (the epilogue's critical path: ~40 %
+// of a 16-step launch) overlaps the last MFMA block and the LDS staging.
 template <typename T, int TM, int TN, int PF>
 struct NtEpiPre {
-    float inv_sigma[TM];
+    float sigma[TM];
+    int m_first;      // PF = 0 (nt_epi_fetch_reg): nothing runs between fetch and use, so nt_epi_stage reads sigma where it is used (row m_first + 16 i)
     float bias[TN][4];
     uint4 mask[PF > 0 ? PF : 1];
 };
 
+// row0 / col0: first row / first window column of the calling wave's accumulators; nw0: global column of the window's first column;
+// NT threads per workgroup.  Rows beyond M read the last row's sigma, columns beyond N no bias (neither is stored).
+// This function and nt_epilogue_lds_pre keep the text they had before the epilogue was folded into the pieces above: the 8-wave
+// kernels sit at their register limits, and with the pieces their input-patch instantiations spilled two more SGPRs and the unsplit
+// bf16 launches of igemm_nt8s ran 0-2 % slower (profiles/nt_epilogue_ab.txt).
 template <typename T, int BM, int BNW, int TM, int TN, int NT, int PF>
 __device__ __forceinline__ void nt_epi_prefetch(NtEpiPre<T, TM, TN, PF>& e, const NtParams& p, const NtPhase& ph, int m0, int nw0, int row0, int col0,
                                                 int tid, int frow, int fq) {
@@ -221,7 +206,7 @@ __device__ __forceinline__ void nt_epi_prefetch(NtEpiPre<T, TM, TN, PF>& e, cons
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
         const int mrow = min(m0 + row0 + i * 16 + frow, p.M - 1);
-        e.inv_sigma[i] = p.sigma ? p.sigma[p.sigma_rows ? mrow / p.sigma_rows : 0] : 1.f;
+        e.sigma[i] = p.sigma ? p.sigma[p.sigma_rows ? mrow / p.sigma_rows : 0] : 1.f;
     }
 #pragma unroll
     for (int j = 0; j < TN; ++j)
@@ -246,37 +231,108 @@ __device__ __forceinline__ void nt_epi_prefetch(NtEpiPre<T, TM, TN, PF>& e, cons
     }
 }
 
-// nt_epilogue_lds with the operands of NtEpiPre (same arithmetic, same results)
-// first half of nt_epilogue_lds_pre: the accumulators with 1/sigma, bias and activation applied go to the fp32 tile in LDS
-template <typename T, int BNW, int TM, int TN, int PF>
-__device__ __forceinline__ void nt_epilogue_stage_pre(const NtEpiPre<T, TM, TN, PF>& e, const NtParams& p, f32x4 (&acc)[TM][TN], char* smem, int nw0,
-                                                      int row0, int col0, int frow, int fq) {
+// the register-staged kernel's form (PF = 0): the lane's bias; sigma is read by nt_epi_stage.  m_first / n_first: row / column of acc[0][0][0]
+template <typename T, int TM, int TN>
+__device__ __forceinline__ void nt_epi_fetch_reg(NtEpiPre<T, TM, TN, 0>& e, const NtParams& p, int m_first, int n_first) {
+    e.m_first = m_first;
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int n = n_first + j * 16 + r;
+            e.bias[j][r] = p.bias && n < p.N ? nt_bias_at(p, n) : 0.f;
+        }
+}
+
+// 16-byte chunk `chunk` of row `row` of the fp32 BM x BNW tile in LDS
+template <int BNW>
+__device__ __forceinline__ float* nt_tile_at(float* ct, int row, int chunk) {
     constexpr int SW = BNW / 4 < 32 ? BNW / 4 - 1 : 31;     // 16-byte fp32 chunks per tile row - 1
+    return ct + row * BNW + ((chunk ^ (row & SW)) << 2);
+}
+// the VEC values of vector column vc of a row
+template <int BNW, int VEC>
+__device__ __forceinline__ void nt_tile_row(float* ct, int row, int vc, float* f) {
+#pragma unroll
+    for (int q = 0; q < VEC / 4; ++q) {
+        const float4 v = *reinterpret_cast<const float4*>(nt_tile_at<BNW>(ct, row, vc * (VEC / 4) + q));
+        f[q * 4 + 0] = v.x; f[q * 4 + 1] = v.y; f[q * 4 + 2] = v.z; f[q * 4 + 3] = v.w;
+    }
+}
+
+// the accumulators with 1/sigma, bias and activation applied go to the fp32 tile in LDS.  Callers __syncthreads() before (the K loop's
+// LDS is reused) and after.
+template <typename T, int BNW, int TM, int TN, int PF>
+__device__ __forceinline__ void nt_epi_stage(const NtEpiPre<T, TM, TN, PF>& e, const NtParams& p, f32x4 (&acc)[TM][TN], char* smem, int nw0, int row0,
+                                             int col0, int frow, int fq) {
     float* ct = reinterpret_cast<float*>(smem);
     const EgActFast af = eg_act_fast(p.act, p.slope);
     eg_if_fast(af.special, [&](auto fast) {
+        EgActFast a = af;
+        a.special = !decltype(fast)::value;             // a compile-time constant inside nt_epi_finish
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const int row = row0 + i * 16 + frow;
-            const float inv_sigma = p.sigma ? 1.f / e.inv_sigma[i] : 1.f;
+            const float inv_sigma = nt_inv_sigma(p, PF > 0 ? e.sigma[i] : nt_sigma_at(p, min(e.m_first + i * 16, p.M - 1)));
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 const int nl = col0 + j * 16 + fq * 4;
                 float4 v;
                 float* ve = reinterpret_cast<float*>(&v);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float x = __fmul_rn(acc[i][j][r], inv_sigma);
-                    if (p.bias && nw0 + nl + r < p.N) x = __fadd_rn(x, e.bias[j][r]);
-                    if constexpr (decltype(fast)::value) ve[r] = eg_act_apply(x, af);
-                    else ve[r] = eg_act(x, p.act, p.slope);
-                }
-                *reinterpret_cast<float4*>(ct + row * BNW + (((nl >> 2) ^ (row & SW)) << 2)) = v;
+                for (int r = 0; r < 4; ++r) ve[r] = nt_epi_finish(acc[i][j][r], inv_sigma, p.bias && nw0 + nl + r < p.N, e.bias[j][r], p, a);
+                *reinterpret_cast<float4*>(nt_tile_at<BNW>(ct, row, nl >> 2)) = v;
             }
         }
     });
 }
 
+// the row walk over the staged tile: thread (vr, vc) takes columns nw0 + vc * VEC .. + VEC - 1 of rows vr, vr + RPP, ...: the row's values
+// times the mask (its first PF vectors come from e), then store(o, f, mv) with o the NHWC offset, f the VEC values and mv the mask vector
+// (zeros without a mask).  RAGGED: rows beyond M and columns beyond N are skipped; otherwise the tile is whole.
+template <typename T, int BM, int BNW, int NT, bool RAGGED, int TM, int TN, int PF, typename F>
+__device__ __forceinline__ void nt_epi_rows(const NtEpiPre<T, TM, TN, PF>& e, const NtParams& p, const NtPhase& ph, char* smem, int m0, int nw0, int tid,
+                                            F&& store) {
+    constexpr int VEC = Elt<T>::VEC;
+    constexpr int VPR = BNW / VEC, RPP = NT / VPR, NIT = BM / RPP;
+    // e.mask[it] needs the whole loop unrolled; without it (PF = 0: the register-staged kernel, its STAT instantiations too, which used to
+    // unroll fully) 4 rows in flight keep the registers low
+    constexpr int UNR = PF > 0 || NIT < 4 ? NIT : 4;
+    float* ct = reinterpret_cast<float*>(smem);
+    const EgGradFast gf = eg_grad_fast(p.mask_act, p.mask_slope);
+    const int vc = tid % VPR, vr = tid / VPR;
+    const T* __restrict__ mask = reinterpret_cast<const T*>(p.mask);
+    const int n = nw0 + vc * VEC;
+    if (RAGGED && n >= p.N) return;
+#pragma unroll UNR
+    for (int it = 0; it < NIT; ++it) {
+        const int row = vr + it * RPP;
+        const int m = m0 + row;
+        if (RAGGED && m >= p.M) break;
+        const size_t o = nt_out_off(p, m, ph.ooy, ph.oox, n);
+        float f[VEC];
+        nt_tile_row<BNW, VEC>(ct, row, vc, f);
+        uint4 mv = make_uint4(0, 0, 0, 0);
+        if (mask) {
+            mv = it < PF ? e.mask[it < PF ? it : 0] : *reinterpret_cast<const uint4*>(mask + o);
+            nt_epi_mask<T, VEC>(f, reinterpret_cast<const T*>(&mv), p, gf);
+        }
+        store(o, f, mv);
+    }
+}
+
+// the epilogue through LDS of the register-staged kernel (PF = 0), made of the pieces
+template <typename T, int BM, int BNW, int TM, int TN, int NT>
+__device__ __forceinline__ void nt_epilogue_lds_reg(const NtEpiPre<T, TM, TN, 0>& e, const NtParams& p, const NtPhase& ph, f32x4 (&acc)[TM][TN], char* smem,
+                                                    int m0, int nw0, int row0, int col0, int tid, int frow, int fq) {
+    nt_epi_stage<T, BNW, TM, TN, 0>(e, p, acc, smem, nw0, row0, col0, frow, fq);
+    __syncthreads();
+    nt_epi_rows<T, BM, BNW, NT, true>(e, p, ph, smem, m0, nw0, tid, [&](size_t o, float* f, const uint4&) {
+        nt_epi_store<T, Elt<T>::VEC>(reinterpret_cast<T*>(p.dst) + o, f);
+    });
+}
+
+// the same for the LDS-DMA kernels (igemm_nt_buf, igemm_nt8s, igemm_nt8h; PF > 0), in its earlier text: see nt_epi_prefetch
 template <typename T, int BM, int BNW, int TM, int TN, int NT, int PF>
 __device__ __forceinline__ void nt_epilogue_lds_pre(const NtEpiPre<T, TM, TN, PF>& e, const NtParams& p, const NtPhase& ph, f32x4 (&acc)[TM][TN],
                                                     char* smem, int m0, int nw0, int row0, int col0, int tid, int frow, int fq) {
@@ -290,7 +346,7 @@ __device__ __forceinline__ void nt_epilogue_lds_pre(const NtEpiPre<T, TM, TN, PF
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const int row = row0 + i * 16 + frow;
-            const float inv_sigma = p.sigma ? 1.f / e.inv_sigma[i] : 1.f;
+            const float inv_sigma = p.sigma ? 1.f / e.sigma[i] : 1.f;
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 const int nl = col0 + j * 16 + fq * 4;
@@ -362,15 +418,11 @@ __device__ __forceinline__ void nt_epilogue_lds_stat(const NtEpiPre<T, TM, TN, P
                                                      int tiles_n) {
     constexpr int VEC = Elt<T>::VEC;
     static_assert(VEC == 8, "16-bit element types");
-    const int OWm = (1 << p.lOW) - 1, OHm = (1 << p.lOH) - 1;
-    constexpr int SW = BNW / 4 < 32 ? BNW / 4 - 1 : 31;
     float* ct = reinterpret_cast<float*>(smem);
-    const EgGradFast gf = eg_grad_fast(p.mask_act, p.mask_slope);
-    nt_epilogue_stage_pre<T, BNW, TM, TN, PF>(e, p, acc, smem, nw0, row0, col0, frow, fq);
+    nt_epi_stage<T, BNW, TM, TN, PF>(e, p, acc, smem, nw0, row0, col0, frow, fq);
     __syncthreads();
-    constexpr int VPR = BNW / VEC, RPP = NT / VPR, NIT = BM / RPP;
+    constexpr int VPR = BNW / VEC, RPP = NT / VPR;
     const int vc = tid % VPR, vr = tid / VPR;
-    const T* __restrict__ mask = reinterpret_cast<const T*>(p.mask);
     const T* __restrict__ aux = reinterpret_cast<const T*>(p.stat_aux);
     const int n = nw0 + vc * VEC;
     const int mode = p.stat_mode;
@@ -394,40 +446,11 @@ __device__ __forceinline__ void nt_epilogue_lds_stat(const NtEpiPre<T, TM, TN, P
     }
     const EgGradFast sgf = eg_grad_fast(p.stat_act, p.stat_slope);
     const float inv_slope = p.stat_slope != 0.f ? 1.f / p.stat_slope : 1.f;
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int row = vr + it * RPP;
-        const int m = m0 + row;
-        const int b = m >> (p.lOW + p.lOH);
-        const int y = ((m >> p.lOW) & OHm) * p.osy + ph.ooy;
-        const int x = (m & OWm) * p.osx + ph.oox;
-        const size_t o = (((size_t)b * p.DH + y) * p.DW + x) * p.N + n;
-        float f[VEC];
-#pragma unroll
-        for (int q = 0; q < VEC / 4; ++q) {
-            const int chunk = (vc * (VEC / 4) + q) ^ (row & SW);
-            const float4 v = *reinterpret_cast<const float4*>(ct + row * BNW + (chunk << 2));
-            f[q * 4 + 0] = v.x; f[q * 4 + 1] = v.y; f[q * 4 + 2] = v.z; f[q * 4 + 3] = v.w;
-        }
-        uint4 mv = make_uint4(0, 0, 0, 0);
-        if (mask) {
-            mv = it < PF ? e.mask[it < PF ? it : 0] : *reinterpret_cast<const uint4*>(mask + o);
-            const T* me = reinterpret_cast<const T*>(&mv);
-            if (!gf.special) {
-#pragma unroll
-                for (int q = 0; q < VEC; ++q) f[q] *= eg_grad_apply(Elt<T>::ld(me + q), gf);
-            } else {
-#pragma unroll
-                for (int q = 0; q < VEC; ++q) f[q] *= eg_act_grad_from_out(Elt<T>::ld(me + q), p.mask_act, p.mask_slope);
-            }
-        }
-        uint4 ov;
-        T* oe = reinterpret_cast<T*>(&ov);
+    nt_epi_rows<T, BM, BNW, NT, false>(e, p, ph, smem, m0, nw0, tid, [&](size_t o, float* f, const uint4& mv) {
         if (mode == EG_STAT_MOMENTS) {
 #pragma unroll
             for (int q = 0; q < VEC; ++q) {
-                Elt<T>::st(oe + q, f[q]);
-                const float d = Elt<T>::ld(oe + q) - k0[q];
+                const float d = round_t(f[q]) - k0[q];
                 s1[q] += d;
                 s2[q] = fmaf(d, d, s2[q]);
             }
@@ -439,7 +462,7 @@ __device__ __forceinline__ void nt_epilogue_lds_stat(const NtEpiPre<T, TM, TN, P
                 const float z = Elt<T>::ld(ze + q);
                 const float xh = (z - k0[q]) * k1[q];
                 const float dy = round_t(f[q]) * eg_grad_apply(fmaf(z, k2[q], k3[q]), sgf);      // the forward's activation input: z * (g * is) + (b - mu * g * is)
-                Elt<T>::st(oe + q, dy);
+                f[q] = dy;
                 s1[q] += dy;
                 s2[q] = fmaf(dy, xh, s2[q]);
             }
@@ -447,16 +470,15 @@ __device__ __forceinline__ void nt_epilogue_lds_stat(const NtEpiPre<T, TM, TN, P
             const T* me = reinterpret_cast<const T*>(&mv);
 #pragma unroll
             for (int q = 0; q < VEC; ++q) {
-                Elt<T>::st(oe + q, f[q]);
-                const float g = Elt<T>::ld(oe + q);
+                const float g = round_t(f[q]);
                 float a = Elt<T>::ld(me + q);
                 a = a > 0.f ? a : a * inv_slope;
                 s1[q] += g;
                 s2[q] = fmaf(g, a - k0[q], s2[q]);
             }
         }
-        *reinterpret_cast<uint4*>(reinterpret_cast<T*>(p.dst) + o) = ov;
-    }
+        nt_epi_store<T, VEC>(reinterpret_cast<T*>(p.dst) + o, f);
+    });
     __syncthreads();                                   // every row of the tile has been read: rows 1.. become the reduction scratch
     float* red = ct + BNW;                             // [2][RPP][BNW]; row 0 of the tile (the pivots) stays
 #pragma unroll

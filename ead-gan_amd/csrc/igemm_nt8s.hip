@@ -507,17 +507,15 @@ __global__ __launch_bounds__(512) void igemm_nt8s_kernel(const NtParams p, const
             for (int j = 0; j < TN; ++j) acc[i][j] = sum[i][j];
         __syncthreads();                               // the flag word is read; the epilogue stages through the same LDS
     }
-    if constexpr (STAT) {
-        // column statistics of the stored tile (eg_epilogue.stat_mode)
-        NtEpiPre<T, TM, TN, 8> epi0;
-        nt_epi_prefetch<T, BM, 128, TM, TN, 512, 8>(epi0, p, ph, m0, n0, wm * TM * 16, wn * 64, tid, frow, fq);
-        nt_epilogue_lds_stat<T, BM, 128, TM, TN, 512, 8>(epi0, p, ph, acc, smem, m0, n0, wm * TM * 16, wn * 64, tid, frow, fq, phase * tiles_m + m_tile,
-                                                         n_tile, tiles_n);
-        return;
-    }
     constexpr int PF = 8;
     NtEpiPre<T, TM, TN, PF> epi;
     nt_epi_prefetch<T, BM, 128, TM, TN, 512, PF>(epi, p, ph, m0, n0, wm * TM * 16, wn * 64, tid, frow, fq);
+    if constexpr (STAT) {
+        // column statistics of the stored tile (eg_epilogue.stat_mode)
+        nt_epilogue_lds_stat<T, BM, 128, TM, TN, 512, PF>(epi, p, ph, acc, smem, m0, n0, wm * TM * 16, wn * 64, tid, frow, fq, phase * tiles_m + m_tile,
+                                                          n_tile, tiles_n);
+        return;
+    }
     if (PROF) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); pe[0] = __builtin_amdgcn_s_memtime(); }
     nt_epilogue_lds_pre<T, BM, 128, TM, TN, 512, PF>(epi, p, ph, acc, smem, m0, n0, wm * TM * 16, wn * 64, tid, frow, fq);
     if (PROF) pe[1] = __builtin_amdgcn_s_memtime();

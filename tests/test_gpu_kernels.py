@@ -626,7 +626,7 @@ def test_spectral_norm_multi_layer_launch_matches_single():
 
 
 # eg_epilogue.nt_variant values (include/eadgan_hip.h EG_NT_*) -> label eg_igemm_nt_tile reports for the 128-column cases below
-NT_REG, NT_BUF128, NT_PERS, NT_S8, NT_S8P = 1, 2, 3, 4, 5
+NT_REG, NT_BUF128, NT_PERS, NT_S8, NT_S8P, NT_S8H = 1, 2, 3, 4, 5, 6
 NT_PATCHED = (NT_S8P,)
 NT_VARIANTS = [(NT_BUF128, 128131), (NT_PERS, 128135), (NT_S8, 256147), (NT_S8P, 256149), (NT_REG, 128128)]
 
@@ -910,6 +910,106 @@ def test_igemm_shallow_single_tap_runs_on_persistent_pipeline(dtype):
     assert torch.equal(outs[0], outs[1])
     rt, at = tol(dtype, Cin)
     torch.testing.assert_close(nchw(outs[0][:16]), F.leaky_relu(F.conv2d(x[:16], rq(w, dtype) / 0.9, b), 0.1), rtol=rt, atol=at)
+
+
+NT_EPILOGUE_VARIANTS = [NT_BUF128, NT_PERS, NT_S8, NT_S8P, NT_S8H]       # each against NT_REG
+NT_EPILOGUE_SPLIT = [NT_BUF128, NT_S8]                                   # once more with two K splits
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_igemm_epilogue_operands_on_every_variant(dtype):
+    """The epilogue operands the other variant tests leave out (they use LeakyReLU only -- the fast activation and mask paths -- and no
+    bias_mod), on the smallest launch every variant can run: 18 images of 8x8, 4x4 / stride 2 / pad 1, M = 288 output rows (one 256-row
+    tile + 32 ragged rows, or two 128-row tiles + 32), 128 output columns.
+      forward 64 -> 128 channels (K = 1024): per-tape sigma (sigma_rows = 144: two tapes of nine images), a 64-entry bias with
+        bias_mod = 64, tanh;
+      backward-data of the 4x4 map into 8x8 x 128 channels (the channel counts swapped so that the output keeps 128 columns; four phases
+        with ooy / oox in {0, 1}, K = 256): the activation-gradient mask of tanh, and once of LeakyReLU.
+    Every variant is forced by hint (never -1 from nt_tile_hinted) and matches the register-staged kernel by same(); that kernel matches an
+    fp32 unfold-matmul reference of the same rounded operands within tol(dtype, K).  NT_BUF128 and NT_S8 run once more with two K splits
+    and scratch lent (the split-K epilogue launch / the reduction inside the launch): two fp32 partial sums added once are another
+    summation order than one pass over K, so these are held to the reference's tolerance, not to the bits of the unsplit kernel, and must repeat bit for bit.
+    The scalar tail of the register-staged kernel (channel counts that are no multiple of the vector width; NCHW fp32 image outputs) runs
+    with the same input and 3 output channels, tanh, bias and per-tape sigma, in both output modes: test_conv_bwd_data reaches the NCHW
+    branch through the planner, nothing else stores NHWC through it."""
+    td = ops.torch_dtype(dtype)
+    g = torch.Generator().manual_seed(27)
+    B, H, OH, C64, C128 = 18, 8, 4, 64, 128
+    sig = torch.tensor([1.3, 0.7])
+    tape = torch.arange(B) // 9
+    ws = torch.zeros(4 << 20, device=DEV, dtype=torch.float32)
+
+    def run_all(launch, shape, bwd, c, K):
+        outs = {}
+        for v in [NT_REG] + NT_EPILOGUE_VARIANTS:
+            assert nt_tile(c, dtype, bwd, v, 1) != -1, v
+            outs[v] = launch(torch.zeros(shape, device=DEV, dtype=td), dict(nt_variant=v, nt_splitk=1))
+        for v in NT_EPILOGUE_SPLIT:
+            assert nt_tile(c, dtype, bwd, v, 2) != -1, v
+            outs[v, 2], again = (launch(torch.zeros(shape, device=DEV, dtype=td), dict(nt_variant=v, nt_splitk=2, splitk_ws=ws)) for _ in range(2))
+            assert torch.equal(outs[v, 2], again), v          # the splits are summed in split order: repeatable bit for bit
+        torch.cuda.synchronize()
+        for v in NT_EPILOGUE_VARIANTS:
+            assert same(outs[v], outs[NT_REG], v, dtype, K), v
+        return outs
+
+    # forward
+    x = rq(torch.randn(B, C64, H, H, generator=g), dtype)
+    w = torch.randn(C128, C64, 4, 4, generator=g) * 0.05
+    b = torch.randn(C64, generator=g)
+    c = ops.make_conv(B, H, H, C64, C128, 4, 2, 1)
+    wp = torch.empty(ops.pack_fwd_elems(c, dtype), device=DEV, dtype=td)
+    ops.pack_fwd(c, dtype, w.to(DEV), wp)
+    xd, bd, sd = nhwc(x, dtype), b.to(DEV), sig.to(DEV)
+
+    def fwd(y, hints):
+        ops.conv_fwd(c, dtype, xd, wp, y, ops.epilogue(bias=bd, bias_mod=C64, sigma=sd, sigma_rows=9 * OH * OH, act=ops.ACT_TANH, **hints))
+        return y
+
+    cols = F.unfold(x, 4, padding=1, stride=2)                            # [B, 64 * 16, 16]
+    lin = lambda wt: (rq(wt, dtype).reshape(wt.shape[0], -1) @ cols).reshape(B, -1, OH, OH) / sig[tape][:, None, None, None]
+    want = torch.tanh(lin(w) + b.repeat(2)[None, :, None, None])
+    rt, at = tol(dtype, C64 * 16)
+    outs = run_all(fwd, (B, OH, OH, C128), 0, c, C64 * 16)
+    for key in [NT_REG] + [(v, 2) for v in NT_EPILOGUE_SPLIT]:
+        torch.testing.assert_close(nchw(outs[key]), want, rtol=rt, atol=at)
+
+    # scalar tail: 3 output channels, NHWC in the compute type and NCHW fp32
+    w3 = torch.randn(3, C64, 4, 4, generator=g) * 0.05
+    b3 = torch.randn(3, generator=g)
+    c3 = ops.make_conv(B, H, H, C64, 3, 4, 2, 1)
+    wp3 = torch.empty(ops.pack_fwd_elems(c3, dtype), device=DEV, dtype=td)
+    ops.pack_fwd(c3, dtype, w3.to(DEV), wp3)
+    want3 = torch.tanh(lin(w3) + b3[None, :, None, None])
+    y3 = torch.zeros(B, OH, OH, 3, device=DEV, dtype=td)
+    y3f = torch.zeros(B, 3, OH, OH, device=DEV, dtype=torch.float32)
+    for y, mode in ((y3, ops.OUT_NHWC), (y3f, ops.OUT_NCHW_F32)):
+        assert nt_tile(c3, dtype, 0, NT_REG, 1) != -1
+        ops.conv_fwd(c3, dtype, xd, wp3, y, ops.epilogue(bias=b3.to(DEV), sigma=sd, sigma_rows=9 * OH * OH, act=ops.ACT_TANH, out_mode=mode,
+                                                         nt_variant=NT_REG, nt_splitk=1))
+    torch.cuda.synchronize()
+    torch.testing.assert_close(nchw(y3), want3, rtol=rt, atol=at)
+    torch.testing.assert_close(y3f.cpu(), want3, rtol=rt, atol=at)
+
+    # backward-data: dY [18, 4, 4, 64] -> dX [18, 8, 8, 128]
+    dy = rq(torch.randn(B, C64, OH, OH, generator=g), dtype)
+    wb = torch.randn(C64, C128, 4, 4, generator=g) * 0.05
+    a = rq(torch.tanh(torch.randn(B, C128, H, H, generator=g)), dtype)
+    cb = ops.make_conv(B, H, H, C128, C64, 4, 2, 1)
+    wpb = torch.empty(ops.pack_bwd_elems(cb, dtype), device=DEV, dtype=td)
+    ops.pack_bwd(cb, dtype, wb.to(DEV), wpb)
+    dyd, ad = nhwc(dy, dtype), nhwc(a, dtype)
+    dxcols = rq(wb, dtype).reshape(C64, -1).t() @ dy.reshape(B, C64, OH * OH)      # [B, 128 * 16, 16]
+    dx = F.fold(dxcols, (H, H), 4, padding=1, stride=2)
+    rt, at = tol(dtype, C64 * 4)
+    for mask_act, grad in ((ops.ACT_TANH, 1.0 - a * a), (ops.ACT_LRELU, torch.where(a > 0, 1.0, 0.1))):
+        def bwd(out, hints):
+            ops.conv_bwd_data(cb, dtype, dyd, wpb, out, ops.epilogue(mask=ad, mask_act=mask_act, mask_slope=0.1, **hints))
+            return out
+
+        outs = run_all(bwd, (B, H, H, C128), 1, cb, C64 * 4)
+        for key in [NT_REG] + [(v, 2) for v in NT_EPILOGUE_SPLIT]:
+            torch.testing.assert_close(nchw(outs[key]), dx * grad, rtol=rt, atol=at)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
