@@ -3,13 +3,17 @@
 //   d(i, j) = sum_t (q[i][t] - x[j][t])^2 is an integer <= 255^2 * 32768 < 2^31.  With q' = q ^ 0x80 and x' = x ^ 0x80 read as int8 (v - 128; one
 //   XOR per four bytes) d = |q'|^2 + |x'|^2 - 2 q'.x': the dot products on the int8 MFMA (v_mfma_i32_32x32x32_i8, int32 accumulation, exact:
 //   |q'.x'| <= 2^29), the norms with v_dot4 while the operands are staged, the epilogue in uint32 (|q'|^2 + |x'|^2 <= 2^30, d <= 2^31).
-//   knn_tile_kernel    a workgroup owns KNN_TQ queries (two such tiles from KNN_WIDE_NQ queries on) and walks its slice of the database in
-//                      tiles of KNN_TR rows; per tile the dot products go to LDS and thread (query, part of the rows) offers them to a
-//                      sorted list of k packed keys (d << 32 | j) it keeps in LDS, after ONE compare with the list's last key; the lists of
-//                      a query's parts are merged before they leave
+//   knn_walk           THE tile loop: a workgroup owns KNN_TQ queries (two such tiles from KNN_WIDE_NQ queries on) and walks its slice of the
+//                      database in tiles of KNN_TR rows; per tile the dot products go to LDS and thread (query, part of the rows) offers
+//                      every distance to the selection step it was given
+//   knn_tile_kernel    the search: the offers go to a sorted list of k packed keys (d << 32 | j) in LDS, after ONE compare with the list's
+//                      last key; the lists of a query's parts are merged before they leave
 //   knn_merge_kernel   [splits][nq][k] partial lists -> the k smallest keys of a query, unpacked
 // The keys of one query are distinct and totally ordered, so the result is the same set in the same order whatever the tiling, the number
 // of slices and the order in which lists are merged: two calls give the same bits.
+// The ball count (quality.prdc): count[i] = #{ j != self0 + i : d(q[i], x[j]) <= rad[j] }, closed balls, over the same tile loop.
+//   knn_ball_kernel      the offers add d <= rad[row] into one register per thread; the parts of a query are summed -> ws[split][query]
+//   knn_ball_sum_kernel  the slices of a query -> count.  Integer sums: any order gives the same bits; nothing is zero-filled or added to.
 #include "eg_common.h"
 
 #define KNN_TQ 64                 // queries per workgroup tile; from KNN_WIDE_NQ queries on a workgroup owns two such tiles
@@ -62,17 +66,19 @@ __device__ __forceinline__ void knn_insert(unsigned long long* list, int k, unsi
     list[j * KNN_THREADS] = key;
 }
 
+// THE tile loop of this file: the workgroup's TQ queries (blockIdx.x) against its slice of the database (blockIdx.y), a tile of KNN_TR rows
+// at a time.  Per tile the exact distances d(query, row) reach thread (query sq = tid % TQ, part sp = tid / TQ of the tile's rows) one by one:
+//   sel.tile(r0, n, tid)     once per tile by every thread, before the barrier that precedes the offers (LDS the offers read is written here;
+//                            two barriers have passed since the previous tile's offers)
+//   sel.offer(row, j, d)     row of the tile, database row j = r0 + row < n, j != the excluded row; only for queries < nq
 // TQ = 64: wave w takes rows 32 w .. of the tile against all 64 queries (2 accumulators).  TQ = 128: the waves form 2 x 2, each 64 rows x 64
 // queries (4 accumulators): 4 LDS fragments per 4 MFMAs instead of 3 per 2, and a third fewer operand bytes staged per multiply-add.
-// KCAP = list capacity, k <= KCAP (1, 8 or 16).
-template <int TQ, int KCAP>
-__global__ __launch_bounds__(KNN_THREADS) void knn_tile_kernel(const unsigned char* __restrict__ q, int nq, const unsigned char* __restrict__ x, int n,
-                                                               int K, int k, long long self0, int tiles_per_split,
-                                                               unsigned long long* __restrict__ part) {
+template <int TQ, class Sel>
+__device__ __forceinline__ void knn_walk(const unsigned char* __restrict__ q, int nq, const unsigned char* __restrict__ x, int n, int K, long long self0,
+                                         int tiles_per_split, Sel& sel) {
     // stage[buf]: KNN_TR rows of x, then TQ rows of q, KNN_LD bytes each; after a tile's last step the same bytes hold dots[row][query]
     __shared__ __attribute__((aligned(16))) unsigned char stage[2][(KNN_TR + TQ) * KNN_LD];
     __shared__ int xn[KNN_TR], qn[TQ];
-    __shared__ unsigned long long lists[KCAP * KNN_THREADS];       // [k][KNN_THREADS]
     static_assert(sizeof(stage) >= KNN_TR * TQ * sizeof(int), "the dot products alias the staging buffers");
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     constexpr int RB = TQ / 64, QP = TQ / 32, PARTS = KNN_THREADS / TQ, RP = KNN_TR / PARTS;
@@ -84,9 +90,6 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_tile_kernel(const unsigned ch
     const int fr = lane & 31, fk = (lane >> 5) * 16;               // fragments: row of the 32 x 32 block, half of the k step
     const int nsteps = (K + KNN_KC - 1) / KNN_KC;
 
-    unsigned long long* mine = lists + tid;
-    for (int j = 0; j < k; ++j) mine[j * KNN_THREADS] = KNN_EMPTY;
-    unsigned long long kth = KNN_EMPTY;
     const int sq = tid % TQ, sp = tid / TQ;                        // selection: query of the tile, part of the tile's rows
     const long long qi = (long long)q0 + sq;
     const long long excl = self0 >= 0 ? self0 + qi : -1;
@@ -161,6 +164,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_tile_kernel(const unsigned ch
                 if ((tid & 7) == 0) qn[p * 32 + srow] = v;
             }
         }
+        sel.tile(r0, n, tid);
         // C layout of the 32 x 32 block (A = x rows, B = queries): column = lane & 31 = query, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
         int* dots = (int*)&stage[0][0];                            // [KNN_TR][TQ]: the last step's barrier has passed, nobody reads operands
 #pragma unroll
@@ -180,27 +184,97 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_tile_kernel(const unsigned ch
                 const long long j = r0 + row;
                 if (j >= n) break;
                 const unsigned int d = qnorm_u + (unsigned int)xn[row] - 2u * (unsigned int)dots[row * TQ + sq];
-                const unsigned long long key = ((unsigned long long)d << 32) | (unsigned int)j;
-                if (key < kth && j != excl) {
-                    knn_insert(mine, k, key);
-                    kth = mine[(k - 1) * KNN_THREADS];
-                }
+                if (j != excl) sel.offer(row, j, d);
             }
         }
     }
+}
+
+// selection step of the search: a sorted list of k packed keys (d << 32 | j) per thread in LDS, ONE compare with its last key per offer
+struct KnnLists {
+    unsigned long long* mine;                                      // slot j at mine[j * KNN_THREADS]
+    unsigned long long kth;
+    int k;
+    __device__ __forceinline__ void tile(long long, int, int) {}
+    __device__ __forceinline__ void offer(int, long long j, unsigned int d) {
+        const unsigned long long key = ((unsigned long long)d << 32) | (unsigned int)j;
+        if (key < kth) {
+            knn_insert(mine, k, key);
+            kth = mine[(k - 1) * KNN_THREADS];
+        }
+    }
+};
+
+// KCAP = list capacity, k <= KCAP (1, 8 or 16).
+template <int TQ, int KCAP>
+__global__ __launch_bounds__(KNN_THREADS) void knn_tile_kernel(const unsigned char* __restrict__ q, int nq, const unsigned char* __restrict__ x, int n,
+                                                               int K, int k, long long self0, int tiles_per_split,
+                                                               unsigned long long* __restrict__ part) {
+    __shared__ unsigned long long lists[KCAP * KNN_THREADS];       // [k][KNN_THREADS]
+    constexpr int PARTS = KNN_THREADS / TQ;
+    const int tid = threadIdx.x, sq = tid % TQ, sp = tid / TQ;
+    const long long qi = (long long)blockIdx.x * TQ + sq;
+    KnnLists sel = {lists + tid, KNN_EMPTY, k};
+    for (int j = 0; j < k; ++j) sel.mine[j * KNN_THREADS] = KNN_EMPTY;
+    knn_walk<TQ>(q, nq, x, n, K, self0, tiles_per_split, sel);
     // the lists of a query's parts -> part 0's list -> part[split][query][k]
     __syncthreads();
     if (sp == 0 && qi < nq) {
         for (int o = 1; o < PARTS; ++o)
             for (int j = 0; j < k; ++j) {
                 const unsigned long long key = lists[j * KNN_THREADS + o * TQ + sq];
-                if (key >= kth) break;                             // sorted: the rest of this list is no better
-                knn_insert(mine, k, key);
-                kth = mine[(k - 1) * KNN_THREADS];
+                if (key >= sel.kth) break;                         // sorted: the rest of this list is no better
+                knn_insert(sel.mine, k, key);
+                sel.kth = sel.mine[(k - 1) * KNN_THREADS];
             }
         unsigned long long* o = part + ((size_t)blockIdx.y * nq + qi) * k;
-        for (int j = 0; j < k; ++j) o[j] = mine[j * KNN_THREADS];
+        for (int j = 0; j < k; ++j) o[j] = sel.mine[j * KNN_THREADS];
     }
+}
+
+// selection step of the ball count: the radii of the tile's rows in LDS beside the norms, ONE counter per thread across all tiles.  d < 2^31,
+// so the compare is signed and a negative radius is an empty ball.
+struct KnnBalls {
+    const int* __restrict__ rad;
+    int* radl;                                                     // [KNN_TR]
+    int count;
+    __device__ __forceinline__ void tile(long long r0, int n, int tid) {
+        if (tid < KNN_TR) radl[tid] = r0 + tid < n ? rad[r0 + tid] : -1;
+    }
+    __device__ __forceinline__ void offer(int row, long long, unsigned int d) { count += (int)d <= radl[row] ? 1 : 0; }
+};
+
+// count of the slice -> ws[split][query]
+template <int TQ>
+__global__ __launch_bounds__(KNN_THREADS) void knn_ball_kernel(const unsigned char* __restrict__ q, int nq, const unsigned char* __restrict__ x, int n,
+                                                               int K, const int* __restrict__ rad, long long self0, int tiles_per_split,
+                                                               int* __restrict__ ws) {
+    __shared__ int radl[KNN_TR], counts[KNN_THREADS];
+    constexpr int PARTS = KNN_THREADS / TQ;
+    const int tid = threadIdx.x, sq = tid % TQ, sp = tid / TQ;
+    const long long qi = (long long)blockIdx.x * TQ + sq;
+    KnnBalls sel = {rad, radl, 0};
+    knn_walk<TQ>(q, nq, x, n, K, self0, tiles_per_split, sel);
+    counts[tid] = sel.count;
+    __syncthreads();
+    if (sp == 0 && qi < nq) {
+        int c = 0;
+#pragma unroll
+        for (int o = 0; o < PARTS; ++o) c += counts[o * TQ + sq];
+        ws[(size_t)blockIdx.y * nq + qi] = c;
+    }
+}
+
+// count[i] = the sum of query i's slices: one wave per query, its lanes stride over the slices (one thread per query would walk up to
+// hundreds of slices through dependent-latency loads, 50 us at 396 slices)
+__global__ __launch_bounds__(256) void knn_ball_sum_kernel(const int* __restrict__ ws, int splits, int nq, int* __restrict__ count) {
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= nq) return;                                           // whole waves leave: the shuffles below see full waves
+    int c = 0;
+    for (int s = lane; s < splits; s += 64) c += ws[(size_t)s * nq + i];
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) c += __shfl_xor(c, o);
+    if (lane == 0) count[i] = c;
 }
 
 // one workgroup per query: round r picks the smallest key above round r - 1's (the keys of a query are distinct)
@@ -285,6 +359,31 @@ extern "C" int eg_knn_u8(const unsigned char* q, int nq, const unsigned char* x,
     }
 #undef KNN_LAUNCH
     hipLaunchKernelGGL(knn_merge_kernel, dim3(nq), dim3(256), 0, (hipStream_t)s, (const unsigned long long*)ws, splits, nq, k, dist, idx);
+    EG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t eg_ball_count_ws_bytes(int nq, int n) {
+    if (nq < 1 || n < 1) return 0;
+    return (size_t)eg_knn_splits(nq, n) * (size_t)nq * sizeof(int);
+}
+
+extern "C" int eg_ball_count_u8(const unsigned char* q, int nq, const unsigned char* x, int n, int K, const int* rad, long long self0, void* ws,
+                                int* count, eg_stream_t s) {
+    EG_REQUIRE(q && x && rad && ws && count, "eg_ball_count_u8: null pointer");
+    EG_REQUIRE(nq >= 1 && n >= 1, "eg_ball_count_u8: need nq >= 1 and n >= 1");
+    EG_REQUIRE(K >= 64 && K <= 32768 && K % 64 == 0, "eg_ball_count_u8: the row length K must be a multiple of 64 in 64 .. 32768 (K = %d)", K);
+    EG_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)x & 15) == 0, "eg_ball_count_u8: q and x must be 16-byte aligned");
+    EG_REQUIRE(((uintptr_t)rad & 3) == 0 && ((uintptr_t)ws & 3) == 0 && ((uintptr_t)count & 3) == 0,
+               "eg_ball_count_u8: rad, ws and count must be 4-byte aligned");
+    const int tps = knn_tiles_per_split(nq, n), splits = eg_knn_splits(nq, n);
+    const int tq = knn_wg_queries(nq), qt = cdiv(nq, tq);
+    EG_REQUIRE(splits <= 65535, "eg_ball_count_u8: too many slices");
+    if (tq == KNN_TQ)
+        hipLaunchKernelGGL((knn_ball_kernel<KNN_TQ>), dim3(qt, splits), dim3(KNN_THREADS), 0, (hipStream_t)s, q, nq, x, n, K, rad, self0, tps, (int*)ws);
+    else
+        hipLaunchKernelGGL((knn_ball_kernel<2 * KNN_TQ>), dim3(qt, splits), dim3(KNN_THREADS), 0, (hipStream_t)s, q, nq, x, n, K, rad, self0, tps, (int*)ws);
+    hipLaunchKernelGGL(knn_ball_sum_kernel, dim3(cdiv(nq, 4)), dim3(256), 0, (hipStream_t)s, (const int*)ws, splits, nq, count);
     EG_LAUNCH_CHECK();
     return 0;
 }

@@ -1045,3 +1045,35 @@ def knn_u8(queries, database, k, self0=-1, out=None):
     ws = torch.empty(lib().query("eg_knn_ws_bytes", nq, n, k) // 8, device=queries.device, dtype=torch.int64)
     lib().call("eg_knn_u8", _p(queries), nq, _p(database), n, K, k, self0, _p(ws), _p(dist), _p(idx), _stream())
     return dist, idx
+
+
+# ---- how many balls contain a row ---------------------------------------------------------
+def ball_count_ws_bytes(nq, n) -> int:
+    """bytes of the per-slice counts eg_ball_count_u8 needs for (nq, n): knn_splits(nq, n) * nq * 4"""
+    return lib().query("eg_ball_count_ws_bytes", int(nq), int(n))
+
+
+def ball_count_u8(queries, database, radii, self0=-1, out=None):
+    """-> count, int32 [nq] on the device: per row of ``queries`` the number of rows j of ``database`` whose CLOSED ball contains it,
+    d(query, database[j]) <= radii[j], by the exact squared L2 distance of ``knn_u8``.  ``radii``: a contiguous int32 device tensor [n];
+    a negative radius is an empty ball.  ``self0 >= 0``: query i is database row self0 + i and is not counted in its own ball.
+    ``out``: a contiguous int32 device tensor [nq] to write instead of a new one."""
+    for name, t in (("queries", queries), ("database", database)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() >= 2 and t.is_contiguous()):
+            raise ValueError(f"ball_count_u8: {name} must be a contiguous uint8 device tensor [rows, ...]")
+    nq, n = int(queries.shape[0]), int(database.shape[0])
+    K = queries[0].numel() if nq else 0
+    if nq < 1 or n < 1 or database[0].numel() != K or queries.device != database.device:
+        raise ValueError(f"ball_count_u8: queries {tuple(queries.shape)} and database {tuple(database.shape)} must have rows of one length on one device")
+    if K % 64 or not 64 <= K <= 32768:
+        raise ValueError(f"ball_count_u8: the row length must be a multiple of 64 in 64 .. 32768, got {K}")
+    if not (isinstance(radii, torch.Tensor) and radii.is_cuda and radii.dtype == torch.int32 and tuple(radii.shape) == (n,) and radii.is_contiguous()
+            and radii.device == database.device):
+        raise ValueError(f"ball_count_u8: radii must be a contiguous int32 device tensor [{n}], one radius per database row")
+    if out is None:
+        out = torch.empty(nq, device=queries.device, dtype=torch.int32)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int32 and tuple(out.shape) == (nq,) and out.is_contiguous()):
+        raise ValueError(f"ball_count_u8: out must be a contiguous int32 device tensor [{nq}]")
+    ws = torch.empty(lib().query("eg_ball_count_ws_bytes", nq, n) // 4, device=queries.device, dtype=torch.int32)
+    lib().call("eg_ball_count_u8", _p(queries), nq, _p(database), n, K, _p(radii), int(self0), _p(ws), _p(out), _stream())
+    return out

@@ -19,6 +19,14 @@ over the uint8 datasets (ops.knn_u8: integer squared L2 distances on the int8 MF
 * ``neighbour_grid`` / ``save_neighbours``       the figure: every query beside its nearest dataset images
 * ``nearest_training_images`` / ``nn_generator`` the two for a generator of an MNIST or CelebA run
 
+Fidelity and diversity apart: the k-NN-ball scores over the same exact distances (ops.ball_count_u8 counts, per row, the closed
+balls of the other set that contain it):
+
+* ``knn_radii(images, k)``                       the distance from every image to its k-th nearest other image of the set
+* ``prdc(real, fake, k)``                        precision and recall (Kynkaanniemi et al. 2019), density and coverage (Naeem et al. 2020)
+* ``prdc_generator(kind, generator, inputs)``    the same for a generator of an MNIST or CelebA run
+* ``NNPlan``                                     what ``train.TrainRun(..., nn=...)`` scores on checkpoint iterations
+
 Per level and set: patch statistics (ops.swd_patch_stats), then per repeat one fused gather-and-project launch (ops.swd_project: the
 descriptors, 0.6 GB per set and level at full size, never exist), one column sort per set (ops.sort_columns) and one reduction
 (ops.l1_mean).  Everything is enqueued on the current stream; ``swd`` reads the device once, at its end.  There is no CPU path.
@@ -48,6 +56,14 @@ class SWDPlan(NamedTuple):
     patches_per_image: int = 128
     repeats: int = 4
     dirs: int = 128
+
+
+class NNPlan(NamedTuple):
+    """the nearest-neighbour scores a training run writes on its checkpoint iterations (``nn_two_sample`` and ``prdc`` at ``k``):
+    ``n_images`` generated against the first ``n_images`` dataset images"""
+    n_images: int
+    k: int = 5
+    seed: int = 0
 
 
 def level_sides(H):
@@ -345,3 +361,57 @@ def nn_generator(kind, generator, inputs, n_images=8192, batch=None, seed=0):
     batch = min(64, int(n_images)) if batch is None else int(batch)
     fake = generate(kind, generator, n_images, batch, seed)
     return nn_two_sample(real_images(kind, inputs, n_images), fake)
+
+
+# ---- precision, recall, density and coverage -------------------------------------------------------------------------------
+def _check_k(k, what, *sizes):
+    k, top = int(k), min(16, *(int(s) - 1 for s in sizes))
+    if not 1 <= k <= top:
+        raise ValueError(f"quality.{what}: k = {k} must be in 1 .. min(16, rows - 1) = {top} (sets of {', '.join(str(int(s)) for s in sizes)} rows)")
+    return k
+
+
+def knn_radii(images, k=5):
+    """-> int32 [N] on the device: the exact squared L2 distance from every image (float in [-1, 1] through ``to_u8``, or uint8) to its
+    ``k``-th nearest OTHER image of the set -- ``knn_u8(S, S, k, self0=0)[0][:, k - 1]``, the radius of its k-NN ball"""
+    rows = _u8_rows(images, "images")
+    k = _check_k(k, "knn_radii", rows.shape[0])
+    return ops.knn_u8(rows, rows, k, self0=0)[0][:, k - 1].contiguous()
+
+
+def prdc(real, fake, k=5):
+    """Improved precision and recall (Kynkaanniemi et al. 2019) and density and coverage (Naeem et al. 2020) between ``real`` [N, C, H, W]
+    and ``fake`` [M, C, H, W] (float in [-1, 1] or uint8; N != M is allowed) over the exact integer distances d between their bytes
+    -> {"precision", "recall", "density", "coverage"}, Python floats, each exactly count / denominator.  With rad_k(S)[j] = the distance
+    from S[j] to its k-th nearest other row of S (``knn_radii``):
+
+        precision = #{ i : fake[i] lies in the ball of some real row } / M
+        density   = sum_i #{ j : fake[i] lies in the ball of real[j] } / (k M)               (can exceed 1)
+        recall    = #{ j : real[j] lies in the ball of some fake row } / N
+        coverage  = #{ j : the nearest fake row of real[j] lies in the ball of real[j] } / N
+
+    The balls are CLOSED, as in both papers: a lies in the ball of S[j] iff d(a, S[j]) <= rad_k(S)[j].  (Naeem et al.'s published code
+    compares with <; on continuous features the two agree, on integer distances they do not.)  Five device calls -- two radii searches,
+    two ball counts (ops.ball_count_u8) and one ``knn_u8(real, fake, 1)`` -- and one host read, of the four integer sums."""
+    A, B = _u8_rows(real, "real"), _u8_rows(fake, "fake")
+    if A.shape[1:] != B.shape[1:] or A.device != B.device:
+        raise ValueError(f"prdc: the two sets must hold images of one shape on one device, got {tuple(A.shape)} and {tuple(B.shape)}")
+    N, M = int(A.shape[0]), int(B.shape[0])
+    k = _check_k(k, "prdc", N, M)
+    rad_real = ops.knn_u8(A, A, k, self0=0)[0][:, k - 1].contiguous()
+    rad_fake = ops.knn_u8(B, B, k, self0=0)[0][:, k - 1].contiguous()
+    in_real = ops.ball_count_u8(B, A, rad_real)                               # [M]: real balls around every fake row
+    in_fake = ops.ball_count_u8(A, B, rad_fake)                               # [N]: fake balls around every real row
+    nearest = ops.knn_u8(A, B, 1)[0][:, 0]
+    sums = torch.stack(((in_real > 0).sum(), in_real.sum(dtype=torch.int64), (in_fake > 0).sum(), (nearest <= rad_real).sum())).cpu()   # THE host read
+    p, d, r, c = (int(v) for v in sums)
+    return {"precision": p / M, "recall": r / N, "density": d / (k * M), "coverage": c / N}
+
+
+def prdc_generator(kind, generator, inputs, n_images=8192, k=5, batch=None, seed=0):
+    """``prdc`` of ``real_images(kind, inputs, n_images)`` against ``generate(kind, generator, n_images, batch, seed)``; ``batch`` as in
+    ``swd_generator``"""
+    _family(kind, "prdc_generator")
+    batch = min(64, int(n_images)) if batch is None else int(batch)
+    fake = generate(kind, generator, n_images, batch, seed)
+    return prdc(real_images(kind, inputs, n_images), fake, k)

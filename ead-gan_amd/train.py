@@ -138,6 +138,11 @@ def swd_seed(seed, batches_done, plan_seed=0):
     return (int(seed) * 1000003 + int(batches_done) * 6151 + int(plan_seed) * 104729 + 54321) % (2 ** 32)
 
 
+def nn_seed(seed, batches_done, plan_seed=0):
+    """seed of a checkpoint iteration's generated images for the nearest-neighbour scores: ``swd_seed``'s form with constants of its own"""
+    return (int(seed) * 1000003 + int(batches_done) * 4447 + int(plan_seed) * 130003 + 98765) % (2 ** 32)
+
+
 class TrainRun:
     """``run(max_iters=None)`` continues from ``batches_done`` until ``n_epochs`` epochs of ``ceil(N / B)`` iterations are done or
     ``max_iters`` more iterations ran; ``save()`` writes ``run_state_<batches_done>.pt``; ``TrainRun.resume(path, ...)`` continues such a
@@ -159,13 +164,18 @@ class TrainRun:
     other ranks do nothing and no collective is added.  The score's one host read follows the checkpoint's ``_wait``: the device is
     already drained, it waits for the score's own launches only.
 
+    ``nn=quality.NNPlan(n_images, k=5, seed=0)`` (the same runs): on checkpoint iterations, after the SWD line if there
+    is one, rank 0 appends ``{"batches_done", "G": {"two_sample": ..., "prdc": ...}[, "G_ema": ...]}`` to ``out_dir/nn.jsonl`` --
+    ``quality.nn_two_sample`` and ``quality.prdc`` at ``k`` of ONE set of generated images per generator (seeded by ``nn_seed``) against
+    the first ``n_images`` dataset images.  The scratch generator is the SWD plan's; nothing else of the run is touched.
+
     Data parallel (``inputs.world`` > 1, the world of the trainer's ``allreduce`` / ``sync_bn``): ``graph=False`` is required; the
     iteration count, cadence, sample seeds and file names are those of one process at the global batch ``B * world``; rank 0 prints and
     writes every file, the other ranks write none (``files == []``) and print nothing but execute every ``_wait`` and keep ``history``
     / ``lines`` of their own shard.  The run adds no collective: rank 0's lines and ``losses.npy`` carry rank 0's shard losses."""
 
     def __init__(self, kind, trainer, inputs, out_dir, n_epochs, sample_interval=None, seed=0, graph=True, log_capacity=1024, log_in_graph=True,
-                 ema_samples=False, swd=None):
+                 ema_samples=False, swd=None, nn=None):
         self.plan = _plan(kind)
         if getattr(trainer, "STATE_KIND", None) != kind:
             raise ValueError(f"a {kind!r} run needs a {kind!r} trainer, got {type(trainer).__name__}")
@@ -209,17 +219,22 @@ class TrainRun:
                 raise ValueError("ema_samples: the trainer keeps no average of its generator -- call trainer.attach_ema(modules=('G', ...)) first")
             if self.rank == 0:
                 self._ema_G = _module_like(trainer.G).to(trainer.losses.device)
-        self.swd, self._swd_G = swd, None
-        if swd is not None:
+        self.swd, self.nn, self._score_G = swd, nn, None            # one scratch generator serves both plans
+        for what, plan, cls in (("swd", swd, quality.SWDPlan), ("nn", nn, quality.NNPlan)):
+            if plan is None:
+                continue
             if kind not in ("mnist", "celeba"):
-                raise ValueError(f"swd: only 'mnist' and 'celeba' runs are scored (quality.generate), not {kind!r}")
-            swd = self.swd = quality.SWDPlan(*swd)
-            if not 1 <= int(swd.n_images) <= self.n_images:
-                raise ValueError(f"swd: n_images = {swd.n_images}, the dataset has {self.n_images} images")
-            if int(swd.n_images) % min(int(trainer.B), int(swd.n_images)):          # the generator runs at the trainer's batch size
-                raise ValueError(f"swd: n_images = {swd.n_images} is no multiple of the trainer's batch size {trainer.B}")
-            if self.rank == 0:
-                self._swd_G = _module_like(trainer.G).to(trainer.losses.device)
+                raise ValueError(f"{what}: only 'mnist' and 'celeba' runs are scored (quality.generate), not {kind!r}")
+            plan = cls(*plan)
+            setattr(self, what, plan)
+            if not 1 <= int(plan.n_images) <= self.n_images:
+                raise ValueError(f"{what}: n_images = {plan.n_images}, the dataset has {self.n_images} images")
+            if int(plan.n_images) % min(int(trainer.B), int(plan.n_images)):        # the generator runs at the trainer's batch size
+                raise ValueError(f"{what}: n_images = {plan.n_images} is no multiple of the trainer's batch size {trainer.B}")
+            if self.rank == 0 and self._score_G is None:
+                self._score_G = _module_like(trainer.G).to(trainer.losses.device)
+        if self.nn is not None and not 1 <= int(self.nn.k) <= min(16, int(self.nn.n_images) - 1):
+            raise ValueError(f"nn: k = {self.nn.k} must be in 1 .. min(16, n_images - 1) for n_images = {self.nn.n_images}")
         if self.plan["minmax"]:
             dev = trainer.losses.device
             self._mm_dev = torch.zeros(4, device=dev, dtype=torch.float32)
@@ -312,19 +327,37 @@ class TrainRun:
 
     def _score(self, it):
         """one line of ``swd.jsonl``: the live generator and, where the trainer averages it, the averaged one, as scratch copies"""
-        if self._swd_G is None:
+        if self._score_G is None or self.swd is None:
             return
         tr, plan = self.trainer, self.swd
         seed = swd_seed(self.seed, it, plan.seed)
         kw = dict(n_images=plan.n_images, batch=min(int(tr.B), int(plan.n_images)), seed=seed, patches_per_image=plan.patches_per_image,
                   repeats=plan.repeats, dirs=plan.dirs)
-        G = self._swd_G
+        self._score_line("swd.jsonl", it, lambda G: quality.swd_generator(self.kind, G, self.inputs, **kw))
+
+    def _score_nn(self, it):
+        """one line of ``nn.jsonl``: the leave-one-out 1-NN two-sample test and precision / recall / density / coverage
+        of ONE set of generated images per generator against the first ``n_images`` dataset images"""
+        if self._score_G is None or self.nn is None:
+            return
+        tr, plan = self.trainer, self.nn
+        n, seed = int(plan.n_images), nn_seed(self.seed, it, plan.seed)
+        real = quality.to_u8(quality.real_images(self.kind, self.inputs, n))
+
+        def score(G):
+            fake = quality.to_u8(quality.generate(self.kind, G, n, min(int(tr.B), n), seed))
+            return {"two_sample": quality.nn_two_sample(real, fake), "prdc": quality.prdc(real, fake, plan.k)}
+        self._score_line("nn.jsonl", it, score)
+
+    def _score_line(self, name, it, score):
+        """``{"batches_done", "G": score(live generator)[, "G_ema": score(averaged generator)]}`` appended to ``out_dir/name``"""
+        tr, G = self.trainer, self._score_G
         G.load_state_dict(tr.G.state_dict())
-        line = {"batches_done": int(it), "G": quality.swd_generator(self.kind, G.train(tr.G.training), self.inputs, **kw)}
+        line = {"batches_done": int(it), "G": score(G.train(tr.G.training))}
         ema = getattr(tr, "ema", None)
         if ema is not None and "G" in ema.names:
-            line["G_ema"] = quality.swd_generator(self.kind, ema.copy_to("G", G).train(tr.G.training), self.inputs, **kw)
-        path = os.path.join(self.out_dir, "swd.jsonl")
+            line["G_ema"] = score(ema.copy_to("G", G).train(tr.G.training))
+        path = os.path.join(self.out_dir, name)
         with open(path, "a") as f:
             f.write(json.dumps(line, sort_keys=True) + "\n")
         if path not in self.files:
@@ -375,6 +408,7 @@ class TrainRun:
                 self._wait("checkpoint")
                 self._checkpoint(it)
                 self._score(it)
+                self._score_nn(it)
             self.batches_done = it + 1
             done += 1
             if do_ckpt:

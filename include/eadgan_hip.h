@@ -780,6 +780,15 @@ int eg_knn_splits(int nq, int n);
 size_t eg_knn_ws_bytes(int nq, int n, int k);
 int eg_knn_u8(const unsigned char* q, int nq, const unsigned char* x, int n, int K, int k, long long self0, void* ws, int* dist, int* idx,
               eg_stream_t s);
+/* --- how many balls contain a row (precision, recall, density and coverage).  count[i] (int32, i < nq) = the number of rows
+ * j in [0, n), j != self0 + i, with d(q[i], x[j]) <= rad[j]: q, x, d, K and self0 as for eg_knn_u8, rad [n] int32.  The balls are CLOSED
+ * (a row at exactly the radius is inside).  d < 2^31 and the compare is signed: a negative rad[j] is an empty ball, which makes rad a mask.
+ * The tile loop, the slices (eg_knn_splits) and the wave layouts are eg_knn_u8's; ws: eg_ball_count_ws_bytes(nq, n) = splits * nq * 4 bytes
+ * of per-slice counts a second kernel sums.  count and ws are written exactly once (no atomic, no zero-fill); integer sums, so two calls
+ * give the same bits.  q and x 16-byte aligned, rad, ws and count 4-byte.  Two launches, no allocation, no sync. */
+size_t eg_ball_count_ws_bytes(int nq, int n);
+int eg_ball_count_u8(const unsigned char* q, int nq, const unsigned char* x, int n, int K, const int* rad, long long self0,
+                     void* ws, int* count, eg_stream_t s);
 
 #ifdef __cplusplus
 }
