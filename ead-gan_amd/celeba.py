@@ -85,7 +85,10 @@ class _GenEngine:
         # the same layer seen from the image side as a 1x1 conv over im2col patches (K = C*16): input/weight gradients on MFMA
         self.kp = gen.channels * 16
         self.l4p = ConvRec(dtype, B, s * 8, s * 8, self.kp, W[3], 1, 1, 0, device=dev, want_bwd=False, ws=ws)
-        self.patches = torch.empty(B * (s * 8) ** 2, self.kp, device=dev, dtype=tdt)
+        # ... its weight gradient straight from d(img) where the streaming kernel takes it (16-bit, 64 x 64: ops.wgrad_img_tn, the bits of
+        # im2col_img + conv_wgrad): no patch rows exist then
+        self.wgrad_tn = engine.WGRAD_IMG_TN and ops.wgrad_img_tn_ok(dtype, gen.channels, s * 16, s * 16, W[3], 4, 2, 1)
+        self.patches = None if self.wgrad_tn else torch.empty(B * (s * 8) ** 2, self.kp, device=dev, dtype=tdt)
         # forward of the same layer as ONE GEMM over the input pixels with N = 16 taps x C columns + a col2im gather (eg_col2im_img): every
         # activation is read once instead of 16 times (4 phases x 4 taps of the implicit transposed convolution)
         self.l4g = ConvRec(dtype, B, s * 8, s * 8, W[3], self.kp, 1, 1, 0, device=dev, want_bwd=False, want_wgrad=False, ws=ws)
@@ -161,9 +164,10 @@ class _GenEngine:
             # wp[t*C + c][ci] = W[ci][c][t]   (master [128][C][4][4])
             ops.pack_strided(dt, self._p(10, "weight"), self.l4g.wp_fwd, self.kp, G_WIDTHS[3], self.l4g.Kpad_fwd, g.channels, 1, 16, self.kp)
 
-    def forward(self, noise, labels, code, training=True, sync=None):
+    def forward(self, noise, labels, code, training=True, sync=None, img_after=None):
         """``training=False``: BatchNorm with the running statistics, nothing updated (module.eval()).  ``sync`` (a dp.SyncBN):
-        batch statistics over all ranks (synchronised BatchNorm)."""
+        batch statistics over all ranks (synchronised BatchNorm).  ``img_after``: an event the LAST launch waits for -- the one that
+        rewrites ``self.img`` -- while the layers above run ahead of it (a lane chain of the caller may still read the previous image)."""
         dt, B, W = self.dtype, self.B, G_WIDTHS
         small = self.ws.small
         ops.concat_cast(dt, noise, labels, code, self.inp, B, self.cpad)
@@ -183,6 +187,7 @@ class _GenEngine:
                              training, fused)
             x = self.a[i]
         # the last transposed convolution + Tanh, in one launch where the kernel takes it: the GEMM's 48 columns per pixel stay in LDS
+        SideStream.wait(img_after)
         convt_img(dt, x, self.l4g, self.cols4, self.l4, self._p(10, "bias"), ACT_TANH, self.img, True)
         return self.img
 
@@ -215,11 +220,15 @@ class _GenEngine:
             ops.im2col_img(dt, self.dimg_z, self.patches, B, C, S, S, 4, 2, 1, self.kp)
 
         def l4_wgrad(wsw):
-            if direct:                                  # the patch rows only feed the weight gradient: built here, beside the main chain
+            if direct:                                  # d(img) * tanh' only feeds the weight gradient: formed here, beside the main chain
                 ops.act_grad_mul_bias_nchw(dimg, self.img, self.dimg_z, B, C, S * S, ACT_TANH, 0.0, wsw.small, gof("conv_blocks.10.bias"),
                                            accumulate=acc)
-                ops.im2col_img(dt, self.dimg_z, self.patches, B, C, S, S, 4, 2, 1, self.kp)
-            ns = ops.conv_wgrad(self.l4p.c, dt, self.patches, self.a[2], wsw.slab, wsw.wgs_target)
+            if direct and self.wgrad_tn:                # straight from dimg_z; the split plan of the per-tap launch below (which takes no target)
+                ns = ops.wgrad_img_tn(dt, [self.dimg_z], self.a[2], wsw.slab, B, C, S, S, W[3])
+            else:
+                if direct:
+                    ops.im2col_img(dt, self.dimg_z, self.patches, B, C, S, S, 4, 2, 1, self.kp)
+                ns = ops.conv_wgrad(self.l4p.c, dt, self.patches, self.a[2], wsw.slab, wsw.wgs_target)
             ops.wgrad_reduce(wsw.slab, ns, W[3], W[3], self.kp, 1, gof("conv_blocks.10.weight"), accumulate=acc)
         if need_wgrad:                                  # (direct: dimg_z and the patch rows feed nothing else)
             wgrad_side(side, ws, 0, l4_wgrad, "G4")
@@ -373,7 +382,11 @@ class _DiscEngine:
             ws.need_small(ops.sn_ws_floats(W[i], self.cin[i] * (16 if i else 1)))
             ws.need_small(ops.bias_grad_sn_ws_floats(NT * B * self.hw[i] ** 2, W[i], B * self.hw[i] ** 2))
         # tapes: contiguous along the batch axis
-        self.patches = torch.empty(NT * B * (S // 2) ** 2, self.kp, device=dev, dtype=tdt)
+        self.img_direct = ops.conv_img_mfma_ok(dtype, C, S, S, W[0], 4, 2, 1)
+        # layer 0's weight gradient straight from the tapes' images (ops.wgrad_img_tn: 16-bit, 64 x 64; the bits of im2col_img + conv_wgrad):
+        # with the forward direct too, no patch rows exist
+        self.wgrad_tn = engine.WGRAD_IMG_TN and self.img_direct and ops.wgrad_img_tn_ok(dtype, C, S, S, W[0], 4, 2, 1)
+        self.patches = None if self.wgrad_tn else torch.empty(NT * B * (S // 2) ** 2, self.kp, device=dev, dtype=tdt)
         self.a = [torch.empty(NT * B, self.hw[i], self.hw[i], W[i], device=dev, dtype=tdt) for i in range(4)]
         self.out = torch.empty(NT * B, self.nout, device=dev, dtype=torch.float32)
         self.dz = [torch.empty_like(t) for t in self.a]
@@ -387,7 +400,6 @@ class _DiscEngine:
         self.coef = [torch.zeros(4, device=dev, dtype=torch.float32) for _ in range(4)]
         self.imgs = [None] * NT
         self.patch_ok = [False] * NT                    # tape has its patch rows (the weight gradient of layer 0 reads them)
-        self.img_direct = ops.conv_img_mfma_ok(dtype, C, S, S, W[0], 4, 2, 1)
         self._stat = {}                                 # (layer, T) -> (row blocks, buffer) of the fused bias-gradient / coefficient sums
         self._sn_arrays = None
         self._sn(0)
@@ -461,11 +473,12 @@ class _DiscEngine:
 
     def prepare(self, t0, imgs, training=True):
         """Image-independent head start of ``forward(imgs, t0, prepared=...)``: the tapes' power iterations (in list order, like
-        consecutive D(...) calls) and the patch rows of the images that already exist (``None`` entries are left to forward).
+        consecutive D(...) calls) and the patch rows of the images that already exist (``None`` entries are left to forward; none are
+        built where the weight gradient reads the images themselves).
         The trainer runs this on a side stream while the previous sub-step is still busy."""
         for k, img in enumerate(imgs):
             self._sn_tape(t0 + k, training)
-            if img is not None:
+            if img is not None and not self.wgrad_tn:
                 self._im2col_tape(t0 + k, img)
 
     def forward(self, imgs, t0=0, training=True, prepared=None, head=True):
@@ -548,16 +561,21 @@ class _DiscEngine:
         for i in (3, 2, 1, 0):
             m = self._m(i)
             geo = g["mid"][i - 1] if i > 0 else g["l1p"]
-            x_in = sl(self.a[i - 1]) if i > 0 else sl(self.patches)
+            x_in = sl(self.a[i - 1]) if i > 0 else (None if self.wgrad_tn else sl(self.patches))
             if need_wgrad:
                 def layer_wgrad(wsw, i=i, m=m, geo=geo, x_in=x_in, fused=fused):
-                    if i == 0:
+                    if i == 0 and not self.wgrad_tn:
                         for t in range(t0, t0 + T):     # patch rows of tapes whose forward ran straight from the image
                             if not self.patch_ok[t]:
                                 self._im2col_tape(t, self.imgs[t])
                     # the weight-gradient GEMM first: the column sums below (only the slab reduce needs their coefficient) do not fit on a CU
                     # beside a resident GEMM workgroup and used to hold the chain's GEMM back by ~50 us
-                    ns = ops.conv_wgrad(geo, dt, x_in, sl(self.dz[i]), wsw.slab, wsw.wgs_target)
+                    if i == 0 and self.wgrad_tn:
+                        # straight from the tapes' images, which stay intact until the caller has this chain behind it (CelebATrainer: READERS
+                        # OF ge.img); the split plan of the per-tap launch it replaces (which takes no target)
+                        ns = ops.wgrad_img_tn(dt, self.imgs[t0:t0 + T], sl(self.dz[0]), wsw.slab, B, self.C, self.S, self.S, W[0])
+                    else:
+                        ns = ops.conv_wgrad(geo, dt, x_in, sl(self.dz[i]), wsw.slab, wsw.wgs_target)
                     if fused[0]:
                         tiles_m = fused[0] // 4         # row blocks (of 256 or 128 lattice rows: the kernel's tile height) per sub-pixel phase
                         ops.bias_grad_sn_fused(fused[1], fused[0], W[i], tiles_m, tiles_m // T, T, self.sigma[i][t0:], gof(f"main.{2 * i}.bias"), self.coef[i],
@@ -867,6 +885,19 @@ class CelebATrainer(ResidentStep):
     # Hazards a store must respect are those the read-modify-write had: a writer of pass k+1 runs behind the Adam launch (and, data
     # parallel, the all-reduce) that read the slice in pass k -- step 3's generator forward waits for evs["g"], its discriminator forward
     # joins every lane, and the iteration ends with a join.  The gradients of step 3 stay in place afterwards: callers and tests read them.
+    #
+    # READERS OF ge.img (the generated image; one buffer, written by the last launch of every generator forward).  With the layer-0 weight
+    # gradient of D read from the images themselves (_DiscEngine.wgrad_tn; before, from patch rows copied on the preparation lane) a lane
+    # chain reads it:
+    #
+    #   writer                         readers before the next writer                                   ordered by
+    #   step 1 forward (main)          step 1 D forward / G backward (main), step 2 D forward (main)    program order of the main stream
+    #                                  step 2 chain D0 (lane): wgrad_img_tn, tape 1                     step 3's LAST generator launch waits for
+    #                                                                                                   the chain's done event (evs["d0"]); the
+    #                                                                                                   layers above it do not wait
+    #   step 3 forward (main)          step 3 D forward / G backward (main), step 3 chain D0 (lane)     the join that ends the iteration
+    #
+    # self.scaled and self.real are rewritten by the next iteration's preparation lane, behind that join.
     def _buckets(self, arena):
         """(tag, lo, hi) element ranges of `arena` per layer bucket, in completion order; the ranges tile the arena"""
         eng = self.ge if arena is self.G.arena else self.de
@@ -967,8 +998,8 @@ class CelebATrainer(ResidentStep):
 
     def _step_body_pipelined(self):
         """The same iteration on five streams.  Main stream: the forward / backward-data chain of the three sub-steps, back to back.
-        Lanes 0,1: weight-gradient GEMMs with their reductions.  Preparation lane: the next sub-step's power iterations and patch
-        rows.  Optimizer lane:
+        Lanes 0,1: weight-gradient GEMMs with their reductions.  Preparation lane: the next sub-step's power iterations (and patch
+        rows, where the layer-0 weight gradient still reads them).  Optimizer lane:
         per network, behind ALL of its weight-gradient chains: (all-reduce over the ranks ->) Adam -> re-packing.  No gradient is cleared:
         every backward pass stores (WRITER TABLE above).
         The main stream never waits for an optimizer update it does not need: step 2 neither reads nor writes G, step 3 starts with
@@ -1114,6 +1145,7 @@ class CelebATrainer(ResidentStep):
             side.wait(evs["g"])                         # test hook only (see __init__): step 1's generator update still reads G's gradients
         self._pre_backward(2)
         de.backward(0, 2, self.dout[:2 * B], da.grad, side=side, head_done=fh1, store=True)
+        evs["d0"] = side.done.get("D0") if de.wgrad_tn else None                      # the chain that reads `gen` itself (READERS OF ge.img)
         update(da, self.mD, self.vD, self.lr[1], 1, True, de, key_w="dw")             # beside step 3's generator forward
 
         # the first layer reads the images themselves (ops.conv_img_mfma): the patch rows are only the weight gradient's operand and are built by
@@ -1126,7 +1158,7 @@ class CelebATrainer(ResidentStep):
         side.defer_prep(prep3)
         # ---- 3) info + affine step (:375-401): D(gen), D(scaled), D(real) batched as tapes 0,1,2 ----
         side.wait(evs["g"])                             # G's panels; its gradients have been read (optimizer lane, step 1): step 3 may store
-        gen = ge.forward(self.z, self.onehot, self.code, sync=self.sync_bn)
+        gen = ge.forward(self.z, self.onehot, self.code, sync=self.sync_bn, img_after=evs["d0"])
         side.join()                                     # D's panels, power iterations, patch rows
         out = de.forward([gen, self.scaled, self.real], 0, prepared=(False, False, False) if lazy else (False, True, True), head=not fh3)
         if fh3:

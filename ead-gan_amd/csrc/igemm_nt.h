@@ -89,6 +89,12 @@ struct Tn8Params {
 // its planner and launcher (igemm_tn8.hip), called by eg_conv_wgrad in igemm_tn.hip
 bool eg_tn8_plan(const eg_conv* c, int dtype, Tn8Params& p, int* nsplit, int wgs_target);
 template <typename T> void eg_launch_tn8(const Tn8Params& p, int nsplit, hipStream_t st);
+// swizzle key of K row `row` of a P tile staged by LDS-DMA (igemm_tn8.hip, wgrad_img_tn.hip): source block b lands in block b ^ key
+__device__ __forceinline__ int tn8_fsw(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
+
+// split plan of the per-tap kernel (igemm_tn.hip): splits and rows per split (a multiple of 32).  wgs_target 0: the plan of eg_conv_wgrad's
+// per-tap launches; > 0: that many splits, down to one 32-row step each (eg_wgrad_img_tn, which walks the same splits)
+void eg_tn_plan(const eg_conv* c, int wgs_target, int* nsplit, int* rps);
 
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 static inline int bk_of(int dtype) { return dtype == EG_F32 ? 32 : 64; }

@@ -1,6 +1,7 @@
 // igemm_tn : S[n][t][c] = sum_m P[m][n] * X[pix(m,t)][c]   (weight gradients, split over m into partial slabs; fp32 or 16-bit MFMA with
 // fp32 accumulate, like igemm.hip).  The per-tap kernel and its launcher; the parity-class kernel of the big 4x4 / stride-2 layers is
 // igemm_tn8.hip.
+#include <algorithm>
 #include <type_traits>
 
 #include "eg_common.h"
@@ -205,7 +206,7 @@ static void tn_tiles(const eg_conv* c, int* bnt, int* bct) {
     *bct = c->Cin >= 128 ? 128 : (c->Cin > 32 ? 64 : 32);
 }
 
-static void tn_plan(const eg_conv* c, int* nsplit, int* rps) {
+void eg_tn_plan(const eg_conv* c, int wgs_target, int* nsplit, int* rps) {
     const int OH = conv_out_dim(c, c->H), OW = conv_out_dim(c, c->W);
     const int M = c->B * OH * OW;
     int bnt, bct;
@@ -222,6 +223,9 @@ static void tn_plan(const eg_conv* c, int* nsplit, int* rps) {
     // (5.50 -> 5.65 ms at 512, profiles/r01_timeline_notes.md item 14).
     const int max_split = bnt * bct <= 64 * 64 ? 512 : 128;
     if (want > max_split) want = max_split;
+    // a caller's own split count (eg_wgrad_img_tn, whose tests reach one-step and ragged splits with it); eg_conv_wgrad's per-tap launches
+    // never had one and plan with 0
+    if (wgs_target > 0) want = std::min<long long>(wgs_target, std::max(1, M / 32));
     int r = round_up((int)((M + want - 1) / want), 32);
     *rps = r;
     *nsplit = cdiv(M, r);
@@ -240,7 +244,7 @@ extern "C" size_t eg_conv_wgrad_ws_bytes(const eg_conv* c, int dtype) {
     Tn8Params p8;
     if (c && !check_conv(c, dtype, NEED_CIN | NEED_COUT) && eg_tn8_plan(c, dtype, p8, &ns, 0))      // the whole-chip target splits furthest
         return (size_t)ns * c->Cout * 16 * c->Cin * sizeof(float);
-    tn_plan(c, &ns, &rps);
+    eg_tn_plan(c, 0, &ns, &rps);
     return (size_t)ns * c->Cout * c->k * c->k * c->Cin * sizeof(float);
 }
 
@@ -305,7 +309,7 @@ extern "C" int eg_conv_wgrad(const eg_conv* c, int dtype, const void* X, const v
     p.TW = c->k; p.ntaps = c->k * c->k;
     p.sy = p.sx = c->stride; p.dy0 = p.dx0 = -c->pad; p.up = c->up;
     int ns, rps, bnt, bct;
-    tn_plan(c, &ns, &rps);
+    eg_tn_plan(c, 0, &ns, &rps);
     tn_tiles(c, &bnt, &bct);
     p.rows_per_split = rps;
     if (dtype == EG_F32) launch_tn<float>(p, bnt, bct, ns, (hipStream_t)s);

@@ -46,8 +46,6 @@
 #include "eg_common.h"
 #include "igemm_nt.h"
 
-__device__ __forceinline__ int tn8_fsw(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
-
 __device__ __forceinline__ void tn8_wait(int n) {        // vmcnt(n) lgkmcnt(0) through the builtin (see igemm_nt8s.hip), n in 0..7
     switch (n) {
         case 0: __builtin_amdgcn_s_waitcnt(0 | (7 << 4)); break;

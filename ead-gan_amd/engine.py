@@ -17,6 +17,9 @@ from .ops import ACT_RELU, EG_BF16, EG_F16, EG_F32, OUT_NCHW_F32
 # whichever module, reads ``engine.<NAME>`` at call time -- never ``from .engine import <NAME>`` -- so one patch here reaches them all.
 # image-side transposed convolutions (128 / 64 -> C) as one GEMM + col2im gather (True) or as the 4-phase implicit GEMM (False)
 IMG_GEMM = True
+# weight gradient of the CelebA image-side layers straight from the fp32 images (ops.wgrad_img_tn, True) or from patch rows (im2col_img +
+# conv_wgrad, False): the same bits; read when an engine is built
+WGRAD_IMG_TN = True
 
 
 def to_categorical(y, num_columns, device=None):

@@ -362,6 +362,39 @@ def wgrad_img(dtype, imgs, P, slab, B, C, H, W, N) -> int:
     return ns.value
 
 
+def wgrad_img_tn_ok(dtype, C, H, W, N, k, stride, pad) -> bool:
+    return bool(lib().query("eg_wgrad_img_tn_ok", dtype, C, H, W, N, k, stride, pad))
+
+
+def wgrad_img_tn_plan(images, C, wgs_target=0):
+    """(splits, rows per split) of a ``wgrad_img_tn`` launch over ``images`` = tapes x batch images: the per-tap kernel's plan for their patch rows"""
+    rps = ctypes.c_int(0)
+    return lib().query("eg_wgrad_img_tn_plan", images, C, wgs_target, ctypes.byref(rps)), rps.value
+
+
+def wgrad_img_tn(dtype, imgs, P, slab, B, C, H, W, N=128, wgs_target=0) -> int:
+    """weight gradient of a CelebA image-side layer straight from the fp32 images of up to three tapes, the bits of ``im2col_img`` (Kp = 16 C) +
+    ``conv_wgrad`` over the patch rows -> number of slabs [N][16 C] written to ``slab``.  ``wgs_target``: 0 = the split plan ``conv_wgrad``
+    uses for those rows, > 0 = that many splits"""
+    im = [_p(t) for t in imgs] + [None] * (3 - len(imgs))
+    ns = ctypes.c_int(0)
+    args = ("eg_wgrad_img_tn", dtype, im[0], im[1], im[2], len(imgs), _p(P), _p(slab), B, C, H, W, N, wgs_target, ctypes.addressof(ns))
+    if RECORDER is None:
+        lib().call(*args, _stream())
+        return ns.value
+    M = len(imgs) * B * (H // 2) * (W // 2)
+    tname = {EG_BF16: "bf16", EG_F16: "f16"}[dtype]
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    _spacer()
+    e0.record()
+    lib().call(*args, _stream())
+    e1.record()
+    # fp32 images + P in, fp32 weight gradient out
+    RECORDER.append((f"wgrad_img_tn_kernel<{tname}>", 2.0 * M * N * 16 * C, e0, e1, f"tn_img B{len(imgs) * B} H{H} C{C} N{N}",
+                     float(len(imgs) * B * C * H * W * 4 + M * N * 2 + N * 16 * C * 4)))
+    return ns.value
+
+
 def convt_img_mfma_ok(dtype, C, Hin, Win, K, k, stride, pad) -> bool:
     return bool(lib().query("eg_convt_img_mfma_ok", dtype, C, Hin, Win, K, k, stride, pad))
 

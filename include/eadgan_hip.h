@@ -259,6 +259,16 @@ int eg_wgrad_img_ok(int dtype, int C, int H, int W, int N, int k, int stride, in
 int eg_wgrad_img_splits(int images, int N);          /* N = 32 / 64, and 128: the first Discriminator layer of the CelebA script (celebA/EAD-GAN_celebA.py:110) */
 int eg_wgrad_img(int dtype, const float* img0, const float* img1, const float* img2, int ntapes, const void* P, float* slab, int B, int C,
                  int H, int W, int N, int* nsplit_out, eg_stream_t s);
+/* The same sum for the CelebA layers (N = 128: Conv2d(C -> 128, 4, 2, 1), celebA/EAD-GAN_celebA.py:110, and ConvTranspose2d(128 -> C, 4, 2, 1),
+ * :90-91, in conv view) as a streaming kernel whose slabs are BIT-IDENTICAL to eg_im2col_img (Kp = 16 C) + eg_conv_wgrad over the patch rows:
+ * one workgroup per K split of the per-tap kernel's plan for those rows, P staged by LDS-DMA, the patch values picked from the staged image
+ * rows; no patch rows in HBM.  wgs_target: 0 = the plan eg_conv_wgrad uses for the patch rows (its per-tap launches take no target), > 0 =
+ * that many splits, down to one 32-row step each.  eg_wgrad_img_tn_plan returns the split count for `images` = ntapes * B images and
+ * stores the rows per split; the slab holds nsplit * 128 * 16 C floats. */
+int eg_wgrad_img_tn_ok(int dtype, int C, int H, int W, int N, int k, int stride, int pad);
+int eg_wgrad_img_tn_plan(int images, int C, int wgs_target, int* rows_per_split);
+int eg_wgrad_img_tn(int dtype, const float* img0, const float* img1, const float* img2, int ntapes, const void* P, float* slab, int B, int C,
+                    int H, int W, int N, int wgs_target, int* nsplit_out, eg_stream_t s);
 /* ConvTranspose2d(128 -> C <= 3, 4, 2, 1) from 16-bit NHWC activations a [B][Hin][Win][128] to an fp32 NCHW image [B][C][2 Hin][2 Win] in ONE
  * launch (the GEMM's columns stay in LDS): out = act(bias + transposed convolution); wp = the [16 * C][128] panel (row t * C + c) of
  * eg_pack_strided.  The Generator's last layer + Tanh (celebA.py:90-91) and the backward-to-image of the first Discriminator layer (:110).
