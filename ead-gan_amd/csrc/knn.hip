@@ -14,6 +14,12 @@
 // The ball count (quality.prdc): count[i] = #{ j != self0 + i : d(q[i], x[j]) <= rad[j] }, closed balls, over the same tile loop.
 //   knn_ball_kernel      the offers add d <= rad[row] into one register per thread; the parts of a query are summed -> ws[split][query]
 //   knn_ball_sum_kernel  the slices of a query -> count.  Integer sums: any order gives the same bits; nothing is zero-filled or added to.
+// The kernel MMD (quality.mmd) takes two more selection steps over the same tile loop:
+//   knn_ksum_kernel      the offers add exp(-d * inv_gamma[b]) into NB double registers per thread -> ws[split][query][b]
+//   knn_ksum_sum_kernel  the slices of a query -> out[query][b], in a fixed order: two calls give the same bits
+//   knn_hist_kernel      one pass of a radix select: the next digit of every distance that matches the prefix -> an LDS histogram
+//   knn_hist_reduce_kernel, knn_hist_scan_kernel  the workgroups' histograms -> 64-bit bins -> the bin that holds the rank -> the next
+//                        prefix and the rank inside it
 #include "eg_common.h"
 
 #define KNN_TQ 64                 // queries per workgroup tile; from KNN_WIDE_NQ queries on a workgroup owns two such tiles
@@ -309,6 +315,194 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const unsigned long long
     }
 }
 
+// ---- kernel sums and the distance select (the kernel MMD with a median bandwidth) -----------------------------------------------
+// selection step of the kernel sums: acc[b] += exp(-(double)d * inv_gamma[b]) in NB double registers that live across the slice's tiles.
+// The argument is ONE rounded product; the exponential is the library's (within an ulp of double).
+template <int NB>
+struct KnnKsum {
+    double ig[NB], acc[NB];
+    __device__ __forceinline__ void tile(long long, int, int) {}
+    __device__ __forceinline__ void offer(int, long long, unsigned int d) {
+        const double dd = (double)d;
+#pragma unroll
+        for (int b = 0; b < NB; ++b) acc[b] += exp(-(dd * ig[b]));
+    }
+};
+
+// sums of the slice -> ws[split][query][b]: the parts of a query are added in the order 0, 1 .. PARTS - 1
+template <int TQ, int NB>
+__global__ __launch_bounds__(KNN_THREADS) void knn_ksum_kernel(const unsigned char* __restrict__ q, int nq, const unsigned char* __restrict__ x, int n,
+                                                               int K, const double* __restrict__ inv_gamma, long long self0, int tiles_per_split,
+                                                               double* __restrict__ ws) {
+    __shared__ double sums[KNN_THREADS];
+    constexpr int PARTS = KNN_THREADS / TQ;
+    const int tid = threadIdx.x, sq = tid % TQ, sp = tid / TQ;
+    const long long qi = (long long)blockIdx.x * TQ + sq;
+    KnnKsum<NB> sel;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        sel.ig[b] = inv_gamma[b];
+        sel.acc[b] = 0.0;
+    }
+    knn_walk<TQ>(q, nq, x, n, K, self0, tiles_per_split, sel);
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        __syncthreads();                                           // the previous bandwidth's sums have been read
+        sums[tid] = sel.acc[b];
+        __syncthreads();
+        if (sp == 0 && qi < nq) {
+            double c = sums[sq];
+#pragma unroll
+            for (int o = 1; o < PARTS; ++o) c += sums[o * TQ + sq];
+            ws[((size_t)blockIdx.y * nq + qi) * NB + b] = c;
+        }
+    }
+}
+
+// out[i][b] = the sum of query i's slices: one wave per query, lane l adds the slices l, l + 64 .. in that order, then a butterfly over the
+// lanes -- a fixed tree, so two calls give the same bits.  Thread 0 of the launch writes the flag word: bit b <- inv_gamma[b] is not a
+// finite positive number.
+__global__ __launch_bounds__(256) void knn_ksum_sum_kernel(const double* __restrict__ ws, int splits, int nq, int nb, const double* __restrict__ inv_gamma,
+                                                           double* __restrict__ out, int* __restrict__ flag) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        int bad = 0;
+        for (int b = 0; b < nb; ++b) {
+            const double g = inv_gamma[b];
+            if (!(g > 0.0 && g < __builtin_huge_val())) bad |= 1 << b;
+        }
+        flag[0] = bad;
+    }
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= nq) return;                                           // whole waves leave: the shuffles below see full waves
+    for (int b = 0; b < nb; ++b) {
+        double c = 0.0;
+        for (int s = lane; s < splits; s += 64) c += ws[((size_t)s * nq + i) * nb + b];
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) c += __shfl_xor(c, o);
+        if (lane == 0) out[(size_t)i * nb + b] = c;
+    }
+}
+
+// The select is a radix select over the distances, most significant digit first, KNN_HBITS bits a pass: a pass counts, among the distances
+// whose higher bits equal the prefix found so far, the next digit.  (2048 bins of a first 11-bit digit would cost the wide layout its
+// second workgroup per CU: its staging buffers leave 7 KB of the CU's half.  A row length above 16512 bytes, whose distances need 31 bits,
+// takes a fourth pass over the one top bit instead.)
+#define KNN_HBITS 10
+#define KNN_HBINS (1 << KNN_HBITS)
+
+struct KnnSelectState {                                            // device resident, written by the scan of every pass
+    unsigned long long rank;                                       // rank among the distances that match the prefix
+    unsigned int prefix;                                           // d >> shift of the pass that wrote it
+    int beyond;                                                    // rank >= the number of pairs
+};
+
+// selection step of the select: the digit of a matching distance goes to the workgroup's LDS histogram.  Distances between natural images
+// concentrate -- in the first pass a thread's run of offers (its 32 or 64 rows of every tile) falls into a handful of bins -- so a thread
+// counts a run of equal digits in a register and adds it once: same-address LDS atomics serialise.
+struct KnnHist {
+    unsigned int* hist;                                            // [KNN_HBINS]
+    unsigned int prefix;
+    int shift, hshift;                                             // digit = (d >> shift) & (KNN_HBINS - 1); it counts iff d >> hshift == prefix
+    unsigned int cur, run;
+    __device__ __forceinline__ void tile(long long, int, int) {}
+    __device__ __forceinline__ void flush() {
+        if (run) atomicAdd(&hist[cur], run);
+    }
+    __device__ __forceinline__ void offer(int, long long, unsigned int d) {
+        if ((d >> hshift) != prefix) return;
+        const unsigned int bin = (d >> shift) & (KNN_HBINS - 1);
+        if (bin == cur) {
+            ++run;
+        } else {
+            flush();
+            cur = bin;
+            run = 1;
+        }
+    }
+};
+
+// histogram of the workgroup's pairs -> hist_ws[workgroup][bin], written once
+template <int TQ>
+__global__ __launch_bounds__(KNN_THREADS) void knn_hist_kernel(const unsigned char* __restrict__ q, int nq, const unsigned char* __restrict__ x, int n,
+                                                               int K, long long self0, int tiles_per_split, int shift, int first,
+                                                               const KnnSelectState* __restrict__ state, unsigned int* __restrict__ hist_ws) {
+    __shared__ unsigned int hist[KNN_HBINS];
+    const int tid = threadIdx.x;
+    for (int b = tid; b < KNN_HBINS; b += KNN_THREADS) hist[b] = 0;
+    __syncthreads();
+    KnnHist sel = {hist, first ? 0u : state->prefix, shift, min(shift + KNN_HBITS, 31), 0u, 0u};      // d < 2^31: d >> 31 == 0
+    knn_walk<TQ>(q, nq, x, n, K, self0, tiles_per_split, sel);
+    sel.flush();
+    __syncthreads();
+    unsigned int* o = hist_ws + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * KNN_HBINS;
+    for (int b = tid; b < KNN_HBINS; b += KNN_THREADS) o[b] = hist[b];
+}
+
+// thread = bin, workgroup g: the histograms of the workgroups g * per .. -> part[g][bin], 64-bit.  One workgroup walking all histograms
+// of a launch (2 MB from 512 workgroups) took 160 us a pass, as long as the pass itself on 1024-byte rows; KNN_HGROUPS workgroups share it.
+#define KNN_HGROUPS 32
+__global__ __launch_bounds__(KNN_HBINS) void knn_hist_reduce_kernel(const unsigned int* __restrict__ hist_ws, int nwg, int per,
+                                                                    unsigned long long* __restrict__ part) {
+    const int tid = threadIdx.x, g0 = blockIdx.x * per, g1 = min(g0 + per, nwg);
+    unsigned long long c = 0;
+#pragma unroll 8
+    for (int g = g0; g < g1; ++g) c += hist_ws[(size_t)g * KNN_HBINS + tid];
+    part[(size_t)blockIdx.x * KNN_HBINS + tid] = c;
+}
+
+// one workgroup, thread = bin: the groups' 64-bit bins -> their sum -> its inclusive scan -> the bin that holds the rank -> the next
+// prefix and the rank inside that bin.  first: the rank is the argument (no state exists yet) and the scan's total is the number of pairs;
+// last: the prefix is the distance.
+__global__ __launch_bounds__(KNN_HBINS) void knn_hist_scan_kernel(const unsigned long long* __restrict__ part, int groups, unsigned long long rank_arg,
+                                                                  int first, int last, KnnSelectState* __restrict__ state, int* __restrict__ out) {
+    __shared__ unsigned long long wsum[KNN_HBINS / 64];
+    __shared__ int found;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    unsigned long long c = 0;
+#pragma unroll 8
+    for (int g = 0; g < groups; ++g) c += part[(size_t)g * KNN_HBINS + tid];
+    unsigned long long incl = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long up = __shfl_up(incl, o);
+        if (lane >= o) incl += up;
+    }
+    if (tid == 0) found = 0;
+    if (lane == 63) wsum[w] = incl;
+    const unsigned long long rank0 = first ? rank_arg : state->rank;
+    const unsigned int prefix0 = first ? 0u : state->prefix;
+    const int beyond0 = first ? 0 : state->beyond;
+    __syncthreads();                                               // every thread has read the state before one of them writes it
+    unsigned long long total = 0;
+    for (int o = 0; o < KNN_HBINS / 64; ++o) {
+        if (o == w) incl += total;
+        total += wsum[o];
+    }
+    // a rank beyond the pairs (the first pass sees all of them) selects the largest distance and raises the mark
+    const int beyond = first ? (rank0 >= total ? 1 : 0) : beyond0;
+    const unsigned long long rank = first && beyond && total ? total - 1 : rank0;
+    if (c && rank >= incl - c && rank < incl) {                    // at most one bin
+        found = 1;
+        state->rank = rank - (incl - c);
+        state->prefix = (prefix0 << KNN_HBITS) | (unsigned int)tid;
+        state->beyond = beyond;
+        if (last) {
+            out[0] = (int)((prefix0 << KNN_HBITS) | (unsigned int)tid);
+            out[1] = beyond;
+        }
+    }
+    __syncthreads();
+    if (tid == 0 && !found) {                                      // no pair at all: the distance reads 0 and the mark is up
+        state->rank = 0;
+        state->prefix = prefix0 << KNN_HBITS;
+        state->beyond = 1;
+        if (last) {
+            out[0] = 0;
+            out[1] = 1;
+        }
+    }
+}
+
 // tiles of KNN_TR rows a workgroup walks for (nq, n): as few as keep about KNN_TARGET_WGS workgroups in the launch
 static int knn_wg_queries(int nq) { return nq >= KNN_WIDE_NQ ? 2 * KNN_TQ : KNN_TQ; }
 static int knn_tiles_per_split(int nq, int n) {
@@ -384,6 +578,83 @@ extern "C" int eg_ball_count_u8(const unsigned char* q, int nq, const unsigned c
     else
         hipLaunchKernelGGL((knn_ball_kernel<2 * KNN_TQ>), dim3(qt, splits), dim3(KNN_THREADS), 0, (hipStream_t)s, q, nq, x, n, K, rad, self0, tps, (int*)ws);
     hipLaunchKernelGGL(knn_ball_sum_kernel, dim3(cdiv(nq, 4)), dim3(256), 0, (hipStream_t)s, (const int*)ws, splits, nq, count);
+    EG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t eg_kernel_sum_ws_bytes(int nq, int n, int nb) {
+    if (nq < 1 || n < 1 || nb < 1) return 0;
+    return (size_t)eg_knn_splits(nq, n) * (size_t)nq * (size_t)nb * sizeof(double);
+}
+
+extern "C" int eg_kernel_sum_u8(const unsigned char* q, int nq, const unsigned char* x, int n, int K, const double* inv_gamma, int nb, long long self0,
+                                void* ws, double* out, int* flag, eg_stream_t s) {
+    EG_REQUIRE(q && x && inv_gamma && ws && out && flag, "eg_kernel_sum_u8: null pointer");
+    EG_REQUIRE(nq >= 1 && n >= 1, "eg_kernel_sum_u8: need nq >= 1 and n >= 1");
+    EG_REQUIRE(K >= 64 && K <= 32768 && K % 64 == 0, "eg_kernel_sum_u8: the row length K must be a multiple of 64 in 64 .. 32768 (K = %d)", K);
+    EG_REQUIRE(nb >= 1 && nb <= 4, "eg_kernel_sum_u8: need 1 <= nb <= 4 bandwidths (nb = %d)", nb);
+    EG_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)x & 15) == 0, "eg_kernel_sum_u8: q and x must be 16-byte aligned");
+    EG_REQUIRE(((uintptr_t)inv_gamma & 7) == 0 && ((uintptr_t)ws & 7) == 0 && ((uintptr_t)out & 7) == 0 && ((uintptr_t)flag & 3) == 0,
+               "eg_kernel_sum_u8: inv_gamma, ws and out must be 8-byte aligned, flag 4-byte");
+    const int tps = knn_tiles_per_split(nq, n), splits = eg_knn_splits(nq, n);
+    const int tq = knn_wg_queries(nq), qt = cdiv(nq, tq);
+    EG_REQUIRE(splits <= 65535, "eg_kernel_sum_u8: too many slices");
+#define KSUM_LAUNCH(TQ, NB) \
+    hipLaunchKernelGGL((knn_ksum_kernel<TQ, NB>), dim3(qt, splits), dim3(KNN_THREADS), 0, (hipStream_t)s, q, nq, x, n, K, inv_gamma, self0, tps, (double*)ws)
+    if (tq == KNN_TQ) {
+        if (nb == 1) KSUM_LAUNCH(KNN_TQ, 1);
+        else if (nb == 2) KSUM_LAUNCH(KNN_TQ, 2);
+        else if (nb == 3) KSUM_LAUNCH(KNN_TQ, 3);
+        else KSUM_LAUNCH(KNN_TQ, 4);
+    } else {
+        if (nb == 1) KSUM_LAUNCH(2 * KNN_TQ, 1);
+        else if (nb == 2) KSUM_LAUNCH(2 * KNN_TQ, 2);
+        else if (nb == 3) KSUM_LAUNCH(2 * KNN_TQ, 3);
+        else KSUM_LAUNCH(2 * KNN_TQ, 4);
+    }
+#undef KSUM_LAUNCH
+    hipLaunchKernelGGL(knn_ksum_sum_kernel, dim3(cdiv(nq, 4)), dim3(256), 0, (hipStream_t)s, (const double*)ws, splits, nq, nb, inv_gamma, out, flag);
+    EG_LAUNCH_CHECK();
+    return 0;
+}
+
+// the state first (64 bytes), then KNN_HGROUPS 64-bit histograms, then one 32-bit histogram per workgroup of the tile loop's launch
+extern "C" size_t eg_dist_select_ws_bytes(int nq, int n) {
+    if (nq < 1 || n < 1) return 0;
+    const size_t wgs = (size_t)cdiv(nq, knn_wg_queries(nq)) * (size_t)eg_knn_splits(nq, n);
+    return 64 + (size_t)KNN_HGROUPS * KNN_HBINS * sizeof(unsigned long long) + wgs * KNN_HBINS * sizeof(unsigned int);
+}
+
+extern "C" int eg_dist_select_u8(const unsigned char* q, int nq, const unsigned char* x, int n, int K, long long self0, unsigned long long rank, void* ws,
+                                 int* out, eg_stream_t s) {
+    EG_REQUIRE(q && x && ws && out, "eg_dist_select_u8: null pointer");
+    EG_REQUIRE(nq >= 1 && n >= 1, "eg_dist_select_u8: need nq >= 1 and n >= 1");
+    EG_REQUIRE(K >= 64 && K <= 32768 && K % 64 == 0, "eg_dist_select_u8: the row length K must be a multiple of 64 in 64 .. 32768 (K = %d)", K);
+    EG_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)x & 15) == 0, "eg_dist_select_u8: q and x must be 16-byte aligned");
+    EG_REQUIRE(((uintptr_t)ws & 7) == 0 && ((uintptr_t)out & 3) == 0, "eg_dist_select_u8: ws must be 8-byte aligned, out 4-byte");
+    const int tps = knn_tiles_per_split(nq, n), splits = eg_knn_splits(nq, n);
+    const int tq = knn_wg_queries(nq), qt = cdiv(nq, tq);
+    EG_REQUIRE(splits <= 65535, "eg_dist_select_u8: too many slices");
+    EG_REQUIRE((long long)tps * KNN_TR * tq < (1ll << 32), "eg_dist_select_u8: a workgroup's pairs do not fit a 32-bit bin");
+    EG_REQUIRE((long long)qt * splits < (1ll << 31), "eg_dist_select_u8: too many workgroups");
+    KnnSelectState* state = (KnnSelectState*)ws;
+    unsigned long long* part = (unsigned long long*)((char*)ws + 64);
+    unsigned int* hist_ws = (unsigned int*)(part + (size_t)KNN_HGROUPS * KNN_HBINS);
+    const int nwg = qt * splits, per = cdiv(nwg, KNN_HGROUPS), groups = cdiv(nwg, per);
+    // d <= 255^2 K: three digits hold it up to K = 16512, the fourth pass takes bit 30
+    const int passes = 65025ll * K >= (1ll << (3 * KNN_HBITS)) ? 4 : 3;
+    for (int p = 0; p < passes; ++p) {
+        const int shift = (passes - 1 - p) * KNN_HBITS, first = p == 0, last = p == passes - 1;
+        if (tq == KNN_TQ)
+            hipLaunchKernelGGL((knn_hist_kernel<KNN_TQ>), dim3(qt, splits), dim3(KNN_THREADS), 0, (hipStream_t)s, q, nq, x, n, K, self0, tps, shift, first,
+                               (const KnnSelectState*)state, hist_ws);
+        else
+            hipLaunchKernelGGL((knn_hist_kernel<2 * KNN_TQ>), dim3(qt, splits), dim3(KNN_THREADS), 0, (hipStream_t)s, q, nq, x, n, K, self0, tps, shift,
+                               first, (const KnnSelectState*)state, hist_ws);
+        hipLaunchKernelGGL(knn_hist_reduce_kernel, dim3(groups), dim3(KNN_HBINS), 0, (hipStream_t)s, (const unsigned int*)hist_ws, nwg, per, part);
+        hipLaunchKernelGGL(knn_hist_scan_kernel, dim3(1), dim3(KNN_HBINS), 0, (hipStream_t)s, (const unsigned long long*)part, groups, rank, first, last, state,
+                           out);
+    }
     EG_LAUNCH_CHECK();
     return 0;
 }

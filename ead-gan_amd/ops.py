@@ -1110,3 +1110,77 @@ def ball_count_u8(queries, database, radii, self0=-1, out=None):
     ws = torch.empty(lib().query("eg_ball_count_ws_bytes", nq, n) // 4, device=queries.device, dtype=torch.int32)
     lib().call("eg_ball_count_u8", _p(queries), nq, _p(database), n, K, _p(radii), int(self0), _p(ws), _p(out), _stream())
     return out
+
+
+# ---- kernel sums and the distance select --------------------------------------------------
+def kernel_sum_ws_bytes(nq, n, nb) -> int:
+    """bytes of the per-slice sums eg_kernel_sum_u8 needs for (nq, n, nb): knn_splits(nq, n) * nq * nb * 8"""
+    return lib().query("eg_kernel_sum_ws_bytes", int(nq), int(n), int(nb))
+
+
+def dist_select_ws_bytes(nq, n) -> int:
+    """bytes of the state and the per-workgroup histograms eg_dist_select_u8 needs for (nq, n)"""
+    return lib().query("eg_dist_select_ws_bytes", int(nq), int(n))
+
+
+def _u8_pair(what, queries, database):
+    """the checks of ``knn_u8`` on its two operands, shape and dtype first and the device last -> (nq, n, K)"""
+    for name, t in (("queries", queries), ("database", database)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.dim() >= 2 and t.is_contiguous()):
+            raise ValueError(f"{what}: {name} must be a contiguous uint8 device tensor [rows, ...]")
+    nq, n = int(queries.shape[0]), int(database.shape[0])
+    K = queries[0].numel() if nq else 0
+    if nq < 1 or n < 1 or database[0].numel() != K or queries.device != database.device:
+        raise ValueError(f"{what}: queries {tuple(queries.shape)} and database {tuple(database.shape)} must have rows of one length on one device")
+    if K % 64 or not 64 <= K <= 32768:
+        raise ValueError(f"{what}: the row length must be a multiple of 64 in 64 .. 32768, got {K}")
+    return nq, n, K
+
+
+def _on_device(what, queries):
+    if not queries.is_cuda:
+        raise ValueError(f"{what}: queries and database must be contiguous uint8 device tensors (there is no CPU path)")
+
+
+def kernel_sum_u8(queries, database, inv_gamma, self0=-1, out=None, flag=None):
+    """-> float64 [nq, nb] on the device: out[i, b] = the sum over the rows j of ``database`` of exp(-d(queries[i], database[j]) *
+    inv_gamma[b]), d the exact squared L2 distance of ``knn_u8`` (operands, row lengths and ``self0`` as there: with ``self0 >= 0`` query i
+    is database row self0 + i and its own term is left out).  ``inv_gamma``: a contiguous float64 DEVICE tensor [nb], 1 <= nb <= 4, so a
+    bandwidth can come from ``dist_select_u8`` without a host read.  ``out``: a contiguous float64 device tensor [nq, nb] to write instead
+    of a new one.  ``flag``: an int32 device tensor [1] that is WRITTEN (not or-ed): bit b says inv_gamma[b] is no finite positive number;
+    without it the word is not reported.  Sums in a fixed order: two calls give the same bits."""
+    nq, n, K = _u8_pair("kernel_sum_u8", queries, database)
+    if not (isinstance(inv_gamma, torch.Tensor) and inv_gamma.dtype == torch.float64 and inv_gamma.dim() == 1 and 1 <= inv_gamma.shape[0] <= 4
+            and inv_gamma.is_contiguous() and inv_gamma.device == queries.device):
+        raise ValueError("kernel_sum_u8: inv_gamma must be a contiguous float64 device tensor [nb] with 1 <= nb <= 4, beside the queries")
+    nb = int(inv_gamma.shape[0])
+    if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and tuple(out.shape) == (nq, nb) and out.is_contiguous()
+                                and out.device == queries.device):
+        raise ValueError(f"kernel_sum_u8: out must be a contiguous float64 device tensor [{nq}, {nb}]")
+    if flag is not None and not (isinstance(flag, torch.Tensor) and flag.dtype == torch.int32 and flag.numel() == 1 and flag.is_contiguous()
+                                 and flag.device == queries.device):
+        raise ValueError("kernel_sum_u8: flag must be an int32 device tensor of one element")
+    _on_device("kernel_sum_u8", queries)
+    if out is None:
+        out = torch.empty(nq, nb, device=queries.device, dtype=torch.float64)
+    if flag is None:
+        flag = torch.empty(1, device=queries.device, dtype=torch.int32)
+    ws = torch.empty(lib().query("eg_kernel_sum_ws_bytes", nq, n, nb) // 8, device=queries.device, dtype=torch.float64)
+    lib().call("eg_kernel_sum_u8", _p(queries), nq, _p(database), n, K, _p(inv_gamma), nb, int(self0), _p(ws), _p(out), _p(flag), _stream())
+    return out
+
+
+def dist_select_u8(queries, database, rank, self0=-1):
+    """-> int32 [2] on the device: [0] = the element of 0-based ``rank`` of all distances d(queries[i], database[j]), j != self0 + i, in
+    ascending order (operands, d and ``self0`` as for ``knn_u8``); [1] = 1 if ``rank`` is not below the number of pairs ([0] is then the
+    largest distance), else 0.  A radix select over histogram passes of the search's tile loop: no distance is stored, nothing is read
+    back between the passes."""
+    nq, n, K = _u8_pair("dist_select_u8", queries, database)
+    rank = int(rank)
+    if not 0 <= rank < 2 ** 64:
+        raise ValueError(f"dist_select_u8: rank = {rank} must be in 0 .. 2^64 - 1")
+    _on_device("dist_select_u8", queries)
+    out = torch.empty(2, device=queries.device, dtype=torch.int32)
+    ws = torch.empty(lib().query("eg_dist_select_ws_bytes", nq, n) // 8, device=queries.device, dtype=torch.int64)
+    lib().call("eg_dist_select_u8", _p(queries), nq, _p(database), n, K, int(self0), rank, _p(ws), _p(out), _stream())
+    return out

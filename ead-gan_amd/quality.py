@@ -27,6 +27,17 @@ balls of the other set that contain it):
 * ``prdc_generator(kind, generator, inputs)``    the same for a generator of an MNIST or CelebA run
 * ``NNPlan``                                     what ``train.TrainRun(..., nn=...)`` scores on checkpoint iterations
 
+A distance between the two distributions: the kernel maximum mean discrepancy (Gretton et al. 2012), the second score Xu et
+al. (2018) found to behave well, with k(a, b) = exp(-d(a, b) / gamma) over the same exact distances and gamma a multiple of their exact
+median (ops.dist_select_u8: a radix select over histogram passes of the search's tile loop; ops.kernel_sum_u8: the row sums in double):
+
+* ``median_distance(images)``                    the lower median distance between different images of a set, an integer
+* ``mmd(real, fake, scales)``                    the unbiased and the biased MMD^2 per bandwidth and the mean over the bandwidths
+* ``mmd_sums(real, fake, inv_gamma)``            the three kernel sums behind them, on the device
+* ``mmd_witness(real, fake, queries, gamma)``    the witness function: which images are over- or under-represented
+* ``mmd_generator(kind, generator, inputs)``     ``mmd`` for a generator of an MNIST or CelebA run
+* ``MMDPlan``                                    what ``train.TrainRun(..., mmd=...)`` scores on checkpoint iterations
+
 Per level and set: patch statistics (ops.swd_patch_stats), then per repeat one fused gather-and-project launch (ops.swd_project: the
 descriptors, 0.6 GB per set and level at full size, never exist), one column sort per set (ops.sort_columns) and one reduction
 (ops.l1_mean).  Everything is enqueued on the current stream; ``swd`` reads the device once, at its end.  There is no CPU path.
@@ -63,6 +74,14 @@ class NNPlan(NamedTuple):
     ``n_images`` generated against the first ``n_images`` dataset images"""
     n_images: int
     k: int = 5
+    seed: int = 0
+
+
+class MMDPlan(NamedTuple):
+    """the kernel MMD a training run writes on its checkpoint iterations (``mmd`` at ``scales`` times the median bandwidth): ``n_images``
+    generated against the first ``n_images`` dataset images"""
+    n_images: int
+    scales: tuple = (0.5, 1.0, 2.0)
     seed: int = 0
 
 
@@ -415,3 +434,105 @@ def prdc_generator(kind, generator, inputs, n_images=8192, k=5, batch=None, seed
     batch = min(64, int(n_images)) if batch is None else int(batch)
     fake = generate(kind, generator, n_images, batch, seed)
     return prdc(real_images(kind, inputs, n_images), fake, k)
+
+
+# ---- kernel MMD with an exact median bandwidth -----------------------------------------------------------------------------
+def median_distance(images):
+    """-> int32 device scalar: the lower median of the exact squared L2 distances between the bytes of all pairs of DIFFERENT images of the
+    set (float in [-1, 1] through ``to_u8``, or uint8) -- the element of 0-based rank (P - 1) // 2 among the P = T (T - 1) ordered pairs,
+    which is the lower median over the unordered pairs as well.  One ``ops.dist_select_u8`` call, no host read."""
+    rows = _u8_rows(images, "images")
+    T = int(rows.shape[0])
+    if T < 2:
+        raise ValueError(f"quality.median_distance: a median over pairs needs at least 2 images, got {T}")
+    return ops.dist_select_u8(rows, rows, (T * (T - 1) - 1) // 2, self0=0)[0]
+
+
+def _positive(values, what, name):
+    try:
+        vals = [float(v) for v in values]
+    except TypeError:
+        raise ValueError(f"quality.{what}: {name} must be a sequence of 1 .. 4 positive finite numbers") from None
+    if not 1 <= len(vals) <= 4 or not all(0.0 < v < float("inf") for v in vals):
+        raise ValueError(f"quality.{what}: {name} must be a sequence of 1 .. 4 positive finite numbers, got {vals}")
+    return vals
+
+
+def mmd_sums(real, fake, inv_gamma):
+    """-> (sums, flags) on the device: sums float64 [3, nb] = (S_xx, S_yy, S_xy) of ``mmd`` for the kernels exp(-d * inv_gamma[b]) over two
+    uint8 image sets, flags int32 [3] = the three calls' marks of an ``inv_gamma`` that is no finite positive number.  Three
+    ``ops.kernel_sum_u8`` calls -- (X, X) and (Y, Y) without the diagonal, and (X, Y) -- and one column sum each; no host read."""
+    dev = real.device
+    flags = torch.empty(3, device=dev, dtype=torch.int32)
+    rows = (ops.kernel_sum_u8(real, real, inv_gamma, self0=0, flag=flags[0:1]), ops.kernel_sum_u8(fake, fake, inv_gamma, self0=0, flag=flags[1:2]),
+            ops.kernel_sum_u8(real, fake, inv_gamma, flag=flags[2:3]))
+    return torch.stack([r.sum(0) for r in rows]), flags
+
+
+def mmd(real, fake, scales=(0.5, 1.0, 2.0), bandwidths=None):
+    """Kernel maximum mean discrepancy (Gretton et al. 2012) between ``real`` [N, C, H, W] and ``fake`` [M, C, H, W] (float in [-1, 1] or
+    uint8; N != M is allowed, N, M >= 2) with the kernels k(a, b) = exp(-d(a, b) / gamma) over the exact integer distances d between
+    their bytes -> {"gamma_median", "bandwidths", "mmd2", "mmd2_biased", "mean"}.  gamma = s * gamma_median for every s of ``scales`` (at
+    most 4), gamma_median the lower median distance of the pooled sets (``median_distance``: no hand-tuned constant); or ``bandwidths``:
+    absolute gamma > 0, then no median is taken and "gamma_median" is None.  Per bandwidth, with S_xx / S_yy the kernel sums over ordered
+    pairs of different rows and S_xy over all pairs:
+
+        mmd2        = S_xx / (N (N - 1)) + S_yy / (M (M - 1)) - 2 S_xy / (N M)         unbiased, may be slightly negative
+        mmd2_biased = (S_xx + N) / N^2 + (S_yy + M) / M^2 - 2 S_xy / (N M)
+
+    "mean" = the mean of "mmd2": the MMD^2 of the mean of the kernels.  One select on the pool and three kernel-sum calls (``mmd_sums``);
+    the inverse bandwidths are formed on the device from the select's result.  A median of 0 (more than half of the pairs are
+    duplicates) raises ValueError.  One host read, at the end: the median, the sums and the flags."""
+    A, B = _u8_rows(real, "real"), _u8_rows(fake, "fake")
+    if A.shape[1:] != B.shape[1:] or A.device != B.device:
+        raise ValueError(f"mmd: the two sets must hold images of one shape on one device, got {tuple(A.shape)} and {tuple(B.shape)}")
+    N, M = int(A.shape[0]), int(B.shape[0])
+    if N < 2 or M < 2:
+        raise ValueError(f"mmd: both sets need at least 2 images, got {N} and {M}")
+    dev = A.device
+    if bandwidths is None:
+        factors = _positive(scales, "mmd", "scales")
+        pool = torch.cat((A, B))
+        T = N + M
+        sel = ops.dist_select_u8(pool, pool, (T * (T - 1) - 1) // 2, self0=0)
+        gamma = sel[0].double() * torch.tensor(factors, device=dev, dtype=torch.float64)
+    else:
+        factors = _positive(bandwidths, "mmd", "bandwidths")
+        sel = torch.zeros(2, device=dev, dtype=torch.int32)
+        gamma = torch.tensor(factors, device=dev, dtype=torch.float64)
+    nb = len(factors)
+    sums, flags = mmd_sums(A, B, gamma.reciprocal())
+    host = torch.cat((sel.double(), flags.double(), sums.reshape(-1))).cpu()       # THE host read
+    med = None if bandwidths is not None else int(host[0])
+    if med == 0:
+        raise ValueError(f"mmd: the median distance of the pooled {N} + {M} images is zero -- more than half of the pairs are duplicates, "
+                         "there is no median bandwidth (pass bandwidths=)")
+    if int(host[1]) or any(int(v) for v in host[2:5]):
+        raise ValueError(f"mmd: the select or a kernel sum refused its arguments (rank mark {int(host[1])}, bandwidth flags {[int(v) for v in host[2:5]]})")
+    S = host[5:].reshape(3, nb).tolist()
+    unbiased = [S[0][b] / (N * (N - 1)) + S[1][b] / (M * (M - 1)) - 2.0 * S[2][b] / (N * M) for b in range(nb)]
+    biased = [(S[0][b] + N) / (N * N) + (S[1][b] + M) / (M * M) - 2.0 * S[2][b] / (N * M) for b in range(nb)]
+    return {"gamma_median": med, "bandwidths": [f * med for f in factors] if med is not None else factors, "mmd2": unbiased, "mmd2_biased": biased,
+            "mean": sum(unbiased) / nb}
+
+
+def mmd_witness(real, fake, queries, bandwidth):
+    """-> float64 [nq] on the device: the witness function of the MMD at ``bandwidth`` (an absolute gamma > 0, e.g. one of ``mmd``'s
+    "bandwidths"), w(z) = (1/N) sum_i k(z, real[i]) - (1/M) sum_j k(z, fake[j]) for every image z of ``queries``: positive where the data
+    are denser than the samples, negative where the generator over-produces.  Two ``ops.kernel_sum_u8`` calls, no host read."""
+    A, B, Z = _u8_rows(real, "real"), _u8_rows(fake, "fake"), _u8_rows(queries, "queries")
+    if A.shape[1:] != B.shape[1:] or A.shape[1:] != Z.shape[1:] or A.device != B.device or A.device != Z.device:
+        raise ValueError(f"mmd_witness: the three sets must hold images of one shape on one device, got {tuple(A.shape)}, {tuple(B.shape)} "
+                         f"and {tuple(Z.shape)}")
+    gamma = _positive((bandwidth,), "mmd_witness", "bandwidth")
+    ig = torch.tensor(gamma, device=A.device, dtype=torch.float64).reciprocal()
+    return ops.kernel_sum_u8(Z, A, ig)[:, 0] / A.shape[0] - ops.kernel_sum_u8(Z, B, ig)[:, 0] / B.shape[0]
+
+
+def mmd_generator(kind, generator, inputs, n_images=8192, batch=None, seed=0, **kw):
+    """``mmd`` of ``real_images(kind, inputs, n_images)`` against ``generate(kind, generator, n_images, batch, seed)``; ``batch`` as in
+    ``swd_generator``; ``kw``: scales, bandwidths"""
+    _family(kind, "mmd_generator")
+    batch = min(64, int(n_images)) if batch is None else int(batch)
+    fake = generate(kind, generator, n_images, batch, seed)
+    return mmd(real_images(kind, inputs, n_images), fake, **kw)

@@ -143,6 +143,32 @@ def nn_seed(seed, batches_done, plan_seed=0):
     return (int(seed) * 1000003 + int(batches_done) * 4447 + int(plan_seed) * 130003 + 98765) % (2 ** 32)
 
 
+def mmd_seed(seed, batches_done, plan_seed=0):
+    """seed of a checkpoint iteration's generated images for the kernel MMD: ``swd_seed``'s form with constants of its own"""
+    return (int(seed) * 1000003 + int(batches_done) * 5381 + int(plan_seed) * 115249 + 24680) % (2 ** 32)
+
+
+def check_plan(what, plan, cls, kind, n_dataset, batch):
+    """-> ``plan`` as a ``cls`` (quality.SWDPlan, NNPlan or MMDPlan) after the checks every score plan of a run passes: the kind of the
+    run, ``n_images`` against the dataset and against the trainer's batch size; an MMD plan also needs two images a set and 1 .. 4
+    positive scales"""
+    if kind not in ("mnist", "celeba"):
+        raise ValueError(f"{what}: only 'mnist' and 'celeba' runs are scored (quality.generate), not {kind!r}")
+    plan = cls(*plan)
+    if not 1 <= int(plan.n_images) <= int(n_dataset):
+        raise ValueError(f"{what}: n_images = {plan.n_images}, the dataset has {n_dataset} images")
+    if int(plan.n_images) % min(int(batch), int(plan.n_images)):                # the generator runs at the trainer's batch size
+        raise ValueError(f"{what}: n_images = {plan.n_images} is no multiple of the trainer's batch size {batch}")
+    if cls is quality.MMDPlan:
+        if int(plan.n_images) < 2:
+            raise ValueError(f"{what}: n_images = {plan.n_images}, the estimate needs at least 2 images a set")
+        try:
+            quality._positive(plan.scales, "MMDPlan", "scales")
+        except ValueError as e:
+            raise ValueError(f"{what}: {e}") from None
+    return plan
+
+
 class TrainRun:
     """``run(max_iters=None)`` continues from ``batches_done`` until ``n_epochs`` epochs of ``ceil(N / B)`` iterations are done or
     ``max_iters`` more iterations ran; ``save()`` writes ``run_state_<batches_done>.pt``; ``TrainRun.resume(path, ...)`` continues such a
@@ -169,13 +195,18 @@ class TrainRun:
     ``quality.nn_two_sample`` and ``quality.prdc`` at ``k`` of ONE set of generated images per generator (seeded by ``nn_seed``) against
     the first ``n_images`` dataset images.  The scratch generator is the SWD plan's; nothing else of the run is touched.
 
+    ``mmd=quality.MMDPlan(n_images, scales=(0.5, 1.0, 2.0), seed=0)`` (the same runs): on checkpoint iterations, after the
+    ``nn.jsonl`` line if there is one, rank 0 appends ``{"batches_done", "G": quality.mmd(...)[, "G_ema": ...]}`` to ``out_dir/mmd.jsonl``
+    -- the kernel MMD at ``scales`` times the median bandwidth of one set of generated images per generator (seeded by ``mmd_seed``)
+    against the first ``n_images`` dataset images.  The same scratch generator; nothing else of the run is touched.
+
     Data parallel (``inputs.world`` > 1, the world of the trainer's ``allreduce`` / ``sync_bn``): ``graph=False`` is required; the
     iteration count, cadence, sample seeds and file names are those of one process at the global batch ``B * world``; rank 0 prints and
     writes every file, the other ranks write none (``files == []``) and print nothing but execute every ``_wait`` and keep ``history``
     / ``lines`` of their own shard.  The run adds no collective: rank 0's lines and ``losses.npy`` carry rank 0's shard losses."""
 
     def __init__(self, kind, trainer, inputs, out_dir, n_epochs, sample_interval=None, seed=0, graph=True, log_capacity=1024, log_in_graph=True,
-                 ema_samples=False, swd=None, nn=None):
+                 ema_samples=False, swd=None, nn=None, mmd=None):
         self.plan = _plan(kind)
         if getattr(trainer, "STATE_KIND", None) != kind:
             raise ValueError(f"a {kind!r} run needs a {kind!r} trainer, got {type(trainer).__name__}")
@@ -219,18 +250,11 @@ class TrainRun:
                 raise ValueError("ema_samples: the trainer keeps no average of its generator -- call trainer.attach_ema(modules=('G', ...)) first")
             if self.rank == 0:
                 self._ema_G = _module_like(trainer.G).to(trainer.losses.device)
-        self.swd, self.nn, self._score_G = swd, nn, None            # one scratch generator serves both plans
-        for what, plan, cls in (("swd", swd, quality.SWDPlan), ("nn", nn, quality.NNPlan)):
+        self.swd, self.nn, self.mmd, self._score_G = swd, nn, mmd, None       # one scratch generator serves every plan
+        for what, plan, cls in (("swd", swd, quality.SWDPlan), ("nn", nn, quality.NNPlan), ("mmd", mmd, quality.MMDPlan)):
             if plan is None:
                 continue
-            if kind not in ("mnist", "celeba"):
-                raise ValueError(f"{what}: only 'mnist' and 'celeba' runs are scored (quality.generate), not {kind!r}")
-            plan = cls(*plan)
-            setattr(self, what, plan)
-            if not 1 <= int(plan.n_images) <= self.n_images:
-                raise ValueError(f"{what}: n_images = {plan.n_images}, the dataset has {self.n_images} images")
-            if int(plan.n_images) % min(int(trainer.B), int(plan.n_images)):        # the generator runs at the trainer's batch size
-                raise ValueError(f"{what}: n_images = {plan.n_images} is no multiple of the trainer's batch size {trainer.B}")
+            setattr(self, what, check_plan(what, plan, cls, kind, self.n_images, trainer.B))
             if self.rank == 0 and self._score_G is None:
                 self._score_G = _module_like(trainer.G).to(trainer.losses.device)
         if self.nn is not None and not 1 <= int(self.nn.k) <= min(16, int(self.nn.n_images) - 1):
@@ -349,6 +373,16 @@ class TrainRun:
             return {"two_sample": quality.nn_two_sample(real, fake), "prdc": quality.prdc(real, fake, plan.k)}
         self._score_line("nn.jsonl", it, score)
 
+    def _score_mmd(self, it):
+        """one line of ``mmd.jsonl``: ``quality.mmd`` of one set of generated images per generator against the first
+        ``n_images`` dataset images"""
+        if self._score_G is None or self.mmd is None:
+            return
+        tr, plan = self.trainer, self.mmd
+        n, seed = int(plan.n_images), mmd_seed(self.seed, it, plan.seed)
+        real = quality.to_u8(quality.real_images(self.kind, self.inputs, n))
+        self._score_line("mmd.jsonl", it, lambda G: quality.mmd(real, quality.generate(self.kind, G, n, min(int(tr.B), n), seed), scales=plan.scales))
+
     def _score_line(self, name, it, score):
         """``{"batches_done", "G": score(live generator)[, "G_ema": score(averaged generator)]}`` appended to ``out_dir/name``"""
         tr, G = self.trainer, self._score_G
@@ -409,6 +443,7 @@ class TrainRun:
                 self._checkpoint(it)
                 self._score(it)
                 self._score_nn(it)
+                self._score_mmd(it)
             self.batches_done = it + 1
             done += 1
             if do_ckpt:

@@ -799,6 +799,25 @@ int eg_knn_u8(const unsigned char* q, int nq, const unsigned char* x, int n, int
 size_t eg_ball_count_ws_bytes(int nq, int n);
 int eg_ball_count_u8(const unsigned char* q, int nq, const unsigned char* x, int n, int K, const int* rad, long long self0,
                      void* ws, int* count, eg_stream_t s);
+/* --- kernel sums and the distance select (the kernel MMD with an exact median bandwidth).  q, x, d, K, self0, the limits, the
+ * alignment of q and x, the tile loop, the slices (eg_knn_splits) and the wave layouts are eg_knn_u8's.
+ * eg_kernel_sum_u8: out[i][b] (double [nq][nb]) = sum over j != self0 + i of exp(-((double)d(q[i], x[j]) * inv_gamma[b])): the argument is
+ * one rounded product, the exponential the device library's.  inv_gamma: a DEVICE pointer to nb doubles, 1 <= nb <= 4.  flag[0] (device
+ * int32) is WRITTEN, not or-ed: bit b says inv_gamma[b] is not a finite positive number (out[.][b] then holds what the arithmetic gives).
+ * ws: eg_kernel_sum_ws_bytes(nq, n, nb) = splits * nq * nb * 8 bytes of per-slice sums; the parts of a query, then its slices, are added
+ * in a fixed order, everything is written exactly once (no atomic, no zero-fill): two calls with the same shapes give the same bits.
+ * inv_gamma, ws and out 8-byte aligned.  Two launches, no allocation, no sync.
+ * eg_dist_select_u8: out[0] (int32) = the element of 0-based rank `rank` of the multiset { d(q[i], x[j]) : j != self0 + i } in ascending
+ * order; out[1] = 1 if rank >= the number of pairs (out[0] is then the largest distance, or 0 if there is no pair), else 0.  A radix
+ * select, 10 bits a pass from the top: three passes of the tile loop (four where 255^2 K >= 2^30), each followed by a sum of the
+ * workgroups' histograms and a one-workgroup scan that leaves the prefix and the remaining rank in ws for the next; all enqueued at once,
+ * no host read.  ws: eg_dist_select_ws_bytes(nq, n) = 64 + 32 * 8192 + workgroups * 4096 bytes, 8-byte aligned. */
+size_t eg_kernel_sum_ws_bytes(int nq, int n, int nb);
+int eg_kernel_sum_u8(const unsigned char* q, int nq, const unsigned char* x, int n, int K, const double* inv_gamma, int nb, long long self0,
+                     void* ws, double* out, int* flag, eg_stream_t s);
+size_t eg_dist_select_ws_bytes(int nq, int n);
+int eg_dist_select_u8(const unsigned char* q, int nq, const unsigned char* x, int n, int K, long long self0, unsigned long long rank,
+                      void* ws, int* out, eg_stream_t s);
 
 #ifdef __cplusplus
 }
