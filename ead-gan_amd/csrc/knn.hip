@@ -20,6 +20,9 @@
 //   knn_hist_kernel      one pass of a radix select: the next digit of every distance that matches the prefix -> an LDS histogram
 //   knn_hist_reduce_kernel, knn_hist_scan_kernel  the workgroups' histograms -> 64-bit bins -> the bin that holds the rank -> the next
 //                        prefix and the rank inside it
+// The Sinkhorn divergence (quality.sinkhorn) takes one more: a streaming log-sum-exp in place of the sum
+//   knn_softmin_kernel        the offers go into a running (maximum, sum of exp(t - maximum)) per thread -> ws[split][query] = (m, s)
+//   knn_softmin_final_kernel  the slices of a query in a fixed order -> log, count, epsilon and the average with the previous potential
 #include "eg_common.h"
 
 #define KNN_TQ 64                 // queries per workgroup tile; from KNN_WIDE_NQ queries on a workgroup owns two such tiles
@@ -383,6 +386,96 @@ __global__ __launch_bounds__(256) void knn_ksum_sum_kernel(const double* __restr
     }
 }
 
+// ---- the soft minimum (one half-iteration of the Sinkhorn divergence) ------------------------------------------------------------
+// A streaming log-sum-exp is a pair (m, s): m the largest argument so far, s = the sum of exp(t - m) over the arguments so far, so s >= 1
+// once an argument has come and nothing overflows or underflows to log 0.  A part or a slice without an offer holds (-inf, 0).
+// merge of two pairs: the pair with the smaller maximum is rescaled by ONE exponential; equal maxima (two empty pairs among them) take no
+// exponential, so -inf - (-inf) is never formed.  The result does not depend on which of the two comes first.
+__device__ __forceinline__ void softmin_merge(double& m, double& s, double m2, double s2) {
+#pragma clang fp contract(off)
+    if (m >= m2) {
+        s = fma(s2, m2 == m ? 1.0 : exp(m2 - m), s);
+    } else {
+        s = fma(s, exp(m - m2), s2);
+        m = m2;
+    }
+}
+
+// selection step of the soft minimum: t = (g[j] - (double)d) * inv_eps, one rounded subtraction and one rounded product, into the thread's
+// running pair with ONE exponential, exp(-|t - m|): it is the new term where t <= m and the rescale of s where t is the new maximum.  The
+// tile's KNN_TR values of g are staged in LDS like the radii of the ball count.
+struct KnnSoftmin {
+    const double* __restrict__ g;
+    double* gl;                                                    // [KNN_TR]
+    double ie, m, s;
+    __device__ __forceinline__ void tile(long long r0, int n, int tid) {
+        if (tid < KNN_TR) gl[tid] = r0 + tid < n ? g[r0 + tid] : 0.0;
+    }
+    __device__ __forceinline__ void offer(int row, long long, unsigned int d) {
+#pragma clang fp contract(off)
+        const double t = (gl[row] - (double)d) * ie;
+        const double up = t - m;                                   // +inf at the first offer: exp(-inf) = 0 and s = 0 * 0 + 1
+        const double e = exp(-fabs(up));
+        const bool keep = up <= 0.0;
+        s = keep ? s + e : fma(s, e, 1.0);
+        m = keep ? m : t;
+    }
+};
+
+// pair of the slice -> ws[split][query] = (m, s): the parts of a query are merged in the order 0, 1 .. PARTS - 1
+template <int TQ>
+__global__ __launch_bounds__(KNN_THREADS) void knn_softmin_kernel(const unsigned char* __restrict__ q, int nq, const unsigned char* __restrict__ x, int n,
+                                                                  int K, const double* __restrict__ g, const double* __restrict__ inv_eps, long long self0,
+                                                                  int tiles_per_split, double* __restrict__ ws) {
+    __shared__ double gl[KNN_TR], pm[KNN_THREADS], ps[KNN_THREADS];
+    constexpr int PARTS = KNN_THREADS / TQ;
+    const int tid = threadIdx.x, sq = tid % TQ, sp = tid / TQ;
+    const long long qi = (long long)blockIdx.x * TQ + sq;
+    KnnSoftmin sel = {g, gl, inv_eps[0], -__builtin_huge_val(), 0.0};
+    knn_walk<TQ>(q, nq, x, n, K, self0, tiles_per_split, sel);
+    pm[tid] = sel.m;
+    ps[tid] = sel.s;
+    __syncthreads();
+    if (sp == 0 && qi < nq) {
+        double m = pm[sq], s = ps[sq];
+#pragma unroll
+        for (int o = 1; o < PARTS; ++o) softmin_merge(m, s, pm[o * TQ + sq], ps[o * TQ + sq]);
+        double* o = ws + ((size_t)blockIdx.y * nq + qi) * 2;
+        o[0] = m;
+        o[1] = s;
+    }
+}
+
+// out[i] from the pairs of query i's slices: one wave per query, lane l merges the slices l, l + 64 .. in that order, then a butterfly over
+// the lanes -- a fixed tree, so two calls give the same bits.  soft = -(m + (log s - log |J_i|)) / inv_eps: the small difference of the two
+// logarithms first, so only one sum and the quotient round at the size of m.  prev[i] is read before out[i] is written by the same thread:
+// prev and out may be one array.  Thread 0 of the launch writes the flag word: bit 0 <- inv_eps[0] is not a finite positive number.
+__global__ __launch_bounds__(256) void knn_softmin_final_kernel(const double* __restrict__ ws, int splits, int nq, int n, long long self0,
+                                                                const double* __restrict__ inv_eps, const double* prev, double* out,
+                                                                int* __restrict__ flag) {
+#pragma clang fp contract(off)
+    const double ie = inv_eps[0];
+    if (blockIdx.x == 0 && threadIdx.x == 0) flag[0] = ie > 0.0 && ie < __builtin_huge_val() ? 0 : 1;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= nq) return;                                           // whole waves leave: the shuffles below see full waves
+    double m = -__builtin_huge_val(), s = 0.0;
+    for (int p = lane; p < splits; p += 64) {
+        const double* w = ws + ((size_t)p * nq + i) * 2;
+        softmin_merge(m, s, w[0], w[1]);
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double m2 = __shfl_xor(m, o), s2 = __shfl_xor(s, o);
+        softmin_merge(m, s, m2, s2);
+    }
+    if (lane == 0) {
+        const long long excl = self0 >= 0 ? self0 + i : -1;
+        const double count = (double)(n - (excl >= 0 && excl < n ? 1 : 0));
+        const double soft = -((m + (log(s) - log(count))) / ie);
+        out[i] = prev ? 0.5 * prev[i] + 0.5 * soft : soft;
+    }
+}
+
 // The select is a radix select over the distances, most significant digit first, KNN_HBITS bits a pass: a pass counts, among the distances
 // whose higher bits equal the prefix found so far, the next digit.  (2048 bins of a first 11-bit digit would cost the wide layout its
 // second workgroup per CU: its staging buffers leave 7 KB of the CU's half.  A row length above 16512 bytes, whose distances need 31 bits,
@@ -614,6 +707,37 @@ extern "C" int eg_kernel_sum_u8(const unsigned char* q, int nq, const unsigned c
     }
 #undef KSUM_LAUNCH
     hipLaunchKernelGGL(knn_ksum_sum_kernel, dim3(cdiv(nq, 4)), dim3(256), 0, (hipStream_t)s, (const double*)ws, splits, nq, nb, inv_gamma, out, flag);
+    EG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t eg_softmin_ws_bytes(int nq, int n) {
+    if (nq < 1 || n < 1) return 0;
+    return (size_t)eg_knn_splits(nq, n) * (size_t)nq * 2 * sizeof(double);
+}
+
+extern "C" int eg_softmin_u8(const unsigned char* q, int nq, const unsigned char* x, int n, int K, const double* g, const double* inv_eps, long long self0,
+                             const double* prev, void* ws, double* out, int* flag, eg_stream_t s) {
+    EG_REQUIRE(q && x && g && inv_eps && ws && out && flag, "eg_softmin_u8: null pointer");
+    EG_REQUIRE(nq >= 1 && n >= 1, "eg_softmin_u8: need nq >= 1 and n >= 1");
+    EG_REQUIRE(K >= 64 && K <= 32768 && K % 64 == 0, "eg_softmin_u8: the row length K must be a multiple of 64 in 64 .. 32768 (K = %d)", K);
+    const long long candidates = (long long)n - (self0 >= 0 && self0 < n ? 1 : 0);         // of query 0, which has the fewest
+    EG_REQUIRE(candidates >= 1, "eg_softmin_u8: a query has no candidate (n = %d, self0 = %lld): need n - 1 >= 1 where a row is excluded", n, self0);
+    EG_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)x & 15) == 0, "eg_softmin_u8: q and x must be 16-byte aligned");
+    EG_REQUIRE(((uintptr_t)g & 7) == 0 && ((uintptr_t)inv_eps & 7) == 0 && ((uintptr_t)prev & 7) == 0 && ((uintptr_t)ws & 7) == 0 &&
+                   ((uintptr_t)out & 7) == 0 && ((uintptr_t)flag & 3) == 0,
+               "eg_softmin_u8: g, inv_eps, prev, ws and out must be 8-byte aligned, flag 4-byte");
+    const int tps = knn_tiles_per_split(nq, n), splits = eg_knn_splits(nq, n);
+    const int tq = knn_wg_queries(nq), qt = cdiv(nq, tq);
+    EG_REQUIRE(splits <= 65535, "eg_softmin_u8: too many slices");
+    if (tq == KNN_TQ)
+        hipLaunchKernelGGL((knn_softmin_kernel<KNN_TQ>), dim3(qt, splits), dim3(KNN_THREADS), 0, (hipStream_t)s, q, nq, x, n, K, g, inv_eps, self0, tps,
+                           (double*)ws);
+    else
+        hipLaunchKernelGGL((knn_softmin_kernel<2 * KNN_TQ>), dim3(qt, splits), dim3(KNN_THREADS), 0, (hipStream_t)s, q, nq, x, n, K, g, inv_eps, self0, tps,
+                           (double*)ws);
+    hipLaunchKernelGGL(knn_softmin_final_kernel, dim3(cdiv(nq, 4)), dim3(256), 0, (hipStream_t)s, (const double*)ws, splits, nq, n, self0, inv_eps, prev, out,
+                       flag);
     EG_LAUNCH_CHECK();
     return 0;
 }

@@ -1170,6 +1170,52 @@ def kernel_sum_u8(queries, database, inv_gamma, self0=-1, out=None, flag=None):
     return out
 
 
+def _f64(what, name, t, shape, like):
+    """``t`` must be a contiguous float64 tensor of ``shape`` on the device of ``like``"""
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == tuple(shape) and t.is_contiguous() and t.device == like.device):
+        raise ValueError(f"{what}: {name} must be a contiguous float64 device tensor {list(shape)}, beside the queries")
+
+
+# ---- the soft minimum (DESIGN 6q) ---------------------------------------------------------------------
+def softmin_ws_bytes(nq, n) -> int:
+    """bytes of the per-slice (maximum, sum) pairs eg_softmin_u8 needs for (nq, n): knn_splits(nq, n) * nq * 16"""
+    return lib().query("eg_softmin_ws_bytes", int(nq), int(n))
+
+
+def softmin_u8(queries, database, g, inv_eps, self0=-1, prev=None, out=None, flag=None):
+    """-> float64 [nq] on the device: the soft minimum over the rows j of ``database`` of d(queries[i], database[j]) - g[j] at the
+    temperature 1 / inv_eps, soft[i] = -(log sum_j exp((g[j] - d) * inv_eps) - log #j) / inv_eps, d the exact squared L2 distance of
+    ``knn_u8`` (operands, row lengths and ``self0`` as there: with ``self0 >= 0`` query i is database row self0 + i and that row is left
+    out; at least one row must remain) -- one half-iteration of a Sinkhorn loop, as a streaming log-sum-exp that neither overflows nor
+    underflows.  ``g``: float64 [n]; ``inv_eps``: a float64 DEVICE tensor of one element, so a whole epsilon schedule is enqueued without
+    a host read.  ``prev``: float64 [nq]; the result is then 0.5 * prev + 0.5 * soft.  ``out``: float64 [nq] to write instead of a new
+    tensor; ``prev``, ``g`` and ``out`` may be one tensor.  ``flag``: an int32 device tensor [1] that is WRITTEN: bit 0 says inv_eps is no
+    finite positive number.  A fixed merge order: two calls give the same bits."""
+    nq, n, K = _u8_pair("softmin_u8", queries, database)
+    _f64("softmin_u8", "g", g, (n,), queries)
+    if not (isinstance(inv_eps, torch.Tensor) and inv_eps.dtype == torch.float64 and inv_eps.numel() == 1 and inv_eps.is_contiguous()
+            and inv_eps.device == queries.device):
+        raise ValueError("softmin_u8: inv_eps must be a float64 device tensor of one element, beside the queries")
+    if prev is not None:
+        _f64("softmin_u8", "prev", prev, (nq,), queries)
+    if out is not None:
+        _f64("softmin_u8", "out", out, (nq,), queries)
+    if flag is not None and not (isinstance(flag, torch.Tensor) and flag.dtype == torch.int32 and flag.numel() == 1 and flag.is_contiguous()
+                                 and flag.device == queries.device):
+        raise ValueError("softmin_u8: flag must be an int32 device tensor of one element")
+    self0 = int(self0)
+    if n - (1 if 0 <= self0 < n else 0) < 1:
+        raise ValueError(f"softmin_u8: a query has no candidate ({n} rows, self0 = {self0}): n - 1 >= 1 is needed where a row is excluded")
+    _on_device("softmin_u8", queries)
+    if out is None:
+        out = torch.empty(nq, device=queries.device, dtype=torch.float64)
+    if flag is None:
+        flag = torch.empty(1, device=queries.device, dtype=torch.int32)
+    ws = torch.empty(lib().query("eg_softmin_ws_bytes", nq, n) // 8, device=queries.device, dtype=torch.float64)
+    lib().call("eg_softmin_u8", _p(queries), nq, _p(database), n, K, _p(g), _p(inv_eps), self0, _p(prev), _p(ws), _p(out), _p(flag), _stream())
+    return out
+
+
 def dist_select_u8(queries, database, rank, self0=-1):
     """-> int32 [2] on the device: [0] = the element of 0-based ``rank`` of all distances d(queries[i], database[j]), j != self0 + i, in
     ascending order (operands, d and ``self0`` as for ``knn_u8``); [1] = 1 if ``rank`` is not below the number of pairs ([0] is then the

@@ -38,6 +38,15 @@ median (ops.dist_select_u8: a radix select over histogram passes of the search's
 * ``mmd_generator(kind, generator, inputs)``     ``mmd`` for a generator of an MNIST or CelebA run
 * ``MMDPlan``                                    what ``train.TrainRun(..., mmd=...)`` scores on checkpoint iterations
 
+A transport cost between the two image sets themselves: the debiased Sinkhorn divergence (Genevay et al. 2018; Feydy et al.
+2019) over the same exact distances, its temperature a multiple of their exact median (ops.softmin_u8: a streaming log-sum-exp over the
+search's tile loop, one call per half-iteration; the distance matrix is never stored):
+
+* ``sinkhorn(real, fake, scale)``                the divergence, its three transport terms and the marginal error left by the fixed loop;
+                                                 with ``terms=True`` the per-image shares as well
+* ``sinkhorn_generator(kind, generator, inputs)`` the same for a generator of an MNIST or CelebA run
+* ``SinkhornPlan``                               what ``train.TrainRun(..., sinkhorn=...)`` scores on checkpoint iterations
+
 Per level and set: patch statistics (ops.swd_patch_stats), then per repeat one fused gather-and-project launch (ops.swd_project: the
 descriptors, 0.6 GB per set and level at full size, never exist), one column sort per set (ops.sort_columns) and one reduction
 (ops.l1_mean).  Everything is enqueued on the current stream; ``swd`` reads the device once, at its end.  There is no CPU path.
@@ -82,6 +91,15 @@ class MMDPlan(NamedTuple):
     generated against the first ``n_images`` dataset images"""
     n_images: int
     scales: tuple = (0.5, 1.0, 2.0)
+    seed: int = 0
+
+
+class SinkhornPlan(NamedTuple):
+    """the Sinkhorn divergence a training run writes on its checkpoint iterations (``sinkhorn`` at ``scale`` times the median distance,
+    ``iterations`` updates): ``n_images`` generated against the first ``n_images`` dataset images"""
+    n_images: int
+    scale: float = 0.1
+    iterations: int = 60
     seed: int = 0
 
 
@@ -536,3 +554,94 @@ def mmd_generator(kind, generator, inputs, n_images=8192, batch=None, seed=0, **
     batch = min(64, int(n_images)) if batch is None else int(batch)
     fake = generate(kind, generator, n_images, batch, seed)
     return mmd(real_images(kind, inputs, n_images), fake, **kw)
+
+
+# ---- debiased Sinkhorn divergence ------------------------------------------------------------------------------------------
+def sinkhorn(real, fake, scale=0.1, epsilon=None, iterations=60, rho=0.5, terms=False):
+    """Debiased Sinkhorn divergence (Genevay et al. 2018; Feydy et al. 2019) between ``real`` [N, C, H, W] and ``fake`` [M, C, H, W] (float
+    in [-1, 1] or uint8; N != M is allowed, N, M >= 2) with uniform weights and the exact integer squared distance between their bytes as
+    the cost: S = OT_eps(X, Y) - OT_eps(X, X) / 2 - OT_eps(Y, Y) / 2, zero for equal sets, the Wasserstein cost as eps -> 0
+    -> {"gamma_median", "epsilon", "iterations", "divergence", "relative", "ot_xy", "ot_xx", "ot_yy", "marginal_error"}.
+
+    eps = ``scale`` x gamma_median, the lower median distance of the pooled sets (one ``ops.dist_select_u8``, as in ``mmd``); or
+    ``epsilon``: an absolute eps > 0, then no median is taken and "gamma_median" and "relative" are None.  Iteration t runs at
+    eps_t = max(eps, eps_0 rho^t), eps_0 the largest pooled distance (a second select, at the last rank); the inverse values are formed
+    on the device.  Three problems, each a fixed number of symmetric (Jacobi) averaged updates by ``ops.softmin_u8`` from potentials 0:
+
+        XY:  f' = (f + softmin(X, Y, g)) / 2 and g' = (g + softmin(Y, X, f)) / 2, both from the OLD potentials
+        XX:  p' = (p + softmin(X, X, p)) / 2, in place, the diagonal included;   YY:  r likewise
+
+    ot_xy = mean f + mean g, ot_xx = 2 mean p, ot_yy = 2 mean r, divergence = mean(f - p) + mean(g - r), relative = divergence /
+    gamma_median.  "marginal_error" = mean_i |exp((f_i - softmin(X, Y, g)_i) / eps) - 1|, the row-marginal error of the XY plan after
+    the loop: how far the fixed iteration count is from convergence.  ``terms=True``: -> (that dictionary, f - p [N], g - r [M]),
+    float64 on the device: the per-image shares, whose means add up to "divergence" -- large for a real image the generator does not
+    reach, and for a sample far from the data.  A median of 0, an eps that is no finite positive number and non-finite potentials raise
+    ValueError.  Every launch is enqueued up front; one host read, at the end."""
+    A, B = _u8_rows(real, "real"), _u8_rows(fake, "fake")
+    if A.shape[1:] != B.shape[1:] or A.device != B.device:
+        raise ValueError(f"sinkhorn: the two sets must hold images of one shape on one device, got {tuple(A.shape)} and {tuple(B.shape)}")
+    N, M = int(A.shape[0]), int(B.shape[0])
+    if N < 2 or M < 2:
+        raise ValueError(f"sinkhorn: both sets need at least 2 images, got {N} and {M}")
+    iterations, rho = int(iterations), float(rho)
+    if iterations < 1 or not 0.0 < rho < 1.0:
+        raise ValueError(f"sinkhorn: iterations = {iterations} must be >= 1 and rho = {rho} in (0, 1)")
+    value, what = (scale, "scale") if epsilon is None else (epsilon, "epsilon")
+    try:
+        value = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"sinkhorn: {what} must be a positive finite number") from None
+    if not 0.0 < value < float("inf"):
+        raise ValueError(f"sinkhorn: {what} must be a positive finite number, got {value}")
+    dev = A.device
+    pool = torch.cat((A, B))
+    P = (N + M) * (N + M - 1)
+    top = ops.dist_select_u8(pool, pool, P - 1, self0=0)                           # eps_0: the largest pooled distance
+    if epsilon is None:
+        sel = ops.dist_select_u8(pool, pool, (P - 1) // 2, self0=0)
+        eps = sel[0].double() * value
+    else:
+        sel = torch.zeros(2, device=dev, dtype=torch.int32)
+        eps = torch.tensor(value, device=dev, dtype=torch.float64)
+    decay = torch.tensor([rho ** t for t in range(iterations)], dtype=torch.float64).to(dev)
+    sched = torch.maximum(eps, top[0].double() * decay)                            # [iterations]
+    inv = sched.reciprocal()
+    flags = torch.empty(iterations + 1, device=dev, dtype=torch.int32)
+    f, g = torch.zeros(N, device=dev, dtype=torch.float64), torch.zeros(M, device=dev, dtype=torch.float64)
+    f2, g2, p, r = torch.empty_like(f), torch.empty_like(g), torch.zeros_like(f), torch.zeros_like(g)
+    for t in range(iterations):
+        ie, fl = inv[t:t + 1], flags[t:t + 1]
+        ops.softmin_u8(A, B, g, ie, prev=f, out=f2, flag=fl)
+        ops.softmin_u8(B, A, f, ie, prev=g, out=g2, flag=fl)
+        ops.softmin_u8(A, A, p, ie, prev=p, out=p, flag=fl)
+        ops.softmin_u8(B, B, r, ie, prev=r, out=r, flag=fl)
+        f, f2, g, g2 = f2, f, g2, g
+    last = ops.softmin_u8(A, B, g, inv[-1:], flag=flags[iterations:])
+    marginal = ((f - last) * inv[-1]).exp().sub(1.0).abs().mean()
+    share_x, share_y = f - p, g - r
+    finite = torch.stack([v.isfinite().all() for v in (f, g, p, r, last)]).all()
+    host = torch.stack((sel[0].double(), sel[1].double(), top[1].double(), flags.max().double(), finite.double(), sched[-1], f.mean(), g.mean(), p.mean(),
+                        r.mean(), share_x.mean(), share_y.mean(), marginal)).cpu().tolist()       # THE host read
+    med = None if epsilon is not None else int(host[0])
+    if med == 0:
+        raise ValueError(f"sinkhorn: the median distance of the pooled {N} + {M} images is zero -- more than half of the pairs are duplicates, "
+                         "there is no median temperature (pass epsilon=)")
+    if host[1] or host[2] or host[3]:
+        raise ValueError(f"sinkhorn: a select or a soft minimum refused its arguments (rank marks {int(host[1])}, {int(host[2])}; epsilon flag "
+                         f"{int(host[3])})")
+    if not host[4]:
+        raise ValueError("sinkhorn: the potentials are not finite")
+    mf, mg, mp, mr, sx, sy = host[6:12]
+    div = sx + sy
+    out = {"gamma_median": med, "epsilon": host[5], "iterations": iterations, "divergence": div, "relative": None if med is None else div / med,
+           "ot_xy": mf + mg, "ot_xx": 2.0 * mp, "ot_yy": 2.0 * mr, "marginal_error": host[12]}
+    return (out, share_x, share_y) if terms else out
+
+
+def sinkhorn_generator(kind, generator, inputs, n_images=8192, batch=None, seed=0, **kw):
+    """``sinkhorn`` of ``real_images(kind, inputs, n_images)`` against ``generate(kind, generator, n_images, batch, seed)``; ``batch`` as in
+    ``swd_generator``; ``kw``: scale, epsilon, iterations, rho, terms"""
+    _family(kind, "sinkhorn_generator")
+    batch = min(64, int(n_images)) if batch is None else int(batch)
+    fake = generate(kind, generator, n_images, batch, seed)
+    return sinkhorn(real_images(kind, inputs, n_images), fake, **kw)

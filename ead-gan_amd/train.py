@@ -148,10 +148,15 @@ def mmd_seed(seed, batches_done, plan_seed=0):
     return (int(seed) * 1000003 + int(batches_done) * 5381 + int(plan_seed) * 115249 + 24680) % (2 ** 32)
 
 
+def sinkhorn_seed(seed, batches_done, plan_seed=0):
+    """seed of a checkpoint iteration's generated images for the Sinkhorn divergence: ``swd_seed``'s form with constants of its own"""
+    return (int(seed) * 1000003 + int(batches_done) * 3571 + int(plan_seed) * 122949 + 13579) % (2 ** 32)
+
+
 def check_plan(what, plan, cls, kind, n_dataset, batch):
-    """-> ``plan`` as a ``cls`` (quality.SWDPlan, NNPlan or MMDPlan) after the checks every score plan of a run passes: the kind of the
-    run, ``n_images`` against the dataset and against the trainer's batch size; an MMD plan also needs two images a set and 1 .. 4
-    positive scales"""
+    """-> ``plan`` as a ``cls`` (quality.SWDPlan, NNPlan, MMDPlan or SinkhornPlan) after the checks every score plan of a run passes: the
+    kind of the run, ``n_images`` against the dataset and against the trainer's batch size; an MMD plan also needs two images a set and
+    1 .. 4 positive scales, a Sinkhorn plan two images a set, a positive scale and at least one iteration"""
     if kind not in ("mnist", "celeba"):
         raise ValueError(f"{what}: only 'mnist' and 'celeba' runs are scored (quality.generate), not {kind!r}")
     plan = cls(*plan)
@@ -166,6 +171,15 @@ def check_plan(what, plan, cls, kind, n_dataset, batch):
             quality._positive(plan.scales, "MMDPlan", "scales")
         except ValueError as e:
             raise ValueError(f"{what}: {e}") from None
+    if cls is quality.SinkhornPlan:
+        if int(plan.n_images) < 2:
+            raise ValueError(f"{what}: n_images = {plan.n_images}, the divergence needs at least 2 images a set")
+        try:
+            quality._positive((plan.scale,), "SinkhornPlan", "scale")
+        except ValueError as e:
+            raise ValueError(f"{what}: {e}") from None
+        if int(plan.iterations) < 1:
+            raise ValueError(f"{what}: iterations = {plan.iterations} must be at least 1")
     return plan
 
 
@@ -200,13 +214,18 @@ class TrainRun:
     -- the kernel MMD at ``scales`` times the median bandwidth of one set of generated images per generator (seeded by ``mmd_seed``)
     against the first ``n_images`` dataset images.  The same scratch generator; nothing else of the run is touched.
 
+    ``sinkhorn=quality.SinkhornPlan(n_images, scale=0.1, iterations=60, seed=0)`` (the same runs): on checkpoint iterations,
+    after the ``mmd.jsonl`` line if there is one, rank 0 appends ``{"batches_done", "G": quality.sinkhorn(...)[, "G_ema": ...]}`` to
+    ``out_dir/sinkhorn.jsonl`` -- the debiased Sinkhorn divergence of one set of generated images per generator (seeded by
+    ``sinkhorn_seed``) against the first ``n_images`` dataset images.  The same scratch generator; nothing else of the run is touched.
+
     Data parallel (``inputs.world`` > 1, the world of the trainer's ``allreduce`` / ``sync_bn``): ``graph=False`` is required; the
     iteration count, cadence, sample seeds and file names are those of one process at the global batch ``B * world``; rank 0 prints and
     writes every file, the other ranks write none (``files == []``) and print nothing but execute every ``_wait`` and keep ``history``
     / ``lines`` of their own shard.  The run adds no collective: rank 0's lines and ``losses.npy`` carry rank 0's shard losses."""
 
     def __init__(self, kind, trainer, inputs, out_dir, n_epochs, sample_interval=None, seed=0, graph=True, log_capacity=1024, log_in_graph=True,
-                 ema_samples=False, swd=None, nn=None, mmd=None):
+                 ema_samples=False, swd=None, nn=None, mmd=None, sinkhorn=None):
         self.plan = _plan(kind)
         if getattr(trainer, "STATE_KIND", None) != kind:
             raise ValueError(f"a {kind!r} run needs a {kind!r} trainer, got {type(trainer).__name__}")
@@ -250,8 +269,9 @@ class TrainRun:
                 raise ValueError("ema_samples: the trainer keeps no average of its generator -- call trainer.attach_ema(modules=('G', ...)) first")
             if self.rank == 0:
                 self._ema_G = _module_like(trainer.G).to(trainer.losses.device)
-        self.swd, self.nn, self.mmd, self._score_G = swd, nn, mmd, None       # one scratch generator serves every plan
-        for what, plan, cls in (("swd", swd, quality.SWDPlan), ("nn", nn, quality.NNPlan), ("mmd", mmd, quality.MMDPlan)):
+        self.swd, self.nn, self.mmd, self.sinkhorn, self._score_G = swd, nn, mmd, sinkhorn, None       # one scratch generator serves every plan
+        for what, plan, cls in (("swd", swd, quality.SWDPlan), ("nn", nn, quality.NNPlan), ("mmd", mmd, quality.MMDPlan),
+                                ("sinkhorn", sinkhorn, quality.SinkhornPlan)):
             if plan is None:
                 continue
             setattr(self, what, check_plan(what, plan, cls, kind, self.n_images, trainer.B))
@@ -383,6 +403,17 @@ class TrainRun:
         real = quality.to_u8(quality.real_images(self.kind, self.inputs, n))
         self._score_line("mmd.jsonl", it, lambda G: quality.mmd(real, quality.generate(self.kind, G, n, min(int(tr.B), n), seed), scales=plan.scales))
 
+    def _score_sinkhorn(self, it):
+        """one line of ``sinkhorn.jsonl``: ``quality.sinkhorn`` of one set of generated images per generator against the first
+        ``n_images`` dataset images"""
+        if self._score_G is None or self.sinkhorn is None:
+            return
+        tr, plan = self.trainer, self.sinkhorn
+        n, seed = int(plan.n_images), sinkhorn_seed(self.seed, it, plan.seed)
+        real = quality.to_u8(quality.real_images(self.kind, self.inputs, n))
+        self._score_line("sinkhorn.jsonl", it, lambda G: quality.sinkhorn(real, quality.generate(self.kind, G, n, min(int(tr.B), n), seed),
+                                                                          scale=plan.scale, iterations=plan.iterations))
+
     def _score_line(self, name, it, score):
         """``{"batches_done", "G": score(live generator)[, "G_ema": score(averaged generator)]}`` appended to ``out_dir/name``"""
         tr, G = self.trainer, self._score_G
@@ -444,6 +475,7 @@ class TrainRun:
                 self._score(it)
                 self._score_nn(it)
                 self._score_mmd(it)
+                self._score_sinkhorn(it)
             self.batches_done = it + 1
             done += 1
             if do_ckpt:

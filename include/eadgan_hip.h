@@ -818,6 +818,24 @@ int eg_kernel_sum_u8(const unsigned char* q, int nq, const unsigned char* x, int
 size_t eg_dist_select_ws_bytes(int nq, int n);
 int eg_dist_select_u8(const unsigned char* q, int nq, const unsigned char* x, int n, int K, long long self0, unsigned long long rank,
                       void* ws, int* out, eg_stream_t s);
+/* --- the soft minimum (one half-iteration of the debiased Sinkhorn divergence).  q, x, d, K, self0, the limits, the alignment of
+ * q and x, the tile loop, the slices (eg_knn_splits) and the wave layouts are eg_knn_u8's.  g: [n] doubles on the device; inv_eps: a
+ * DEVICE pointer to one double, so a whole epsilon schedule is enqueued without a host read.  With J_i = { j in [0, n) : j != self0 + i }
+ * and t_ij = (g[j] - (double)d(q[i], x[j])) * inv_eps[0] (one rounded subtraction, one rounded product):
+ *     soft[i] = -(log sum_{j in J_i} exp(t_ij) - log |J_i|) / inv_eps[0]
+ *     out[i]  = prev ? 0.5 * prev[i] + 0.5 * soft[i] : soft[i]
+ * as a streaming log-sum-exp: a running pair (m, s), m the maximum and s = sum exp(t - m), one exponential per pair of rows; two pairs
+ * are merged by rescaling the one with the smaller maximum (equal maxima, two empty pairs (-inf, 0) among them, take no exponential), and
+ * soft = -(m + (log s - log |J_i|)) / inv_eps[0].  |J_i| >= 1 is an argument check: n - 1 >= 1 where a row is excluded.
+ * ws: eg_softmin_ws_bytes(nq, n) = splits * nq * 16 bytes of per-slice pairs; the parts of a query, then its slices, are merged in a
+ * fixed order and everything is written exactly once (no atomic, no zero-fill): two calls with the same shapes give the same bits.
+ * prev may be NULL; prev, g and out may alias one another: the tile kernel only reads g and writes ws, the second kernel reads prev[i]
+ * before the same thread writes out[i].  flag[0] (device int32) is WRITTEN, not or-ed: bit 0 says inv_eps[0] is not a finite positive
+ * number (out then holds what the arithmetic gives).  g, inv_eps, prev, ws and out 8-byte aligned.  Two launches, no allocation, no
+ * sync. */
+size_t eg_softmin_ws_bytes(int nq, int n);
+int eg_softmin_u8(const unsigned char* q, int nq, const unsigned char* x, int n, int K, const double* g, const double* inv_eps, long long self0,
+                  const double* prev, void* ws, double* out, int* flag, eg_stream_t s);
 
 #ifdef __cplusplus
 }
