@@ -1230,3 +1230,205 @@ def dist_select_u8(queries, database, rank, self0=-1):
     ws = torch.empty(lib().query("eg_dist_select_ws_bytes", nq, n) // 8, device=queries.device, dtype=torch.int64)
     lib().call("eg_dist_select_u8", _p(queries), nq, _p(database), n, K, int(self0), rank, _p(ws), _p(out), _stream())
     return out
+
+
+# ---- k-means over uint8 rows --------------------------------------------------------------
+GROUP_FLAG_LABEL = 1                                  # eg_group_rows: a label outside [0, bins)
+SEED_FLAG_DUPLICATES, SEED_FLAG_U = 1, 2              # eg_kmeans_seed_u8: fewer than bins distinct rows; a u outside [0, 1)
+KMEANS_MAX_BINS = 1024
+
+
+def group_rows_block() -> int:
+    """labels per workgroup of eg_group_rows' count and scatter kernels"""
+    return lib().query("eg_group_rows_block")
+
+
+def kmeans_segment_rows() -> int:
+    """member rows per segment of eg_kmeans_update_u8"""
+    return lib().query("eg_kmeans_segment_rows")
+
+
+def kmeans_column_chunk() -> int:
+    """bytes of a row one workgroup of eg_kmeans_update_u8 sums"""
+    return lib().query("eg_kmeans_column_chunk")
+
+
+def kmeans_seed_rows() -> int:
+    """rows per workgroup of eg_kmeans_seed_u8's streaming kernel"""
+    return lib().query("eg_kmeans_seed_rows")
+
+
+def group_rows_ws_bytes(n, bins) -> int:
+    return lib().query("eg_group_rows_ws_bytes", int(n), int(bins))
+
+
+def kmeans_update_ws_bytes(n, K, bins) -> int:
+    return lib().query("eg_kmeans_update_ws_bytes", int(n), int(K), int(bins))
+
+
+def kmeans_seed_ws_bytes(n) -> int:
+    return lib().query("eg_kmeans_seed_ws_bytes", int(n))
+
+
+def _ws_bytes(ws, need, what, like):
+    """a workspace of at least ``need`` bytes: ``ws`` (a contiguous device tensor, 16-byte aligned) or a new one"""
+    if ws is None:
+        return torch.empty((need + 15) // 16 * 2, device=like.device, dtype=torch.int64)
+    if not (isinstance(ws, torch.Tensor) and ws.is_contiguous() and ws.device == like.device and ws.numel() * ws.element_size() >= need
+            and ws.data_ptr() % 16 == 0):
+        raise ValueError(f"{what}: ws must be a contiguous 16-byte aligned device tensor of at least {need} bytes")
+    return ws
+
+
+def _check_bins(what, bins):
+    bins = int(bins)
+    if not 1 <= bins <= KMEANS_MAX_BINS:
+        raise ValueError(f"{what}: bins = {bins} must be in 1 .. {KMEANS_MAX_BINS}")
+    return bins
+
+
+def _u8_table(what, rows):
+    """the checks of ``knn_u8`` on one operand -> (n, K)"""
+    if not (isinstance(rows, torch.Tensor) and rows.dtype == torch.uint8 and rows.dim() >= 2 and rows.is_contiguous()):
+        raise ValueError(f"{what}: rows must be a contiguous uint8 device tensor [n, ...]")
+    n = int(rows.shape[0])
+    K = rows[0].numel() if n else 0
+    if n < 1:
+        raise ValueError(f"{what}: rows {tuple(rows.shape)} holds no row")
+    if K % 64 or not 64 <= K <= 32768:
+        raise ValueError(f"{what}: the row length must be a multiple of 64 in 64 .. 32768, got {K}")
+    if not rows.is_cuda:
+        raise ValueError(f"{what}: rows must be a contiguous uint8 device tensor (there is no CPU path)")
+    return n, K
+
+
+def _i32(what, name, t, shape, like):
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and tuple(t.shape) == tuple(shape) and t.is_contiguous() and t.device == like.device):
+        raise ValueError(f"{what}: {name} must be a contiguous int32 device tensor {list(shape)}, beside the rows")
+
+
+def group_rows(labels, bins, ws=None, flag=None):
+    """-> (counts [bins], offsets [bins + 1], order [n]), int32 on the device: a stable counting sort of the int32 device labels [n] into
+    ``bins`` cells (1 .. 1024).  The rows of cell c are ``order[offsets[c]:offsets[c + 1]]``, ascending.  A label outside [0, bins) joins
+    no cell: ``offsets[bins]`` counts the rows that joined one, the tail of ``order`` holds -1 and bit ``GROUP_FLAG_LABEL`` of ``flag``
+    (an int32 device tensor [1], WRITTEN; not reported without it) is raised.  Three launches, no host read."""
+    if not (isinstance(labels, torch.Tensor) and labels.dtype == torch.int32 and labels.dim() == 1 and labels.is_contiguous() and labels.shape[0] >= 1):
+        raise ValueError("group_rows: labels must be a contiguous int32 device tensor [n], n >= 1")
+    if not labels.is_cuda:
+        raise ValueError("group_rows: labels must be on the device (there is no CPU path)")
+    bins, n = _check_bins("group_rows", bins), int(labels.shape[0])
+    if flag is None:
+        flag = torch.empty(1, device=labels.device, dtype=torch.int32)
+    else:
+        _i32("group_rows", "flag", flag, (1,), labels)
+    ws = _ws_bytes(ws, group_rows_ws_bytes(n, bins), "group_rows", labels)
+    counts = torch.empty(bins, device=labels.device, dtype=torch.int32)
+    offsets = torch.empty(bins + 1, device=labels.device, dtype=torch.int32)
+    order = torch.empty(n, device=labels.device, dtype=torch.int32)
+    lib().call("eg_group_rows", _p(labels), n, bins, _p(ws), _p(counts), _p(offsets), _p(order), _p(flag), _stream())
+    return counts, offsets, order
+
+
+def _check_centres(what, centres, bins, K, like):
+    if not (isinstance(centres, torch.Tensor) and centres.dtype == torch.uint8 and centres.dim() >= 2 and centres.is_contiguous()
+            and centres.shape[0] == bins and centres[0].numel() == K and centres.device == like.device):
+        raise ValueError(f"{what}: centres must be a contiguous uint8 device tensor [{bins}, ...] with rows of {K} bytes, beside the rows")
+
+
+def kmeans_update_u8(rows, order, offsets, counts, centres, ws=None):
+    """centres [bins, ...] (uint8, IN PLACE) <- the rounded means of the cells ``group_rows`` made of ``rows`` [n, ...]: for a cell with
+    count > 0, centre[t] = (2 sum[t] + count) // (2 count) -- round half up from exact int32 column sums, so n * 255 < 2^31 --; a cell
+    with count == 0 keeps its bytes.  Returns ``centres``.  Three launches, no host read."""
+    n, K = _u8_table("kmeans_update_u8", rows)
+    if n * 255 >= 2 ** 31:
+        raise ValueError(f"kmeans_update_u8: n = {n} rows: n * 255 must stay below 2^31 (the column sums are int32)")
+    if not (isinstance(counts, torch.Tensor) and counts.dim() == 1):
+        raise ValueError("kmeans_update_u8: counts must be a contiguous int32 device tensor [bins]")
+    bins = _check_bins("kmeans_update_u8", counts.shape[0])
+    _i32("kmeans_update_u8", "counts", counts, (bins,), rows)
+    _i32("kmeans_update_u8", "offsets", offsets, (bins + 1,), rows)
+    _i32("kmeans_update_u8", "order", order, (n,), rows)
+    _check_centres("kmeans_update_u8", centres, bins, K, rows)
+    ws = _ws_bytes(ws, kmeans_update_ws_bytes(n, K, bins), "kmeans_update_u8", rows)
+    lib().call("eg_kmeans_update_u8", _p(rows), n, K, _p(order), _p(offsets), _p(counts), bins, _p(ws), _p(centres), _stream())
+    return centres
+
+
+def kmeans_seed_u8(rows, bins, u, flag=None):
+    """-> (idx int32 [bins], centres uint8 [bins, ...]) on the device: k-means++ seeding of ``rows`` [n, ...] driven by ``u``, a
+    contiguous fp32 device tensor of ``bins`` uniforms in [0, 1).  Centre 0 is row min(floor(u[0] n), n - 1); for j >= 1, with mind[i]
+    the exact squared distance from row i to its nearest chosen centre and total its int64 sum, the pick is the lowest row whose
+    inclusive prefix sum of mind exceeds min(floor((double)u[j] * (double)total), total - 1): a copy of a chosen centre is never picked.
+    ``flag`` (int32 device tensor [1], WRITTEN; not reported without it): ``SEED_FLAG_DUPLICATES`` = fewer than ``bins`` distinct rows,
+    ``SEED_FLAG_U`` = a u outside [0, 1).  n * 2^31 <= 2^53.  All 2 bins - 1 launches are enqueued at once, no host read."""
+    n, K = _u8_table("kmeans_seed_u8", rows)
+    bins = _check_bins("kmeans_seed_u8", bins)
+    if n > 2 ** 22:
+        raise ValueError(f"kmeans_seed_u8: n = {n} rows: n * 2^31 must not exceed 2^53 (the sum of the distances is exact in a double)")
+    if not (isinstance(u, torch.Tensor) and u.dtype == torch.float32 and tuple(u.shape) == (bins,) and u.is_contiguous() and u.device == rows.device):
+        raise ValueError(f"kmeans_seed_u8: u must be a contiguous fp32 device tensor [{bins}], beside the rows")
+    if flag is None:
+        flag = torch.empty(1, device=rows.device, dtype=torch.int32)
+    else:
+        _i32("kmeans_seed_u8", "flag", flag, (1,), rows)
+    ws = _ws_bytes(None, kmeans_seed_ws_bytes(n), "kmeans_seed_u8", rows)
+    idx = torch.empty(bins, device=rows.device, dtype=torch.int32)
+    centres = torch.empty((bins,) + tuple(rows.shape[1:]), device=rows.device, dtype=torch.uint8)
+    lib().call("eg_kmeans_seed_u8", _p(rows), n, K, bins, _p(u), _p(ws), _p(idx), _p(centres), _p(flag), _stream())
+    return idx, centres
+
+
+def kmeans_u8(rows, bins, iterations=20, u=None, init=None, flag=None):
+    """Lloyd's k-means over uint8 rows with byte centres -> (centres uint8 [bins, ...], labels int32 [n], counts int32 [bins], log), all
+    on the device; log = {"inertia": int64 [iterations + 1], "changed": int32 [iterations]}.
+
+    The centres start from ``kmeans_seed_u8(rows, bins, u)`` or from ``init``: int row indices [bins] or uint8 centres [bins, ...].  For
+    t < iterations: labels_t = the nearest centre (``knn_u8(rows, centres_t, 1)``: exact distances, ties to the lower centre),
+    inertia[t] = the sum of the rows' distances to their centres, changed[t] = the rows whose label differs from labels_{t-1} (n at
+    t = 0), centres_{t+1} = ``kmeans_update_u8``.  A last assignment gives the returned labels, counts and inertia[iterations].  The
+    iteration count is fixed: after changed == 0 the remaining iterations are fixed points.  Centres are bytes, so the inertia need not
+    fall monotonically.  ``flag`` (int32 device tensor [1], WRITTEN): the seeding's flag word, 0 with ``init``.  Every launch is
+    enqueued up front; there is no host read."""
+    n, K = _u8_table("kmeans_u8", rows)
+    bins, iterations = _check_bins("kmeans_u8", bins), int(iterations)
+    if iterations < 0:
+        raise ValueError(f"kmeans_u8: iterations = {iterations} must be >= 0")
+    if n * 255 >= 2 ** 31:
+        raise ValueError(f"kmeans_u8: n = {n} rows: n * 255 must stay below 2^31 (the column sums are int32)")
+    if (u is None) == (init is None):
+        raise ValueError("kmeans_u8: pass either u (the seeding's uniforms) or init (row indices or centres)")
+    dev = rows.device
+    if flag is None:
+        flag = torch.empty(1, device=dev, dtype=torch.int32)
+    else:
+        _i32("kmeans_u8", "flag", flag, (1,), rows)
+    if init is None:
+        _, centres = kmeans_seed_u8(rows, bins, u, flag=flag)
+    else:
+        if not (isinstance(init, torch.Tensor) and init.device == dev):
+            raise ValueError("kmeans_u8: init must be a device tensor beside the rows: int row indices [bins] or uint8 centres [bins, ...]")
+        if init.dtype in (torch.int32, torch.int64) and tuple(init.shape) == (bins,):
+            centres = rows[init.long()].contiguous()                # an index outside the rows is torch's device-side assertion
+        else:
+            _check_centres("kmeans_u8", init, bins, K, rows)
+            centres = init.clone()
+        flag.zero_()
+    inertia = torch.empty(iterations + 1, device=dev, dtype=torch.int64)
+    changed = torch.empty(iterations, device=dev, dtype=torch.int32)
+    group_ws = _ws_bytes(None, group_rows_ws_bytes(n, bins), "kmeans_u8", rows)
+    update_ws = _ws_bytes(None, kmeans_update_ws_bytes(n, K, bins), "kmeans_u8", rows)
+    pair = [(torch.empty(n, 1, device=dev, dtype=torch.int32), torch.empty(n, 1, device=dev, dtype=torch.int32)) for _ in range(2)]
+    gflag = torch.empty(1, device=dev, dtype=torch.int32)
+    prev = None
+    for t in range(iterations + 1):
+        dist, idx = knn_u8(rows, centres, 1, out=pair[t & 1])
+        labels = idx.reshape(n)
+        inertia[t] = dist.sum(dtype=torch.int64)
+        if t == iterations:
+            break
+        changed[t] = n if prev is None else (labels != prev).sum()
+        counts, offsets, order = group_rows(labels, bins, ws=group_ws, flag=gflag)
+        kmeans_update_u8(rows, order, offsets, counts, centres, ws=update_ws)
+        prev = labels
+    counts = group_rows(labels, bins, ws=group_ws, flag=gflag)[0]
+    return centres, labels, counts, {"inertia": inertia, "changed": changed}

@@ -47,6 +47,23 @@ search's tile loop, one call per half-iteration; the distance matrix is never st
 * ``sinkhorn_generator(kind, generator, inputs)`` the same for a generator of an MNIST or CelebA run
 * ``SinkhornPlan``                               what ``train.TrainRun(..., sinkhorn=...)`` scores on checkpoint iterations
 
+Which modes of the data the generator drops or over-produces: the Number of statistically Different Bins of Richardson &
+Weiss, "On GANs and GMMs" (2018).  The real images are cut into Voronoi cells by k-means over their bytes (ops.kmeans_u8: centres are
+bytes, i.e. images; k-means++ seeding and the centre update are streaming passes on the device, the assignment is ops.knn_u8), real and
+generated images are counted per cell and every cell takes a two-proportion z-test:
+
+* ``image_bins(images, bins)``                   the fitted cells: ``Bins(centres, counts, labels, inertia, changed)``
+* ``bin_counts(images, centres)``                how many images fall into every cell
+* ``ndb(real, fake, bins)``                      the number of cells whose share differs at the 5 % level, the Jensen-Shannon divergence of
+                                                 the two histograms; with ``terms=True`` the per-cell z, real and generated counts as well
+* ``bin_grid`` / ``save_bins``                   the figure: the cell centres ordered by z, most under-produced first
+* ``ndb_generator(kind, generator, inputs)``     ``ndb`` for a generator of an MNIST or CelebA run
+* ``NDBPlan``                                    what ``train.TrainRun(..., ndb=...)`` scores on checkpoint iterations
+
+Bins fitted on ``real`` itself are biased towards ``real`` (the cells are where its rows are dense): two samples of one distribution do
+NOT give 0.05 x bins.  In a numpy trial of this contract two samples of one 30-mode mixture (4000 rows, 50 bins) gave NDB 2 .. 8 against
+the nominal 2.5, so read a number against the NDB of a held-out real split, or fit the bins elsewhere (``centres=``).
+
 Per level and set: patch statistics (ops.swd_patch_stats), then per repeat one fused gather-and-project launch (ops.swd_project: the
 descriptors, 0.6 GB per set and level at full size, never exist), one column sort per set (ops.sort_columns) and one reduction
 (ops.l1_mean).  Everything is enqueued on the current stream; ``swd`` reads the device once, at its end.  There is no CPU path.
@@ -64,6 +81,7 @@ PATCH, MIN_SIDE = 7, 16
 # Philox stream ids of this module's draws (ops.rng_fill): a block no sampler uses (the samplers' ids are 1 .. 8).  The device counter of
 # a draw holds the level (centres), level * repeats + repeat (directions) or the batch index (generator inputs).
 SID_POSITIONS, SID_DIRECTIONS, SID_NOISE, SID_LABELS, SID_CODE = 0x5D00, 0x5D01, 0x5D10, 0x5D11, 0x5D12
+SID_BINS = 0x5D20                # the k-means seeding's uniforms (image_bins); the device counter holds 0
 # how the trainers see a dataset image: eg_gather_u8_images' scale and shift (celebA/EAD-GAN_celebA.py:194-201, MNIST/EAD-GAN_rpqmnxy.py:235-243)
 _REAL_SCALE = {"mnist": (2.0 / 255.0, -1.0), "celeba": (2.0 / 255.0, -1.0)}
 _SPRITES = ("dsprites", "colored", "pxy")
@@ -101,6 +119,25 @@ class SinkhornPlan(NamedTuple):
     scale: float = 0.1
     iterations: int = 60
     seed: int = 0
+
+
+class NDBPlan(NamedTuple):
+    """the NDB score a training run writes on its checkpoint iterations (``ndb`` over ``bins`` k-means cells of the real images, fitted
+    once with ``iterations`` Lloyd iterations): ``n_images`` generated against the first ``n_images`` dataset images"""
+    n_images: int
+    bins: int = 100
+    iterations: int = 20
+    seed: int = 0
+
+
+class Bins(NamedTuple):
+    """k-means cells of an image set (``image_bins``), on the device: ``centres`` uint8 [bins, C, H, W]; ``counts`` int32 [bins] and
+    ``labels`` int32 [N] of the fitted images; ``inertia`` int64 [iterations + 1]; ``changed`` int32 [iterations]"""
+    centres: torch.Tensor
+    counts: torch.Tensor
+    labels: torch.Tensor
+    inertia: torch.Tensor
+    changed: torch.Tensor
 
 
 def level_sides(H):
@@ -645,3 +682,161 @@ def sinkhorn_generator(kind, generator, inputs, n_images=8192, batch=None, seed=
     batch = min(64, int(n_images)) if batch is None else int(batch)
     fake = generate(kind, generator, n_images, batch, seed)
     return sinkhorn(real_images(kind, inputs, n_images), fake, **kw)
+
+
+# ---- k-means bins and the NDB score ------------------------------------------------------------------------------------------
+Z_975 = 1.959963984540054                                                    # the 0.975 quantile of the normal distribution: a two-sided 5 % test
+
+
+def bin_uniforms(seed, bins, device="cuda"):
+    """-> fp32 [bins] in [0, 1) on the device: the uniforms ``image_bins(..., seed=seed)`` seeds its k-means with (one ops.rng_fill draw
+    on this module's stream SID_BINS; the generator's largest value rounds to 1.0 in fp32 and is clamped to the largest fp32 below 1)"""
+    u = torch.empty(int(bins), device=torch.device(device), dtype=torch.float32)
+    step = torch.zeros(1, device=u.device, dtype=torch.int32)
+    ops.rng_fill(ops.RNG_UNIFORM, u, 0.0, 1.0, seed, step, SID_BINS)
+    return u.clamp_(0.0, 1.0 - 2.0 ** -24)
+
+
+def _check_fit(what, bins, iterations, n):
+    bins, iterations = int(bins), int(iterations)
+    if not 1 <= bins <= min(ops.KMEANS_MAX_BINS, int(n)):
+        raise ValueError(f"quality.{what}: bins = {bins} must be in 1 .. min({ops.KMEANS_MAX_BINS}, images = {int(n)})")
+    if iterations < 0:
+        raise ValueError(f"quality.{what}: iterations = {iterations} must be >= 0")
+    return bins, iterations
+
+
+def _fit_bins(rows, bins, iterations, seed):
+    """-> (Bins, the seeding's flag word on the device) for uint8 rows: no host read"""
+    flag = torch.empty(1, device=rows.device, dtype=torch.int32)
+    centres, labels, counts, log = ops.kmeans_u8(rows, bins, iterations, u=bin_uniforms(seed, bins, rows.device), flag=flag)
+    return Bins(centres, counts, labels, log["inertia"], log["changed"]), flag
+
+
+def _raise_seed_flag(what, flag, bins):
+    if flag & ops.SEED_FLAG_DUPLICATES:
+        raise ValueError(f"quality.{what}: the images hold fewer than bins = {bins} distinct ones: there is nothing left to seed a cell with")
+    if flag:
+        raise ValueError(f"quality.{what}: the seeding refused its uniforms (flag {flag})")
+
+
+def image_bins(images, bins=100, iterations=20, seed=0):
+    """k-means cells of an image set [N, C, H, W] (float in [-1, 1] through ``to_u8``, or uint8) over the exact squared L2 distance between
+    the bytes -> ``Bins(centres, counts, labels, inertia, changed)`` on the device (``ops.kmeans_u8``: k-means++ seeding from ``seed``, a
+    fixed number of Lloyd ``iterations``, centres rounded to bytes -- they are images --, ties to the lower cell, empty cells keep their
+    centre).  Deterministic: the same images and seed give the same bits.  Fewer than ``bins`` distinct images raise ValueError (the one
+    host read, of the seeding's flag)."""
+    rows = _u8_rows(images, "images")
+    bins, iterations = _check_fit("image_bins", bins, iterations, rows.shape[0])
+    fit, flag = _fit_bins(rows, bins, iterations, seed)
+    _raise_seed_flag("image_bins", int(flag.cpu()), bins)                    # THE host read
+    return fit
+
+
+def _check_centres(what, centres, rows):
+    if not (isinstance(centres, torch.Tensor) and centres.dtype == torch.uint8 and centres.dim() == 4 and centres.shape[1:] == rows.shape[1:]
+            and centres.device == rows.device and 1 <= centres.shape[0] <= ops.KMEANS_MAX_BINS):
+        raise ValueError(f"quality.{what}: centres must be a uint8 device tensor [bins <= {ops.KMEANS_MAX_BINS}, ...] of images shaped like the "
+                         f"others, {tuple(rows.shape[1:])}")
+    return centres.contiguous()
+
+
+def bin_counts(images, centres):
+    """-> int32 [bins] on the device: how many of ``images`` (float in [-1, 1] or uint8) have ``centres[c]`` (uint8 [bins, C, H, W], e.g.
+    ``image_bins(...).centres``) as their nearest centre, ties to the lower cell: one ``ops.knn_u8`` and a count, no host read"""
+    rows = _u8_rows(images, "images")
+    centres = _check_centres("bin_counts", centres, rows)
+    labels = ops.knn_u8(rows, centres, 1)[1].reshape(-1)
+    return ops.group_rows(labels, int(centres.shape[0]))[0]
+
+
+def ndb_statistics(a, b, z_threshold=Z_975):
+    """the host half of ``ndb``: from the real and generated counts per bin (sequences of ints) -> (dictionary, z) over Python floats.
+    p = a / N, q = b / M, P = (a + b) / (N + M), SE = sqrt(P (1 - P) (1 / N + 1 / M)), z = (q - p) / SE and 0 where SE = 0; "ndb" = the
+    bins with |z| > z_threshold; "js" = the Jensen-Shannon divergence of p and q in bits, with 0 log 0 = 0, in [0, 1]"""
+    import math
+    a, b = [int(v) for v in a], [int(v) for v in b]
+    N, M = sum(a), sum(b)
+    if len(a) != len(b) or not a or N < 1 or M < 1:
+        raise ValueError("quality.ndb_statistics: two count vectors of one length >= 1, each with a positive sum")
+    z, js = [], 0.0
+    for x, y in zip(a, b):
+        p, q, P = x / N, y / M, (x + y) / (N + M)
+        se = math.sqrt(P * (1.0 - P) * (1.0 / N + 1.0 / M))
+        z.append((q - p) / se if se > 0.0 else 0.0)
+        m = 0.5 * (p + q)
+        if p > 0.0:
+            js += 0.5 * (p * math.log2(p / m))
+        if q > 0.0:
+            js += 0.5 * (q * math.log2(q / m))
+    different = sum(1 for v in z if abs(v) > z_threshold)
+    return {"bins": len(z), "ndb": different, "ndb_over_bins": different / len(z), "js": min(1.0, max(0.0, js)),
+            "empty_real": sum(1 for v in a if v == 0), "empty_fake": sum(1 for v in b if v == 0)}, z
+
+
+def ndb(real, fake, bins=100, iterations=20, seed=0, centres=None, z_threshold=Z_975, terms=False):
+    """Number of statistically Different Bins (Richardson & Weiss 2018) between ``real`` [N, C, H, W] and ``fake`` [M, C, H, W] (float in
+    [-1, 1] or uint8; N != M is allowed): ``real`` is cut into ``bins`` k-means cells (``image_bins(real, bins, iterations, seed)``), both
+    sets are counted per cell (a, b) and every cell takes the two-proportion z-test of ``ndb_statistics``
+    -> {"bins", "ndb", "ndb_over_bins", "js", "empty_real", "empty_fake", "inertia", "changed_last"}: "ndb" = the cells with
+    |z| > ``z_threshold`` (default: the two-sided 5 % level), "js" the Jensen-Shannon divergence of the two histograms in bits,
+    "empty_*" the cells without a real / generated image, "inertia" the fit's final sum of squared distances and "changed_last" the rows
+    that changed cell in its last iteration (0: the fit is at a fixed point).  ``centres=``: uint8 [bins, C, H, W] fitted elsewhere, e.g.
+    on the whole dataset; nothing is fitted then, and "inertia" and "changed_last" are None.  ``terms=True``: -> (that dictionary, z, a,
+    b), Python lists per cell; z < 0 marks a cell the generator under-produces.
+
+    Cells fitted on ``real`` itself are biased towards ``real``: two samples of one distribution give more than 0.05 x bins (2 .. 8
+    instead of 2.5 for 50 bins in a numpy trial), so compare with the NDB of a held-out real split.  All numbers are Python numbers
+    computed on the host from the exact integer counts.  Every launch is enqueued up front; one host read."""
+    A, B = _u8_rows(real, "real"), _u8_rows(fake, "fake")
+    if A.shape[1:] != B.shape[1:] or A.device != B.device:
+        raise ValueError(f"ndb: the two sets must hold images of one shape on one device, got {tuple(A.shape)} and {tuple(B.shape)}")
+    try:
+        z_threshold = float(z_threshold)
+    except (TypeError, ValueError):
+        raise ValueError("ndb: z_threshold must be a positive finite number") from None
+    if not 0.0 < z_threshold < float("inf"):
+        raise ValueError(f"ndb: z_threshold must be a positive finite number, got {z_threshold}")
+    dev = A.device
+    if centres is None:
+        nb, iterations = _check_fit("ndb", bins, iterations, A.shape[0])
+        fit, flag = _fit_bins(A, nb, iterations, seed)
+        centres, a = fit.centres, fit.counts
+        last = fit.changed[-1:].long() if iterations else torch.zeros(1, device=dev, dtype=torch.int64)
+        head = torch.cat((flag.long(), fit.inertia[-1:], last))
+    else:
+        centres = _check_centres("ndb", centres, A)
+        nb, iterations = int(centres.shape[0]), None
+        a = bin_counts(A, centres)
+        head = torch.zeros(3, device=dev, dtype=torch.int64)
+    b = bin_counts(B, centres)
+    host = torch.cat((head, a.long(), b.long())).cpu().tolist()               # THE host read
+    _raise_seed_flag("ndb", host[0], nb)
+    out, z = ndb_statistics(host[3:3 + nb], host[3 + nb:], z_threshold)
+    out["inertia"] = None if iterations is None else host[1]
+    out["changed_last"] = host[2] if iterations else None
+    return (out, z, host[3:3 + nb], host[3 + nb:]) if terms else out
+
+
+def bin_grid(centres, z):
+    """-> fp32 [bins, C, H, W] in [0, 1] on the device: the cell centres ordered by ``z`` ascending (``ndb(..., terms=True)``'s second
+    result), the most under-produced cell first; equal z keep the cell order"""
+    if not (isinstance(centres, torch.Tensor) and centres.is_cuda and centres.dtype == torch.uint8 and centres.dim() == 4 and len(z) == centres.shape[0]):
+        raise ValueError("quality.bin_grid: centres must be a uint8 device tensor [bins, C, H, W] and z one number per cell")
+    order = sorted(range(len(z)), key=lambda c: (float(z[c]), c))
+    table = torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255.0)).to(centres.device)      # u / 255 correctly rounded
+    return table[centres[torch.tensor(order, device=centres.device)].long()]
+
+
+def save_bins(fp, centres, z, nrow=10):
+    """writes ``bin_grid`` as a PNG, ``nrow`` centres a row, reading order = ascending z"""
+    sampling.save_image(bin_grid(centres, z), fp, nrow=int(nrow))
+
+
+def ndb_generator(kind, generator, inputs, n_images=8192, batch=None, seed=0, **kw):
+    """``ndb`` of ``real_images(kind, inputs, n_images)`` against ``generate(kind, generator, n_images, batch, seed)``, the bins seeded by
+    ``seed`` as well; ``batch`` as in ``swd_generator``; ``kw``: bins, iterations, centres, z_threshold, terms"""
+    _family(kind, "ndb_generator")
+    batch = min(64, int(n_images)) if batch is None else int(batch)
+    fake = generate(kind, generator, n_images, batch, seed)
+    return ndb(real_images(kind, inputs, n_images), fake, seed=seed, **kw)

@@ -153,10 +153,17 @@ def sinkhorn_seed(seed, batches_done, plan_seed=0):
     return (int(seed) * 1000003 + int(batches_done) * 3571 + int(plan_seed) * 122949 + 13579) % (2 ** 32)
 
 
+def ndb_seed(seed, batches_done, plan_seed=0):
+    """seed of a checkpoint iteration's generated images for the NDB score: ``swd_seed``'s form with constants of its own.  (The bins of
+    the real images are fitted once, from the plan's own seed.)"""
+    return (int(seed) * 1000003 + int(batches_done) * 2909 + int(plan_seed) * 137911 + 86420) % (2 ** 32)
+
+
 def check_plan(what, plan, cls, kind, n_dataset, batch):
-    """-> ``plan`` as a ``cls`` (quality.SWDPlan, NNPlan, MMDPlan or SinkhornPlan) after the checks every score plan of a run passes: the
-    kind of the run, ``n_images`` against the dataset and against the trainer's batch size; an MMD plan also needs two images a set and
-    1 .. 4 positive scales, a Sinkhorn plan two images a set, a positive scale and at least one iteration"""
+    """-> ``plan`` as a ``cls`` (quality.SWDPlan, NNPlan, MMDPlan, SinkhornPlan or NDBPlan) after the checks every score plan of a run
+    passes: the kind of the run, ``n_images`` against the dataset and against the trainer's batch size; an MMD plan also needs two images
+    a set and 1 .. 4 positive scales, a Sinkhorn plan two images a set, a positive scale and at least one iteration, an NDB plan
+    1 .. min(1024, n_images) bins and no negative iteration count"""
     if kind not in ("mnist", "celeba"):
         raise ValueError(f"{what}: only 'mnist' and 'celeba' runs are scored (quality.generate), not {kind!r}")
     plan = cls(*plan)
@@ -180,6 +187,11 @@ def check_plan(what, plan, cls, kind, n_dataset, batch):
             raise ValueError(f"{what}: {e}") from None
         if int(plan.iterations) < 1:
             raise ValueError(f"{what}: iterations = {plan.iterations} must be at least 1")
+    if cls is quality.NDBPlan:
+        if not 1 <= int(plan.bins) <= min(ops.KMEANS_MAX_BINS, int(plan.n_images)):
+            raise ValueError(f"{what}: bins = {plan.bins} must be in 1 .. min({ops.KMEANS_MAX_BINS}, n_images = {plan.n_images})")
+        if int(plan.iterations) < 0:
+            raise ValueError(f"{what}: iterations = {plan.iterations} must not be negative")
     return plan
 
 
@@ -219,13 +231,20 @@ class TrainRun:
     ``out_dir/sinkhorn.jsonl`` -- the debiased Sinkhorn divergence of one set of generated images per generator (seeded by
     ``sinkhorn_seed``) against the first ``n_images`` dataset images.  The same scratch generator; nothing else of the run is touched.
 
+    ``ndb=quality.NDBPlan(n_images, bins=100, iterations=20, seed=0)`` (the same runs): on checkpoint iterations, after the
+    ``sinkhorn.jsonl`` line if there is one, rank 0 appends ``{"batches_done", "G": quality.ndb(...)[, "G_ema": ...]}`` to
+    ``out_dir/ndb.jsonl`` -- the number of statistically different bins of one set of generated images per generator (seeded by
+    ``ndb_seed``) against the first ``n_images`` dataset images.  The real set does not change during a run: its bins are fitted once,
+    at the first scored checkpoint, from the plan's seed, and kept on the run object (``ndb_bins``).  They are no part of
+    ``run_state_%d.pt``: a resumed run refits them, and the fit is deterministic, so it gets the same bits.
+
     Data parallel (``inputs.world`` > 1, the world of the trainer's ``allreduce`` / ``sync_bn``): ``graph=False`` is required; the
     iteration count, cadence, sample seeds and file names are those of one process at the global batch ``B * world``; rank 0 prints and
     writes every file, the other ranks write none (``files == []``) and print nothing but execute every ``_wait`` and keep ``history``
     / ``lines`` of their own shard.  The run adds no collective: rank 0's lines and ``losses.npy`` carry rank 0's shard losses."""
 
     def __init__(self, kind, trainer, inputs, out_dir, n_epochs, sample_interval=None, seed=0, graph=True, log_capacity=1024, log_in_graph=True,
-                 ema_samples=False, swd=None, nn=None, mmd=None, sinkhorn=None):
+                 ema_samples=False, swd=None, nn=None, mmd=None, sinkhorn=None, ndb=None):
         self.plan = _plan(kind)
         if getattr(trainer, "STATE_KIND", None) != kind:
             raise ValueError(f"a {kind!r} run needs a {kind!r} trainer, got {type(trainer).__name__}")
@@ -270,8 +289,9 @@ class TrainRun:
             if self.rank == 0:
                 self._ema_G = _module_like(trainer.G).to(trainer.losses.device)
         self.swd, self.nn, self.mmd, self.sinkhorn, self._score_G = swd, nn, mmd, sinkhorn, None       # one scratch generator serves every plan
+        self.ndb, self.ndb_bins = ndb, None                         # ndb_bins: quality.Bins of the real images, fitted at the first scored checkpoint
         for what, plan, cls in (("swd", swd, quality.SWDPlan), ("nn", nn, quality.NNPlan), ("mmd", mmd, quality.MMDPlan),
-                                ("sinkhorn", sinkhorn, quality.SinkhornPlan)):
+                                ("sinkhorn", sinkhorn, quality.SinkhornPlan), ("ndb", ndb, quality.NDBPlan)):
             if plan is None:
                 continue
             setattr(self, what, check_plan(what, plan, cls, kind, self.n_images, trainer.B))
@@ -414,6 +434,25 @@ class TrainRun:
         self._score_line("sinkhorn.jsonl", it, lambda G: quality.sinkhorn(real, quality.generate(self.kind, G, n, min(int(tr.B), n), seed),
                                                                           scale=plan.scale, iterations=plan.iterations))
 
+    def _score_ndb(self, it):
+        """one line of ``ndb.jsonl``: ``quality.ndb`` of one set of generated images per generator against the bins of the
+        first ``n_images`` dataset images, which are fitted here once"""
+        if self._score_G is None or self.ndb is None:
+            return
+        tr, plan = self.trainer, self.ndb
+        n, seed = int(plan.n_images), ndb_seed(self.seed, it, plan.seed)
+        real = quality.to_u8(quality.real_images(self.kind, self.inputs, n))
+        if self.ndb_bins is None:
+            self.ndb_bins = quality.image_bins(real, plan.bins, plan.iterations, plan.seed)
+        fit = self.ndb_bins
+        inertia, changed = int(fit.inertia[-1]), (int(fit.changed[-1]) if int(plan.iterations) else None)
+
+        def score(G):
+            out = quality.ndb(real, quality.generate(self.kind, G, n, min(int(tr.B), n), seed), centres=fit.centres)
+            out["inertia"], out["changed_last"] = inertia, changed      # the line of quality.ndb(real, fake, bins, iterations, plan.seed)
+            return out
+        self._score_line("ndb.jsonl", it, score)
+
     def _score_line(self, name, it, score):
         """``{"batches_done", "G": score(live generator)[, "G_ema": score(averaged generator)]}`` appended to ``out_dir/name``"""
         tr, G = self.trainer, self._score_G
@@ -476,6 +515,7 @@ class TrainRun:
                 self._score_nn(it)
                 self._score_mmd(it)
                 self._score_sinkhorn(it)
+                self._score_ndb(it)
             self.batches_done = it + 1
             done += 1
             if do_ckpt:

@@ -837,6 +837,46 @@ size_t eg_softmin_ws_bytes(int nq, int n);
 int eg_softmin_u8(const unsigned char* q, int nq, const unsigned char* x, int n, int K, const double* g, const double* inv_eps, long long self0,
                   const double* prev, void* ws, double* out, int* flag, eg_stream_t s);
 
+/* --- k-means over rows of uint8 (the bins of the NDB score; not in the reference).  rows [n][K] contiguous uint8, 16-byte
+ * aligned, K a multiple of 64 in 64 .. 32768 (eg_knn_u8's limits); 1 <= bins <= 1024.  The contract:
+ *   centres  are BYTES, [bins][K] uint8: a centre is an image, it can be shown and passed to every *_u8 entry point.  The rounding moves a
+ *            centre by at most half a grey level per pixel; Lloyd's inertia is therefore not guaranteed to be monotone.
+ *   assign   label[i] = the nearest centre by the exact squared L2 distance, ties to the lower index: eg_knn_u8(rows, centres, 1).
+ *   update   a cell with count > 0: centre[t] = (2 sum[t] + count) / (2 count) in integers (round half up) from exact int32 column sums
+ *            (n * 255 < 2^31 is an argument check); a cell with count == 0 keeps its bytes.
+ *   seeding  k-means++ driven by u, bins fp32 uniforms in [0, 1) on the device: centre 0 is row min(floor((double)u[0] * n), n - 1); for
+ *            j >= 1, with mind[i] the exact distance from row i to its nearest chosen centre and total its int64 sum,
+ *            target = min(floor((double)u[j] * (double)total), total - 1) and the pick is the lowest row whose inclusive prefix sum of
+ *            mind exceeds target: a row at distance 0 from a chosen centre is never picked.  n * 2^31 <= 2^53 is an argument check, so
+ *            total is exact in a double and the product is one rounded multiplication.
+ * No allocation, no sync; every output and workspace word is written once per launch that owns it, nothing is zero-filled or added to,
+ * results do not depend on earlier workspace contents, all sums are integers: two calls give the same bits.
+ * eg_group_rows: a stable counting sort of labels [n] (int32) into cells.  counts [bins], offsets [bins + 1] (the exclusive scan of the
+ * counts; offsets[bins] = the rows that joined a cell), order [n]: the rows of cell c are order[offsets[c] .. offsets[c + 1]), ascending.
+ * A label outside [0, bins) raises flag[0] bit 0 (flag is WRITTEN, not or-ed) and its row joins no cell; order[offsets[bins] .. n) = -1.
+ * The count and scatter kernels give a workgroup eg_group_rows_block() labels.  ws: eg_group_rows_ws_bytes(n, bins), 16-byte aligned.
+ * eg_kmeans_update_u8: rows, order, offsets, counts (eg_group_rows' outputs) -> centres [bins][K] in place under the update rule.  Every
+ * member row is read once, contiguously; the member lists are cut into segments of eg_kmeans_segment_rows() rows, a workgroup sums
+ * eg_kmeans_column_chunk() bytes of its segment's rows into int32 partial sums, a second kernel adds a cell's segments and
+ * divides.  ws: eg_kmeans_update_ws_bytes(n, K, bins) = the segment table and (ceil(n / segment) + bins) * K * 4 bytes of partial sums.
+ * eg_kmeans_seed_u8: the seeding above -> idx [bins] (int32, the picked rows), centres [bins][K] (their bytes) and flag[0] (WRITTEN):
+ * bit 0 = some total was 0 (fewer than bins distinct rows; that pass picks row 0), bit 1 = a u outside [0, 1) (clamped).  All passes are
+ * enqueued by this one call: per pass a streaming kernel (one centre against all rows with v_dot4, a workgroup per eg_kmeans_seed_rows()
+ * rows, mind folded and an int64 partial sum per workgroup) and a one-workgroup kernel that scans the partial sums, finds the row and
+ * copies it into centres, where the next pass reads it; nothing is read back.  ws: eg_kmeans_seed_ws_bytes(n), 16-byte aligned. */
+int eg_group_rows_block(void);
+size_t eg_group_rows_ws_bytes(int n, int bins);
+int eg_group_rows(const int* labels, int n, int bins, void* ws, int* counts, int* offsets, int* order, int* flag, eg_stream_t s);
+int eg_kmeans_segment_rows(void);
+int eg_kmeans_column_chunk(void);
+size_t eg_kmeans_update_ws_bytes(int n, int K, int bins);
+int eg_kmeans_update_u8(const unsigned char* rows, int n, int K, const int* order, const int* offsets, const int* counts, int bins, void* ws,
+                        unsigned char* centres, eg_stream_t s);
+int eg_kmeans_seed_rows(void);
+size_t eg_kmeans_seed_ws_bytes(int n);
+int eg_kmeans_seed_u8(const unsigned char* rows, int n, int K, int bins, const float* u, void* ws, int* idx, unsigned char* centres, int* flag,
+                      eg_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
