@@ -1432,3 +1432,82 @@ def kmeans_u8(rows, bins, iterations=20, u=None, init=None, flag=None):
         prev = labels
     counts = group_rows(labels, bins, ws=group_ws, flag=gflag)[0]
     return centres, labels, counts, {"inertia": inertia, "changed": changed}
+
+
+# ---- radial power spectrum of uint8 images -------------------------------------------------
+SPECTRUM_SIDES = {16: 12, 32: 24, 64: 46}             # image side -> rings
+SPECTRUM_MAX_C = 4
+_SPECTRUM_TABLES = {}
+
+
+def spectrum_host_tables(H):
+    """the integer ring tables and the twiddle table of ``eg_spectrum_u8`` for side ``H`` (16, 32 or 64) as numpy arrays ->
+    {"rings": B, "cell_ring": int32 [H, H/2 + 1], "ring_start": int32 [B + 1], "ring_cells": int32 [H (H/2 + 1)], "ring_count":
+    int32 [B], "weight": int32 [H/2 + 1], "cos_sin": float64 [2, H]}.  The ring of cell (ky, kx): fy = min(ky, H - ky), q = fy^2 + kx^2,
+    s = isqrt(q), b = s if q <= s^2 + s else s + 1 -- integers only.  ``ring_cells`` lists the cells ky (H/2 + 1) + kx of ring 0, then
+    of ring 1 ..., each ascending; ``ring_count[b]`` = the sum of the column weights (1 for kx in {0, H/2}, else 2) over the ring."""
+    import math
+    import numpy as np
+    H = int(H)
+    if H not in SPECTRUM_SIDES:
+        raise ValueError(f"spectrum: the image side must be one of {sorted(SPECTRUM_SIDES)}, got {H}")
+    KX = H // 2 + 1
+    weight = np.array([1 if kx in (0, H // 2) else 2 for kx in range(KX)], np.int32)
+    cell_ring = np.empty((H, KX), np.int32)
+    for ky in range(H):
+        fy = min(ky, H - ky)
+        for kx in range(KX):
+            q = fy * fy + kx * kx
+            s = math.isqrt(q)
+            cell_ring[ky, kx] = s if q <= s * s + s else s + 1
+    B = int(cell_ring.max()) + 1
+    assert B == SPECTRUM_SIDES[H]
+    flat = cell_ring.reshape(-1)
+    ring_cells = np.argsort(flat, kind="stable").astype(np.int32)            # stable: ascending (ky, kx) inside a ring
+    sizes = np.bincount(flat, minlength=B)
+    ring_start = np.concatenate(([0], np.cumsum(sizes))).astype(np.int32)
+    ring_count = np.bincount(flat, weights=np.tile(weight, H), minlength=B).astype(np.int32)
+    k = np.arange(H, dtype=np.float64)
+    cos_sin = np.stack((np.cos(2.0 * np.pi * k / H), np.sin(2.0 * np.pi * k / H)))
+    return {"rings": B, "cell_ring": cell_ring, "ring_start": ring_start, "ring_cells": ring_cells, "ring_count": ring_count,
+            "weight": weight, "cos_sin": cos_sin}
+
+
+def spectrum_tables(H, device):
+    """``spectrum_host_tables(H)`` on ``device``, built once per (H, device): {"rings", "cell_ring", "ring_start", "ring_cells",
+    "ring_count", "cos_sin"} (the tables as contiguous device tensors)"""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError("spectrum_tables: the tables live on the GPU (there is no CPU path)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(H), device)
+    if key not in _SPECTRUM_TABLES:
+        host = spectrum_host_tables(H)
+        _SPECTRUM_TABLES[key] = {k: (v if k == "rings" else torch.from_numpy(v).contiguous().to(device)) for k, v in host.items()}
+    return _SPECTRUM_TABLES[key]
+
+
+def spectrum_u8(images, full=False):
+    """-> profile, float64 [N, B] on the device, or (profile, full [N, H, H/2 + 1]) with ``full=True``: the azimuthally averaged power
+    spectrum of uint8 device images [N, C, H, H] (H = 16, 32 or 64 -> B = 12, 24 or 46 rings; C = 1 .. 4), ``eg_spectrum_u8``.
+    P = |DFT of the bytes|^2 / H^2; profile[n, b] = the weighted mean of P over ring b and the channels, full[n] = the mean of P over the
+    channels on the half spectrum kx = 0 .. H/2.  One launch, one workgroup per image, no host read; the bits of an image's row depend
+    on its bytes alone."""
+    if not (isinstance(images, torch.Tensor) and images.dtype == torch.uint8 and images.dim() == 4 and images.is_contiguous()):
+        raise ValueError("spectrum_u8: images must be a contiguous uint8 device tensor [N, C, H, H]")
+    if not images.is_cuda:
+        raise ValueError("spectrum_u8: images must be a contiguous uint8 device tensor (there is no CPU path)")
+    N, C, H, W = (int(v) for v in images.shape)
+    if H != W or H not in SPECTRUM_SIDES:
+        raise ValueError(f"spectrum_u8: the images must be square with a side in {sorted(SPECTRUM_SIDES)}, got {H} x {W}")
+    if not 1 <= C <= SPECTRUM_MAX_C:
+        raise ValueError(f"spectrum_u8: C = {C} channels must be in 1 .. {SPECTRUM_MAX_C}")
+    if not 1 <= N < 2 ** 31:
+        raise ValueError(f"spectrum_u8: images {tuple(images.shape)} holds no image (or 2^31 and more)")
+    tab = spectrum_tables(H, images.device)
+    profile = torch.empty(N, tab["rings"], device=images.device, dtype=torch.float64)
+    whole = torch.empty(N, H, H // 2 + 1, device=images.device, dtype=torch.float64) if full else None
+    lib().call("eg_spectrum_u8", _p(images), N, C, H, _p(tab["cos_sin"]), _p(tab["cell_ring"]), _p(tab["ring_start"]), _p(tab["ring_cells"]),
+               _p(tab["ring_count"]), _p(profile), _p(whole) if full else None, _stream())
+    return (profile, whole) if full else profile

@@ -64,6 +64,21 @@ Bins fitted on ``real`` itself are biased towards ``real`` (the cells are where 
 NOT give 0.05 x bins.  In a numpy trial of this contract two samples of one 30-mode mixture (4000 rows, 50 bins) gave NDB 2 .. 8 against
 the nominal 2.5, so read a number against the NDB of a held-out real split, or fit the bins elsewhere (``centres=``).
 
+What up-convolutions do to the high frequencies: the azimuthally averaged power spectrum of Durall et al., "Watch your
+Up-Convolution" (2020).  Every score above but the SWD rests on the L2 distance between the bytes, which the low frequencies dominate;
+this one reads the other end.  P = |DFT of the bytes|^2 / H^2 per image (ops.spectrum_u8: a direct fp64 matrix DFT, one workgroup per
+image), averaged over integer rings of the frequency plane, in dB, real against generated:
+
+* ``radial_bins(H)``                             the integer ring tables, numpy arrays on the host
+* ``power_profile(images)``                      float64 [N, B] on the device: every image's ring means
+* ``mean_spectrum(images)``                      float64 [H, H] on the device: the set's mean 2-D spectrum in dB, zero frequency at the centre
+* ``spectrum(real, fake)``                       per ring the two mean log-profiles, their gap and effect size; the rms gap, the mean gap
+                                                 of the high rings, the ring of the largest gap
+* ``spectrum_grid`` / ``save_spectra``           the figure: the two mean spectra side by side (checkerboard peaks are dots on the axes
+                                                 and in the corners)
+* ``spectrum_generator(kind, generator, inputs)`` ``spectrum`` for a generator of an MNIST or CelebA run
+* ``SpectrumPlan``                               what ``train.TrainRun(..., spectrum=...)`` scores on checkpoint iterations
+
 Per level and set: patch statistics (ops.swd_patch_stats), then per repeat one fused gather-and-project launch (ops.swd_project: the
 descriptors, 0.6 GB per set and level at full size, never exist), one column sort per set (ops.sort_columns) and one reduction
 (ops.l1_mean).  Everything is enqueued on the current stream; ``swd`` reads the device once, at its end.  There is no CPU path.
@@ -127,6 +142,13 @@ class NDBPlan(NamedTuple):
     n_images: int
     bins: int = 100
     iterations: int = 20
+    seed: int = 0
+
+
+class SpectrumPlan(NamedTuple):
+    """the radial power-spectrum score a training run writes on its checkpoint iterations (``spectrum``): ``n_images`` generated against
+    the first ``n_images`` dataset images"""
+    n_images: int
     seed: int = 0
 
 
@@ -840,3 +862,119 @@ def ndb_generator(kind, generator, inputs, n_images=8192, batch=None, seed=0, **
     batch = min(64, int(n_images)) if batch is None else int(batch)
     fake = generate(kind, generator, n_images, batch, seed)
     return ndb(real_images(kind, inputs, n_images), fake, seed=seed, **kw)
+
+
+# ---- the radial power spectrum -----------------------------------------------------------------------------------------------
+SPECTRUM_FLOOR = 1.0 / 12.0      # the power per cell of the byte rounding itself (uniform noise of variance 1/12): keeps log10 of a flat image finite
+_DB = 10.0
+
+
+def radial_bins(H):
+    """the integer ring tables of an H x H spectrum (H = 16, 32 or 64) as numpy arrays on the host -> {"rings": B, "cell_ring": int32
+    [H, H/2 + 1], "ring_start": int32 [B + 1], "ring_cells": int32 [H (H/2 + 1)], "ring_count": int32 [B], "weight": int32 [H/2 + 1]}
+    (``ops.spectrum_host_tables`` without the twiddles): cell (ky, kx) of the half spectrum lies in ring b with
+    (b - 1/2)^2 <= min(ky, H - ky)^2 + kx^2 < (b + 1/2)^2; ``ring_count`` sums the column weights and adds up to H^2"""
+    tab = ops.spectrum_host_tables(H)
+    return {k: (v if k == "rings" else v.copy()) for k, v in tab.items() if k != "cos_sin"}
+
+
+def power_profile(images):
+    """-> float64 [N, B] on the device: the ring means of P = |DFT of the bytes|^2 / H^2 of every image of ``images`` [N, C, H, H] (float in
+    [-1, 1] through ``to_u8``, or uint8; H = 16, 32 or 64, C = 1 .. 4), averaged over the channels; ring 0 is the zero frequency.  No
+    host read."""
+    return ops.spectrum_u8(_u8_rows(images, "images"))
+
+
+def mean_spectrum(images):
+    """-> float64 [H, H] on the device: 10 log10(the mean over the images of the channel-mean P + 1/12), the half spectrum mirrored to
+    the full plane (P[ky, kx] = P[-ky, -kx]) and shifted so that the zero frequency sits at [H/2, H/2].  No host read."""
+    half = ops.spectrum_u8(_u8_rows(images, "images"), full=True)[1].mean(0)
+    H, KX = int(half.shape[0]), int(half.shape[1])
+    db = _DB * torch.log10(half + SPECTRUM_FLOOR)
+    ky = (-torch.arange(H, device=db.device)) % H
+    kx = H - torch.arange(KX, H, device=db.device)
+    plane = torch.cat((db, db[ky][:, kx]), 1)
+    return torch.roll(plane, (H // 2, H // 2), (0, 1))
+
+
+def spectrum_grid(real, fake):
+    """-> fp32 [2, 1, H, H] in [0, 1] on the device: ``mean_spectrum(real)`` and ``mean_spectrum(fake)``, scaled jointly (one minimum, one
+    maximum for both; all zeros if they are equal)"""
+    both = torch.stack((mean_spectrum(real), mean_spectrum(fake)))
+    lo, hi = both.min(), both.max()
+    span = torch.where(hi > lo, hi - lo, torch.ones_like(hi))
+    return ((both - lo) / span).float().unsqueeze(1)
+
+
+def save_spectra(fp, real, fake):
+    """writes ``spectrum_grid`` as a PNG: the real set's mean spectrum on the left, the generated set's on the right"""
+    sampling.save_image(spectrum_grid(real, fake), fp, nrow=2)
+
+
+def spectrum_statistics(mean_real, var_real, mean_fake, var_fake, H):
+    """the host half of ``spectrum``: from the per-ring mean and unbiased variance of the log-profiles in dB of the two sets (sequences of
+    B numbers, ring 0 first) -> the dictionary of ``spectrum`` over Python floats.  gap = fake - real; "distance_db" = sqrt(mean of gap^2
+    over the rings 1 .. B - 1) (ring 0 is brightness, not texture); "high_db" = the mean gap over the rings b > H / 4; "peak_ring" = the
+    ring b >= 1 of largest |gap|, ties to the lower ring, "peak_db" its gap; effect = gap / sqrt((var_real + var_fake) / 2), 0 where
+    that is 0."""
+    import math
+    mr, vr, mf, vf = ([float(v) for v in seq] for seq in (mean_real, var_real, mean_fake, var_fake))
+    B, H = len(mr), int(H)
+    if not (len(vr) == len(mf) == len(vf) == B and B >= 2 and 0 < H // 4 < B - 1):
+        raise ValueError("quality.spectrum_statistics: four vectors of one length B >= 2 and a side H with H / 4 < B - 1")
+    gap = [f - r for r, f in zip(mr, mf)]
+    high = gap[H // 4 + 1:]
+    peak = 1
+    for b in range(2, B):
+        if abs(gap[b]) > abs(gap[peak]):
+            peak = b
+    effect = []
+    for g, a, b in zip(gap, vr, vf):
+        pooled = math.sqrt(0.5 * (a + b))
+        effect.append(g / pooled if pooled > 0.0 else 0.0)
+    return {"rings": B, "real_db": mr, "fake_db": mf, "gap_db": gap, "distance_db": math.sqrt(sum(g * g for g in gap[1:]) / (B - 1)),
+            "high_db": sum(high) / len(high), "peak_db": gap[peak], "peak_ring": peak, "effect": effect}
+
+
+def spectrum_moments(images):
+    """-> (moments float64 [2, B], profile float64 [N, B]) on the device: the per-ring mean and unbiased variance over the images of
+    L = 10 log10(``power_profile`` + 1/12) in dB; N >= 2.  No host read."""
+    rows = _u8_rows(images, "images")
+    if rows.shape[0] < 2:
+        raise ValueError(f"quality.spectrum: a set needs at least 2 images (the variance over the set), got {int(rows.shape[0])}")
+    profile = ops.spectrum_u8(rows)
+    L = _DB * torch.log10(profile + SPECTRUM_FLOOR)
+    return torch.stack((L.mean(0), L.var(0, unbiased=True))), profile
+
+
+def spectrum_from_moments(real_moments, fake_moments, H):
+    """``spectrum``'s dictionary from two ``spectrum_moments`` results [2, B] on one device: THE host read, then ``spectrum_statistics``"""
+    host = torch.cat((real_moments, fake_moments)).cpu().tolist()
+    return spectrum_statistics(host[0], host[1], host[2], host[3], H)
+
+
+def spectrum(real, fake, terms=False):
+    """The azimuthally averaged power spectrum (Durall et al. 2020) of ``real`` [N, C, H, H] against ``fake`` [M, C, H, H] (float in
+    [-1, 1] or uint8; H = 16, 32 or 64, C = 1 .. 4, N, M >= 2, N != M is allowed) -> {"rings", "real_db", "fake_db", "gap_db",
+    "distance_db", "high_db", "peak_db", "peak_ring", "effect"}: per ring the mean over each set of L = 10 log10(profile + 1/12) in dB
+    and their gap fake - real; the rms gap over the rings >= 1, the mean gap over the rings above H / 4 (where an up-convolution's
+    spectrum bends), the ring >= 1 of the largest |gap| and its gap, and per ring the gap in pooled standard deviations of L over the
+    images (Cohen's d).  A generator that stamps a lattice on its images shows as a peak of tens of dB in the top rings while every
+    distance between the bytes barely moves.  ``terms=True``: -> (that dictionary, profile_real [N, B], profile_fake [M, B]), the
+    float64 device tensors of ``power_profile``.  One host read."""
+    A, B = _u8_rows(real, "real"), _u8_rows(fake, "fake")
+    if A.shape[1:] != B.shape[1:] or A.device != B.device:
+        raise ValueError(f"spectrum: the two sets must hold images of one shape on one device, got {tuple(A.shape)} and {tuple(B.shape)}")
+    ma, pa = spectrum_moments(A)
+    mb, pb = spectrum_moments(B)
+    out = spectrum_from_moments(ma, mb, A.shape[2])
+    return (out, pa, pb) if terms else out
+
+
+def spectrum_generator(kind, generator, inputs, n_images=8192, batch=None, seed=0, **kw):
+    """``spectrum`` of ``real_images(kind, inputs, n_images)`` against ``generate(kind, generator, n_images, batch, seed)``; ``batch`` as in
+    ``swd_generator``; ``kw``: terms"""
+    _family(kind, "spectrum_generator")
+    batch = min(64, int(n_images)) if batch is None else int(batch)
+    fake = generate(kind, generator, n_images, batch, seed)
+    return spectrum(real_images(kind, inputs, n_images), fake, **kw)

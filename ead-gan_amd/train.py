@@ -159,11 +159,17 @@ def ndb_seed(seed, batches_done, plan_seed=0):
     return (int(seed) * 1000003 + int(batches_done) * 2909 + int(plan_seed) * 137911 + 86420) % (2 ** 32)
 
 
+def spectrum_seed(seed, batches_done, plan_seed=0):
+    """seed of a checkpoint iteration's generated images for the radial power-spectrum score: ``swd_seed``'s form with constants of its
+    own"""
+    return (int(seed) * 1000003 + int(batches_done) * 4099 + int(plan_seed) * 150989 + 24680) % (2 ** 32)
+
+
 def check_plan(what, plan, cls, kind, n_dataset, batch):
-    """-> ``plan`` as a ``cls`` (quality.SWDPlan, NNPlan, MMDPlan, SinkhornPlan or NDBPlan) after the checks every score plan of a run
-    passes: the kind of the run, ``n_images`` against the dataset and against the trainer's batch size; an MMD plan also needs two images
-    a set and 1 .. 4 positive scales, a Sinkhorn plan two images a set, a positive scale and at least one iteration, an NDB plan
-    1 .. min(1024, n_images) bins and no negative iteration count"""
+    """-> ``plan`` as a ``cls`` (quality.SWDPlan, NNPlan, MMDPlan, SinkhornPlan, NDBPlan or SpectrumPlan) after the checks every score plan
+    of a run passes: the kind of the run, ``n_images`` against the dataset and against the trainer's batch size; an MMD plan also needs
+    two images a set and 1 .. 4 positive scales, a Sinkhorn plan two images a set, a positive scale and at least one iteration, an NDB
+    plan 1 .. min(1024, n_images) bins and no negative iteration count, a spectrum plan two images a set"""
     if kind not in ("mnist", "celeba"):
         raise ValueError(f"{what}: only 'mnist' and 'celeba' runs are scored (quality.generate), not {kind!r}")
     plan = cls(*plan)
@@ -192,6 +198,9 @@ def check_plan(what, plan, cls, kind, n_dataset, batch):
             raise ValueError(f"{what}: bins = {plan.bins} must be in 1 .. min({ops.KMEANS_MAX_BINS}, n_images = {plan.n_images})")
         if int(plan.iterations) < 0:
             raise ValueError(f"{what}: iterations = {plan.iterations} must not be negative")
+    if cls is quality.SpectrumPlan:
+        if int(plan.n_images) < 2:
+            raise ValueError(f"{what}: n_images = {plan.n_images}, the variance over a set needs at least 2 images")
     return plan
 
 
@@ -238,13 +247,19 @@ class TrainRun:
     at the first scored checkpoint, from the plan's seed, and kept on the run object (``ndb_bins``).  They are no part of
     ``run_state_%d.pt``: a resumed run refits them, and the fit is deterministic, so it gets the same bits.
 
+    ``spectrum=quality.SpectrumPlan(n_images, seed=0)`` (the same runs): on checkpoint iterations, after the ``ndb.jsonl`` line
+    if there is one, rank 0 appends ``{"batches_done", "G": quality.spectrum(...)[, "G_ema": ...]}`` to ``out_dir/spectrum.jsonl`` -- the
+    radial power spectrum of one set of generated images per generator (seeded by ``spectrum_seed``) against that of the first
+    ``n_images`` dataset images.  The real set's per-ring mean and variance are computed once, at the first scored checkpoint, and kept
+    on the run object (``spectrum_real``); they are no part of ``run_state_%d.pt``: a resumed run recomputes the same bits.
+
     Data parallel (``inputs.world`` > 1, the world of the trainer's ``allreduce`` / ``sync_bn``): ``graph=False`` is required; the
     iteration count, cadence, sample seeds and file names are those of one process at the global batch ``B * world``; rank 0 prints and
     writes every file, the other ranks write none (``files == []``) and print nothing but execute every ``_wait`` and keep ``history``
     / ``lines`` of their own shard.  The run adds no collective: rank 0's lines and ``losses.npy`` carry rank 0's shard losses."""
 
     def __init__(self, kind, trainer, inputs, out_dir, n_epochs, sample_interval=None, seed=0, graph=True, log_capacity=1024, log_in_graph=True,
-                 ema_samples=False, swd=None, nn=None, mmd=None, sinkhorn=None, ndb=None):
+                 ema_samples=False, swd=None, nn=None, mmd=None, sinkhorn=None, ndb=None, spectrum=None):
         self.plan = _plan(kind)
         if getattr(trainer, "STATE_KIND", None) != kind:
             raise ValueError(f"a {kind!r} run needs a {kind!r} trainer, got {type(trainer).__name__}")
@@ -290,8 +305,10 @@ class TrainRun:
                 self._ema_G = _module_like(trainer.G).to(trainer.losses.device)
         self.swd, self.nn, self.mmd, self.sinkhorn, self._score_G = swd, nn, mmd, sinkhorn, None       # one scratch generator serves every plan
         self.ndb, self.ndb_bins = ndb, None                         # ndb_bins: quality.Bins of the real images, fitted at the first scored checkpoint
+        self.spectrum, self.spectrum_real = spectrum, None          # spectrum_real: quality.spectrum_moments of the real images [2, B], computed once
         for what, plan, cls in (("swd", swd, quality.SWDPlan), ("nn", nn, quality.NNPlan), ("mmd", mmd, quality.MMDPlan),
-                                ("sinkhorn", sinkhorn, quality.SinkhornPlan), ("ndb", ndb, quality.NDBPlan)):
+                                ("sinkhorn", sinkhorn, quality.SinkhornPlan), ("ndb", ndb, quality.NDBPlan),
+                                ("spectrum", spectrum, quality.SpectrumPlan)):
             if plan is None:
                 continue
             setattr(self, what, check_plan(what, plan, cls, kind, self.n_images, trainer.B))
@@ -453,6 +470,19 @@ class TrainRun:
             return out
         self._score_line("ndb.jsonl", it, score)
 
+    def _score_spectrum(self, it):
+        """one line of ``spectrum.jsonl``: ``quality.spectrum`` of one set of generated images per generator against the
+        first ``n_images`` dataset images, whose per-ring moments are computed here once"""
+        if self._score_G is None or self.spectrum is None:
+            return
+        tr, plan = self.trainer, self.spectrum
+        n, seed = int(plan.n_images), spectrum_seed(self.seed, it, plan.seed)
+        if self.spectrum_real is None:
+            self.spectrum_real = quality.spectrum_moments(quality.real_images(self.kind, self.inputs, n))[0]
+        H = int(self.inputs.data.shape[2])
+        self._score_line("spectrum.jsonl", it, lambda G: quality.spectrum_from_moments(
+            self.spectrum_real, quality.spectrum_moments(quality.generate(self.kind, G, n, min(int(tr.B), n), seed))[0], H))
+
     def _score_line(self, name, it, score):
         """``{"batches_done", "G": score(live generator)[, "G_ema": score(averaged generator)]}`` appended to ``out_dir/name``"""
         tr, G = self.trainer, self._score_G
@@ -516,6 +546,7 @@ class TrainRun:
                 self._score_mmd(it)
                 self._score_sinkhorn(it)
                 self._score_ndb(it)
+                self._score_spectrum(it)
             self.batches_done = it + 1
             done += 1
             if do_ckpt:

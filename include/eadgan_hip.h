@@ -877,6 +877,27 @@ size_t eg_kmeans_seed_ws_bytes(int n);
 int eg_kmeans_seed_u8(const unsigned char* rows, int n, int K, int bins, const float* u, void* ws, int* idx, unsigned char* centres, int* flag,
                       eg_stream_t s);
 
+/* --- the azimuthally averaged power spectrum of uint8 images (not in the reference).  images [N][C][H][H] contiguous uint8,
+ * 4-byte aligned, H = 16, 32 or 64, 1 <= C <= 4, N >= 1.  The contract, for image n and channel c:
+ *   X[ky][kx] = sum_y sum_x u[y][x] exp(-2 pi i (ky y + kx x) / H) over the bytes as they are (nothing is subtracted),
+ *   P[ky][kx] = |X|^2 / H^2 (Parseval: sum_k P = sum u^2), on the half spectrum kx = 0 .. H/2; a cell of column kx weighs w = 1 for
+ *   kx in {0, H/2} and w = 2 otherwise.
+ *   rings    with fy = min(ky, H - ky), q = fy^2 + kx^2 the ring of a cell is the integer b with (b - 1/2)^2 <= q < (b + 1/2)^2, i.e.
+ *            s = isqrt(q), b = s if q <= s^2 + s, else s + 1: B = 12, 24, 46 rings for H = 16, 32, 64.  The CALLER builds the tables in
+ *            integers, on the device: cell_ring [H][H/2 + 1] (the ring of every cell; part of the table set, not read by the launch),
+ *            ring_start [B + 1] and ring_cells [H (H/2 + 1)] (the cells ky (H/2 + 1) + kx of every ring, ascending), ring_count [B] =
+ *            the sum of w over the ring (they sum to H^2).  The library forms no radius.
+ *   twiddles cos_sin [2][H] = cos(2 pi k / H), sin(2 pi k / H) in doubles from the caller, indexed by (k x) mod H in integers: the
+ *            library evaluates no sine or cosine.
+ *   profile [N][B]          = sum_{cells of ring b} w sum_c P / (C ring_count[b])
+ *   full    [N][H][H/2 + 1] = sum_c P / C, written when full is not NULL.
+ * float64 throughout; the direct matrix DFT in two stages (rows, then columns), every sum of H terms in index order, a cell's channels in
+ * channel order, a ring's cells in ring_cells order (lane l of a wave takes the cells l, l + 64, ...; the lane sums meet in a fixed
+ * tree).  One workgroup per image, no atomics, no allocation, no sync: the bits of image n depend on its bytes alone, not on N, its
+ * position or the run.  |profile - exact| <= 4 H 2^-53 S^2 / H^2 with S the image's largest per-channel byte sum. */
+int eg_spectrum_u8(const unsigned char* images, int N, int C, int H, const double* cos_sin, const int* cell_ring, const int* ring_start,
+                   const int* ring_cells, const int* ring_count, double* profile, double* full, eg_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
