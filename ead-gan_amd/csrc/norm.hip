@@ -6,6 +6,24 @@
 
 #define BN_RPB 256   // rows per block in the partial kernels
 
+// THE argument contract of the family (stated in the header above the BatchNorm block): every entry point checks it before any arithmetic
+// on C (bn_gx and bn_apply_blocks divide by C / vector width) and before any launch.  nullptr: fine; else what is wrong.
+static const char* bn_shape_fault(int dtype, int M, int C) {
+    if (dtype != EG_F32 && dtype != EG_BF16 && dtype != EG_F16) return "dtype must be EG_F32, EG_BF16 or EG_F16";
+    if (M <= 0) return "M must be positive";
+    if (C <= 0) return "C must be positive";
+    if (C % (dtype == EG_F32 ? 4 : 8)) return "C must be a multiple of the 16-byte vector width (4 in fp32, 8 in the 16-bit types)";
+    return nullptr;
+}
+#define BN_REQUIRE_SHAPE(name, dtype, M, C)                     \
+    do {                                                        \
+        const char* fault__ = bn_shape_fault((dtype), (M), (C)); \
+        EG_REQUIRE(!fault__, name ": %s", fault__);             \
+    } while (0)
+// the activations pre_act_grad has a derivative for: a forward with another one would get the identity gradient back
+static bool bn_act_ok(int act) { return act == EG_ACT_NONE || act == EG_ACT_RELU || act == EG_ACT_LRELU; }
+#define BN_REQUIRE_ACT(name, act) EG_REQUIRE(bn_act_ok(act), name ": act must be EG_ACT_NONE, EG_ACT_RELU or EG_ACT_LRELU")
+
 // rows per workgroup of the partial kernels: 256, halved (down to 16) until the launch has >= 512 workgroups
 static int bn_rpb(int M, int gx) {
     int rpb = BN_RPB;
@@ -18,7 +36,10 @@ static int bn_gx(int C, int dtype) {
 }
 
 // block = 256 threads = (C/VEC chunk columns) x (row lanes); 16-byte loads; ONE pass: sums of (x - pivot) and (x - pivot)^2 with the
-// block's first row as pivot (no cancellation for row blocks of <= 256 rows), LDS combine of the row lanes in a fixed order
+// block's first row as pivot, LDS combine of the row lanes in a fixed order.  The pivot bounds the cancellation in tq - ts * ts / cnt: the
+// float32 roundings of the two sums are amplified by 1 + (pivot - mean_b)^2 / var_b, about 10 in the worst of a thousand channels.  It
+// shows where one lane adds all rows of a block (C / VEC >= 256): M2 of 33 rows x 1024 channels misses float64 by 8e-7 of its largest
+// value, 6 times what a float32 two-pass variance misses it by (tests/test_gpu_norm.py, cases cpr256 / cpr257)
 template <typename T>
 __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const T* __restrict__ x, int M, int C, int rpb, float* __restrict__ partial) {
     constexpr int VEC = Elt<T>::VEC;
@@ -150,8 +171,9 @@ extern "C" size_t eg_bn_ws_floats(int M, int C) { return (size_t)(cdiv(M, BN_RPB
 extern "C" int eg_bn_fwd_train(int dtype, const void* x, void* y, int M, int C, const float* gamma, const float* beta, float eps,
                                float momentum, float* running_mean, float* running_var, long long* num_batches_tracked,
                                float* save_mean, float* save_invstd, float* ws, int act, float slope, eg_stream_t s) {
-    EG_REQUIRE(x && y && gamma && beta && save_mean && save_invstd && ws && M > 0 && C > 0, "eg_bn_fwd_train: bad argument");
-    EG_REQUIRE(C % (dtype == EG_F32 ? 4 : 8) == 0, "eg_bn_fwd_train: C must be a multiple of the 16-byte vector width");
+    EG_REQUIRE(x && y && gamma && beta && save_mean && save_invstd && ws, "eg_bn_fwd_train: null pointer");
+    BN_REQUIRE_SHAPE("eg_bn_fwd_train", dtype, M, C);
+    BN_REQUIRE_ACT("eg_bn_fwd_train", act);
     const int gx = bn_gx(C, dtype), rpb = bn_rpb(M, gx);
     const int nrb = cdiv(M, rpb);
     dim3 g1(gx, nrb);
@@ -230,9 +252,11 @@ extern "C" int eg_bn_fwd_train_fused(int dtype, const void* x, void* y, int M, i
                                      const float* gamma, const float* beta, float eps, float momentum, float* running_mean, float* running_var,
                                      long long* num_batches_tracked, float* save_mean, float* save_invstd, float* ws, int act, float slope,
                                      eg_stream_t s) {
-    EG_REQUIRE(x && y && stat && gamma && beta && save_mean && save_invstd && ws && M > 0 && C > 0 && nrb > 0, "eg_bn_fwd_train_fused: bad argument");
+    EG_REQUIRE(x && y && stat && gamma && beta && save_mean && save_invstd && ws, "eg_bn_fwd_train_fused: null pointer");
+    BN_REQUIRE_SHAPE("eg_bn_fwd_train_fused", dtype, M, C);
+    BN_REQUIRE_ACT("eg_bn_fwd_train_fused", act);
+    EG_REQUIRE(nrb > 0, "eg_bn_fwd_train_fused: nrb must be positive");
     EG_REQUIRE((long long)nrb * rows_per_block == M, "eg_bn_fwd_train_fused: nrb * rows_per_block must be M (whole row blocks of equal size)");
-    EG_REQUIRE(C % (dtype == EG_F32 ? 4 : 8) == 0, "eg_bn_fwd_train_fused: C must be a multiple of the 16-byte vector width");
     hipStream_t st = (hipStream_t)s;
     float* coef = ws;                                   // 2*C floats
     if (nrb >= EG_FINAL_WIDE_NRB)
@@ -295,7 +319,8 @@ static void launch_bn_stats_partial(const void* x, int M, int C, int dtype, floa
 }
 
 extern "C" int eg_bn_stats_local(int dtype, const void* x, int M, int C, float* ws, float* stats, eg_stream_t s) {
-    EG_REQUIRE(x && ws && stats && M > 0 && C > 0 && C % (dtype == EG_F32 ? 4 : 8) == 0, "eg_bn_stats_local: bad argument");
+    EG_REQUIRE(x && ws && stats, "eg_bn_stats_local: null pointer");
+    BN_REQUIRE_SHAPE("eg_bn_stats_local", dtype, M, C);
     int nrb = 0;
     hipStream_t st = (hipStream_t)s;
     if (dtype == EG_F32) launch_bn_stats_partial<float>(x, M, C, dtype, ws, &nrb, st);
@@ -310,9 +335,10 @@ extern "C" int eg_bn_fwd_from_stats(int dtype, const void* x, void* y, int M_loc
                                     const float* gamma, const float* beta, float eps, float momentum, float* running_mean, float* running_var,
                                     long long* num_batches_tracked, float* save_mean, float* save_invstd, float* ws, int act, float slope,
                                     eg_stream_t s) {
-    EG_REQUIRE(x && y && stats_all && gamma && beta && save_mean && save_invstd && ws && M_local > 0 && M_global >= M_local && nranks > 0,
-               "eg_bn_fwd_from_stats: bad argument");
-    EG_REQUIRE(C % (dtype == EG_F32 ? 4 : 8) == 0, "eg_bn_fwd_from_stats: C must be a multiple of the 16-byte vector width");
+    EG_REQUIRE(x && y && stats_all && gamma && beta && save_mean && save_invstd && ws, "eg_bn_fwd_from_stats: null pointer");
+    BN_REQUIRE_SHAPE("eg_bn_fwd_from_stats", dtype, M_local, C);
+    BN_REQUIRE_ACT("eg_bn_fwd_from_stats", act);
+    EG_REQUIRE(M_global >= M_local && nranks > 0, "eg_bn_fwd_from_stats: M_global must be at least M_local, and nranks positive");
     hipStream_t st = (hipStream_t)s;
     float* coef = ws;                                   // 2*C floats
     hipLaunchKernelGGL(bn_stats_final_kernel, dim3(cdiv(C, 4)), dim3(256), 0, st, stats_all, nranks, C, M_global, eps, momentum, running_mean, running_var,
@@ -338,8 +364,9 @@ __global__ void bn_eval_coef_kernel(const float* __restrict__ gamma, const float
 
 extern "C" int eg_bn_fwd_eval(int dtype, const void* x, void* y, int M, int C, const float* gamma, const float* beta, float eps,
                               const float* running_mean, const float* running_var, float* ws, int act, float slope, eg_stream_t s) {
-    EG_REQUIRE(x && y && gamma && beta && running_mean && running_var && ws && M > 0 && C > 0, "eg_bn_fwd_eval: bad argument");
-    EG_REQUIRE(C % (dtype == EG_F32 ? 4 : 8) == 0, "eg_bn_fwd_eval: C must be a multiple of the 16-byte vector width");
+    EG_REQUIRE(x && y && gamma && beta && running_mean && running_var && ws, "eg_bn_fwd_eval: null pointer");
+    BN_REQUIRE_SHAPE("eg_bn_fwd_eval", dtype, M, C);
+    BN_REQUIRE_ACT("eg_bn_fwd_eval", act);
     hipStream_t st = (hipStream_t)s;
     hipLaunchKernelGGL(bn_eval_coef_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, gamma, beta, running_mean, running_var, eps, C, ws);
     const int cpr = C / (dtype == EG_F32 ? 4 : 8);
@@ -389,9 +416,8 @@ __global__ void bn_bwd_eval_kernel(const T* __restrict__ z, const T* __restrict_
 extern "C" int eg_bn_bwd_eval(int dtype, const void* z, const void* da, void* dz, int M, int C, const float* gamma, const float* beta, float eps,
                               const float* running_mean, const float* running_var, float* ws, int act, float slope, eg_stream_t s) {
     EG_REQUIRE(z && da && dz && gamma && beta && running_mean && running_var && ws, "eg_bn_bwd_eval: null pointer");
-    EG_REQUIRE(dtype == EG_F32 || dtype == EG_BF16 || dtype == EG_F16, "dtype must be EG_F32, EG_BF16 or EG_F16");
-    EG_REQUIRE(M > 0 && C > 0 && C % (dtype == EG_F32 ? 4 : 8) == 0, "eg_bn_bwd_eval: C must be a multiple of the 16-byte vector width");
-    EG_REQUIRE(act == EG_ACT_NONE || act == EG_ACT_RELU || act == EG_ACT_LRELU, "eg_bn_bwd_eval: act must be EG_ACT_NONE, EG_ACT_RELU or EG_ACT_LRELU");
+    BN_REQUIRE_SHAPE("eg_bn_bwd_eval", dtype, M, C);
+    BN_REQUIRE_ACT("eg_bn_bwd_eval", act);
     hipStream_t st = (hipStream_t)s;
     hipLaunchKernelGGL(bn_eval_coef_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, gamma, beta, running_mean, running_var, eps, C, ws);
     const int cpr = C / (dtype == EG_F32 ? 4 : 8);
@@ -540,7 +566,9 @@ static int bn_bwd_impl(int dtype, const void* z, const void* da, void* dz, int M
 extern "C" int eg_bn_bwd_sums_local(int dtype, const void* z, const void* da, int M, int C, const float* gamma, const float* beta,
                                     const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta,
                                     float* sums, float* ws, int accumulate, eg_stream_t s) {
-    EG_REQUIRE(z && da && gamma && beta && save_mean && save_invstd && sums && ws && M > 0 && C > 0, "eg_bn_bwd_sums_local: bad argument");
+    EG_REQUIRE(z && da && gamma && beta && save_mean && save_invstd && sums && ws, "eg_bn_bwd_sums_local: null pointer");
+    BN_REQUIRE_SHAPE("eg_bn_bwd_sums_local", dtype, M, C);
+    BN_REQUIRE_ACT("eg_bn_bwd_sums_local", act);
     hipStream_t st = (hipStream_t)s;
     const int gx = bn_gx(C, dtype), rpb = bn_rpb(M, gx);
     const int nrb = cdiv(M, rpb);
@@ -571,8 +599,10 @@ __global__ void bn_bwd_coef_kernel(const float* __restrict__ sums, int C, int M,
 extern "C" int eg_bn_bwd_from_sums(int dtype, const void* z, const void* da, void* dz, int M_local, int C, const float* sums_global, int M_global,
                                    const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, int act, float slope,
                                    float* ws, eg_stream_t s) {
-    EG_REQUIRE(z && da && dz && sums_global && gamma && beta && save_mean && save_invstd && ws && M_local > 0 && M_global >= M_local,
-               "eg_bn_bwd_from_sums: bad argument");
+    EG_REQUIRE(z && da && dz && sums_global && gamma && beta && save_mean && save_invstd && ws, "eg_bn_bwd_from_sums: null pointer");
+    BN_REQUIRE_SHAPE("eg_bn_bwd_from_sums", dtype, M_local, C);
+    BN_REQUIRE_ACT("eg_bn_bwd_from_sums", act);
+    EG_REQUIRE(M_global >= M_local, "eg_bn_bwd_from_sums: M_global must be at least M_local");
     hipStream_t st = (hipStream_t)s;
     float* coef = ws;                                   // 5*C floats
     hipLaunchKernelGGL(bn_bwd_coef_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, sums_global, C, M_global, gamma, beta, save_mean, save_invstd, coef);
@@ -623,8 +653,9 @@ __global__ void bn_bwd_final_t_kernel(const float* __restrict__ stat, int nrb, i
 extern "C" int eg_bn_bwd_fused(int dtype, const void* z, const void* dy, void* dz, int M, int C, const float* stat, int nrb,
                                const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta,
                                float* sums, float* ws, int accumulate, eg_stream_t s) {
-    EG_REQUIRE(z && dy && dz && stat && gamma && beta && save_mean && save_invstd && sums && ws && M > 0 && C > 0 && nrb > 0, "eg_bn_bwd_fused: bad argument");
-    EG_REQUIRE(C % (dtype == EG_F32 ? 4 : 8) == 0, "eg_bn_bwd_fused: C must be a multiple of the 16-byte vector width");
+    EG_REQUIRE(z && dy && dz && stat && gamma && beta && save_mean && save_invstd && sums && ws, "eg_bn_bwd_fused: null pointer");
+    BN_REQUIRE_SHAPE("eg_bn_bwd_fused", dtype, M, C);
+    EG_REQUIRE(nrb > 0, "eg_bn_bwd_fused: nrb must be positive");
     hipStream_t st = (hipStream_t)s;
     float* coef = ws;                                   // 5*C floats
     if (nrb >= EG_FINAL_WIDE_NRB)
@@ -645,6 +676,8 @@ extern "C" int eg_bn_bwd(int dtype, const void* z, const void* da, void* dz, int
                          const float* save_mean, const float* save_invstd, int act, float slope, float* dgamma, float* dbeta,
                          float* sums, float* ws, int accumulate, eg_stream_t s) {
     EG_REQUIRE(z && da && dz && gamma && beta && save_mean && save_invstd && sums && ws, "eg_bn_bwd: null pointer");
+    BN_REQUIRE_SHAPE("eg_bn_bwd", dtype, M, C);
+    BN_REQUIRE_ACT("eg_bn_bwd", act);
     bn_bwd_impl(dtype, z, da, dz, M, C, gamma, beta, save_mean, save_invstd, act, slope, dgamma, dbeta, sums, ws, EG_ACT_NONE, 0.f, nullptr, accumulate, (hipStream_t)s);
     EG_LAUNCH_CHECK();
     return 0;
@@ -654,6 +687,9 @@ extern "C" int eg_bn_bwd_post(int dtype, const void* z, const void* da, void* dz
                               const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta, float* sums, float* ws,
                               int post_act, float post_slope, const float* post_sigma, eg_stream_t s) {
     EG_REQUIRE(z && da && dz && gamma && beta && save_mean && save_invstd && sums && ws, "eg_bn_bwd_post: null pointer");
+    BN_REQUIRE_SHAPE("eg_bn_bwd_post", dtype, M, C);
+    EG_REQUIRE(post_act == EG_ACT_NONE || post_act == EG_ACT_LRELU || post_act == EG_ACT_RELU || post_act == EG_ACT_TANH || post_act == EG_ACT_SIGMOID,
+               "eg_bn_bwd_post: post_act must be one of the EG_ACT_* codes");
     bn_bwd_impl(dtype, z, da, dz, M, C, gamma, beta, save_mean, save_invstd, EG_ACT_NONE, 0.f, dgamma, dbeta, sums, ws, post_act, post_slope, post_sigma, 1, (hipStream_t)s);
     EG_LAUNCH_CHECK();
     return 0;

@@ -328,7 +328,21 @@ int eg_dense_small_wgrad(int dtype, const float* dy, const void* x, float* gw, f
 int eg_dense_small_bgrad(const float* dy, float* gb, int B, int N, int accumulate, eg_stream_t s);   /* gb[n] (+)= sum_b dy[b][n] */
 
 /* --- BatchNorm2d, training mode (celebA/EAD-GAN_celebA.py:79,83,87; MNIST/EAD-GAN_rpqmnxy.py:80,83,87,145) ----
- * x,y: [M][C] dtype T; updates running stats (momentum, unbiased var) and num_batches_tracked; fused activation */
+ * x,y: [M][C] dtype T; updates running stats (momentum, unbiased var: M2 / (M - 1), M2 / M for M = 1) and num_batches_tracked; fused
+ * activation.
+ * Argument contract of EVERY eg_bn_* entry point below (checked before anything is computed from C or launched; a call that breaks it
+ * returns a negative value and leaves its reason, with the entry point's name, in eg_last_error()):
+ *   - dtype is EG_F32, EG_BF16 or EG_F16;
+ *   - M > 0 (M_local > 0 for the data-parallel pair, which also needs M_global >= M_local, and nranks > 0 in the forward);
+ *   - C > 0 and C % 4 == 0 in fp32, C % 8 == 0 in the 16-bit types (rows are walked in 16-byte vectors);
+ *   - act is EG_ACT_NONE, EG_ACT_RELU or EG_ACT_LRELU, in the forwards too: the backwards have no derivative for another one;
+ *   - post_act of eg_bn_bwd_post is any EG_ACT_* code and nothing else;
+ *   - the fused pair needs nrb > 0, the forward also nrb * rows_per_block == M;
+ *   - pointers are non-null except where a comment says otherwise: running_mean, running_var and num_batches_tracked of the training
+ *     forwards, dgamma and dbeta of the backwards and post_sigma may each be NULL (that output is skipped; post_sigma: no division).
+ * y is formed as x * A[c] + B[c] from the two fp32 coefficients A = gamma * invstd, B = beta - mean * A, and the backwards decide act'(y)
+ * on that very expression; dz = A * dy - Bz * z - Cc with Bz = A * invstd * sum(dy * xhat) / M and
+ * Cc = A * (sum(dy) / M - mean * invstd * sum(dy * xhat) / M). */
 size_t eg_bn_ws_floats(int M, int C);
 int eg_bn_fwd_train(int dtype, const void* x, void* y, int M, int C, const float* gamma, const float* beta, float eps,
                     float momentum, float* running_mean, float* running_var, long long* num_batches_tracked,
