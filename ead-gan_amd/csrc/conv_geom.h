@@ -17,9 +17,14 @@ enum { NEED_CIN = 1, NEED_COUT = 2 };
 static inline int check_conv(const eg_conv* c, int dtype, int need) {
     EG_REQUIRE(c && c->B > 0 && c->k > 0 && c->stride > 0 && c->pad >= 0 && (c->up == 0 || c->up == 1), "eg_conv: bad field");
     EG_REQUIRE(dtype == EG_F32 || dtype == EG_BF16 || dtype == EG_F16, "dtype must be EG_F32, EG_BF16 or EG_F16");
+    // zero channels pass every `% vec` test below, and the kernels' tap walks (`while (kc >= C) kc -= C`) never end on C == 0
+    EG_REQUIRE(c->Cin > 0 && c->Cout > 0 && c->H > 0 && c->W > 0, "eg_conv: Cin, Cout, H and W must be positive (Cin=%d Cout=%d H=%d W=%d)",
+               c->Cin, c->Cout, c->H, c->W);
     const int OH = conv_out_dim(c, c->H), OW = conv_out_dim(c, c->W);
     EG_REQUIRE(ilog2_exact(c->H) >= 0 && ilog2_exact(c->W) >= 0 && ilog2_exact(OH) >= 0 && ilog2_exact(OW) >= 0,
                "spatial extents must be powers of two (H=%d W=%d OH=%d OW=%d)", c->H, c->W, OH, OW);
+    // the kernels index the B * OH * OW lattice rows with an int
+    EG_REQUIRE((long long)c->B * OH * OW < (1LL << 31), "eg_conv: B * OH * OW must be below 2^31 (B=%d OH=%d OW=%d)", c->B, OH, OW);
     EG_REQUIRE((!(need & NEED_CIN) || c->Cin % vec_of(dtype) == 0) && (!(need & NEED_COUT) || c->Cout % vec_of(dtype) == 0),
                "gathered channel count must be a multiple of %d for this dtype (Cin=%d Cout=%d); pad the tensor", vec_of(dtype), c->Cin, c->Cout);
     return 0;
@@ -53,6 +58,8 @@ static inline int geom_bwd(const eg_conv* c, int dtype, NtParams& p, int* nphase
     const int OH = conv_out_dim(c, c->H), OW = conv_out_dim(c, c->W);
     const int s = c->stride;
     EG_REQUIRE(s == 1 || s == 2, "stride must be 1 or 2");
+    // k < stride leaves sub-pixel phases without a tap (TH or TW == 0): the kernels divide by TW and walk taps until ty reaches TH
+    EG_REQUIRE(c->k >= s, "backward-data needs k >= stride (k=%d s=%d)", c->k, s);
     const int XH = c->H << c->up, XW = c->W << c->up;   // dX is produced at the (upsampled) conv-input resolution
     EG_REQUIRE(XH % s == 0 && XW % s == 0 && XH / s == OH && XW / s == OW,
                "backward-data needs OH == H/stride (k=%d s=%d p=%d)", c->k, s, c->pad);

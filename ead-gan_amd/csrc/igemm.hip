@@ -835,6 +835,21 @@ static void fill_epilogue(NtParams& p, const eg_epilogue* ep) {
     p.stat_slope = ep ? ep->stat_slope : 0.f;
 }
 
+// The one validator of eg_epilogue, run by nt_describe before any launch and before any query answers.  Everything it refuses would
+// otherwise compute something else without a word: the kernels' switches fall through to EG_ACT_NONE for an unknown act / mask_act /
+// stat_act (the mask's gradient becomes 1), every out_mode but EG_OUT_NHWC stores NCHW fp32, `n % bias_mod` of a negative bias_mod is
+// `n % -bias_mod`, and a negative sigma_rows reads sigma[] in front of its first element.
+static int check_epilogue(const eg_epilogue* ep) {
+    if (!ep) return 0;
+    EG_REQUIRE(ep->act >= EG_ACT_NONE && ep->act <= EG_ACT_SIGMOID, "eg_epilogue.act %d is no EG_ACT_* code", ep->act);
+    EG_REQUIRE(ep->mask_act >= EG_ACT_NONE && ep->mask_act <= EG_ACT_SIGMOID, "eg_epilogue.mask_act %d is no EG_ACT_* code", ep->mask_act);
+    EG_REQUIRE(ep->out_mode == EG_OUT_NHWC || ep->out_mode == EG_OUT_NCHW_F32, "eg_epilogue.out_mode %d is no EG_OUT_* code", ep->out_mode);
+    EG_REQUIRE(ep->bias_mod >= 0 && ep->sigma_rows >= 0, "eg_epilogue.bias_mod (%d) and sigma_rows (%d) must not be negative", ep->bias_mod, ep->sigma_rows);
+    EG_REQUIRE(ep->stat_mode == EG_STAT_NONE || (ep->stat_act >= EG_ACT_NONE && ep->stat_act <= EG_ACT_SIGMOID),
+               "eg_epilogue.stat_act %d is no EG_ACT_* code", ep->stat_act);
+    return 0;
+}
+
 // row blocks of the fused column statistics if this plan can produce them (the 8-wave kernel on whole 256-row tiles, K splits reduced
 // inside the launch), else 0
 static int nt_stat_blocks(const NtParams& p, int nphase, const NtPlan& plan, bool half) {
@@ -867,6 +882,7 @@ struct NtCall {
 // `unlimited`: plan as if any amount of split-K scratch were lent (what the problem could use, asked before there is a scratch)
 static int nt_describe(const eg_conv* c, int dtype, int bwd, const eg_epilogue* ep, bool unlimited, NtCall& call) {
     if (int e = check_conv(c, dtype, bwd ? NEED_COUT : NEED_CIN)) return e;
+    if (int e = check_epilogue(ep)) return e;
     NtParams& p = call.p;
     memset(&p, 0, sizeof(p));
     call.nphase = 1;

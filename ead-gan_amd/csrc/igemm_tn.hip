@@ -242,7 +242,8 @@ extern "C" int eg_conv_wgrad_variant(const eg_conv* c, int dtype) {
 extern "C" size_t eg_conv_wgrad_ws_bytes(const eg_conv* c, int dtype) {
     int ns, rps;
     Tn8Params p8;
-    if (c && !check_conv(c, dtype, NEED_CIN | NEED_COUT) && eg_tn8_plan(c, dtype, p8, &ns, 0))      // the whole-chip target splits furthest
+    if (!c || check_conv(c, dtype, NEED_CIN | NEED_COUT)) return 0;      // a convolution eg_conv_wgrad refuses needs no slab
+    if (eg_tn8_plan(c, dtype, p8, &ns, 0))      // the whole-chip target splits furthest
         return (size_t)ns * c->Cout * 16 * c->Cin * sizeof(float);
     eg_tn_plan(c, 0, &ns, &rps);
     return (size_t)ns * c->Cout * c->k * c->k * c->Cin * sizeof(float);

@@ -325,7 +325,8 @@ bool eg_tn8_plan(const eg_conv* c, int dtype, Tn8Params& p, int* nsplit, int wgs
     const long long base = (long long)p.ntn * p.ntc * 4;
     // (wgs_target: the caller's share of the chip -- a launch forked beside the main chain's GEMMs runs the step fastest at 128: half the
     //  slab bytes to write and reduce, and the other CUs stay with the main chain; profiles/r02_i_ab_tn8_target.txt)
-    const int target = wgs_target > 0 ? wgs_target : 256;
+    // (never above the whole-chip 256 that eg_conv_wgrad_ws_bytes sizes the slab for: the split count grows with the target)
+    const int target = wgs_target > 0 ? std::min(wgs_target, 256) : 256;
     long long want = base >= target ? 1 : (target + base - 1) / base;
     const long long steps = M / 64;
     want = std::min(want, std::max(1LL, steps / 4));

@@ -38,7 +38,10 @@ int eg_clear_errors(void);
 
 /* One square 2-D convolution in conv view.  X is [B,H,W,Cin] (NHWC); if up==1 the conv reads the
  * nearest-2x-upsampled X (nn.Upsample fused, MNIST/EAD-GAN_rpqmnxy.py:81,85).  Y is [B,OH,OW,Cout],
- * OH = ((H<<up) + 2*pad - k)/stride + 1.  All spatial extents must be powers of two. */
+ * OH = ((H<<up) + 2*pad - k)/stride + 1.  All spatial extents must be powers of two.
+ * Refused (-1, before anything is launched; the queries answer -1 / 0): B, k, stride, Cin, Cout, H or W <= 0, pad < 0, up outside 0 / 1,
+ * B * OH * OW >= 2^31, a gathered channel count that is no multiple of the 16-byte vector (4 fp32 / 8 16-bit elements); for the
+ * backward-data pass also stride > 2, OH != (H<<up)/stride and k < stride (a sub-pixel phase without a tap). */
 typedef struct eg_conv {
     int B, H, W, Cin, Cout, k, stride, pad, up;
 } eg_conv;
@@ -47,7 +50,11 @@ typedef struct eg_conv {
  * v = act(v) ; [v *= act'(mask)] ; store.  `mask` holds the activation OUTPUT of the layer whose
  * gradient is being formed (same dtype and layout as dst), so LeakyReLU/ReLU backward never needs a
  * separate pass.  Several forwards of one network ("tapes", each with its own spectral-norm sigma) can be
- * batched along M: tape = lattice_row / sigma_rows (sigma_rows == 0: one sigma for the whole launch). */
+ * batched along M: tape = lattice_row / sigma_rows (sigma_rows == 0: one sigma for the whole launch).
+ * Contract, checked in one place before any launch (eg_conv_fwd / eg_conv_bwd_data return -1; eg_igemm_nt_tile_ep answers -1,
+ * eg_conv_stat_blocks 0): act, mask_act and (with a stat_mode) stat_act are EG_ACT_* codes, out_mode is an EG_OUT_* code, bias_mod >= 0
+ * (0: bias[n]) and sigma_rows >= 0.  EG_OUT_NCHW_F32 stores fp32 [B][N][DH][DW] and reads `mask` in that layout and type; only the
+ * register-staged kernel writes it (a forced DMA variant is refused). */
 typedef struct eg_epilogue {
     const float* bias;
     int bias_mod;
