@@ -21,7 +21,7 @@ extern "C" int eg_clear_errors(void) {
     while (hipGetLastError() != hipSuccess && n < 16) ++n;
     return n;
 }
-extern "C" int eg_version(void) { return 115; }
+extern "C" int eg_version(void) { return 116; }
 
 // out[b][0:wa|wa:wa+wb|..] = cast(a|b|c), zero padded to Cpad  (generator input, celebA/EAD-GAN_celebA.py:97)
 template <typename T>

@@ -1511,3 +1511,114 @@ def spectrum_u8(images, full=False):
     lib().call("eg_spectrum_u8", _p(images), N, C, H, _p(tab["cos_sin"]), _p(tab["cell_ring"]), _p(tab["ring_start"]), _p(tab["ring_cells"]),
                _p(tab["ring_count"]), _p(profile), _p(whole) if full else None, _stream())
     return (profile, whole) if full else profile
+
+
+# ---- structural similarity between pairs of uint8 images ---------------------------------------
+SSIM_SIDES = (16, 32, 64)
+SSIM_MAX_C = 4
+SSIM_MAX_K = 11
+SSIM_FLAG_PAIR = 2                                    # eg_ssim_u8: a pair with a row index outside its set
+_SSIM_WINDOWS = {}
+
+
+def _ssim_taps(K, what):
+    if not (isinstance(K, int) and 3 <= K <= SSIM_MAX_K and K % 2 == 1):
+        raise ValueError(f"{what}: the window must have an odd number of taps K in 3 .. {SSIM_MAX_K}, got {K!r}")
+    return K
+
+
+def ssim_window(K=11, sigma=1.5):
+    """-> numpy float64 [K]: the one-dimensional window of ``eg_ssim_u8``, exp(-(k - K // 2)^2 / (2 sigma^2)) divided by its sum (Wang et
+    al.: K = 11, sigma = 1.5); ``sigma=None``: the uniform window 1 / K.  K odd, 3 .. 11.  The library evaluates no exp: the table is the
+    caller's."""
+    import numpy as np
+    K = _ssim_taps(K, "ssim_window")
+    if sigma is None:
+        return np.full(K, 1.0 / K, np.float64)
+    sigma = float(sigma)
+    if not (sigma > 0.0 and sigma < float("inf")):
+        raise ValueError(f"ssim_window: sigma = {sigma} must be positive and finite (None: the uniform window)")
+    k = np.arange(K, dtype=np.float64) - (K // 2)
+    w = np.exp(-(k * k) / (2.0 * sigma * sigma))
+    return w / w.sum()
+
+
+def ssim_window_table(K, sigma, device):
+    """``ssim_window(K, sigma)`` on ``device`` as a contiguous float64 tensor, built once per (K, sigma, device)"""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError("ssim_window_table: the table lives on the GPU (there is no CPU path)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(K), None if sigma is None else float(sigma), device)
+    if key not in _SSIM_WINDOWS:
+        _SSIM_WINDOWS[key] = torch.from_numpy(ssim_window(K, sigma)).contiguous().to(device)
+    return _SSIM_WINDOWS[key]
+
+
+def ssim_levels(H, K):
+    """-> the largest number of levels L of ``eg_ssim_u8`` for side ``H`` (16, 32 or 64) and a K-tap window: the largest L with
+    H >> (L - 1) >= K (64 px: 3 at K = 11; 32 px: 2; 16 px: 1)"""
+    H, K = int(H), _ssim_taps(K, "ssim_levels")
+    if H not in SSIM_SIDES:
+        raise ValueError(f"ssim_levels: the image side must be one of {list(SSIM_SIDES)}, got {H}")
+    L = 1
+    while (H >> L) >= K:
+        L += 1
+    return L
+
+
+def ssim_u8(a, b, pairs, window=None, levels=None, k1=0.01, k2=0.03, flag=None):
+    """-> (stats float64 [P, L, 2], sse int64 [P]) on the device, ``eg_ssim_u8``: for every row (i, j) of the int32 device table ``pairs``
+    [P, 2], image a[i] against image b[j] of the uint8 device sets a [na, C, H, H] and b [nb, C, H, H] (H = 16, 32 or 64; C = 1 .. 4; a
+    may be b).  stats[p, l] = (mean SSIM, mean contrast-structure term cs) over channels and valid window positions of level l of a 2 x 2
+    mean pyramid, with c1 = (k1 255)^2, c2 = (k2 255)^2; sse[p] = sum (a - b)^2 over the bytes, exact.  ``window``: a numpy / torch table
+    [K] of the one-dimensional window, K odd in 3 .. 11, normalised by the caller (None: the 11-tap Gaussian of ``ssim_window``);
+    ``levels``: L with H >> (L - 1) >= K (None: ``ssim_levels``).  A pair with an index outside its set gets NaN and -1 and sets
+    ``SSIM_FLAG_PAIR`` in ``flag`` (an int32 device tensor [1], ZEROED BY THE CALLER; not reported without it).  One workgroup per pair,
+    no host read; the bits of a pair depend on its two images and the arguments alone."""
+    import math
+    for name, t in (("a", a), ("b", b)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.dim() == 4 and t.is_contiguous()):
+            raise ValueError(f"ssim_u8: {name} must be a contiguous uint8 device tensor [N, C, H, H]")
+        if not t.is_cuda:
+            raise ValueError(f"ssim_u8: {name} must be a contiguous uint8 device tensor (there is no CPU path)")
+    na, C, H, W = (int(v) for v in a.shape)
+    nb = int(b.shape[0])
+    if H != W or H not in SSIM_SIDES:
+        raise ValueError(f"ssim_u8: the images must be square with a side in {list(SSIM_SIDES)}, got {H} x {W}")
+    if not 1 <= C <= SSIM_MAX_C:
+        raise ValueError(f"ssim_u8: C = {C} channels must be in 1 .. {SSIM_MAX_C}")
+    if tuple(b.shape[1:]) != (C, H, H) or b.device != a.device:
+        raise ValueError(f"ssim_u8: the two sets must hold images of one shape on one device, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if not (1 <= na < 2 ** 31 and 1 <= nb < 2 ** 31):
+        raise ValueError(f"ssim_u8: a {tuple(a.shape)} or b {tuple(b.shape)} holds no image (or 2^31 and more)")
+    if not (isinstance(pairs, torch.Tensor) and pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 2 and pairs.is_contiguous()
+            and pairs.device == a.device and 1 <= pairs.shape[0] < 2 ** 31):
+        raise ValueError("ssim_u8: pairs must be a contiguous int32 device tensor [P, 2], P >= 1, beside the images")
+    P = int(pairs.shape[0])
+    if window is None:
+        win = ssim_window_table(11, 1.5, a.device)
+    else:
+        if not isinstance(window, torch.Tensor):
+            import numpy as np
+            window = torch.from_numpy(np.ascontiguousarray(np.asarray(window, dtype=np.float64)))
+        if window.dim() != 1 or not window.is_floating_point():
+            raise ValueError("ssim_u8: window must be a floating-point table [K]")
+        win = window.detach().to(device=a.device, dtype=torch.float64).contiguous()
+    K = _ssim_taps(int(win.shape[0]), "ssim_u8")
+    top = ssim_levels(H, K)
+    L = top if levels is None else int(levels)
+    if not 1 <= L <= top:
+        raise ValueError(f"ssim_u8: levels = {L} must be in 1 .. {top} (H >> (L - 1) >= K with H = {H}, K = {K})")
+    c1, c2 = (float(k1) * 255.0) ** 2, (float(k2) * 255.0) ** 2
+    if not (c1 > 0.0 and c2 > 0.0 and math.isfinite(c1) and math.isfinite(c2)):
+        raise ValueError(f"ssim_u8: k1 = {k1} and k2 = {k2} must be positive and finite")
+    if flag is None:
+        flag = torch.zeros(1, device=a.device, dtype=torch.int32)
+    else:
+        _i32("ssim_u8", "flag", flag, (1,), a)
+    stats = torch.empty(P, L, 2, device=a.device, dtype=torch.float64)
+    sse = torch.empty(P, device=a.device, dtype=torch.int64)
+    lib().call("eg_ssim_u8", _p(a), na, _p(b), nb, C, H, _p(pairs), P, _p(win), K, L, c1, c2, _p(stats), _p(sse), _p(flag), _stream())
+    return stats, sse

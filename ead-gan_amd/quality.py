@@ -79,6 +79,25 @@ image), averaged over integer rings of the frequency plane, in dB, real against 
 * ``spectrum_generator(kind, generator, inputs)`` ``spectrum`` for a generator of an MNIST or CelebA run
 * ``SpectrumPlan``                               what ``train.TrainRun(..., spectrum=...)`` scores on checkpoint iterations
 
+Image against image: every score above is a statement about two SETS.  Two daily questions are about PAIRS: how good is a
+reconstruction (PSNR and SSIM of an output against its target: ``sampling.project_images`` reports only its own loss), and has the
+generator collapsed (the mean MS-SSIM over random pairs of generated images beside the same figure for real images, Odena et al. 2017: a
+value close to 1, or well above the real images', means mode collapse; per class for the class-conditional generators, where collapse
+inside one class hides in every set-level score).  Both rest on ops.ssim_u8: the windowed five-moment filter of Wang et al. (2004) over the
+levels of a 2 x 2 mean pyramid, in float64, one workgroup per pair, thousands of pairs per launch:
+
+* ``pair_table(n, n_pairs, seed)``               int32 [n_pairs, 2] on the device: ordered pairs of different rows of one set
+* ``ssim`` / ``ms_ssim`` / ``psnr(a, b, pairs)``   float64 [P] on the device, no host read
+* ``reconstruction(target, output)``             PSNR, mean squared error, mean SSIM and MS-SSIM of a set of outputs against their targets
+* ``projection_quality(kind, generator, ...)``   ``reconstruction`` of what ``sampling.project_images`` found
+* ``diversity(images, n_pairs, seed, labels)``   mean MS-SSIM and SSIM over random pairs, the number of identical pairs; per class with labels
+* ``diversity_generator(kind, generator, inputs)`` ``diversity`` of real and generated images of an MNIST or CelebA run over ONE pair table
+* ``SSIMPlan``                                   what ``train.TrainRun(..., ssim=...)`` scores on checkpoint iterations
+
+With the 11-tap window a level needs a side of 11 px, so MNIST's 32 px give L = 2 levels and CelebA's 64 px L = 3, weighted by the first L
+of Wang's five weights divided by their sum.  The numbers are therefore comparable within a workload, not across workloads or with papers
+that use 5 levels on larger images.
+
 Per level and set: patch statistics (ops.swd_patch_stats), then per repeat one fused gather-and-project launch (ops.swd_project: the
 descriptors, 0.6 GB per set and level at full size, never exist), one column sort per set (ops.sort_columns) and one reduction
 (ops.l1_mean).  Everything is enqueued on the current stream; ``swd`` reads the device once, at its end.  There is no CPU path.
@@ -97,6 +116,7 @@ PATCH, MIN_SIDE = 7, 16
 # a draw holds the level (centres), level * repeats + repeat (directions) or the batch index (generator inputs).
 SID_POSITIONS, SID_DIRECTIONS, SID_NOISE, SID_LABELS, SID_CODE = 0x5D00, 0x5D01, 0x5D10, 0x5D11, 0x5D12
 SID_BINS = 0x5D20                # the k-means seeding's uniforms (image_bins); the device counter holds 0
+SID_PAIRS = 0x5D30               # the pair tables (pair_table, class_pair_table); the device counter holds 0 for the first row of a pair, 1 for the second
 # how the trainers see a dataset image: eg_gather_u8_images' scale and shift (celebA/EAD-GAN_celebA.py:194-201, MNIST/EAD-GAN_rpqmnxy.py:235-243)
 _REAL_SCALE = {"mnist": (2.0 / 255.0, -1.0), "celeba": (2.0 / 255.0, -1.0)}
 _SPRITES = ("dsprites", "colored", "pxy")
@@ -149,6 +169,14 @@ class SpectrumPlan(NamedTuple):
     """the radial power-spectrum score a training run writes on its checkpoint iterations (``spectrum``): ``n_images`` generated against
     the first ``n_images`` dataset images"""
     n_images: int
+    seed: int = 0
+
+
+class SSIMPlan(NamedTuple):
+    """the pair diversity a training run writes on its checkpoint iterations (``diversity``): the mean MS-SSIM over ``n_pairs`` random
+    pairs of ``n_images`` generated images beside that of the first ``n_images`` dataset images, one pair table (from ``seed``) for all"""
+    n_images: int
+    n_pairs: int = 4096
     seed: int = 0
 
 
@@ -978,3 +1006,274 @@ def spectrum_generator(kind, generator, inputs, n_images=8192, batch=None, seed=
     batch = min(64, int(n_images)) if batch is None else int(batch)
     fake = generate(kind, generator, n_images, batch, seed)
     return spectrum(real_images(kind, inputs, n_images), fake, **kw)
+
+
+# ---- SSIM, MS-SSIM and PSNR over image pairs -----------------------------------------------------------------------------------
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)      # Wang, Simoncelli & Bovik (2003), finest level first
+PAIR_DRAW_BITS = 24              # a draw inside a class is (r m) >> 24 with r uniform in [0, 2^24): the draws are fp32-ranged integers
+_FLAG_CLASS = 1 << 8             # diversity's own bit beside ops.SSIM_FLAG_PAIR: a class with fewer than 2 rows
+
+
+def _pairs_from_draws(i, jp):
+    j = jp + (jp >= i).to(jp.dtype)
+    return torch.stack((i, j), 1).to(torch.int32).contiguous()
+
+
+def pair_draws(n_pairs, seed, high_i, high_j, device="cuda"):
+    """-> (r_i, r_j), int64 [n_pairs] on the device: the two draws behind a pair table, uniform integers in [0, high_i) and [0, high_j)
+    (two ops.rng_fill(RNG_RANDINT) draws on this module's stream SID_PAIRS, device counters 0 and 1)"""
+    dev = torch.device(device)
+    ri = torch.empty(int(n_pairs), device=dev, dtype=torch.int64)
+    rj = torch.empty(int(n_pairs), device=dev, dtype=torch.int64)
+    step = torch.zeros(1, device=dev, dtype=torch.int32)
+    ops.rng_fill(ops.RNG_RANDINT, ri, 0, int(high_i), seed, step, SID_PAIRS)
+    step.fill_(1)
+    ops.rng_fill(ops.RNG_RANDINT, rj, 0, int(high_j), seed, step, SID_PAIRS)
+    return ri, rj
+
+
+def pair_table(n, n_pairs, seed=0, device="cuda"):
+    """-> int32 [n_pairs, 2] on the device: ordered pairs (i, j) of DIFFERENT rows of one set of ``n`` >= 2 images, i ~ U{0 .. n - 1},
+    j' ~ U{0 .. n - 2}, j = j' + (j' >= i) (``pair_draws(n_pairs, seed, n, n - 1)``): every ordered pair is equally likely.  The same
+    ``seed`` gives the same table.  n <= 2^24 (the draw's bounds are fp32).  No host read."""
+    n, P = int(n), int(n_pairs)
+    if not (2 <= n <= 2 ** PAIR_DRAW_BITS and P >= 1):
+        raise ValueError(f"quality.pair_table: need 2 <= n <= 2^{PAIR_DRAW_BITS} rows and n_pairs >= 1, got n = {n}, n_pairs = {P}")
+    return _pairs_from_draws(*pair_draws(P, seed, n, n - 1, device))
+
+
+def class_pair_table(labels, n_classes, n_pairs, seed=0):
+    """-> (pairs int32 [n_pairs, 2], flag int32 [1]) on the device of ``labels`` (int64 [N], values in [0, n_classes)): pairs of different
+    rows of ONE class.  The rows are ordered by a stable sort of the labels; pair p belongs to class k = p % n_classes, whose segment
+    holds m rows; with r_i, r_j = ``pair_draws(n_pairs, seed, 2^24, 2^24)`` the places inside the segment are i = (r_i m) >> 24,
+    j' = (r_j (m - 1)) >> 24, j = j' + (j' >= i) (integers; a place's probability differs from 1 / m by less than 2^-24).  A class with
+    fewer than 2 rows, or a label outside [0, n_classes), raises bit 8 of ``flag`` (its pairs hold row 0 twice).  No host read."""
+    if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int64 and labels.dim() == 1 and labels.shape[0] >= 2):
+        raise ValueError("quality.class_pair_table: labels must be an int64 device tensor [N], N >= 2")
+    K, P, N = int(n_classes), int(n_pairs), int(labels.shape[0])
+    if not (K >= 1 and P >= 1 and N <= 2 ** PAIR_DRAW_BITS):
+        raise ValueError(f"quality.class_pair_table: need n_classes >= 1, n_pairs >= 1 and N <= 2^{PAIR_DRAW_BITS}, got {K}, {P}, {N}")
+    inside = (labels >= 0) & (labels < K)
+    order = torch.sort(labels.clamp(0, K - 1), stable=True).indices
+    counts = torch.bincount(labels.clamp(0, K - 1), minlength=K)
+    start = torch.cumsum(counts, 0) - counts
+    k = torch.arange(P, device=labels.device, dtype=torch.int64) % K
+    m = counts[k]
+    ri, rj = pair_draws(P, seed, 2 ** PAIR_DRAW_BITS, 2 ** PAIR_DRAW_BITS, labels.device)
+    i = (ri * m) >> PAIR_DRAW_BITS
+    jp = (rj * (m - 1).clamp_min(0)) >> PAIR_DRAW_BITS
+    j = jp + (jp >= i).to(torch.int64)
+    ok = m >= 2
+    rows_i = torch.where(ok, order[(start[k] + i).clamp(0, N - 1)], torch.zeros_like(i))
+    rows_j = torch.where(ok, order[(start[k] + j).clamp(0, N - 1)], torch.zeros_like(j))
+    flag = ((~ok).any() | (~inside).any()).to(torch.int32).mul(_FLAG_CLASS).reshape(1)
+    return torch.stack((rows_i, rows_j), 1).to(torch.int32).contiguous(), flag
+
+
+def ms_ssim_weights(L, weights=None):
+    """-> the L per-level exponents of ``ms_ssim`` as a tuple of floats: ``weights`` as given (L positive numbers), or the first L of
+    ``MS_SSIM_WEIGHTS`` divided by their sum (all five, L = 5, as they are)"""
+    L = int(L)
+    if weights is None:
+        if not 1 <= L <= len(MS_SSIM_WEIGHTS):
+            raise ValueError(f"quality.ms_ssim: levels = {L} must be in 1 .. {len(MS_SSIM_WEIGHTS)}")
+        total = sum(MS_SSIM_WEIGHTS[:L]) if L < len(MS_SSIM_WEIGHTS) else 1.0     # the full five are Wang's own, as published
+        return tuple(w / total for w in MS_SSIM_WEIGHTS[:L])
+    w = tuple(float(v) for v in weights)
+    if len(w) != L or not all(0.0 < v < float("inf") for v in w):
+        raise ValueError(f"quality.ms_ssim: weights must be {L} positive numbers, one per level")
+    return w
+
+
+def ms_ssim_from_stats(stats, weights=None):
+    """-> float64 [P] on the device from ``ops.ssim_u8``'s stats [P, L, 2]: prod_{l < L - 1} max(cs_l, 0)^w_l * max(ssim_{L-1}, 0)^w_{L-1}
+    in torch float64; the clamp at 0 is the TensorFlow implementation's (unrelated images do give a negative cs)"""
+    L = int(stats.shape[1])
+    w = torch.tensor(ms_ssim_weights(L, weights), device=stats.device, dtype=torch.float64)
+    base = torch.cat((stats[:, :L - 1, 1], stats[:, L - 1:, 0]), 1).clamp_min(0.0)
+    return torch.pow(base, w).prod(1)
+
+
+def _pair_sets(a, b, pairs, what):
+    """-> (A, B, pairs): the two sets as uint8 rows and the pair table (None: row i against row i)"""
+    for name, t in (("a", a), ("b", b)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise ValueError(f"quality.{what}: {name} must be a float or uint8 device tensor [N, C, H, W] (there is no CPU path)")
+    A = _u8_rows(a, "a")
+    B = A if b is a else _u8_rows(b, "b")
+    if A.shape[1:] != B.shape[1:] or A.device != B.device:
+        raise ValueError(f"quality.{what}: the two sets must hold images of one shape on one device, got {tuple(A.shape)} and {tuple(B.shape)}")
+    if pairs is None:
+        if A.shape[0] != B.shape[0]:
+            raise ValueError(f"quality.{what}: without a pair table row i meets row i: the sets need one size, got {A.shape[0]} and {B.shape[0]}")
+        idx = torch.arange(A.shape[0], device=A.device, dtype=torch.int32)
+        pairs = torch.stack((idx, idx), 1).contiguous()
+    elif not (isinstance(pairs, torch.Tensor) and pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 2 and pairs.device == A.device):
+        raise ValueError(f"quality.{what}: pairs must be an int32 device tensor [P, 2] beside the images")
+    return A, B, pairs.contiguous()
+
+
+def _window(window, sigma, device):
+    return ops.ssim_window_table(int(window), sigma, device) if isinstance(window, int) else window
+
+
+def ssim(a, b, pairs=None, window=11, sigma=1.5):
+    """-> float64 [P] on the device: the mean SSIM (Wang et al. 2004, "valid" windows, k1 = 0.01, k2 = 0.03 on the bytes) of a[i] against
+    b[j] for every row (i, j) of ``pairs`` (int32 [P, 2] on the device; None: row i against row i of two sets of one size).  Images
+    [N, C, H, H], float in [-1, 1] through ``to_u8`` or uint8, H = 16, 32 or 64, C = 1 .. 4.  ``window``: the number of taps of the
+    Gaussian of width ``sigma`` (``sigma=None``: uniform), or a [K] table.  No host read; a row index outside its set gives NaN."""
+    A, B, pairs = _pair_sets(a, b, pairs, "ssim")
+    return ops.ssim_u8(A, B, pairs, _window(window, sigma, A.device), levels=1)[0][:, 0, 0].contiguous()
+
+
+def ms_ssim(a, b, pairs=None, levels=None, weights=None, window=11, sigma=1.5):
+    """-> float64 [P] on the device: the multi-scale SSIM (Wang et al. 2003) of the pairs of ``ssim`` over ``levels`` levels of a 2 x 2
+    mean pyramid (None: as many as the side allows, ``ops.ssim_levels``: 3 at 64 px, 2 at 32 px, 1 at 16 px with 11 taps):
+    prod_{l < L - 1} max(cs_l, 0)^w_l * max(ssim_{L-1}, 0)^w_{L-1}.  ``weights``: L positive exponents; None: for L < 5 levels the first
+    L of ``MS_SSIM_WEIGHTS`` divided by their sum, so the value is comparable within a workload, not with 5-level figures.  No host read."""
+    A, B, pairs = _pair_sets(a, b, pairs, "ms_ssim")
+    stats = ops.ssim_u8(A, B, pairs, _window(window, sigma, A.device), levels=levels)[0]
+    return ms_ssim_from_stats(stats, weights)
+
+
+def _psnr_from_sse(sse, numel):
+    mse = sse.double() / float(numel)
+    return torch.where(sse == 0, torch.full_like(mse, float("inf")), 10.0 * torch.log10(255.0 ** 2 / mse.clamp_min(2.0 ** -60)))
+
+
+def psnr(a, b, pairs=None):
+    """-> float64 [P] on the device: 10 log10(255^2 C H W / sse) of the pairs of ``ssim`` from the exact integer squared error of the bytes,
+    +inf where the two images are equal.  No host read."""
+    A, B, pairs = _pair_sets(a, b, pairs, "psnr")
+    sse = ops.ssim_u8(A, B, pairs, ops.ssim_window_table(3, None, A.device), levels=1)[1]
+    return _psnr_from_sse(sse, A[0].numel())
+
+
+def _pair_scores(A, B, pairs, levels, weights, window, sigma):
+    """one launch -> (ssim [P], ms_ssim [P], sse [P], flag [1], L) on the device"""
+    flag = torch.zeros(1, device=A.device, dtype=torch.int32)
+    stats, sse = ops.ssim_u8(A, B, pairs, _window(window, sigma, A.device), levels=levels, flag=flag)
+    return stats[:, 0, 0].contiguous(), ms_ssim_from_stats(stats, weights), sse, flag, int(stats.shape[1])
+
+
+def _raise_pair_flag(what, flag):
+    if flag & _FLAG_CLASS:
+        raise ValueError(f"quality.{what}: a class holds fewer than 2 images (or a label lies outside [0, n_classes)): there is no pair inside it")
+    if flag & ops.SSIM_FLAG_PAIR:
+        raise ValueError(f"quality.{what}: the pair table names a row outside its set")
+
+
+def _reconstruction_device(target, output, levels, weights, window, sigma):
+    A, B, pairs = _pair_sets(target, output, None, "reconstruction")
+    ss, ms, sse, flag, L = _pair_scores(A, B, pairs, levels, weights, window, sigma)
+    numel = A[0].numel()
+    vec = torch.stack((sse.double().mean() / float(numel), ss.mean(), ms.mean(), flag[0].double()))
+    return vec, (_psnr_from_sse(sse, numel), ss, ms), L
+
+
+def _reconstruction_dict(host, L):
+    import math
+    mse = float(host[0])
+    _raise_pair_flag("reconstruction", int(host[3]))
+    return {"psnr": 10.0 * math.log10(255.0 ** 2 / mse) if mse > 0.0 else float("inf"), "mse": mse, "ssim": float(host[1]),
+            "ms_ssim": float(host[2]), "levels": L}
+
+
+def reconstruction(target, output, terms=False, levels=None, weights=None, window=11, sigma=1.5):
+    """How good is a reconstruction: ``output`` [N, C, H, H] against ``target`` [N, C, H, H], image i against image i (float in [-1, 1] or
+    uint8) -> {"psnr", "mse", "ssim", "ms_ssim", "levels"}: "mse" = the mean over the set of sse / (C H W) in squared byte units, "psnr" =
+    10 log10(255^2 / mse) (inf when it is 0), "ssim" and "ms_ssim" the means of ``ssim`` and ``ms_ssim`` over the set.  ``terms=True``:
+    -> (that dictionary, psnr [N], ssim [N], ms_ssim [N]), the per-image float64 device tensors.  One launch, one host read."""
+    vec, per, L = _reconstruction_device(target, output, levels, weights, window, sigma)
+    out = _reconstruction_dict(vec.cpu().tolist(), L)                       # THE host read
+    return (out,) + per if terms else out
+
+
+def projection_quality(kind, generator, target, labels, steps, lr, **kw):
+    """``reconstruction(target, G(inputs))`` for the inputs ``sampling.project_images(kind, generator, target, labels, steps, lr, **kw)``
+    finds, plus "loss": the mean of the last row of its ``losses`` (the mean squared error in [-1, 1] units it minimised).  The eval-mode
+    generator is called as there: the sprite generators take (labels, code), the others (noise, labels, code).  One host read."""
+    noise, onehot, code, losses = sampling.project_images(kind, generator, target, labels, steps, lr, **kw)
+    with torch.no_grad():
+        image = generator(onehot, code) if noise is None else generator(noise, onehot, code)
+    vec, _, L = _reconstruction_device(sampling._dev(target), image, None, None, 11, 1.5)
+    host = torch.cat((vec, losses[-1].double().mean().reshape(1))).cpu().tolist()        # THE host read
+    out = _reconstruction_dict(host, L)
+    out["loss"] = float(host[4])
+    return out
+
+
+def _diversity_device(images, n_pairs, seed, labels, n_classes, pairs, levels, weights, window, sigma):
+    """-> (vec float64 on the device: [mean ms_ssim, mean ssim, duplicates, flags, by_class ...], (pairs, ms_ssim, ssim, sse), meta)"""
+    if not (isinstance(images, torch.Tensor) and images.is_cuda):
+        raise ValueError("quality.diversity: images must be a float or uint8 device tensor [N, C, H, W] (there is no CPU path)")
+    rows = _u8_rows(images, "images")
+    N = int(rows.shape[0])
+    if N < 2:
+        raise ValueError(f"quality.diversity: a set needs at least 2 images, got {N}")
+    flags = torch.zeros(1, device=rows.device, dtype=torch.int32)
+    K = 0
+    if labels is not None:
+        if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int64 and tuple(labels.shape) == (N,)):
+            raise ValueError(f"quality.diversity: labels must be an int64 device tensor [{N}], one per image")
+        if n_classes is None or int(n_classes) < 1:
+            raise ValueError("quality.diversity: labels need n_classes >= 1 (reading it off the labels would be a host read)")
+        K = int(n_classes)
+    if pairs is None:
+        if labels is None:
+            pairs = pair_table(N, n_pairs, seed, rows.device)
+        else:
+            pairs, flags = class_pair_table(labels, K, n_pairs, seed)
+    A, B, pairs = _pair_sets(rows, rows, pairs, "diversity")
+    ss, ms, sse, flag, L = _pair_scores(A, B, pairs, levels, weights, window, sigma)
+    P = int(pairs.shape[0])
+    parts = [ms.mean().reshape(1), ss.mean().reshape(1), (sse == 0).sum().double().reshape(1), (flag | flags).double()]
+    if K:
+        if P < K:
+            raise ValueError(f"quality.diversity: n_pairs = {P} leaves a class of {K} without a pair")
+        k = torch.arange(P, device=rows.device, dtype=torch.int64) % K
+        sums = torch.zeros(K, device=rows.device, dtype=torch.float64).index_add_(0, k, ms)
+        parts.append(sums / torch.bincount(k, minlength=K).double())
+    return torch.cat(parts), (pairs, ms, ss, sse), {"pairs": P, "levels": L, "classes": K}
+
+
+def _diversity_dict(host, meta):
+    _raise_pair_flag("diversity", int(host[3]))
+    out = {"ms_ssim": float(host[0]), "ssim": float(host[1]), "pairs": meta["pairs"], "duplicates": int(host[2]), "levels": meta["levels"]}
+    if meta["classes"]:
+        out["by_class"] = [float(v) for v in host[4:4 + meta["classes"]]]
+    return out
+
+
+def diversity(images, n_pairs=16384, seed=0, labels=None, n_classes=None, pairs=None, terms=False, levels=None, weights=None, window=11,
+              sigma=1.5):
+    """Has the generator collapsed: the mean MS-SSIM over random pairs of different images of ONE set [N, C, H, H] (float in [-1, 1] or
+    uint8; Odena et al. 2017) -> {"ms_ssim", "ssim", "pairs", "duplicates", "levels"}: the means of ``ms_ssim`` and ``ssim`` over
+    ``pair_table(N, n_pairs, seed)``, the number of pairs of identical images (sse == 0) and the number of levels.  Read it beside the same
+    figure of the real images: a value close to 1, or well above theirs, means mode collapse.  With ``labels`` (int64 [N] on the device)
+    and ``n_classes`` the pairs are drawn inside classes (``class_pair_table``: pair p belongs to class p % n_classes) and the result
+    gains "by_class": the mean MS-SSIM of every class's pairs -- collapse inside one class hides in every set-level score; a class with
+    fewer than 2 images raises ValueError.  ``pairs`` (int32 [P, 2] on the device) overrides the draw; with labels, pair p still counts
+    for class p % n_classes.  ``terms=True``: -> (that dictionary, pairs, ms_ssim [P], ssim [P], sse [P]) with the device tensors.
+    Deterministic: the same images and seed give the same bits.  One launch, one host read (which carries the flags)."""
+    vec, per, meta = _diversity_device(images, n_pairs, seed, labels, n_classes, pairs, levels, weights, window, sigma)
+    out = _diversity_dict(vec.cpu().tolist(), meta)                          # THE host read
+    return (out,) + per if terms else out
+
+
+def diversity_generator(kind, generator, inputs, n_images=8192, n_pairs=16384, batch=None, seed=0):
+    """-> {"real": ``diversity`` of ``real_images(kind, inputs, n_images)``, "fake": ``diversity`` of ``generate(kind, generator, n_images,
+    batch, seed)``, "gap": fake's ms_ssim - real's}: ONE pair table, ``pair_table(n_images, n_pairs, seed)``, serves both sets.  A gap
+    well above 0 means that the generated images resemble each other more than the data do.  ``batch`` as in ``swd_generator``.  One
+    host read."""
+    _family(kind, "diversity_generator")
+    batch = min(64, int(n_images)) if batch is None else int(batch)
+    fake = generate(kind, generator, n_images, batch, seed)
+    real = real_images(kind, inputs, n_images)
+    table = pair_table(int(n_images), n_pairs, seed, real.device)
+    rv, _, rmeta = _diversity_device(real, n_pairs, seed, None, None, table, None, None, 11, 1.5)
+    fv, _, fmeta = _diversity_device(fake, n_pairs, seed, None, None, table, None, None, 11, 1.5)
+    host = torch.cat((rv, fv)).cpu().tolist()                                # THE host read
+    out = {"real": _diversity_dict(host[:len(rv)], rmeta), "fake": _diversity_dict(host[len(rv):], fmeta)}
+    out["gap"] = out["fake"]["ms_ssim"] - out["real"]["ms_ssim"]
+    return out

@@ -165,11 +165,18 @@ def spectrum_seed(seed, batches_done, plan_seed=0):
     return (int(seed) * 1000003 + int(batches_done) * 4099 + int(plan_seed) * 150989 + 24680) % (2 ** 32)
 
 
+def ssim_seed(seed, batches_done, plan_seed=0):
+    """seed of a checkpoint iteration's generated images for the pair diversity (MS-SSIM): ``swd_seed``'s form with constants of its own.
+    (The pair table is drawn once, from the plan's own seed.)"""
+    return (int(seed) * 1000003 + int(batches_done) * 4597 + int(plan_seed) * 163841 + 97531) % (2 ** 32)
+
+
 def check_plan(what, plan, cls, kind, n_dataset, batch):
-    """-> ``plan`` as a ``cls`` (quality.SWDPlan, NNPlan, MMDPlan, SinkhornPlan, NDBPlan or SpectrumPlan) after the checks every score plan
-    of a run passes: the kind of the run, ``n_images`` against the dataset and against the trainer's batch size; an MMD plan also needs
-    two images a set and 1 .. 4 positive scales, a Sinkhorn plan two images a set, a positive scale and at least one iteration, an NDB
-    plan 1 .. min(1024, n_images) bins and no negative iteration count, a spectrum plan two images a set"""
+    """-> ``plan`` as a ``cls`` (quality.SWDPlan, NNPlan, MMDPlan, SinkhornPlan, NDBPlan, SpectrumPlan or SSIMPlan) after the checks every
+    score plan of a run passes: the kind of the run, ``n_images`` against the dataset and against the trainer's batch size; an MMD plan
+    also needs two images a set and 1 .. 4 positive scales, a Sinkhorn plan two images a set, a positive scale and at least one iteration,
+    an NDB plan 1 .. min(1024, n_images) bins and no negative iteration count, a spectrum plan two images a set, an SSIM plan two images
+    a set and at least one pair"""
     if kind not in ("mnist", "celeba"):
         raise ValueError(f"{what}: only 'mnist' and 'celeba' runs are scored (quality.generate), not {kind!r}")
     plan = cls(*plan)
@@ -201,6 +208,11 @@ def check_plan(what, plan, cls, kind, n_dataset, batch):
     if cls is quality.SpectrumPlan:
         if int(plan.n_images) < 2:
             raise ValueError(f"{what}: n_images = {plan.n_images}, the variance over a set needs at least 2 images")
+    if cls is quality.SSIMPlan:
+        if int(plan.n_images) < 2:
+            raise ValueError(f"{what}: n_images = {plan.n_images}, a pair needs at least 2 images a set")
+        if int(plan.n_pairs) < 1:
+            raise ValueError(f"{what}: n_pairs = {plan.n_pairs} must be at least 1")
     return plan
 
 
@@ -253,13 +265,21 @@ class TrainRun:
     ``n_images`` dataset images.  The real set's per-ring mean and variance are computed once, at the first scored checkpoint, and kept
     on the run object (``spectrum_real``); they are no part of ``run_state_%d.pt``: a resumed run recomputes the same bits.
 
+    ``ssim=quality.SSIMPlan(n_images, n_pairs=4096, seed=0)`` (the same runs): on checkpoint iterations, after the
+    ``spectrum.jsonl`` line if there is one, rank 0 appends ``{"batches_done", "G": {...}[, "G_ema": {...}]}`` to ``out_dir/ssim.jsonl``;
+    every entry is ``quality.diversity`` (the mean MS-SSIM and SSIM over random pairs) of one set of generated images per generator
+    (seeded by ``ssim_seed``) plus ``"real"``, the same dictionary of the first ``n_images`` dataset images, and ``"gap"``, the generated
+    set's ms_ssim minus the real set's.  One pair table, drawn from the plan's seed, serves every set and every line.  The real set's
+    diversity is computed once, at the first scored checkpoint, and kept on the run object (``ssim_real``); it is no part of
+    ``run_state_%d.pt``: a resumed run recomputes the same bits.
+
     Data parallel (``inputs.world`` > 1, the world of the trainer's ``allreduce`` / ``sync_bn``): ``graph=False`` is required; the
     iteration count, cadence, sample seeds and file names are those of one process at the global batch ``B * world``; rank 0 prints and
     writes every file, the other ranks write none (``files == []``) and print nothing but execute every ``_wait`` and keep ``history``
     / ``lines`` of their own shard.  The run adds no collective: rank 0's lines and ``losses.npy`` carry rank 0's shard losses."""
 
     def __init__(self, kind, trainer, inputs, out_dir, n_epochs, sample_interval=None, seed=0, graph=True, log_capacity=1024, log_in_graph=True,
-                 ema_samples=False, swd=None, nn=None, mmd=None, sinkhorn=None, ndb=None, spectrum=None):
+                 ema_samples=False, swd=None, nn=None, mmd=None, sinkhorn=None, ndb=None, spectrum=None, ssim=None):
         self.plan = _plan(kind)
         if getattr(trainer, "STATE_KIND", None) != kind:
             raise ValueError(f"a {kind!r} run needs a {kind!r} trainer, got {type(trainer).__name__}")
@@ -306,9 +326,10 @@ class TrainRun:
         self.swd, self.nn, self.mmd, self.sinkhorn, self._score_G = swd, nn, mmd, sinkhorn, None       # one scratch generator serves every plan
         self.ndb, self.ndb_bins = ndb, None                         # ndb_bins: quality.Bins of the real images, fitted at the first scored checkpoint
         self.spectrum, self.spectrum_real = spectrum, None          # spectrum_real: quality.spectrum_moments of the real images [2, B], computed once
+        self.ssim, self.ssim_real, self._ssim_pairs = ssim, None, None     # ssim_real: quality.diversity of the real images, computed once
         for what, plan, cls in (("swd", swd, quality.SWDPlan), ("nn", nn, quality.NNPlan), ("mmd", mmd, quality.MMDPlan),
                                 ("sinkhorn", sinkhorn, quality.SinkhornPlan), ("ndb", ndb, quality.NDBPlan),
-                                ("spectrum", spectrum, quality.SpectrumPlan)):
+                                ("spectrum", spectrum, quality.SpectrumPlan), ("ssim", ssim, quality.SSIMPlan)):
             if plan is None:
                 continue
             setattr(self, what, check_plan(what, plan, cls, kind, self.n_images, trainer.B))
@@ -483,6 +504,25 @@ class TrainRun:
         self._score_line("spectrum.jsonl", it, lambda G: quality.spectrum_from_moments(
             self.spectrum_real, quality.spectrum_moments(quality.generate(self.kind, G, n, min(int(tr.B), n), seed))[0], H))
 
+    def _score_ssim(self, it):
+        """one line of ``ssim.jsonl``: ``quality.diversity`` of one set of generated images per generator, beside that of the
+        first ``n_images`` dataset images, which is computed here once; one pair table for all"""
+        if self._score_G is None or self.ssim is None:
+            return
+        tr, plan = self.trainer, self.ssim
+        n, seed = int(plan.n_images), ssim_seed(self.seed, it, plan.seed)
+        if self.ssim_real is None:
+            real = quality.real_images(self.kind, self.inputs, n)
+            self._ssim_pairs = quality.pair_table(n, int(plan.n_pairs), plan.seed, real.device)
+            self.ssim_real = quality.diversity(real, pairs=self._ssim_pairs)
+
+        def score(G):
+            out = quality.diversity(quality.generate(self.kind, G, n, min(int(tr.B), n), seed), pairs=self._ssim_pairs)
+            out["real"] = dict(self.ssim_real)
+            out["gap"] = out["ms_ssim"] - self.ssim_real["ms_ssim"]
+            return out
+        self._score_line("ssim.jsonl", it, score)
+
     def _score_line(self, name, it, score):
         """``{"batches_done", "G": score(live generator)[, "G_ema": score(averaged generator)]}`` appended to ``out_dir/name``"""
         tr, G = self.trainer, self._score_G
@@ -547,6 +587,7 @@ class TrainRun:
                 self._score_sinkhorn(it)
                 self._score_ndb(it)
                 self._score_spectrum(it)
+                self._score_ssim(it)
             self.batches_done = it + 1
             done += 1
             if do_ckpt:

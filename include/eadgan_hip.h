@@ -919,6 +919,32 @@ int eg_kmeans_seed_u8(const unsigned char* rows, int n, int K, int bins, const f
 int eg_spectrum_u8(const unsigned char* images, int N, int C, int H, const double* cos_sin, const int* cell_ring, const int* ring_start,
                    const int* ring_cells, const int* ring_count, double* profile, double* full, eg_stream_t s);
 
+/* --- structural similarity between PAIRS of uint8 images (not in the reference): SSIM, its contrast-structure term per level
+ * of a 2 x 2 mean pyramid (MS-SSIM is a product of their powers), and the squared error (PSNR).  a [na][C][H][H] and b [nb][C][H][H]
+ * contiguous uint8, 4-byte aligned, a == b is allowed; H = 16, 32 or 64, 1 <= C <= 4; pairs [P][2] int32 on the device = (row of a, row of
+ * b), 1 <= P < 2^31; win [K] doubles on the device, the one-dimensional window, normalised by the CALLER (the library evaluates no exp), K
+ * odd, 3 <= K <= 11; 1 <= L and H >> (L - 1) >= K; c1, c2 positive and finite.  Anything else returns non-zero and launches nothing.
+ * The contract, for pair p = (i, j):
+ *   levels   x_l[y][x] = 4^-l (integer sum of the 2^l x 2^l block of bytes), l = 0 .. L - 1: l-fold 2 x 2 mean pooling, exact in fp64,
+ *            every value <= 255.  Side H_l = H >> l; the valid window positions are 0 <= r, q <= n_l - 1 with n_l = H_l - K + 1 (Wang's
+ *            "valid" form, no padding).
+ *   moments  per level, channel and position mu_a, mu_b, E_aa, E_bb, E_ab of x, y, x^2, y^2, x y, each
+ *            sum_dy win[dy] sum_dx win[dx] (.)[r + dy][q + dx]: rows first, then columns, every sum in index order, fp64 throughout (the
+ *            products are exact in fp64).
+ *   values   s_aa = E_aa - mu_a^2, s_bb = E_bb - mu_b^2, s_ab = E_ab - mu_a mu_b,
+ *            cs = (2 s_ab + c2) / (s_aa + s_bb + c2), lum = (2 mu_a mu_b + c1) / (mu_a^2 + mu_b^2 + c1), ssim = lum cs.
+ *   stats [P][L][2]: stats[p][l][0] = the mean of ssim, stats[p][l][1] = the mean of cs over channels and positions, summed in a fixed
+ *            order: an output column's rows in row order (one thread), then per level the C n_l column sums, channel then column, lane k of
+ *            a wave taking the columns k, k + 64, ..., the lane sums meeting in a fixed tree.
+ *   sse [P]: sum (a - b)^2 over all bytes of the pair, an exact integer.
+ *   A pair with an index outside [0, na) x [0, nb): nothing is read, stats[p] = NaN, sse[p] = -1, and *flag (int32, ZEROED BY THE CALLER)
+ *   is set to 2 (bit 1) by a plain store of that constant; all other pairs are unaffected.
+ * One workgroup per pair, no atomics, no allocation, no sync: the bits of pair p depend on its two images, win, c1, c2, K and L alone, not
+ * on P, its place in the table, other pairs or the run.  |ssim - exact| <= (8 / k1^2 + 12 / k2^2) (2 K + 2) 2^-53 with c1 = (255 k1)^2,
+ * c2 = (255 k2)^2 (2.5e-10 at K = 11 and the usual k1 = 0.01, k2 = 0.03); the means inherit it. */
+int eg_ssim_u8(const unsigned char* a, int na, const unsigned char* b, int nb, int C, int H, const int* pairs, int P, const double* win, int K,
+               int L, double c1, double c2, double* stats, long long* sse, int* flag, eg_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
